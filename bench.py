@@ -267,6 +267,42 @@ def verified_ok(vg, ve):
     return bool(ok)
 
 
+DUMP_LIMIT_BYTES = 64_000_000   # all files of one --dump-outputs together
+DUMP_COLUMNS, DUMP_TOP = 256, 16  # eigenvectors kept when Z does not fit: the DUMP_TOP largest + a seeded sample of the rest
+
+
+def dump_outputs(out_dir, w, Z, seed=0):
+    """Write what one step of the timed path returned (``kernels.symeig``'s eigenvalues and eigenvectors) as float32 / float64
+    .npy files in ``out_dir``, for comparing two builds output for output.  Returns ``{file name: shape}``.
+
+    eigenvalues.npy        all n eigenvalues, ascending (float32)
+    eigenvectors.npy       [n, k] eigenvector columns (float32): all of Z when it fits in DUMP_LIMIT_BYTES, else the DUMP_TOP
+                           largest eigenvalues' plus a sample of the others drawn from ``seed`` (the same columns every run)
+    eigenvector_columns.npy  the column of Z (= index into eigenvalues) of each of them (float64, exact integers)
+    An eigenvector is defined up to its sign: each column is flipped so that its entry of largest magnitude is positive."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"eigenvalues": w.float().cpu().numpy()}
+    if Z is not None:
+        n = Z.shape[1]
+        if 4 * n * (n + 1) + 8 * n <= DUMP_LIMIT_BYTES:
+            cols = torch.arange(n)
+        else:
+            g = torch.Generator().manual_seed(seed)
+            rest = torch.randperm(n - DUMP_TOP, generator=g)[:DUMP_COLUMNS - DUMP_TOP]
+            cols = torch.cat([rest.sort().values, torch.arange(n - DUMP_TOP, n)])
+        S = Z[:, cols.to(Z.device)].float()
+        sign = S.gather(0, S.abs().argmax(0, keepdim=True)).sign()
+        S *= torch.where(sign == 0, torch.ones_like(sign), sign)
+        arrays["eigenvectors"] = S.cpu().numpy()
+        arrays["eigenvector_columns"] = cols.double().numpy()
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    return {f"{name}.npy": list(a.shape) for name, a in arrays.items()}
+
+
 def mlp_factorised_factors(dims, batch, device, seed=0):
     """The same MLP's factors in the form ViViTGGNExact keeps them (vivit/extensions/secondorder/vivit/linear.py:41-42):
     per Linear layer ``(s [C, N, out], z [N, in])`` with ``V_t(weight)[c,n,o,i] = s[c,n,o] z[n,i]``, ``V_t(bias) = s``."""
@@ -627,7 +663,12 @@ def main():
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"],
                     help="torch.distributed backend of a multi-rank run (default nccl = RCCL over xGMI; gloo: functional "
                          "runs, several ranks may share one card)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's eigenvalues and (a seeded sample of) its eigenvectors as .npy "
+                         "files in DIR (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_spawn_ranks(args.gpus))
@@ -784,6 +825,10 @@ def main():
 
     if rank == 0:
         _progress(f"timed region done: {elapsed / args.steps:.3f} s per step")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, w, Z)
+        _progress(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
     verified = None
     if not args.no_verify:
         # parity of THIS shape (not timed): rebuild G, sampled fp64 entries / symmetry / trace, then the
@@ -1031,6 +1076,8 @@ def main():
         }
         if verified is not None:
             out["verified"] = verified
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         if secondary_lines is not None:
             out["secondary"] = secondary_lines
         if world == 1 and not args.no_configs:

@@ -21,6 +21,10 @@ def test_error_paths_under_host_sanitizers():
     env = dict(os.environ)
     env.update(VIVIT_HIP_LIB=lib, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:abort_on_error=0:exitcode=66",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    # The sanitized process must never bring up a GPU, also on a box that has one: the library has no device code, and the
+    # runtimes under a sanitizer do not belong on the device.  An index that matches no GPU hides them all from ROCr
+    # (before it creates any agent) and from HIP, so the child sees what it sees on a CPU-only box.
+    env.update(ROCR_VISIBLE_DEVICES="-1", HIP_VISIBLE_DEVICES="-1")
     proc = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_abi_errors.py"), "-q", "-x",
                            "-p", "no:cacheprovider"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                           text=True, timeout=900)

@@ -67,3 +67,42 @@ def test_rank_watchdog_ends_the_survivors_when_one_rank_dies():
     # all ranks fine -> 0
     ok = [subprocess.Popen([sys.executable, "-c", "pass"], start_new_session=True) for _ in range(2)]
     assert bench._watch_ranks(ok, poll_s=0.1) == 0
+
+
+def test_dump_outputs_writes_what_the_step_returned(tmp_path):
+    """bench.dump_outputs (``--dump-outputs DIR``): eigenvalues whole, eigenvectors whole while they fit the size limit, else
+    the same seeded sample of columns on every call (the largest eigenvalues' included); each column's sign fixed."""
+    import os
+
+    import numpy as np
+
+    g = torch.Generator().manual_seed(0)
+    A = torch.randn(50, 50, generator=g, dtype=torch.float64)
+    w, Z = torch.linalg.eigh(A + A.T)
+    w, Z = w.float(), Z.float()
+    assert bench.dump_outputs(str(tmp_path / "small"), w, Z) == {
+        "eigenvalues.npy": [50], "eigenvectors.npy": [50, 50], "eigenvector_columns.npy": [50]}
+    d = {k: np.load(tmp_path / "small" / f"{k}.npy") for k in ("eigenvalues", "eigenvectors", "eigenvector_columns")}
+    assert d["eigenvalues"].dtype == d["eigenvectors"].dtype == np.float32 and d["eigenvector_columns"].dtype == np.float64
+    np.testing.assert_array_equal(d["eigenvalues"], w.numpy())
+    np.testing.assert_array_equal(d["eigenvector_columns"], np.arange(50))
+    np.testing.assert_array_equal(np.abs(d["eigenvectors"]), np.abs(Z.numpy()))
+    assert (d["eigenvectors"][np.abs(d["eigenvectors"]).argmax(0), np.arange(50)] > 0).all()
+    flipped = Z * torch.where(torch.arange(50) % 2 == 0, -1.0, 1.0)
+    bench.dump_outputs(str(tmp_path / "flipped"), w, flipped)
+    np.testing.assert_array_equal(np.load(tmp_path / "flipped" / "eigenvectors.npy"), d["eigenvectors"])
+
+    n = 4096                                    # Z alone is 67 MB: sampled
+    Z = torch.randn(n, n, generator=g)
+    w = torch.arange(n, dtype=torch.float32)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), w, Z)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_LIMIT_BYTES
+    for f in files:
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+    cols = np.load(tmp_path / "a" / "eigenvector_columns.npy").astype(np.int64)
+    assert len(cols) == bench.DUMP_COLUMNS == len(set(cols)) and set(range(n - bench.DUMP_TOP, n)) <= set(cols)
+    np.testing.assert_array_equal(np.abs(np.load(tmp_path / "a" / "eigenvectors.npy")), np.abs(Z.numpy()[:, cols]))
+
+    assert bench.dump_outputs(str(tmp_path / "values"), w, None) == {"eigenvalues.npy": [n]}

@@ -15,15 +15,21 @@ def close(a, b, rtol=1e-5, atol=1e-6):
 
 @pytest.mark.parametrize("case", CASES)
 def test_contractions(case):
+    """fp32 contractions: their rounding depends on the BLAS kernel the CPU selects, and its absolute size on the size of the
+    result, so the absolute floor scales with the reference's largest entry (as in test_api_golden.py:test_eig_utils)."""
     g = load_golden(case)
     V, G = golden_factors(g)
-    close(oracle.compute_gram_mat(V, 2), g["gram_flat"])
-    close(oracle.gram_sqrt_ggn(V), g["gram_hook"])
-    close(oracle.partial_contract(V[0], G[0], (2, 1)), g["V_t_g0"])
-    close(oracle.Vmp(V[0], torch.from_numpy(g["mat"]), 2), g["Vmp0"])
-    close(oracle.mVp(V[0], torch.from_numpy(g["pmat"]), 2), g["mVp0"])
-    close(oracle.gram_batch_grad([x.clone() for x in G], center=False), g["gram_batch_grad"])
-    close(oracle.gram_batch_grad([x.clone() for x in G], center=True), g["gram_batch_grad_centered"])
+
+    def check(have, key):
+        close(have, g[key], atol=1e-6 * max(1.0, float(np.abs(g[key]).max())))
+
+    check(oracle.compute_gram_mat(V, 2), "gram_flat")
+    check(oracle.gram_sqrt_ggn(V), "gram_hook")
+    check(oracle.partial_contract(V[0], G[0], (2, 1)), "V_t_g0")
+    check(oracle.Vmp(V[0], torch.from_numpy(g["mat"]), 2), "Vmp0")
+    check(oracle.mVp(V[0], torch.from_numpy(g["pmat"]), 2), "mVp0")
+    check(oracle.gram_batch_grad([x.clone() for x in G], center=False), "gram_batch_grad")
+    check(oracle.gram_batch_grad([x.clone() for x in G], center=True), "gram_batch_grad_centered")
 
 
 @pytest.mark.parametrize("case", CASES)

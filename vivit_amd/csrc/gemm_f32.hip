@@ -3199,7 +3199,9 @@ int vivit_gram_syrk_f32(const float *A, int64_t n, int64_t p, int64_t lda, float
                         float beta, void *workspace, size_t workspace_bytes, void *stream) {
   BxStrictScope strict;  // public product: both range bits reroute a chunk to the fp32 MFMA kernel
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool fix_diag = A && G && workspace && n > 0 && p >= SYRK_DIAG_MIN_K && workspace_bytes >= syrk_diag_bytes(n) + gemm_workspace_bytes(n, n, p, true);
+  // (the leading dimensions are checked here too: gemm_launch refuses lda < p / ldg < n, and nothing may be launched before it does)
+  const bool fix_diag = A && G && workspace && n > 0 && p >= SYRK_DIAG_MIN_K && lda >= p && ldg >= n &&
+                        workspace_bytes >= syrk_diag_bytes(n) + gemm_workspace_bytes(n, n, p, true);
   float *diag = nullptr;
   if (fix_diag) {
     diag = reinterpret_cast<float *>(align_up(reinterpret_cast<uintptr_t>(workspace), 256));
