@@ -102,8 +102,13 @@ const char *vivit_hip_status_string(int status);
  * of a flagged chunk returns at once and the fp32 MFMA kernel, always launched behind it on the same columns (and
  * returning at once for an unflagged chunk -- there is no host synchronisation), computes that chunk instead.  Every
  * entry point in this header thus has the semantics of a k-ordered fp32 fma chain for EVERY input: inf/NaN propagate
- * as in IEEE fp32, 3.4e38 * 0.5 is finite, denormal inputs are multiplied as fp32 denormals.  (Internal products of
- * the eigensolver honour bit 0 only.) */
+ * as in IEEE fp32, 3.4e38 * 0.5 is finite, denormal inputs are multiplied as fp32 denormals.  The 64-row streaming
+ * product (outputs of at most 64 rows, N and K >= 2048) gathers the same two bits over both whole operands while it
+ * splits them, always writes its split-K slab, and the fp32 MFMA kernel behind it on the same grid rewrites the slab
+ * when a bit is set; its bf16 form is used only while every lane's byte offset into B fits in 32 bits (K-contiguous
+ * B: ldb <= 4 210 751 floats; k-major B: ldb <= 71 582 771), wider operands take the fp32 kernel
+ * (tests/test_gemm_contract_gpu.py checks every route).  Internal products of the eigensolver on the 256-tile and
+ * split-K routes honour bit 0 only; the band reduction's internal 64-row product does not gate at all. */
 int vivit_gemm_split_mode(void);
 size_t vivit_gram_syrk_f32_workspace_bytes(int64_t n, int64_t p);
 int vivit_gram_syrk_f32(const float *A, int64_t n, int64_t p, int64_t lda, float *G, int64_t ldg,

@@ -1731,6 +1731,8 @@ constexpr int GEMM64_LDS_BYTES = G64_NST * G64_STG * 4;                        /
 template <int ALAY, int BLAY>
 __global__ __launch_bounds__(256, 1) void gemm64_dma_kernel(GemmArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem3[];
+  // stand-in for a public gemm64_bx_kernel launch (same grid and slab): runs only when that launch flagged an operand
+  if (p.gate && (*p.gate & p.gate_mask) == 0) return;
   const int tj = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 31, h = lane >> 5;
@@ -1750,7 +1752,7 @@ __global__ __launch_bounds__(256, 1) void gemm64_dma_kernel(GemmArgs p) {
   };
   clear_acc();
 
-  const bool partial = p.ksplit > 1;
+  const bool partial = p.ksplit > 1 || p.gate;
   gptr Cout = (gptr)(partial ? p.slab + (int64_t)blockIdx.y * p.M * p.N : p.C);
   const int64_t ldc = partial ? p.N : p.ldc;
   const float alpha = partial ? 1.f : p.alpha;
@@ -1889,8 +1891,28 @@ constexpr int G64X_CHAIN = 2048 / BK;
 // this lane's K index inside a K tile for element j of its MFMA fragment
 __device__ __forceinline__ int g64x_k(int h, int j) { return 8 * (j >> 2) + 4 * h + (j & 3); }
 
-template <int ALAY>
-__global__ __launch_bounds__(128) void g64_split_a_kernel(const float *__restrict__ A, int64_t lda, int64_t M, uint4 *__restrict__ out) {
+// Range gate of the PUBLIC 64-row product (STRICT instances; the band reduction's own product keeps the plain ones): the
+// two bits of bx_split_kernel, gathered per lane as the largest 2|a| bit pattern (bit 0: >= 2 x 0x7F7F8000, NaN above it)
+// and the smallest 2|a| - 1 (bit 1: below 2 x 0x0D800000 - 1, i.e. 0 < |a| < 2^-100; an exact zero wraps to the top) --
+// three VALU instructions per value, no compare per value -- and ORed into one flag per launch.  A flagged product is
+// recomputed by gemm64_dma_kernel (fp32 MFMA) behind the bf16-pipe launch; see gemm64_launch.
+struct G64Range {
+  unsigned mx = 0u, mn = 0xffffffffu;
+};
+__device__ __forceinline__ void g64_range_add(G64Range &g, float a) {
+  const unsigned u = __float_as_uint(a) << 1;
+  g.mx = max(g.mx, u);
+  g.mn = min(g.mn, u - 1u);
+}
+__device__ __forceinline__ void g64_range_flag(const G64Range &g, int *flag) {
+  const bool big = g.mx >= (0x7F7F8000u << 1), tiny = g.mn < (0x0D800000u << 1) - 1u;
+  const unsigned long long m0 = __builtin_amdgcn_ballot_w64(big), m1 = __builtin_amdgcn_ballot_w64(tiny);
+  if ((m0 | m1) != 0 && (threadIdx.x & 63) == 0) atomicOr(flag, (m0 ? BX_GATE_RANGE : 0) | (m1 ? BX_GATE_TINY : 0));  // rare
+}
+
+template <int ALAY, bool STRICT = false>
+__global__ __launch_bounds__(128) void g64_split_a_kernel(const float *__restrict__ A, int64_t lda, int64_t M, uint4 *__restrict__ out,
+                                                          int *__restrict__ flag) {
   const int64_t kt = blockIdx.x;
   const int i = threadIdx.x >> 6, l = threadIdx.x & 63, h = l >> 5;
   const int64_t row = 32 * i + (l & 31);
@@ -1899,6 +1921,12 @@ __global__ __launch_bounds__(128) void g64_split_a_kernel(const float *__restric
   for (int j = 0; j < 8; ++j) {
     const int64_t k = kt * BK + g64x_k(h, j);
     f[j] = row < M ? (ALAY == LAY_K ? A[row * lda + k] : A[k * lda + row]) : 0.f;
+  }
+  if constexpr (STRICT) {
+    G64Range g;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) g64_range_add(g, f[j]);
+    g64_range_flag(g, flag);
   }
   unsigned hh[4], mm[4], ll[4];
 #pragma unroll
@@ -1909,8 +1937,10 @@ __global__ __launch_bounds__(128) void g64_split_a_kernel(const float *__restric
   o[128] = make_uint4(ll[0], ll[1], ll[2], ll[3]);
 }
 
-template <int BLAY>
-__global__ __launch_bounds__(256, 1) void gemm64_bx_kernel(GemmArgs p, const uint4 *__restrict__ apieces) {
+// STRICT (public products): also gathers the range bits of every B value it splits (G64Range) into *flag, and always writes
+// the split-K slab (one slice when ksplit is 1), so that the gated fp32 kernel behind it can still replace the whole result.
+template <int BLAY, bool STRICT = false>
+__global__ __launch_bounds__(256, 1) void gemm64_bx_kernel(GemmArgs p, const uint4 *__restrict__ apieces, int *__restrict__ flag) {
   extern __shared__ __attribute__((aligned(16))) float smem3[];
   const int tj = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1998,8 +2028,17 @@ __global__ __launch_bounds__(256, 1) void gemm64_bx_kernel(GemmArgs p, const uin
       frag_half<BLAY, 256>(sb, wave * 64 + j * 32 + r, 1, h, *reinterpret_cast<float(*)[4]>(&raw[j][4]));
     }
   };
+  // (STRICT: every split_raw call sees real B values of this workgroup -- the one after its last tile reads the stage of tile
+  // nt - 7, and every split has more than 40 K tiles (gemm64_workspace_bytes) -- so no uninitialised LDS reaches the flag)
+  G64Range rng;
   auto split_raw = [&](int par) __attribute__((always_inline)) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    if constexpr (STRICT) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int u = 0; u < 8; ++u) g64_range_add(rng, raw[j][u]);
+    }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       unsigned hh[4], mm[4], ll[4];
@@ -2062,10 +2101,11 @@ __global__ __launch_bounds__(256, 1) void gemm64_bx_kernel(GemmArgs p, const uin
     for (int j = 0; j < 2; ++j)
       __asm__ volatile("" : "+v"(pb[par ^ 1][j].h), "+v"(pb[par ^ 1][j].m), "+v"(pb[par ^ 1][j].l));
     // the split's ~100 VALU instructions between the MFMAs: 4 MFMAs first (the LDS reads are on their way), then 5 : 1
+    // (STRICT: ~150 with the range bits, 7 : 1)
     __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
 #pragma unroll
     for (int u = 0; u < 20; ++u) {
-      __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);
+      __builtin_amdgcn_sched_group_barrier(0x002, STRICT ? 7 : 5, 0);
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -2091,7 +2131,8 @@ __global__ __launch_bounds__(256, 1) void gemm64_bx_kernel(GemmArgs p, const uin
         }
   }
 
-  const bool partial = p.ksplit > 1;
+  if constexpr (STRICT) g64_range_flag(rng, flag);
+  const bool partial = STRICT || p.ksplit > 1;
   gptr Cout = (gptr)(partial ? p.slab + (int64_t)blockIdx.y * p.M * p.N : p.C);
   const int64_t ldc = partial ? p.N : p.ldc;
   const float alpha = partial ? 1.f : p.alpha, beta = partial ? 0.f : p.beta;
@@ -2882,10 +2923,21 @@ static size_t gemm64_workspace_bytes(int64_t M, int64_t N, int64_t K, int *kspli
   const int ksplit = (int)cdiv(K, kchunk);
   if (ksplit_out) *ksplit_out = ksplit;
   if (kchunk_out) *kchunk_out = kchunk;
-  const size_t slab = ksplit > 1 ? (size_t)ksplit * (size_t)M * (size_t)N * sizeof(float) : 0;
+  // a public product on the bf16 pipe always goes through the slab (its gated fp32 stand-in may replace the partial sums)
+  const bool strict = gemm64_bx_enabled() && bx_public_product();
+  const size_t slab = (ksplit > 1 || strict) ? (size_t)ksplit * (size_t)M * (size_t)N * sizeof(float) : 0;
   if (slab_out) *slab_out = slab;
-  // + the bf16 pieces of the 64-row operand (gemm64_bx_kernel): 6 KB per K tile, after the slab
-  return gemm64_bx_enabled() ? align_up(slab, 256) + (size_t)ktiles * 6144 : slab;
+  if (!gemm64_bx_enabled()) return slab;
+  // + the bf16 pieces of the 64-row operand (gemm64_bx_kernel): 6 KB per K tile, after the slab; + the range flag
+  const size_t pieces_end = align_up(slab, 256) + (size_t)ktiles * 6144;
+  return strict ? align_up(pieces_end, 256) + 256 : pieces_end;
+}
+
+// gemm64_bx_kernel addresses B as a scalar base + a 32-bit byte offset per lane: up to 255 rows of ldb floats (K-contiguous B)
+// or 15 k rows (k-major B), + 1 KB inside a row.  Wider leading dimensions would wrap it (silently: the request reads another row
+// of the same operand), so they take gemm64_dma_kernel, whose lane addresses are 64-bit.
+static bool gemm64_bx_reach(int blay, int64_t ldb) {
+  return (int64_t)(blay == LAY_K ? 255 : 15) * ldb * 4 + 1024 < ((int64_t)1 << 32);
 }
 
 static int gemm64_launch(int alay, int blay, GemmArgs p, void *workspace, size_t workspace_bytes, hipStream_t stream) {
@@ -2901,52 +2953,77 @@ static int gemm64_launch(int alay, int blay, GemmArgs p, void *workspace, size_t
       for (int f = 0; f < 4; ++f)
         if (!ensure_dynamic_lds(fns[f], GEMM64_LDS_BYTES, attr_done)) return VIVIT_E_LAUNCH;
       if (!ensure_dynamic_lds(reinterpret_cast<const void *>(gemm64_bx_kernel<LAY_K>), GEMM64X_LDS_BYTES, attr_done) ||
-          !ensure_dynamic_lds(reinterpret_cast<const void *>(gemm64_bx_kernel<LAY_M>), GEMM64X_LDS_BYTES, attr_done))
+          !ensure_dynamic_lds(reinterpret_cast<const void *>(gemm64_bx_kernel<LAY_M>), GEMM64X_LDS_BYTES, attr_done) ||
+          !ensure_dynamic_lds(reinterpret_cast<const void *>(gemm64_bx_kernel<LAY_K, true>), GEMM64X_LDS_BYTES, attr_done) ||
+          !ensure_dynamic_lds(reinterpret_cast<const void *>(gemm64_bx_kernel<LAY_M, true>), GEMM64X_LDS_BYTES, attr_done))
         return VIVIT_E_LAUNCH;
       attr_done |= 1ull << (dev & 63);
     }
   }
   size_t slab_bytes = 0;
   const size_t need = gemm64_workspace_bytes(p.M, p.N, p.K, &p.ksplit, &p.kchunk, &slab_bytes);
+  // Which kernel runs depends on SHAPE (leading dimensions included) and ENVIRONMENT only (results are bit-identical from call
+  // to call, include/vivit_hip.h): a workspace smaller than the query's answer is refused -- it is never a silent switch to the
+  // fp32 kernel, whose summation order (and speed) differs.
+  const bool bx = gemm64_bx_enabled() && gemm64_bx_reach(blay, p.ldb);
+  // Public products on the bf16 pipe (INPUT RANGE CONTRACT): both split kernels OR the range bits of their operand into a flag,
+  // the bf16-pipe product writes the slab, gemm64_dma_kernel on the same grid returns at once unless the flag is set and
+  // otherwise rewrites the whole slab in fp32, and the reduce applies alpha and beta once.  No host synchronisation.
+  const bool strict = bx && bx_public_product();
   p.slab = nullptr;
-  if (p.ksplit > 1) {
+  if (p.ksplit > 1 || strict) {
     if (!workspace || workspace_bytes < slab_bytes) return VIVIT_E_WORKSPACE;
     p.slab = static_cast<float *>(workspace);
   }
-  // The bf16-pipe form needs room for the pieces of A behind the slab.  Which kernel runs depends on SHAPE and ENVIRONMENT
-  // only (results are bit-identical from call to call, include/vivit_hip.h): a workspace smaller than the query's answer is
-  // refused -- it is never a silent switch to the fp32 kernel, whose summation order (and speed) differs.
   uint4 *apieces = nullptr;
-  if (gemm64_bx_enabled()) {
+  int *flag = nullptr;
+  if (bx) {   // the pieces of A behind the slab, the range flag behind them
     if (!workspace || workspace_bytes < need) return VIVIT_E_WORKSPACE;
-    apieces = reinterpret_cast<uint4 *>(static_cast<char *>(workspace) + align_up(slab_bytes, 256));
+    const size_t off = align_up(slab_bytes, 256);
+    apieces = reinterpret_cast<uint4 *>(static_cast<char *>(workspace) + off);
+    if (strict) {
+      flag = reinterpret_cast<int *>(static_cast<char *>(workspace) + align_up(off + (size_t)(p.K / BK) * 6144, 256));
+      if (hipMemsetAsync(flag, 0, sizeof(int), stream) != hipSuccess) return VIVIT_E_LAUNCH;
+    }
   }
   p.tiles_m = 1;
   p.tiles_n = (int)cdiv(p.N, 256);
   p.syrk = 0;
   p.desc = nullptr;
   dim3 grid((unsigned)p.tiles_n, (unsigned)p.ksplit, 1);
-  if (apieces) {   // products on the bf16 pipe: split the 64-row operand once, then stream
-    if (alay == LAY_K)
-      g64_split_a_kernel<LAY_K><<<(unsigned)(p.K / BK), 128, 0, stream>>>(p.A, p.lda, p.M, apieces);
+  auto launch_dma = [&](const GemmArgs &q) {
+    if (alay == LAY_K && blay == LAY_K)
+      gemm64_dma_kernel<LAY_K, LAY_K><<<grid, 256, GEMM64_LDS_BYTES, stream>>>(q);
+    else if (alay == LAY_K && blay == LAY_M)
+      gemm64_dma_kernel<LAY_K, LAY_M><<<grid, 256, GEMM64_LDS_BYTES, stream>>>(q);
+    else if (alay == LAY_M && blay == LAY_K)
+      gemm64_dma_kernel<LAY_M, LAY_K><<<grid, 256, GEMM64_LDS_BYTES, stream>>>(q);
     else
-      g64_split_a_kernel<LAY_M><<<(unsigned)(p.K / BK), 128, 0, stream>>>(p.A, p.lda, p.M, apieces);
-    if (blay == LAY_K)
-      gemm64_bx_kernel<LAY_K><<<grid, 256, GEMM64X_LDS_BYTES, stream>>>(p, apieces);
-    else
-      gemm64_bx_kernel<LAY_M><<<grid, 256, GEMM64X_LDS_BYTES, stream>>>(p, apieces);
+      gemm64_dma_kernel<LAY_M, LAY_M><<<grid, 256, GEMM64_LDS_BYTES, stream>>>(q);
+  };
+  const unsigned kt = (unsigned)(p.K / BK);
+  if (strict) {
+    if (alay == LAY_K) g64_split_a_kernel<LAY_K, true><<<kt, 128, 0, stream>>>(p.A, p.lda, p.M, apieces, flag);
+    else g64_split_a_kernel<LAY_M, true><<<kt, 128, 0, stream>>>(p.A, p.lda, p.M, apieces, flag);
+    if (blay == LAY_K) gemm64_bx_kernel<LAY_K, true><<<grid, 256, GEMM64X_LDS_BYTES, stream>>>(p, apieces, flag);
+    else gemm64_bx_kernel<LAY_M, true><<<grid, 256, GEMM64X_LDS_BYTES, stream>>>(p, apieces, flag);
+    int st = launch_status();
+    if (st != VIVIT_OK) return st;
+    GemmArgs f = p;
+    f.gate = flag;
+    f.gate_mask = tls_bx_gate_mask;
+    launch_dma(f);
+  } else if (bx) {   // products on the bf16 pipe: split the 64-row operand once, then stream
+    if (alay == LAY_K) g64_split_a_kernel<LAY_K><<<kt, 128, 0, stream>>>(p.A, p.lda, p.M, apieces, nullptr);
+    else g64_split_a_kernel<LAY_M><<<kt, 128, 0, stream>>>(p.A, p.lda, p.M, apieces, nullptr);
+    if (blay == LAY_K) gemm64_bx_kernel<LAY_K><<<grid, 256, GEMM64X_LDS_BYTES, stream>>>(p, apieces, nullptr);
+    else gemm64_bx_kernel<LAY_M><<<grid, 256, GEMM64X_LDS_BYTES, stream>>>(p, apieces, nullptr);
+  } else {
+    launch_dma(p);
   }
-  else if (alay == LAY_K && blay == LAY_K)
-    gemm64_dma_kernel<LAY_K, LAY_K><<<grid, 256, GEMM64_LDS_BYTES, stream>>>(p);
-  else if (alay == LAY_K && blay == LAY_M)
-    gemm64_dma_kernel<LAY_K, LAY_M><<<grid, 256, GEMM64_LDS_BYTES, stream>>>(p);
-  else if (alay == LAY_M && blay == LAY_K)
-    gemm64_dma_kernel<LAY_M, LAY_K><<<grid, 256, GEMM64_LDS_BYTES, stream>>>(p);
-  else
-    gemm64_dma_kernel<LAY_M, LAY_M><<<grid, 256, GEMM64_LDS_BYTES, stream>>>(p);
   int st = launch_status();
   if (st != VIVIT_OK) return st;
-  if (p.ksplit > 1) {
+  if (p.slab) {
     gemm_reduce_kernel<<<(unsigned)cdiv(p.M * p.N, 256), 256, 0, stream>>>(p.slab, p.C, p.M, p.N, p.ldc, p.ksplit, p.alpha,
                                                                            p.beta, 0);
     st = launch_status();
