@@ -18,6 +18,10 @@ back-transformations (independent per eigenvector) are sharded and the eigenvect
 That is strong scaling; `phases` reports the exchange / Gram / all-reduce / symeig split so the Gram-build
 scaling can be read off directly.
 
+A plain run does only what the headline needs: set up, warm up, time the steps, write `--dump-outputs`, print the line.
+`--full` adds the extras (see `extras`): the ranks' bitwise self-check, the parity check of the timed shape, the secondary
+lines, the other BASELINE configurations and the CPU baseline.
+
 Prints ONE JSON line on rank 0 (contract: see DESIGN.md section "Measurement").
 """
 import argparse
@@ -646,30 +650,53 @@ def _stage_rooflines(stage_ms, n, steps, vectors, row_frac=1.0, split=0):
     return out
 
 
-def main():
+def extras(args, world):
+    """What this run does besides its warm-up and timed steps, ``--dump-outputs`` and the line itself: nothing without
+    ``--full``; with it every extra that applies to ``world`` ranks and that no ``--no-*`` flag switches off.
+      rank_check    the ranks' eigenvalues and eigenvector checksum bit-identical after the warm-up (several ranks)
+      verify        parity of the timed shape: rebuilt Gram matrix and its eigendecomposition vs fp64 (``verified``)
+      secondary     values only, top-10, factorised Gram, public API on the same matrix (``secondary``, one rank)
+      configs       BASELINE configs 1, 3, 4, 5 through the public API (``configs``, one rank)
+      cpu_baseline  the oracle on the host's cores, extrapolated to the full size (``cpu_baseline``, one rank)"""
+    if not args.full:
+        return set()
+    wanted = {"rank_check": world > 1 and args.warmup > 0, "verify": not args.no_verify,
+              "secondary": world == 1 and not args.no_secondary, "configs": world == 1 and not args.no_configs,
+              "cpu_baseline": world == 1 and not args.no_cpu_baseline}
+    return {k for k, on in wanted.items() if on}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="mlp784-512-10_b4096", choices=sorted(WORKLOADS))
     ap.add_argument("--values-only", action="store_true", help="EigvalshComputation flavour (no eigenvectors)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the parity check after the timed loop")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the values-only / top-10 secondary lines")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extras: ranks' self-check, parity check, secondary lines, other configurations, CPU "
+                         "baseline (see extras; a plain run only times the headline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the parity check after the timed loop")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the values-only / top-10 secondary lines")
     ap.add_argument("--cpu-batches", default="128,256,512", help="batch sizes of the CPU baseline's einsum-Gram sample")
     ap.add_argument("--cpu-eig-batches", default="512,1024,1600", help="batch sizes of the CPU baseline's eigh sample (n = 10 x batch; 2048 = "
                     "half the full size costs 62 s for its one eigh and put the driver's run at 381 s; 1600: 31 s)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configurations (configs block)")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the other BASELINE configurations (configs block)")
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"],
                     help="torch.distributed backend of a multi-rank run (default nccl = RCCL over xGMI; gloo: functional "
                          "runs, several ranks may share one card)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the last step's eigenvalues and (a seeded sample of) its eigenvectors as .npy "
                          "files in DIR (see dump_outputs)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(_spawn_ranks(args.gpus))
     rank = int(os.environ.get("RANK", "0"))
@@ -677,6 +704,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    todo = extras(args, world)
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (HIP device); there is no CPU fallback")
     # (functional testing on a 1-GPU box: VIVIT_DIST_BACKEND=gloo lets several ranks share device 0)
@@ -773,7 +801,7 @@ def main():
         w, Z = step(i)
         if rank == 0:
             _progress(f"warm-up step {i + 1} issued")
-    if dist is not None and args.warmup > 0:
+    if "rank_check" in todo:
         # self-check before timing: the replicated stages (band reduction, bulge chase, tridiagonal solve) run on every rank
         # and nothing is broadcast -- the eigenvalues (and the gathered eigenvectors) must be BIT-identical on all ranks
         gathered = [torch.empty_like(w) for _ in range(world)]
@@ -830,7 +858,7 @@ def main():
         dumped = dump_outputs(args.dump_outputs, w, Z)
         _progress(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
     verified = None
-    if not args.no_verify:
+    if "verify" in todo:
         # parity of THIS shape (not timed): rebuild G, sampled fp64 entries / symmetry / trace, then the
         # eigendecomposition's properties on that matrix
         del w, Z
@@ -859,7 +887,7 @@ def main():
         del Gv, wv, Zv
 
     secondary_lines = None
-    if world == 1 and not args.no_secondary:
+    if "secondary" in todo:
         # secondary lines: the same Gram matrix, (i) values only (EigvalshComputation flavour),
         # (ii) criterion = top-10 (reduction + all eigenvalues, host callback, 10 eigenvectors)
         def timed(fn):
@@ -1049,6 +1077,7 @@ def main():
                 {"band_reduction": "replicated" if world > 1 else "single GPU", "collectives_per_solve": {"all_gather": 1} if (world > 1 and vectors) else {}})),
             "steps": args.steps,
             "warmup": args.warmup,
+            "extras": sorted(todo),
             "ms_per_step": elapsed / args.steps * 1e3,
             "ms_per_step_spread": step_spread,
             "higher_is_better": True,
@@ -1080,7 +1109,7 @@ def main():
             out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         if secondary_lines is not None:
             out["secondary"] = secondary_lines
-        if world == 1 and not args.no_configs:
+        if "configs" in todo:
             # BASELINE configs 1, 3, 4, 5 (one GPU) through the public API on real factors (bench_configs.py)
             import bench_configs
 
@@ -1088,7 +1117,7 @@ def main():
             G = w = Z = None
             torch.cuda.empty_cache()
             out["configs"] = bench_configs.run_configs(device, progress=_progress)
-        if world == 1 and not args.no_cpu_baseline:
+        if "cpu_baseline" in todo:
             out["cpu_baseline"] = cpu_baseline(dims, C, n, P_total,
                                                batches=tuple(sorted({min(int(b), batch) for b in args.cpu_batches.split(",")})),
                                                eig_batches=tuple(sorted({min(int(b), batch) for b in args.cpu_eig_batches.split(",")})))

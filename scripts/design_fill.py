@@ -1,5 +1,5 @@
 """DESIGN.md = scripts/design_template.md with the numbers of one bench.py JSON line filled in (phase table, measured block,
-config table).   usage: python scripts/design_fill.py profiles/r06_bench_n40960_s16.json"""
+config table; the line of a `--full` run).   usage: python scripts/design_fill.py profiles/r06_bench_n40960_s16.json"""
 import json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 bench = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -27,7 +27,7 @@ t = t.replace("{{STEP_S}}", f"{bench['ms_per_step'] / 1e3:.3f}").replace("{{GRAM
 t = t.replace("{{BENCH_FILE}}", os.path.basename(sys.argv[1])).replace("{{VALUE}}", f"{bench['value']:.0f}").replace("{{BOX}}", "one MI355X, 20 steps after 5 warm-up steps")
 rf, cb, v = bench["roofline"], bench["cpu_baseline"], bench["verified"]
 sp = bench["ms_per_step_spread"]
-blk = (f"Last run with the driver's flags (`python bench.py --steps 20 --warmup 5`, `profiles/{os.path.basename(sys.argv[1])}`): **{bench['value']:.0f} eigenpairs/s** "
+blk = (f"Last run with the driver's flags and every extra (`python bench.py --steps 20 --warmup 5 --full`, `profiles/{os.path.basename(sys.argv[1])}`): **{bench['value']:.0f} eigenpairs/s** "
        f"({bench['ms_per_step']:.1f} ms per step; per-step min / median / max {sp['min']:.1f} / {sp['median']:.1f} / {sp['max']:.1f} ms); `roofline`: {rf['achieved']:.1f} TF of "
        f"fp32 work = **{rf['frac']:.3f}** of the bf16 / 6 ceiling (= {rf['vs_fp32_mfma_peak']:.2f} x the fp32 MFMA peak), traffic {rf['traffic'] / 1e12:.2f} TB per SYRK against "
        f"0.069 TB algorithmic (tile re-reads through L2 / MALL: not the limiter), clock under load {{CLOCK_TXT}}; `cpu_baseline` (oracle, {cb['cores']} threads of an "

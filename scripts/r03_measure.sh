@@ -7,7 +7,7 @@ O=$R/gpurun_out/r03
 mkdir -p $O
 python scripts/probe/bx_clock.py real  2>&1 | grep -v amdgpu.ids | tee $O/bx_clock_real.txt
 python scripts/probe/bx_clock.py randn 2>&1 | grep -v amdgpu.ids | tee $O/bx_clock_randn.txt
-python bench.py --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+python bench.py --steps 3 --warmup 1 --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 tail -c 600 $O/bench.json; echo
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $O/ktrace -o kt --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-verify --no-secondary --no-configs > $O/ktrace.log 2>&1 || { tail -5 $O/ktrace.log; exit 1; }

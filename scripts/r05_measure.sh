@@ -8,7 +8,7 @@ R=$PWD
 O=$R/gpurun_out/r05
 mkdir -p $O
 if [ "$1" != "nobench" ]; then
-  python bench.py --steps 3 --warmup 1 > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  python bench.py --steps 3 --warmup 1 --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   tail -c 400 $O/bench.json; echo
 fi
 cd /tmp

@@ -9,7 +9,7 @@ R=$PWD
 O=$R/gpurun_out/r06m
 mkdir -p $O
 if [ "$1" != "nobench" ]; then
-  python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   tail -c 300 $O/bench.json; echo
 fi
 cd /tmp

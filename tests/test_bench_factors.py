@@ -106,3 +106,18 @@ def test_dump_outputs_writes_what_the_step_returned(tmp_path):
     np.testing.assert_array_equal(np.abs(np.load(tmp_path / "a" / "eigenvectors.npy")), np.abs(Z.numpy()[:, cols]))
 
     assert bench.dump_outputs(str(tmp_path / "values"), w, None) == {"eigenvalues.npy": [n]}
+
+
+def test_plain_run_has_no_extras():
+    """A plain ``bench.py`` run only times the headline; ``--full`` adds every extra its world size allows, and the ``--no-*``
+    flags drop single ones again."""
+    all_one_rank = {"verify", "secondary", "configs", "cpu_baseline"}
+    assert bench.extras(bench.parse_args([]), 1) == set()
+    assert bench.extras(bench.parse_args(["--no-verify", "--no-configs"]), 1) == set()
+    assert bench.extras(bench.parse_args(["--gpus", "2"]), 2) == set()
+    assert bench.extras(bench.parse_args(["--full"]), 1) == all_one_rank
+    assert bench.extras(bench.parse_args(["--full", "--no-verify", "--no-cpu-baseline"]), 1) == {"secondary", "configs"}
+    assert bench.extras(bench.parse_args(["--full", "--gpus", "2"]), 2) == {"rank_check", "verify"}
+    assert bench.extras(bench.parse_args(["--full", "--gpus", "2", "--warmup", "0"]), 2) == {"verify"}
+    args = bench.parse_args(["--steps", "3", "--warmup", "2", "--dump-outputs", "out"])
+    assert (args.full, args.steps, args.warmup, args.dump_outputs) == (False, 3, 2, "out")
