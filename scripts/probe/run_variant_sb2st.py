@@ -1,6 +1,6 @@
-"""Bulge chasing alone at n = 40960 (random band) against a (possibly experimental) build of the library:
-python run_variant_sb2st.py <path/to/libvivit_hip.so>.  Variants built with -DSB2ST_VARIANT=1 (no compute) or
-=2 (no block loads/stores) give invalid results; they attribute the 11.5 us wavefront step."""
+"""Bulge chasing alone at n = 40960 (random band) against a build of the library:
+python run_variant_sb2st.py <path/to/libvivit_hip.so> [n].  (The timing-only builds without compute / without the block
+loads and stores that attributed the 11.5 us wavefront step were removed from sb2st.hip; their results are in profiles/HISTORY.md.)"""
 import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import vivit_amd._lib as L

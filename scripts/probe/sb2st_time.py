@@ -1,5 +1,6 @@
-"""Wall time of the bulge chase alone at n (default 40960) with the library of VIVIT_LIB (timing-only variants of the persistent
-kernel: -DSB2ST_PVAR=1 no arithmetic, =2 no waiting)."""
+"""Wall time of the bulge chase alone at n (default 40960) with the library of VIVIT_LIB (default: the product library).  (The
+timing-only builds of the persistent kernel without arithmetic / without waiting were removed from sb2st.hip; their results are
+in profiles/HISTORY.md.)"""
 import os, sys, time, ctypes
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import torch

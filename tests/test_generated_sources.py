@@ -87,26 +87,3 @@ def test_product_block_keeps_the_arithmetic_contract():
             for q in range(4):
                 assert G.acc(2 * i + (q >> 1), 2 * j + (q & 1)) == f"a[{16 * (4 * i + j) + 4 * q}:{16 * (4 * i + j) + 4 * q + 3}]"
 
-
-def test_32x32x16_block_keeps_the_arithmetic_contract():
-    """-DBX_SHAPE16=0 form: per K tile every accumulator tile receives exactly the six partial products of mfma_row<6>, in that order
-    (lo hi, hi lo, mid mid, mid hi, hi mid, hi hi); 96 MFMAs per tile; never more than two fragment reads between two MFMAs."""
-    _, lines, G = gen.block_text("BX_KLOOP_ASM32")
-    body, tiles = _tiles(lines, f"v_add_u32 {G.v_aa},", 3)
-    a_piece = {G.va(s_, pc): pc for s_ in (0, 1) for pc in range(3)}
-    b_piece = {G.vb(j, pc): (j, pc) for j in range(G.nj) for pc in range(3)}
-    for tile in tiles:
-        mfma = [l for l in tile if l.startswith("v_mfma_f32_32x32x16_bf16")]
-        assert len(mfma) == 96
-        per_acc = {}
-        for l in mfma:
-            acc, a, b, c = [x.strip() for x in l.split(" ", 1)[1].split(", ")]
-            assert acc == c
-            j, pb = b_piece[b]
-            per_acc.setdefault(acc, []).append((a_piece[a], pb))
-        assert len(per_acc) == 16 and all(v == gen.PRODUCTS for v in per_acc.values())
-        _common_tile_checks(tile, 2)
-    for i, l in enumerate(body):
-        if l.startswith("global_load_lds_dwordx4"):
-            assert body[i - 1] == "s_nop 0" and body[i - 2].startswith("s_add_u32 m0,")
-            assert re.fullmatch(r"global_load_lds_dwordx4 v\d+, s\[\d+:\d+\]", l)

@@ -47,7 +47,7 @@ def _digest(paths, extra=()):
 
 
 def _headers():
-    # (csrc/bx_kloop_asm.inc: the generated asm K loop; the experiment blocks of bx_kloop_asm_variants.inc are not part of the product)
+    # (csrc/bx_kloop_asm.inc: the generated asm K loop)
     return (sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(CSRC, "bx_kloop_asm.inc")]
             + [os.path.join(HERE, "..", "include", "vivit_hip.h")])
 

@@ -843,14 +843,8 @@ typedef const unsigned short __attribute__((address_space(1))) *gcptr16;
 constexpr int BX_PIECE = 8 * 1024;               // bytes of one piece of one operand tile (256 rows x 16 k bf16)
 constexpr int BX_OPER = 3 * BX_PIECE;            // 24 KB
 constexpr int BX_STAGE = 2 * BX_OPER;            // A and B: 48 KB
-#if defined(BX_EXP) && BX_EXP == 3   // timing only: 144 KB of LDS as in round 2 (the flush patch then aliases the stages: wrong results)
+// three stages = 144 KB: one workgroup per CU (two would need 288 KB; a CU has 160 KB)
 constexpr int GEMM256BX_LDS_BYTES = 3 * BX_STAGE;
-#define BX_PATCH_OFFSET (2 * BX_STAGE)
-#else
-#define BX_PATCH_OFFSET (3 * BX_STAGE)
-constexpr int GEMM256BX_LDS_BYTES = 3 * BX_STAGE + 4 * 4096;
-#endif
-// (three stages of 48 KB + a 32 x 32 flush patch per wave = 160 KB)
 
 __device__ __forceinline__ void bx_split2(float a, float b, unsigned &hi, unsigned &mid, unsigned &lo) {
   const bf16x2 h = {(__bf16)a, (__bf16)b};
@@ -995,41 +989,7 @@ __device__ unsigned long long *g_bx_stamp = nullptr;
 __device__ unsigned int g_bx_stamp_cap = 0;
 #endif
 
-#ifndef BX_S16_TRANSPOSED
-#define BX_S16_TRANSPOSED 0   // 1: B fragment first (a lane holds four consecutive columns of a row; needs the asm block BX_KLOOP_ASM_F9)
-#endif
-#ifndef BX_FLUSH_ROWS
-#define BX_FLUSH_ROWS 1   // rows of 32 x 32 blocks whose old values are in flight together in the register flush (2: the same time; 4: spills, + 4 %)
-#endif
-#ifndef BX_SWZ_MASK
-#define BX_SWZ_MASK 7   // rows of the flush patch are rotated by (row & mask) float4 units (experiments: 3)
-#endif
-#ifndef BX_SHAPE16
-#define BX_SHAPE16 1   // 0: the six-product kernel on v_mfma_f32_32x32x16_bf16 as in rounds 2-5 (same-box comparisons)
-#endif
 #include "bx_kloop_asm.inc"
-// (both forms are parsed in every build: the text of a discarded `if constexpr` branch is still checked against its operand list)
-#define BX_KLOOP_TEXT16 BX_KLOOP_ASM_TEXT
-#define BX_KLOOP_CLOB16 BX_KLOOP_ASM_CLOBBERS
-#define BX_KLOOP_TEXT32 BX_KLOOP_ASM32_TEXT
-#define BX_KLOOP_CLOB32 BX_KLOOP_ASM32_CLOBBERS
-#define BX_KLOOP_UNROLL 3
-static_assert(BX_KLOOP_ASM_UNROLL == BX_KLOOP_UNROLL && BX_KLOOP_ASM32_UNROLL == BX_KLOOP_UNROLL, "tiles per trip of the asm blocks");
-#if defined(BX_KLOOP_TEXT_OVERRIDE)     // attribution / experiment builds: a block of bx_kloop_asm_variants.inc by name, of the
-#include "bx_kloop_asm_variants.inc"    // form BX_SHAPE16 selects (python scripts/gen_bx_kloop.py --variants; not part of the product)
-static_assert(BX_KLOOP_UNROLL_OVERRIDE == BX_KLOOP_UNROLL, "tiles per trip of the asm blocks");
-#if BX_SHAPE16
-#undef BX_KLOOP_TEXT16
-#undef BX_KLOOP_CLOB16
-#define BX_KLOOP_TEXT16 BX_KLOOP_TEXT_OVERRIDE
-#define BX_KLOOP_CLOB16 BX_KLOOP_CLOB_OVERRIDE
-#else
-#undef BX_KLOOP_TEXT32
-#undef BX_KLOOP_CLOB32
-#define BX_KLOOP_TEXT32 BX_KLOOP_TEXT_OVERRIDE
-#define BX_KLOOP_CLOB32 BX_KLOOP_CLOB_OVERRIDE
-#endif
-#endif
 
 // ASM (default since round 6): the steady part of the K loop runs as ONE hand-scheduled inline-asm block (bx_kloop_asm.inc,
 // generated by scripts/gen_bx_kloop.py: fixed register map, every memory instruction placed between the MFMAs by hand);
@@ -1043,8 +1003,8 @@ static_assert(BX_KLOOP_UNROLL_OVERRIDE == BX_KLOOP_UNROLL, "tiles per trip of th
 // either way; in-kernel stamps, profiles/r06_bx16_timeline*.log: 3440-3470 against 3250-3280, 40 fragment reads instead of 27)
 // -- and runs faster, because the kernel is power-limited and the chip holds a higher clock on this shape (2.0-2.1 against 1.8 GHz
 // on half-zero data, 1.8 against 1.7 on N(0,1); MI355X_MICROARCH.md, DVFS give-back item 7): the headline-shaped SYRK takes
-// 875 / 780 ms (N(0,1) / half zeros) against 921 / 819 ms on the same box (profiles/r06_syrk_ab_s16.log).  -DBX_SHAPE16=0 builds
-// the 32 x 32 x 16 form (its own asm block, BX_KLOOP_ASM32) for such comparisons.
+// 875 / 780 ms (N(0,1) / half zeros) against 921 / 819 ms on the same box (profiles/r06_syrk_ab_s16.log; the 32 x 32 x 16 form
+// with its own asm block was a build option until it was removed after these measurements).
 //
 // What the blocks do differently from the compiler's schedule, in core cycles per K tile (32 x 32 x 16 form, where they were
 // measured one by one; profiles/r06_bx_attribution*.log; the C++ loop: 3525):
@@ -1063,13 +1023,11 @@ static_assert(BX_KLOOP_UNROLL_OVERRIDE == BX_KLOOP_UNROLL, "tiles per trip of th
 template <int NPROD, bool ASM = false>
 __global__ __launch_bounds__(256, 1) void gemm256_bx_kernel(GemmBxArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_bx[];
-  constexpr bool S16 = NPROD == 6 && BX_SHAPE16 != 0;   // the MFMA shape (accumulator layout below)
+  constexpr bool S16 = NPROD == 6;   // the MFMA shape (accumulator layout below)
 #if defined(BX_STAMP) && BX_STAMP == 2   // timeline build (scripts/probe/bx_timeline.py): 8 words per workgroup
   const unsigned long long stamp_entry = __builtin_amdgcn_s_memrealtime();
 #endif
-#if !(defined(BX_EXP) && BX_EXP == 2)   // (experiment 2: timing without the gate check)
   if (p.gate && (*p.gate & p.gate_mask) != 0) return;  // the fp32 MFMA kernel takes this chunk
-#endif
   int ti, tj, zsplit;
   {
     const int nt_all = (int)(p.K / BK);
@@ -1099,19 +1057,16 @@ __global__ __launch_bounds__(256, 1) void gemm256_bx_kernel(GemmBxArgs p) {
   const int r = lane & 31, h = lane >> 5;
   // Accumulator layout.  The six-product kernel computes on v_mfma_f32_16x16x32_bf16 (S16): the 32 x 32 block acc[i][j] is four
   // 16 x 16 tiles (tr, tc) in registers 4 (2 tr + tc) .. + 3, lane l holding rows 4 (l / 16) .. + 3 of column l % 16 of each.
-  // (S16T, -DBX_S16_TRANSPOSED=1: with the B fragment as the instruction's first operand a lane holds row l % 16 and the four
-  // CONSECUTIVE columns 4 (l / 16) .. + 3 instead -- bit-identical sums, one 16-byte access per tile in the flush and a mirrored
-  // store that is coalesced as it stands; measured SLOWER on the same box, profiles/r06_syrk_ab_transposed.log: headline-shaped
-  // SYRK 875 / 783 against 866 / 772 ms, rank-1024 update of 20480^2 4.18 against 3.94 ms.)
+  // (With the B fragment as the instruction's first operand a lane would hold row l % 16 and the four CONSECUTIVE columns
+  // 4 (l / 16) .. + 3 instead -- bit-identical sums, one 16-byte access per tile in the flush and a mirrored store that is
+  // coalesced as it stands; measured SLOWER on the same box, profiles/r06_syrk_ab_transposed.log: headline-shaped SYRK 875 / 783
+  // against 866 / 772 ms, rank-1024 update of 20480^2 4.18 against 3.94 ms.)
   // The other kernels on v_mfma_f32_32x32x16_bf16 (register e = rows (e & 3) + 8 (e >> 2) + 4 (l / 32) of column l % 32).
   const int r16 = lane & 15, kb = lane >> 4;
   // element e of a block: (row, column) = (lrow + erc(e), lcol + ecc(e)), a lane part and a part that is a constant per register
-  constexpr bool S16T = S16 && BX_S16_TRANSPOSED != 0;
-  const int lrow = S16T ? r16 : S16 ? 4 * kb : 4 * h, lcol = S16T ? 4 * kb : S16 ? r16 : r;
-  auto erc = [](int e) __attribute__((always_inline)) -> int {
-    return S16T ? 16 * (e >> 3) : S16 ? 16 * (e >> 3) + (e & 3) : (e & 3) + 8 * (e >> 2);
-  };
-  auto ecc = [](int e) __attribute__((always_inline)) -> int { return S16T ? 16 * ((e >> 2) & 1) + (e & 3) : S16 ? 16 * ((e >> 2) & 1) : 0; };
+  const int lrow = S16 ? 4 * kb : 4 * h, lcol = S16 ? r16 : r;
+  auto erc = [](int e) __attribute__((always_inline)) -> int { return S16 ? 16 * (e >> 3) + (e & 3) : (e & 3) + 8 * (e >> 2); };
+  auto ecc = [](int e) __attribute__((always_inline)) -> int { return S16 ? 16 * ((e >> 2) & 1) : 0; };
   auto erow = [&](int e) __attribute__((always_inline)) -> int { return lrow + erc(e); };
   auto ecol = [&](int e) __attribute__((always_inline)) -> int { return lcol + ecc(e); };
   const int64_t row0 = (int64_t)ti * B2, col0 = (int64_t)tj * B2;
@@ -1147,93 +1102,53 @@ __global__ __launch_bounds__(256, 1) void gemm256_bx_kernel(GemmBxArgs p) {
   auto ld_l2 = [](gptr q) __attribute__((always_inline)) -> float {
     return __hip_atomic_load((const float *)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
-  typedef f32x4 __attribute__((address_space(1))) *gptr4w;
-  const bool c_vec = (reinterpret_cast<uintptr_t>(Cout) & 15) == 0 && (ldc & 3) == 0 && (col0 & 3) == 0;
   auto flush_to_c = [&](bool first) __attribute__((always_inline)) {
     const float beta = first ? beta_ : 1.f;
     int opaque = 0;
     __asm__ volatile("" : "+v"(opaque));  // keeps the 256 output addresses out of LICM's reach (see gemm256_kernel)
-    // BX_FLUSH_ROWS rows of four 32 x 32 blocks at a time: 64 loads per row in flight, then as many stores (block by block - 16
-    // loads, wait, 16 stores - the read-modify-write cost ~40 us per 256 x 256 tile: half of a K = 512 update's time)
-    constexpr int NR = BX_FLUSH_ROWS;
-    // (the 16-byte loads of the vector path are plain loads: earlier chains of this tile went into C by L2 atomics, which the L1
-    // does not see -- drop its lines first)
-    if (S16T && !first) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    // One row of four 32 x 32 blocks at a time: 64 loads in flight, then as many stores (block by block - 16 loads, wait, 16
+    // stores - the read-modify-write cost ~40 us per 256 x 256 tile: half of a K = 512 update's time; two rows in flight together
+    // took the same time, four spilled: + 4 %)
 #pragma unroll
-    for (int i0 = 0; i0 < 4; i0 += NR) {
+    for (int i = 0; i < 4; ++i) {
       __asm__ volatile("" ::: "memory");
-      const int64_t rbase0 = row0 + wm * 128 + i0 * 32 + lrow + opaque;
-      if (S16T && full_tile && c_vec) {
-        // a lane's four values of a 16 x 16 tile are consecutive in its row of C: one 16-byte load and store per tile
-        f32x4 old[NR][4][4];
+      const int64_t rbase = row0 + wm * 128 + i * 32 + lrow + opaque;
+      if (full_tile) {
+        float old[4][16];
         if (beta != 0.f) {
 #pragma unroll
-          for (int ii = 0; ii < NR; ++ii)
+          for (int j = 0; j < 4; ++j) {
+            gptr cbase = Cout + rbase * ldc + (col0 + wn * 128 + j * 32 + lcol);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              gptr cbase = Cout + (rbase0 + ii * 32) * ldc + (col0 + wn * 128 + j * 32 + lcol);
-#pragma unroll
-              for (int q = 0; q < 4; ++q) old[ii][j][q] = *(gptr4w)(cbase + (int64_t)erc(4 * q) * ldc + ecc(4 * q));
-            }
+            for (int e = 0; e < 16; ++e) old[j][e] = ld_l2(cbase + (int64_t)erc(e) * ldc + ecc(e));
+          }
         }
 #pragma unroll
-        for (int ii = 0; ii < NR; ++ii)
+        for (int j = 0; j < 4; ++j) {
+          gptr cbase = Cout + rbase * ldc + (col0 + wn * 128 + j * 32 + lcol);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            gptr cbase = Cout + (rbase0 + ii * 32) * ldc + (col0 + wn * 128 + j * 32 + lcol);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              f32x4 v;
-#pragma unroll
-              for (int e4 = 0; e4 < 4; ++e4) v[e4] = alpha_ * aget(i0 + ii, j, 4 * q + e4);
-              if (beta != 0.f) v += beta * old[ii][j][q];
-              *(gptr4w)(cbase + (int64_t)erc(4 * q) * ldc + ecc(4 * q)) = v;
-#pragma unroll
-              for (int e4 = 0; e4 < 4; ++e4) aset(i0 + ii, j, 4 * q + e4, v[e4]);
-            }
+          for (int e = 0; e < 16; ++e) {
+            float v = alpha_ * aget(i, j, e);
+            if (beta != 0.f) v += beta * old[j][e];
+            cbase[(int64_t)erc(e) * ldc + ecc(e)] = v;
+            aset(i, j, e, v);
           }
-      } else if (full_tile) {
-        float old[NR][4][16];
-        if (beta != 0.f) {
-#pragma unroll
-          for (int ii = 0; ii < NR; ++ii)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              gptr cbase = Cout + (rbase0 + ii * 32) * ldc + (col0 + wn * 128 + j * 32 + lcol);
-#pragma unroll
-              for (int e = 0; e < 16; ++e) old[ii][j][e] = ld_l2(cbase + (int64_t)erc(e) * ldc + ecc(e));
-            }
         }
-#pragma unroll
-        for (int ii = 0; ii < NR; ++ii)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            gptr cbase = Cout + (rbase0 + ii * 32) * ldc + (col0 + wn * 128 + j * 32 + lcol);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-              float v = alpha_ * aget(i0 + ii, j, e);
-              if (beta != 0.f) v += beta * old[ii][j][e];
-              cbase[(int64_t)erc(e) * ldc + ecc(e)] = v;
-              aset(i0 + ii, j, e, v);
-            }
-          }
       } else {
 #pragma unroll
-        for (int ii = 0; ii < NR; ++ii)
+        for (int j = 0; j < 4; ++j) {
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-              const int64_t row = rbase0 + ii * 32 + erc(e), col = col0 + wn * 128 + j * 32 + ecol(e);
-              float v = alpha_ * aget(i0 + ii, j, e);
-              if (row < p.M && col < p.N) {
-                gptr c = Cout + row * ldc + col;
-                if (beta != 0.f) v += beta * ld_l2(c);
-                *c = v;
-              }
-              aset(i0 + ii, j, e, v);
+          for (int e = 0; e < 16; ++e) {
+            const int64_t row = rbase + erc(e), col = col0 + wn * 128 + j * 32 + ecol(e);
+            float v = alpha_ * aget(i, j, e);
+            if (row < p.M && col < p.N) {
+              gptr c = Cout + row * ldc + col;
+              if (beta != 0.f) v += beta * ld_l2(c);
+              *c = v;
             }
+            aset(i, j, e, v);
           }
+        }
       }
     }
   };
@@ -1249,9 +1164,6 @@ __global__ __launch_bounds__(256, 1) void gemm256_bx_kernel(GemmBxArgs p) {
   auto flush_mid = [&](bool store) __attribute__((always_inline)) {
     int opaque = 0;
     __asm__ volatile("" : "+v"(opaque));
-#if defined(BX_VARIANT) && BX_VARIANT == 2   // timing only: no flush at all
-    return;
-#endif
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -1283,9 +1195,11 @@ __global__ __launch_bounds__(256, 1) void gemm256_bx_kernel(GemmBxArgs p) {
     srcB[u] = (gcptr16)p.B + (kt0 * p.nrbB + bb) * 512 + 8 * lane;
   }
   const int64_t stepA = p.nrbA * 512, stepB = p.nrbB * 512;  // one k tile further
-  // (The addresses stay per-lane 64-bit registers, advanced by one v_lshl_add_u64 per request.  The scalar form -- block address in an
-  // SGPR pair advanced by s_add_u32 / s_addc_u32, one shared 32-bit lane offset, `global_load_lds_dwordx4 v, s[..]` -- measured 1.5-4 %
-  // SLOWER on the SYRK shape (225.1 / 248.8 against 227-234 / 252.5 TFLOP/s, round 5, scripts/probe/syrk_ab.sh).)
+  // (In the C++ loop -- the reference implementation, ASM = false, and the tiles around the asm block -- the addresses stay per-lane
+  // 64-bit registers, advanced by one v_lshl_add_u64 per request.  The asm block takes the scalar form -- block address in an SGPR
+  // pair advanced by s_add_u32 / s_addc_u32, one shared 32-bit lane offset, `global_load_lds_dwordx4 v, s[..]` -- which in this
+  // C++ loop measured 1.5-4 % SLOWER on the SYRK shape (225.1 / 248.8 against 227-234 / 252.5 TFLOP/s, round 5,
+  // scripts/probe/syrk_ab.sh).)
   const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem_bx +
                                                        (unsigned)(wave * 1024));
   auto dma16b = [&](gcptr16 src, unsigned lds_byte_addr) __attribute__((always_inline)) {
@@ -1376,8 +1290,7 @@ __global__ __launch_bounds__(256, 1) void gemm256_bx_kernel(GemmBxArgs p) {
         for (int m = 0; m < 3; ++m)   // (the four tiles in turn: consecutive instructions never share an accumulator)
 #pragma unroll
           for (int t = 0; t < 4; ++t)
-            acc[i][j][t] = S16T ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb.v[m == 0 ? 0 : 1][2 * j + (t & 1)], fa.v[m][t >> 1], acc[i][j][t], 0, 0, 0)
-                                : __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa.v[m][t >> 1], fb.v[m == 0 ? 0 : 1][2 * j + (t & 1)], acc[i][j][t], 0, 0, 0);
+            acc[i][j][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa.v[m][t >> 1], fb.v[m == 0 ? 0 : 1][2 * j + (t & 1)], acc[i][j][t], 0, 0, 0);
       } else {
         f32x16 c = acc[i][j][0];
         if (NPROD >= 9) {
@@ -1483,29 +1396,18 @@ __global__ __launch_bounds__(256, 1) void gemm256_bx_kernel(GemmBxArgs p) {
         // loop stay where they are)
         // (a whole number of the block's trips AND of this loop's two-tile trips)
         int na = (tc < t1 - 2 ? tc : t1 - 2) - t;
-        na -= na % (2 * BX_KLOOP_UNROLL);
+        na -= na % (2 * BX_KLOOP_ASM_UNROLL);
         if (na > 0) {
           const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem_bx;
           const int64_t strideA_b = 2 * p.strideA, strideB_b = 2 * p.strideB, stepA_b = 2 * stepA, stepB_b = 2 * stepB;
           __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the fragment sets of the C++ loop are not carried into the block)
-          if constexpr (S16) {
-            // the block names its accumulators: acc[i][j][q] is pinned to a[16 (4 i + j) + 4 q .. + 3]
-            __asm__ volatile(BX_KLOOP_TEXT16
-                             : BX_KLOOP_ASM_ACC(acc)
-                             : "v"(lds_base + cofsA[0]), "v"(lds_base + cofsA[1]), "v"(lds_base + cofsA[2]), "v"(lds_base + cofsB[0]),
-                               "v"(lds_base + cofsB[1]), "v"(srcA[0]), "v"(srcA[1]), "v"(srcB[0]), "v"(srcB[1]), "s"(strideA_b), "s"(strideB_b),
-                               "s"(stepA_b), "s"(stepB_b), "s"(lds0), "s"(st), "s"(na), "s"(0)
-                             : BX_KLOOP_CLOB16);
-          } else {
-            const unsigned fa_lds = lds_base + fofsA, fb_lds = lds_base + BX_OPER + fofsB;
-            __asm__ volatile(BX_KLOOP_TEXT32
-                             : "+a"(acc[0][0][0]), "+a"(acc[0][1][0]), "+a"(acc[0][2][0]), "+a"(acc[0][3][0]), "+a"(acc[1][0][0]), "+a"(acc[1][1][0]),
-                               "+a"(acc[1][2][0]), "+a"(acc[1][3][0]), "+a"(acc[2][0][0]), "+a"(acc[2][1][0]), "+a"(acc[2][2][0]), "+a"(acc[2][3][0]),
-                               "+a"(acc[3][0][0]), "+a"(acc[3][1][0]), "+a"(acc[3][2][0]), "+a"(acc[3][3][0])
-                             : "v"(fa_lds), "v"(fb_lds), "v"(srcA[0]), "v"(srcA[1]), "v"(srcB[0]), "v"(srcB[1]), "s"(strideA_b), "s"(strideB_b),
-                               "s"(stepA_b), "s"(stepB_b), "s"(lds0), "s"(st), "s"(na), "s"(0)
-                             : BX_KLOOP_CLOB32);
-          }
+          // the block names its accumulators: acc[i][j][q] is pinned to a[16 (4 i + j) + 4 q .. + 3]
+          __asm__ volatile(BX_KLOOP_ASM_TEXT
+                           : BX_KLOOP_ASM_ACC(acc)
+                           : "v"(lds_base + cofsA[0]), "v"(lds_base + cofsA[1]), "v"(lds_base + cofsA[2]), "v"(lds_base + cofsB[0]),
+                             "v"(lds_base + cofsB[1]), "v"(srcA[0]), "v"(srcA[1]), "v"(srcB[0]), "v"(srcB[1]), "s"(strideA_b), "s"(strideB_b),
+                             "s"(stepA_b), "s"(stepB_b), "s"(lds0), "s"(st), "s"(na), "s"(0)
+                           : BX_KLOOP_ASM_CLOBBERS);
           // the block leaves the request pointers na tiles further and the stage of the new tile t: redo both here (cheap,
           // and the operands above stay plain inputs -- 16 read-write accumulator operands already count twice)
           srcA[0] += (int64_t)na * stepA; srcA[1] += (int64_t)na * stepA;
@@ -1554,139 +1456,16 @@ __global__ __launch_bounds__(256, 1) void gemm256_bx_kernel(GemmBxArgs p) {
   }
 #endif
 #endif
-  // The LAST flush of a full, 16-byte-aligned tile that must read C (beta != 0 on a single-chain product, or a SYRK tile
-  // whose final values also go to the transposed tile).  The operand stages are dead now, so the old values of C are
-  // fetched by the same global -> LDS DMA as the operands, two 32 x 32 tiles (8 KB) per wave and request, three requests
-  // (24 KB per wave, no registers) in flight while a pair of tiles is combined and stored (a plain read-modify-write in
-  // registers holds 64 four-byte loads = 16 KB in flight).  `mirror`: the final values are written back to the patch and read
-  // column-wise: lane r stores element (row r, col c) to C[col0 + c][row0 + r], 128 contiguous bytes per mirror row.
-  auto flush_final = [&](bool first, bool mirror) __attribute__((always_inline)) {
-    const float beta = first ? beta_ : 1.f;
-    float *ts = reinterpret_cast<float *>(smem_bx + BX_PATCH_OFFSET) + wave * 1024;
-    const int rr = lane >> 3, c4 = lane & 7;
-    int opaque = 0;
-    __asm__ volatile("" : "+v"(opaque));
-    gptr cwave = Cout + (row0 + wm * 128 + rr + opaque) * ldc + (col0 + wn * 128 + 4 * c4);
-    const bool pre = beta != 0.f;
-    const unsigned oldb = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(wave * (32768 - 1024)));   // this wave's 4 x 8 KB of the stages
-    const unsigned char *oldp = smem_bx + wave * 32768 + lane * 16;
-    auto issue_pair = [&](int k) __attribute__((always_inline)) {   // old values of tiles 2 k, 2 k + 1 into buffer k & 3
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          const int u = 2 * k + t;
-          dma16b((gcptr16)(const void __attribute__((address_space(1))) *)(cwave + (int64_t)((u >> 2) * 32 + 8 * it) * ldc + (u & 3) * 32),
-                 oldb + (unsigned)((k & 3) * 8192 + t * 4096 + it * 1024));
-        }
-    };
-    auto wait_vm = [](int n) __attribute__((always_inline)) {
-      switch (n) {
-        case 16: __asm__ volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-        case 24: __asm__ volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-        case 32: __asm__ volatile("s_waitcnt vmcnt(32)" ::: "memory"); break;
-        case 56: __asm__ volatile("s_waitcnt vmcnt(56)" ::: "memory"); break;
-        default: __asm__ volatile("s_waitcnt vmcnt(63)" ::: "memory"); break;
-      }
-    };
-    __syncthreads();   // every wave is past its last fragment reads: the stages may be overwritten
-    if (pre) {
-      // earlier chains of this tile may have been added into C by L2 atomics: the DMA must not be served from a stale L1 line
-      if (!first) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      issue_pair(0); issue_pair(1); issue_pair(2);
-    }
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if (pre) {
-        // operations issued after the requests of pair k: the later requests (8 each) and the stores of the pairs in
-        // between (8 per pair, + 32 mirror stores); vmcnt counts in issue order
-        const int S = mirror ? 40 : 8;
-        const int after = k == 0 ? 16 : k == 1 ? 16 + S : k < 6 ? 16 + 2 * S : k == 6 ? 8 + 2 * S : 2 * S;
-        wait_vm(after < 24 ? 16 : after < 32 ? 24 : after < 56 ? 32 : after < 63 ? 56 : 63);
-      }
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int u = 2 * k + t;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int row = erow(e);
-#if defined(BX_FLUSH_EXP) && BX_FLUSH_EXP == 1   // timing only: no patch writes
-          if (p.alpha == 12345.678f)
-#endif
-          ts[row * 32 + (ecol(e) ^ ((row & BX_SWZ_MASK) << 2))] = aget(u >> 2, u & 3, e);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          float *tp = ts + (8 * it + rr) * 32 + 4 * (c4 ^ (rr & BX_SWZ_MASK));
-          f32x4 v = *reinterpret_cast<const f32x4 *>(tp);
-          v = alpha_ * v;
-          if (pre) v += beta * *reinterpret_cast<const f32x4 *>(oldp + (k & 3) * 8192 + t * 4096 + it * 1024);
-          *(gptr4w)(cwave + (int64_t)((u >> 2) * 32 + 8 * it) * ldc + (u & 3) * 32) = v;
-          if (mirror) *reinterpret_cast<f32x4 *>(tp) = v;
-        }
-        if (mirror) {   // transposed copy of tile u = (i, j)
-          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-          gptr mbase = (gptr)p.C + (col0 + wn * 128 + (u & 3) * 32 + h) * p.ldc + (row0 + wm * 128 + (u >> 2) * 32 + r);
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            const int col = 2 * q + h;
-            mbase[(int64_t)(2 * q) * p.ldc] = ts[r * 32 + (col ^ ((r & BX_SWZ_MASK) << 2))];
-          }
-        }
-      }
-      if (pre && k + 3 < 8) {
-        __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the LDS reads of buffer (k + 3) & 3 == (k - 1) & 3 are done
-        issue_pair(k + 3);
-      }
-    }
-  };
-  // Which last flush: since the asm K loop the register read-modify-write (flush_to_c) wins -- inside flush_final hipcc reloads
-  // spilled lane constants from scratch and waits for them with vmcnt(0), which also waits for every old-value request in flight
-  // (same box, headline-shaped SYRK on N(0,1) / half-zero data and a rank-1024 update of 20480^2, profiles/r06_syrk_ab_flush.log:
-  // flush_final 893 / 801 ms, 4.47 ms; flush_to_c 867 / 773 ms, 3.97 ms; flush_final for mirrored tiles only 916 / 807 ms, 5.04 ms).
-  // -DBX_FINAL_DMA=1 / 2 builds the LDS-DMA flush for every full tile / for mirrored tiles only.
-#if defined(BX_FINAL_DMA) && BX_FINAL_DMA == 2
-  const bool fast_tile = full_tile && c_vec && mirrored;
-#elif defined(BX_FINAL_DMA) && BX_FINAL_DMA == 1
-  const bool fast_tile = full_tile && c_vec;
-#else
-  const bool fast_tile = false;
-#endif
-#if defined(BX_EXP) && BX_EXP == 1   // timing only: no final flush
-  if (p.alpha == 12345.678f)
-#endif
-#if defined(BX_FINAL_ATOMIC) && BX_FINAL_ATOMIC
-  // experiment: C += alpha acc by no-return L2 atomics whenever the launch accumulates (beta = 1) and nothing needs the final values.
-  // Nothing is loaded or waited for -- and it is slower: the 1024 atomic instructions of a tile take 43 us to issue against 18 us for the
-  // read-modify-write (headline-shaped SYRK 865 / 759 against 843 / 744 ms, rank-1024 update 4.62 against 3.84 ms; profiles/r06_syrk_ab_atomic.log)
-  if (!mirrored && (!first_flush || beta_ == 1.f))
-    flush_mid(false);
-  else
-#endif
-  if (!fast_tile)
-    flush_to_c(first_flush);          // edge tiles / unaligned C; the mirror store below takes the values from the registers
-  else if (mirrored || first_flush)
-    flush_final(first_flush, mirrored);   // final values to the tile (and, for a SYRK, to its transposed image)
-  else
-    flush_mid(false);
+  // The last flush: the register read-modify-write, which leaves the final values in the accumulators for the mirror store below.
+  // Two alternatives measured slower on the same box (headline-shaped SYRK on N(0,1) / half-zero data; rank-1024 update of 20480^2):
+  //   * an LDS-DMA flush that fetched the old values of C into the dead operand stages: 893 / 801 ms, 4.47 ms (mirrored tiles only:
+  //     916 / 807 ms, 5.04 ms) against 867 / 773 ms, 3.97 ms.  Inside it hipcc reloaded spilled lane constants from scratch and
+  //     waited for them with vmcnt(0), which also waited for every old-value request in flight (profiles/r06_syrk_ab_flush.log);
+  //   * no-return L2 atomics where nothing needs the final values: 865 / 759 against 843 / 744 ms, 4.62 against 3.84 ms -- the 1024
+  //     atomic instructions of a tile take 43 us to issue against 18 us for the read-modify-write (profiles/r06_syrk_ab_atomic.log).
+  flush_to_c(first_flush);
 
-  if (S16T && mirrored && !fast_tile) {
-    // the transposed image: for a fixed register the lanes of a row group hold 16 consecutive ROWS of one column of the tile,
-    // i.e. 64 consecutive bytes of the image's row -- stored as they are
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int64_t mcol = row0 + wm * 128 + i * 32 + lrow, mrow0 = col0 + wn * 128 + j * 32 + lcol;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int64_t mr = mrow0 + ecc(e), mc = mcol + erc(e);
-          if (mr < p.N && mc < p.M) *((gptr)p.C + mr * p.ldc + mc) = aget(i, j, e);
-        }
-      }
-  } else if (mirrored && !fast_tile) {
+  if (mirrored) {
     __syncthreads();
     float *ts = reinterpret_cast<float *>(smem_bx) + wave * (32 * 33);
 #pragma unroll
@@ -1779,9 +1558,6 @@ __global__ __launch_bounds__(256, 1) void gemm64_dma_kernel(GemmArgs p) {
 
   float fa[2][2][4], fb[2][2][4];  // [half parity][tile][k pair]
   auto frags = [&](int st, int q, int par) __attribute__((always_inline)) {
-#if defined(G64_VAR) && G64_VAR >= 2   // timing-only: no LDS reads either (the DMA stream and the barriers alone)
-    return;
-#endif
     const float *sa = smem3 + st * G64_STG, *sb = sa + G64_TA;
 #pragma unroll
     for (int i = 0; i < 2; ++i) frag_half<ALAY, 64>(sa, i * 32 + r, q, h, fa[par][i]);
@@ -1789,12 +1565,6 @@ __global__ __launch_bounds__(256, 1) void gemm64_dma_kernel(GemmArgs p) {
     for (int j = 0; j < 2; ++j) frag_half<BLAY, 256>(sb, wave * 64 + j * 32 + r, q, h, fb[par][j]);
   };
   auto mfma_half = [&](int par) __attribute__((always_inline)) {
-#if defined(G64_VAR) && G64_VAR >= 1   // timing-only builds (scripts/probe/variants.sh): no products, fragments kept alive
-#pragma unroll
-    for (int tt = 0; tt < 4; ++tt)
-#pragma unroll
-      for (int i = 0; i < 2; ++i) __asm__ volatile("" ::"v"(fa[par][i][tt]), "v"(fb[par][i][tt]));
-#else
 #pragma unroll
     for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
@@ -1802,7 +1572,6 @@ __global__ __launch_bounds__(256, 1) void gemm64_dma_kernel(GemmArgs p) {
 #pragma unroll
         for (int j = 0; j < 2; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[par][i][tt], fb[par][j][tt], acc[i][j], 0, 0, 0);
-#endif
   };
 
   // DMA sources: wave w moves block w of the A tile and blocks w, w+4, w+8, w+12 of the B tile
@@ -1870,7 +1639,7 @@ __global__ __launch_bounds__(256, 1) void gemm64_dma_kernel(GemmArgs p) {
 
 // ---- The same 64-row streaming product on the bf16 pipe (round 4).
 // The fp32 kernel above is bound by its own MFMAs (32 of 64 cycles per K tile and wave: 2.1 ms for 64 x 40960 x 40960
-// where the DMA stream alone takes 1.1 ms, scripts/probe/panel_product.py with the G64_VAR builds).  Here every product is
+// where the DMA stream alone takes 1.1 ms, scripts/probe/panel_product.py on timing-only builds, since removed).  Here every product is
 // six v_mfma_f32_32x32x16_bf16 on exact three-way bf16 splits (24 MFMAs of 32 cycles per K tile and wave):
 //   * the small operand A (64 x K, read by every workgroup) is split ONCE by g64_split_a_kernel into the fragment
 //     order of the MFMA -- per K tile [row tile 2][piece 3][lane 64][8 bf16] = 6 KB -- and streamed by DMA like B;
@@ -1960,9 +1729,6 @@ __global__ __launch_bounds__(256, 1) void gemm64_bx_kernel(GemmArgs p, const uin
 
   // DMA sources: wave w moves bytes [1536 w, 1536 w + 1536) of the A pieces (one full and one half-wave request) and
   // blocks w, w+4, w+8, w+12 of the B tile
-#if defined(G64_VADDR)
-  gcptr srcA = (gcptr)(reinterpret_cast<const char *>(apieces) + (kbeg / BK) * 6144 + wave * 1536 + lane * 16);
-#endif
   gcptr srcB[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u)
@@ -1971,13 +1737,12 @@ __global__ __launch_bounds__(256, 1) void gemm64_bx_kernel(GemmArgs p, const uin
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)smem3;
   const unsigned ldsA = __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(wave * 1536)),
                  ldsB = __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(G64X_TA * 4 + wave * 1024));
-#if !defined(G64_VADDR)
   // Round 6: the requests take a wave-uniform base in scalar registers + ONE 32-bit offset per lane and stream instead of a
   // 64-bit pointer per lane (global_load_lds_dwordx4 v, s[..]): in the 256-tile kernel's K loop that is what a request's cost
   // to the SIMD hangs on (~25 cycles against ~3, gemm256_bx_kernel).  A lane's offset from the first row of the tile is
-  // below 256 rows x ldb x 4 bytes; it does not change along K.  (-DG64_VADDR: the per-lane pointers of rounds 4-5.)  Same-box
-  // A/B on N(0,1) data (scripts/probe/g64_ab.sh, profiles/r06_g64_ab.log): m = 40 960: 1820-1886 against 1884-1898 us;
-  // m = 20 480: 470-484 against 509-515 us.
+  // below 256 rows x ldb x 4 bytes; it does not change along K.  Same-box A/B against the per-lane pointers
+  // of rounds 4-5 on N(0,1) data (profiles/r06_g64_ab.log): m = 40 960: 1820-1886 against 1884-1898 us; m = 20 480: 470-484
+  // against 509-515 us.
   gcptr baseA = (gcptr)(reinterpret_cast<const char *>(apieces) + (kbeg / BK) * 6144) + __builtin_amdgcn_readfirstlane(wave * (1536 / 4));
   gcptr baseB = (gcptr)p.B + (BLAY == LAY_K ? (col0 < p.N ? col0 : 0) * p.ldb + kbeg : kbeg * p.ldb + (col0 < p.N ? col0 : 0));
   const unsigned voffA = (unsigned)lane * 16u;
@@ -1996,19 +1761,6 @@ __global__ __launch_bounds__(256, 1) void gemm64_bx_kernel(GemmArgs p, const uin
     for (int u = 0; u < 4; ++u) dma16s(baseB, voffB[u], ldsB + so + (unsigned)(4 * u * 1024));
     baseB += stepB;
   };
-#else
-  auto issue = [&](int st) __attribute__((always_inline)) {   // 6 requests per wave
-    const unsigned so = (unsigned)(st * G64X_STG * 4);
-    dma16(srcA, ldsA + so);
-    if (lane < 32) dma16(srcA + 256, ldsA + so + 1024);   // (+256 floats = 1 KB; counted by vmcnt whatever the exec mask)
-    srcA += 6144 / 4;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      dma16(srcB[u], ldsB + so + (unsigned)(4 * u * 1024));
-      srcB[u] += stepB;
-    }
-  };
-#endif
 
   struct P3 { bf16x8 h, m, l; };
   P3 pa[2][2], pb[2][2];   // [tile parity][row / column tile]
@@ -2042,15 +1794,10 @@ __global__ __launch_bounds__(256, 1) void gemm64_bx_kernel(GemmArgs p, const uin
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       unsigned hh[4], mm[4], ll[4];
-#if defined(G64_VAR) && G64_VAR == 4   // timing-only: the products without the split
-#pragma unroll
-      for (int u = 0; u < 4; ++u) hh[u] = __float_as_uint(raw[j][u]), mm[u] = __float_as_uint(raw[j][4 + u]), ll[u] = hh[u] ^ mm[u];
-#else
       // (13 instructions per pair as hipcc compiles it; a 9-instruction form -- packed subtractions in inline asm, the
       // packed conversion hidden from the optimiser -- ran 7 % SLOWER on the same box: hazard s_nops around the asm)
 #pragma unroll
       for (int u = 0; u < 4; ++u) bx_split2(raw[j][2 * u], raw[j][2 * u + 1], hh[u], mm[u], ll[u]);
-#endif
       pb[par][j].h = __builtin_bit_cast(bf16x8, (u32x4){hh[0], hh[1], hh[2], hh[3]});
       pb[par][j].m = __builtin_bit_cast(bf16x8, (u32x4){mm[0], mm[1], mm[2], mm[3]});
       pb[par][j].l = __builtin_bit_cast(bf16x8, (u32x4){ll[0], ll[1], ll[2], ll[3]});
@@ -2061,12 +1808,7 @@ __global__ __launch_bounds__(256, 1) void gemm64_bx_kernel(GemmArgs p, const uin
 #define G64_BX4(PA, PB)                                                                                                 \
   _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j) acc[i][j] =             \
       __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[par][i].PA, pb[par][j].PB, acc[i][j], 0, 0, 0);
-#if defined(G64_VAR) && G64_VAR == 3   // timing-only: the split without the products
-    _Pragma("unroll") for (int i = 0; i < 2; ++i) __asm__ volatile("" ::"v"(pa[par][i].h), "v"(pa[par][i].m), "v"(pa[par][i].l),
-                                                                   "v"(pb[par][i].h), "v"(pb[par][i].m), "v"(pb[par][i].l));
-#else
     G64_BX4(l, h) G64_BX4(h, l) G64_BX4(m, m) G64_BX4(m, h) G64_BX4(h, m) G64_BX4(h, h)
-#endif
 #undef G64_BX4
   };
 
@@ -2083,9 +1825,7 @@ __global__ __launch_bounds__(256, 1) void gemm64_bx_kernel(GemmArgs p, const uin
     if (issued < nt) {
       // own part of tile t+1 landed: tiles t+2 .. t+NST-2 (NST-3 of them) may still be in flight
       __asm__ volatile("s_waitcnt vmcnt(24)" ::: "memory");
-#if !(defined(G64_VAR) && G64_VAR == 5)   // timing-only 5: no requests after the first NST-1 tiles
       issue(ist);  // tile t+NST-1 into the stage tile t-1 has left (its LDS reads ended before the previous barrier)
-#endif
       ++issued;
       ist = ist + 1 == G64X_NST ? 0 : ist + 1;
     } else {
@@ -2570,15 +2310,12 @@ struct BxStrictScope {
   ~BxStrictScope() { tls_bx_gate_mask = saved; }
 };
 
-#ifndef BX_ASM_DEFAULT
-#define BX_ASM_DEFAULT 1
-#endif
 // VIVIT_BX_ASM=1 / 0: the hand-scheduled K loop (gemm256_bx_kernel<6, true>) or the C++ loop (the reference implementation)
 static bool bx_asm_enabled() {
   static int on = -1;
   if (on < 0) {
     const char *e = getenv("VIVIT_BX_ASM");
-    on = e ? (atoi(e) != 0) : BX_ASM_DEFAULT;
+    on = e ? (atoi(e) != 0) : 1;
   }
   return on != 0;
 }
@@ -2716,7 +2453,6 @@ static int gemm256_launch(int alay, int blay, GemmArgs p, bool syrk, void *works
       f.a_vec = ((reinterpret_cast<uintptr_t>(f.A) & 15) == 0 && (f.lda & 3) == 0) ? 1 : 0;
       f.b_vec = ((reinterpret_cast<uintptr_t>(f.B) & 15) == 0 && (f.ldb & 3) == 0) ? 1 : 0;
       f.gate = flag; f.gate_mask = q.gate_mask;
-#if !defined(BX_NO_STANDIN)
       if (alay == LAY_K && blay == LAY_K)
         gemm256_kernel<LAY_K, LAY_K><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f);
       else if (alay == LAY_K && blay == LAY_M)
@@ -2725,7 +2461,6 @@ static int gemm256_launch(int alay, int blay, GemmArgs p, bool syrk, void *works
         gemm256_kernel<LAY_M, LAY_K><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f);
       else
         gemm256_kernel<LAY_M, LAY_M><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f);
-#endif
       st = launch_status();
     }
     if (st == VIVIT_OK && p.syrk == 1) {

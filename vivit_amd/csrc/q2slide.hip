@@ -34,22 +34,6 @@
 
 namespace vivit {
 
-// QS_VAR: timing-only builds (WRONG results; scripts/probe/q2_variants.sh builds them as separate libraries) that leave one
-// ingredient out -- 1 no arithmetic (images, barriers and Zt traffic only), 2 no image requests by the compute waves, 3 no
-// image requests and no barriers, 4 no Zt loads / stores, 5 no split arithmetic, 6 no LDS fragment reads, 7 = 3 + 4,
-// 8 = 5 + 6 + 7, 9 no Zt loads, 10 no Zt stores.  (Mind what hipcc removes with them: without the final store of a unit
-// the MFMAs that only feed it go as well.)
-#ifndef QS_VAR
-#define QS_VAR 0
-#endif
-#define QS_NO_SYNC (QS_VAR == 3 || QS_VAR == 7 || QS_VAR == 8)
-#define QS_NO_ZT (QS_VAR == 4 || QS_VAR == 7 || QS_VAR == 8)
-#if QS_VAR == 9
-#define QS_NO_ZLOAD 1
-#elif QS_VAR == 10
-#define QS_NO_ZSTORE 1
-#endif
-
 typedef __bf16 qbf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 qbf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned qu32x4 __attribute__((ext_vector_type(4)));
@@ -156,17 +140,6 @@ struct QsPieces {
 
 // eight fp32 values (element j of an MFMA operand: x = j 0..3, y = j 4..7) -> three bf16x8 operands
 __device__ __forceinline__ QsPieces qs_split8(const float4 x, const float4 y) {
-#if QS_VAR == 5 || QS_VAR == 8   // timing only: no split arithmetic
-  {
-    QsPieces p;
-    qu32x4 a = {__float_as_uint(x.x), __float_as_uint(x.y), __float_as_uint(x.z), __float_as_uint(x.w)};
-    qu32x4 b = {__float_as_uint(y.x), __float_as_uint(y.y), __float_as_uint(y.z), __float_as_uint(y.w)};
-    p.h = __builtin_bit_cast(qbf16x8, a);
-    p.m = __builtin_bit_cast(qbf16x8, b);
-    p.l = p.h;
-    return p;
-  }
-#endif
   qu32x4 h, m, l;
   qs_split8_asm(x, y, h, m, l);
   QsPieces p;
@@ -407,15 +380,6 @@ struct QsFrag {
 };
 __device__ __forceinline__ QsFrag qs_frag(qs_lds_ptr frag, int i) {
   QsFrag f;
-#if QS_VAR == 6 || QS_VAR == 8   // timing only: no LDS reads
-  {
-    qu32x4 a = {(unsigned)(uintptr_t)frag, 0x3f803f80u, (unsigned)i, 0x3f803f80u};
-    f.h = __builtin_bit_cast(qbf16x8, a);
-    f.m = f.h;
-    f.l = f.h;
-    return f;
-  }
-#endif
   f.h = *reinterpret_cast<qs_lds_frag>(frag + (3 * i + 0) * 1024);
   f.m = *reinterpret_cast<qs_lds_frag>(frag + (3 * i + 1) * 1024);
   f.l = *reinterpret_cast<qs_lds_frag>(frag + (3 * i + 2) * 1024);
@@ -431,12 +395,6 @@ __device__ __forceinline__ QsFrag qs_frag(qs_lds_ptr frag, int i) {
 // "start-of-segment VALU penalty" -- and a wave that reaches the barrier early splits while it would otherwise wait).
 template <int Q0, class Mid>
 __device__ __forceinline__ void qs_apply_block(float4 (&sw)[12], qs_lds_ptr frag, Mid mid, const QsPieces &bp0) {
-#if QS_VAR == 1
-  __asm__ volatile("" : "+v"(sw[Q0].x), "+v"(sw[Q0 + 7].w));
-  (void)bp0;
-  qs_static_for<QS_NSTEP>([&](auto itag) __attribute__((always_inline)) { mid(decltype(itag)::value); });
-  return;
-#endif
   f32x4 acc2[4];
 #pragma unroll
   for (int ta = 0; ta < 4; ++ta)
@@ -454,13 +412,7 @@ __device__ __forceinline__ void qs_apply_block(float4 (&sw)[12], qs_lds_ptr frag
     if constexpr (st.ks >= 0) {
       if constexpr (i == 0) bp = bp0;
       else if constexpr (st.ks != prev.ks) bp = qs_split8(sw[Q0 + 2 * st.ks], sw[Q0 + 2 * st.ks + 1]);
-#if defined(QS_PRIO)
-      __builtin_amdgcn_s_setprio(1);
-#endif
       QS_MFMA6(acc2[st.ta], cur.h, cur.m, cur.l, bp)
-#if defined(QS_PRIO)
-      __builtin_amdgcn_s_setprio(0);
-#endif
     } else {
       if constexpr (i == QS_NW2) {
         wp[0] = qs_split8(make_float4(acc2[0][0], acc2[0][1], acc2[0][2], acc2[0][3]),
@@ -472,13 +424,7 @@ __device__ __forceinline__ void qs_apply_block(float4 (&sw)[12], qs_lds_ptr frag
 #pragma unroll
         for (int e = 0; e < 4; ++e) u[e] = 0.f;
       }
-#if defined(QS_PRIO)
-      __builtin_amdgcn_s_setprio(1);
-#endif
       QS_MFMA6(u, cur.h, cur.m, cur.l, wp[st.kt])
-#if defined(QS_PRIO)
-      __builtin_amdgcn_s_setprio(0);
-#endif
       if constexpr (i + 1 == QS_NSTEP || next.wt != st.wt) {
         float4 &x = sw[Q0 + st.wt];
         x.x -= u[0]; x.y -= u[1]; x.z -= u[2]; x.w -= u[3];
@@ -552,9 +498,7 @@ __global__ __launch_bounds__(64 * MAXW) void qs_apply_kernel(QsArgs a) {
         slowest = v == 0 ? 0x7fffffff : v;
       }
       __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of image seq have landed
-#if !QS_NO_SYNC
       __builtin_amdgcn_s_barrier();                           // ... everybody's; and every wave is done with image seq - 1
-#endif
       if (pace) {
 #pragma unroll
         for (int o = 16; o > 0; o >>= 1) {
@@ -637,16 +581,7 @@ __global__ __launch_bounds__(64 * MAXW) void qs_apply_kernel(QsArgs a) {
     const int c0 = 64 * u + 4 * kq;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      if (rok && c0 + 16 * q < n) {
-#if defined(QS_NT_STORE)
-        __builtin_nontemporal_store(src[q].x, zbase + (int64_t)64 * u + zoff + 16 * q);
-        __builtin_nontemporal_store(src[q].y, zbase + (int64_t)64 * u + zoff + 16 * q + 1);
-        __builtin_nontemporal_store(src[q].z, zbase + (int64_t)64 * u + zoff + 16 * q + 2);
-        __builtin_nontemporal_store(src[q].w, zbase + (int64_t)64 * u + zoff + 16 * q + 3);
-#else
-        *reinterpret_cast<float4 *>(zbase + (int64_t)64 * u + zoff + 16 * q) = src[q];
-#endif
-      }
+      if (rok && c0 + 16 * q < n) *reinterpret_cast<float4 *>(zbase + (int64_t)64 * u + zoff + 16 * q) = src[q];
   };
 
   // The Zt loads and stores are plain C++ (hipcc counts them), the image DMAs are asm (hipcc does not): a wait that hipcc
@@ -691,24 +626,16 @@ __global__ __launch_bounds__(64 * MAXW) void qs_apply_kernel(QsArgs a) {
         if (steady) __asm__ volatile("s_waitcnt vmcnt(4)" ::: "memory");
         else __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-#if !QS_NO_SYNC
       __builtin_amdgcn_s_barrier();
-#endif
       const int64_t seq_a = seq + 1 < nseq ? seq + 1 : 0;   // (the very last block re-requests image 0: never read)
       // next group's left unit (g - 1 + 2K < G0: inside the matrix).  Unconditional (the last group of a pass fetches a
       // unit it does not use): a branch around the loads makes hipcc wait for them at the join
       float4 pre[4];
       const int up = g - 1 + 2 * K;
       qs_apply_block<0>(sw, myfrag + (seq & 1) * QS_IMG, [&](int i) __attribute__((always_inline)) {
-#if QS_VAR != 2 && !QS_NO_SYNC
         dma_step(seq_a, i);
-#endif
         if (i == QS_DMA_STEPS) {
-#if QS_NO_ZT || defined(QS_NO_ZLOAD)
-          for (int q = 0; q < 4; ++q) pre[q] = sw[8 + q];
-#else
           load_unit(up > 0 ? up : 0, pre);
-#endif
           __builtin_amdgcn_sched_barrier(0);   // (the loads stay here: behind the image requests, in front of the rest)
         }
       }, bpa);
@@ -716,31 +643,17 @@ __global__ __launch_bounds__(64 * MAXW) void qs_apply_kernel(QsArgs a) {
       {
         // ---- block (g, 2K + 1) (g = gmax: the identity block); its first operand is split in front of the barrier
         const QsPieces bpb = qs_split8(sw[4], sw[5]);
-        if (self_load) {
-#if QS_NO_ZT
-          __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-          __asm__ volatile("s_waitcnt vmcnt(4)" ::: "memory");   // the image; `pre` stays in flight
-#endif
-        }
-#if !QS_NO_SYNC
+        if (self_load) __asm__ volatile("s_waitcnt vmcnt(4)" ::: "memory");   // the image; `pre` stays in flight
         __builtin_amdgcn_s_barrier();
-#endif
         const int64_t seq_b = seq + 1 < nseq ? seq + 1 : 0;
-        qs_apply_block<4>(sw, myfrag + (seq & 1) * QS_IMG, [&](int i) __attribute__((always_inline)) {
-#if QS_VAR != 2 && !QS_NO_SYNC
-          dma_step(seq_b, i);
-#endif
-        }, bpb);
+        qs_apply_block<4>(sw, myfrag + (seq & 1) * QS_IMG, [&](int i) __attribute__((always_inline)) { dma_step(seq_b, i); }, bpb);
         ++seq;
       }
       // hipcc waits for `pre` here (and with it for the image requests of the block just computed)
       __asm__ volatile("" : QS_USE4(pre[0]), QS_USE4(pre[1]), QS_USE4(pre[2]), QS_USE4(pre[3]));
       // the right unit is final: store it, slide the window
       const int ur = g + 2 * K + 2;
-#if !QS_NO_ZT && !defined(QS_NO_ZSTORE)
       store_unit(ur, &sw[8]);
-#endif
       steady = wave_valid && 64 * ur + 63 < n;
 #pragma unroll
       for (int q = 0; q < 4; ++q) { sw[8 + q] = sw[4 + q]; sw[4 + q] = sw[q]; sw[q] = pre[q]; }
@@ -769,9 +682,7 @@ constexpr size_t QS_WS_TARGET = (size_t)2 << 30;   // images of ~2 GB per chunk 
 // profiles/r06_q2_lockstep_pmc.log), window -> ms / FETCH_SIZE per two solves: off 1224.7 / 2.518e9 KiB; 2: 1200.6 / 1.201e9; 4: 1207.5 /
 // 1.232e9; 8: 1210.2 / 1.289e9; 16: 1204.5 / 1.369e9; 128: 1266 -- half of the kernel's fabric traffic was block images fetched once
 // per CU instead of once per XCD; the time follows only by 1.5-2 % (the kernel is bound by its MFMA chains and the L2 -> LDS stream).
-#ifndef QS_LOCKSTEP_DEFAULT
-#define QS_LOCKSTEP_DEFAULT 4
-#endif
+constexpr int QS_LOCKSTEP_DEFAULT = 4;
 
 size_t q2_slide_workspace_bytes(int64_t n) {
   if (n < 3) return 0;

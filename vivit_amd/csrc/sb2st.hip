@@ -22,9 +22,6 @@
 
 namespace vivit {
 
-#ifndef SB2ST_VARIANT
-#define SB2ST_VARIANT 0
-#endif
 constexpr int NB = 64;             // half bandwidth
 constexpr int LDAB = SB2ST_LDP;    // band row stride inside the library: 2 NB + 1 entries + 3 floats of padding (eig_internal.h)
 static_assert(LDAB >= 2 * NB + 1 + 3 && LDAB % 4 == 0, "a 16-byte store of a row's last entries needs three floats of padding");
@@ -203,8 +200,8 @@ __device__ __forceinline__ float sb2st_core(int k, int L, int wave, int lane, fl
 // diagonal entry, the last entry of the band row; lane h writes floats 4 h .. 4 h + 3 of it, and what the last store of a row
 // writes beyond the diagonal entry lands in the row's three floats of padding.  (The addresses are 4-byte aligned only.)  A
 // task's 128 single-float store instructions per workgroup kept the write-through queue full for 2.5 us (timing-only builds, all
-// on 256 workgroups with nobody waiting: 298 ms per chase, 171 ms without the bulk stores, 235 ms with these: SB2ST_PVAR notes
-// in DESIGN.md section 8); 32 sixteen-byte ones take half of that.
+// on 256 workgroups with nobody waiting: 298 ms per chase, 171 ms without the bulk stores, 235 ms with these:
+// profiles/HISTORY.md); 32 sixteen-byte ones take half of that.
 template <bool COH>
 __device__ __forceinline__ void band_st4(float *p, float4 v) {
   typedef float f4v __attribute__((ext_vector_type(4)));
@@ -347,9 +344,7 @@ __global__ __launch_bounds__(256) void sb2st_persist_kernel(float *__restrict__ 
     for (int k = 0; k < ks; ++k) {
       const int c0 = s + 1 + k * NB;
       const int L = (n - c0) < NB ? (n - c0) : NB;
-#if !(defined(SB2ST_PVAR) && SB2ST_PVAR == 2)   // (2: timing only, wrong results: nobody waits -- the throughput without the chain)
       if (tid == 0 && s > 0) wait_for(s - 1, false, k + 1);
-#endif
       __syncthreads();   // (also: the previous task's LDS reads are done)
       if (s_info[1]) break;
       Sb2stRows rows;
@@ -357,9 +352,7 @@ __global__ __launch_bounds__(256) void sb2st_persist_kernel(float *__restrict__ 
       // into LDS while the hand-over of the last row is awaited: off the chain of the wavefront step (the stale copy of that row goes
       // along and is replaced below)
       sb2st_stage(k, L, wave, lane, rows, lds, 0, NB / 4);
-#if !(defined(SB2ST_PVAR) && SB2ST_PVAR == 2)
       if (tid == 0 && s > 0) wait_for(s - 1, true, k + 2 < kprev ? k + 2 : kprev);
-#endif
       __syncthreads();
       if (s_info[1]) break;
       if (wave == 3 && L == NB) {   // the last row again, now that its owner has stored it
@@ -370,16 +363,7 @@ __global__ __launch_bounds__(256) void sb2st_persist_kernel(float *__restrict__ 
       }
       float x = 0.f;
       if (k == 0) x = lane < L ? band_ld<true>(AB + (int64_t)(c0 + lane) * LDAB + (2 * NB - 1 - lane)) : 0.f;  // column s of the band
-#if defined(SB2ST_PVAR) && SB2ST_PVAR == 3   // timing only (wrong results): counter A goes out BEFORE the arithmetic -- the step without it
-      if (tid == 0) __hip_atomic_store(prog(s), ((k + 1) << 16) | k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-#if defined(SB2ST_PVAR) && SB2ST_PVAR == 1   // timing only (wrong results): no arithmetic, the hand-over chain alone
-      float beta = x;
-      lds.sE[tid] = rows.ev[0]; lds.sD[tid] = rows.dv[0];
-      __syncthreads();
-#else
       const float beta = sb2st_core(k, L, wave, lane, x, pv, ptau, lds);
-#endif
       // ---- first row out, counter A
       if (wave == 0) {
         if (k == 0 && lane == 0) band_st<true>(AB + (int64_t)c0 * LDAB + (2 * NB - 1), beta);
