@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box stage times of the headline step under different environment settings (bench.py without the extras, 3 steps each).
-#   scripts/probe/bench_env_ab.sh "VIVIT_BT_NSUB=32" "VIVIT_GEMM_SPLIT_KC=8192" ...   (the empty setting runs first and last)
+#   scripts/probe/bench_env_ab.sh "VIVIT_TWO_STAGE=0" "VIVIT_Q2_LOCKSTEP=0" ...   (the empty setting runs first and last)
 cd "$(dirname "$0")/../.."
 run() { env $1 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-verify --no-secondary --no-configs 2>/dev/null | python -c "
 import json, sys

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Same-box timing of the headline-shaped Gram SYRK with the product library under different environment settings, interleaved.
-#   scripts/probe/syrk_env_ab.sh "VIVIT_BX_SYNC=1" "VIVIT_BX_FLUSH=8192" ...      (the empty setting runs first in every round)
+#   scripts/probe/syrk_env_ab.sh "VIVIT_BX_ASM=0" "VIVIT_GEMM_SPLIT=9" ...      (the empty setting runs first in every round)
 cd "$(dirname "$0")/../.."
 run() { env $1 python - "$1" <<'PY' 2>&1 | grep -v "amdgpu.ids\|arn"
 import os, sys, time

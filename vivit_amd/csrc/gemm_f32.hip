@@ -18,7 +18,6 @@
 // SYRK mode (the Gram build, K1): B == A, only super-blocks/tiles with tile_i >= tile_j are
 // computed (n(n+1)p flops instead of 2n^2p) and off-diagonal tiles are stored twice, the mirror
 // image transposed through LDS so that both stores are coalesced.
-#include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 
@@ -236,40 +235,6 @@ __device__ __forceinline__ bool map_tile_z(int syrk, int SBW, int tiles_m, int t
     tj = idx % tiles_n;
   }
   return true;
-}
-
-// Number of valid tiles map_tile hands XCD `blockIdx.x & 7` in this workgroup's super-block (the members of its XCD
-// group: they share their operand panels through that XCD's L2), and the group's index.  Same geometry as map_tile.
-__device__ __forceinline__ int xcd_group(int syrk, int SBW, int tiles_m, int tiles_n, int &group) {
-  const int sb = blockIdx.x >> 8;
-  const int xcd = (blockIdx.x - blockIdx.y) & 7;
-  const int SBH = 256 / SBW;
-  int I, J;
-  if (syrk) {
-    I = (int)((sqrtf(8.f * (float)sb + 1.f) - 1.f) * 0.5f);
-    while ((I + 1) * (I + 2) / 2 <= sb) ++I;
-    while (I * (I + 1) / 2 > sb) --I;
-    J = I - (sb - I * (I + 1) / 2);
-  } else {
-    const int sbn = (tiles_n + SBW - 1) / SBW;
-    I = sb / sbn;
-    J = sb - I * sbn;
-  }
-  group = sb * 8 + xcd;
-  const int vr = tiles_m - I * SBH < SBH ? tiles_m - I * SBH : SBH;
-  const int vc = tiles_n - J * SBW < SBW ? tiles_n - J * SBW : SBW;
-  int v;
-  if (syrk && I == J) {
-    const int d = vr < vc ? vr : vc;
-    v = d * (d + 1) / 2;
-  } else if (vr < SBH || vc < SBW) {
-    v = vr > 0 && vc > 0 ? vr * vc : 0;
-  } else {
-    return 32;
-  }
-  const int c = (v + 7) >> 3;
-  const int left = v - c * xcd;
-  return left < 0 ? 0 : (left < c ? left : c);
 }
 
 // WM = waves along M: 2 -> 128 x 128 tile (2 x 2 waves), 1 -> 64 x 256 tile (1 x 4 waves) for outputs
@@ -977,8 +942,6 @@ struct GemmBxArgs {
   // K tiles accumulated in one MFMA chain before the sum is added into C with a VALU add (see bx_flush_tiles);
   // flush_diag: the same for the diagonal tiles of a SYRK (sums of squares: every product has the same sign)
   int flush_tiles, flush_diag;
-  // optional start barrier of an XCD group (VIVIT_BX_SYNC, see bx_sync_enabled): one zeroed counter per group
-  int *sync;
 };
 
 #if defined(BX_STAMP)
@@ -1035,23 +998,6 @@ __global__ __launch_bounds__(256, 1) void gemm256_bx_kernel(GemmBxArgs p) {
   }
 
   const int tid = threadIdx.x;
-  if (p.sync) {
-    // The 32 workgroups of an XCD group stream the same 12 operand panels; they hit in that XCD's L2 only while they are
-    // within ~14 K tiles of each other.  Workgroups start when a CU frees up, so the start times of a group random-walk
-    // apart over the rounds of a launch.  Start barrier: wait (at most 50 us: no deadlock if fewer CUs are available)
-    // until the whole group has arrived.  Older groups never wait for newer ones.
-    if (tid == 0) {
-      int group;
-      const int expect = xcd_group(p.syrk, p.sbw, p.tiles_m, p.tiles_n, group);
-      int *cnt = p.sync + (int64_t)blockIdx.y * (gridDim.x >> 5) + group;
-      __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-      while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < expect &&
-             __builtin_amdgcn_s_memrealtime() - t0 < 5000ull)
-        __builtin_amdgcn_s_sleep(4);
-    }
-    __syncthreads();
-  }
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int r = lane & 31, h = lane >> 5;
@@ -2025,13 +1971,29 @@ __global__ __launch_bounds__(256) void gemm_tsk_reduce_kernel(const float *__res
   }
 }
 
+// Calls f with the operand layouts as std::integral_constant arguments, so that a launch can pass them on as template
+// arguments: with_layouts(alay, blay, [&](auto LA, auto LB) { kernel<LA, LB><<<...>>>(...); })
+template <class F>
+static void with_layouts(int alay, int blay, F &&f) {
+  using K = std::integral_constant<int, LAY_K>;
+  using M = std::integral_constant<int, LAY_M>;
+  if (alay == LAY_K && blay == LAY_K) f(K{}, K{});
+  else if (alay == LAY_K && blay == LAY_M) f(K{}, M{});
+  else if (alay == LAY_M && blay == LAY_K) f(M{}, K{});
+  else f(M{}, M{});
+}
+// the same for one operand
+template <class F>
+static void with_layout(int lay, F &&f) {
+  if (lay == LAY_K) f(std::integral_constant<int, LAY_K>{});
+  else f(std::integral_constant<int, LAY_M>{});
+}
+
 static bool tsk_shape(int64_t M, int64_t N, int64_t K) { return M <= 64 && N <= 1024 && K >= 2048 && (K & 3) == 0; }
 
 static void tsk_plan(int64_t N, int64_t K, int &nsplit, int64_t &kchunk) {
   const int64_t nblk = cdiv(N, 64);
-  static int total = -1;
-  if (total < 0) { const char *e = getenv("VIVIT_TSK_WGS"); total = e ? atoi(e) : 512; }
-  int64_t want = total / nblk, maxs = K / (2 * TSK_KC);   // two workgroups per CU; at least two steps per split
+  int64_t want = 512 / nblk, maxs = K / (2 * TSK_KC);   // two workgroups per CU; at least two steps per split
   if (want < 1) want = 1;
   int64_t s = want < maxs ? want : maxs;
   if (s < 1) s = 1;
@@ -2093,18 +2055,13 @@ static void choose_split(int64_t M, int64_t N, int64_t K, bool syrk, int &ksplit
     // one resident round (2 workgroups per CU x 256 CUs) for compute-bound shapes; a one-tile-wide
     // output streams its big operand once and is bandwidth-bound: more, shorter splits keep enough
     // bytes in flight
-    static int skinny_want = -1;
-    if (skinny_want < 0) { const char *e = getenv("VIVIT_SKINNY_WANT"); skinny_want = e ? atoi(e) : 2048; }
-    int64_t want = (tm == 1 || tn == 1) ? skinny_want / tiles : 512 / tiles;
+    int64_t want = (tm == 1 || tn == 1) ? 2048 / tiles : 512 / tiles;
     int64_t maxs = (tm == 1 || tn == 1) ? ktiles / 8 : ktiles / 32;
     int64_t s = want < maxs ? want : maxs;
     // a single-tile output (the 64 x 64 Gram blocks of the band reduction's panels: both operands stream 64 rows
     // x m) has nothing but split-K to spread over the chip (with the slot rotation of map_tile: before it every
-    // split's only valid workgroup sat on XCD 0 and more splits bought nothing)
-    static int cap1 = -1;
-    if (cap1 < 0) { const char *e = getenv("VIVIT_SPLIT_CAP1"); cap1 = e ? atoi(e) : 64; }
-    const int64_t cap = tiles <= 2 ? cap1 : 64;
-    if (s > cap) s = cap;
+    // split's only valid workgroup sat on XCD 0 and more splits bought nothing); at most 64 splits for any output
+    if (s > 64) s = 64;
     while (s > 1 && (size_t)s * (size_t)M * (size_t)N * 4 > ((size_t)1 << 30)) --s;
     if (s > 1) {
       kchunk = cdiv(ktiles, s) * BK;
@@ -2164,30 +2121,25 @@ __global__ __launch_bounds__(256) void scale_c_kernel(float *__restrict__ C, int
 }
 
 // The 256 x 256 tile pays off once the output has enough of them to fill the chip (one per CU).
-// Split-K (slabs + fixed-order reduce) is implemented for small outputs with a deep contraction, but stays
-// opt-in (VIVIT_GEMM256_SPLIT=1): measured on the Gram matrices of small batches (n = 1280, P = 4e5) the
-// streamed K-major operand then reaches only 0.2 TB/s - 17 splits x 1280 row streams 1.6 MB apart - and the
-// 128 x 128 tile with its 2 workgroups per CU is twice as fast (27 ms vs 59 ms); to be revisited with the
-// seven-stage pipeline of gemm64_dma_kernel.
+// Small outputs with a deep contraction stay on the 128 x 128 tile: measured with the 256 tile's split-K on the Gram
+// matrices of small batches (n = 1280, P = 4e5) the streamed K-major operand reached only 0.2 TB/s - 17 splits x 1280
+// row streams 1.6 MB apart - and the 128 x 128 tile with its 2 workgroups per CU was twice as fast (27 ms vs 59 ms).
+// Split-K here only fills the last round of workgroups of a large output (at most 4 splits).
 static bool gemm256_plan(int64_t M, int64_t N, int64_t K, bool syrk, int *ksplit_out, int64_t *kchunk_out, int max_split) {
-  static int forced = -2, split = 0;
+  static int forced = -2;
   if (forced == -2) {
     const char *e = getenv("VIVIT_GEMM256");
     forced = e ? atoi(e) : -1;
-    const char *e2 = getenv("VIVIT_GEMM256_SPLIT");
-    split = e2 ? atoi(e2) : 0;
   }
   if (ksplit_out) *ksplit_out = 1;
   if (kchunk_out) *kchunk_out = cdiv(K, BK) * BK;
-  static int kmin = -1;
-  if (kmin < 0) { const char *e = getenv("VIVIT_GEMM256_KMIN"); kmin = e ? atoi(e) : 512; }
-  if (forced == 0 || K < kmin) return false;
+  if (forced == 0 || K < 512) return false;
   const int64_t tm = cdiv(M, B2), tn = cdiv(N, B2);
   const int64_t tiles = syrk ? tm * (tm + 1) / 2 : tm * tn;
   // one workgroup per CU: prologue (first DMA round trip) and epilogue (256 KB of C) are not overlapped with
   // another workgroup's main loop, so the contraction must be long enough to amortise them
-  if (!split && tiles < 200) return false;
-  if (!split) max_split = max_split < 4 ? max_split : 4;  // large outputs: only to fill the last round of workgroups
+  if (tiles < 200) return false;
+  if (max_split > 4) max_split = 4;
   if (M < 512 || N < 512) return false;
   const int64_t ktiles = K / BK;
   const double flops = (syrk ? 1.0 : 2.0) * (double)M * (double)N * (double)K;
@@ -2242,33 +2194,23 @@ static int gemm_split_mode() {
 // kernel's random-sign error) on ALL tiles -- the same-sign sums of a Gram matrix are its diagonal ENTRIES, which the
 // public SYRK computes separately in fp64 (syrk_diag_kernel: 16 ms instead of 140) --, 1024 k in the split-K form for
 // small outputs (whose yardstick is the 128-tile fp32 kernel with its chains of 2048); the eigensolver's internal
-// products on orthogonal factors (random signs, the measured off-diagonal case) keep 8192.
-// VIVIT_BX_FLUSH / VIVIT_BX_FLUSH_DIAG / VIVIT_BX_FLUSH_SPLITK / VIVIT_BX_FLUSH_INTERNAL override (in k).
-static int bx_env_tiles(const char *name, int dflt_k) {
-  const char *e = getenv(name);
-  int ft = (e ? atoi(e) : dflt_k) / BK;
-  return ft < 1 ? 1 : ft;
-}
-static int bx_flush_tiles() { static int ft = -1; if (ft < 0) ft = bx_env_tiles("VIVIT_BX_FLUSH", 4096); return ft; }
-static int bx_flush_diag() { static int ft = -1; if (ft < 0) ft = bx_env_tiles("VIVIT_BX_FLUSH_DIAG", 4096); return ft; }
-static int bx_flush_internal() { static int ft = -1; if (ft < 0) ft = bx_env_tiles("VIVIT_BX_FLUSH_INTERNAL", 8192); return ft; }
-static int bx_flush_splitk() { static int ft = -1; if (ft < 0) ft = bx_env_tiles("VIVIT_BX_FLUSH_SPLITK", 1024); return ft; }
+// products on orthogonal factors (random signs, the measured off-diagonal case) keep 8192.  The chain lengths were swept
+// in profiles/r03_flush_sweep_n5120.log.
+constexpr int bx_flush_tiles = 4096 / BK;
+constexpr int bx_flush_diag = 4096 / BK;
+constexpr int bx_flush_internal = 8192 / BK;
+constexpr int bx_flush_splitk = 1024 / BK;
 
 // columns of an operand split at a time (workspace: 6 bytes per element of the chunk and operand)
 // Public products (the Gram SYRKs of the caller) take ONE accumulation chain per launch (round 4): 4096 columns instead of
 // 65 536 made the headline Gram build 3-4 % faster on four boxes (2.78-2.80 -> 2.67-2.71 s; 32 768: - 1.5 %, 16 384: - 2.5 %,
 // 6144 = a chain and a half: worse than either neighbour, 2048: + 5 %) -- no flush in the middle of a launch, and the
 // workgroups of an XCD start every chain together again (they drift apart by whole tiles otherwise, which is what the
-// re-fetch traffic of section 4.1b pays for).  The eigensolver's internal products keep 65 536 (their step was 12 ms
-// slower with the short chunks).  VIVIT_GEMM_SPLIT_KC sets both.
+// re-fetch traffic of section 4.1b pays for; a start barrier per XCD group on top of that was 1 % slower,
+// profiles/r06_syrk_env_sync.log).  The eigensolver's internal products keep 65 536 (their step was 12 ms slower with the
+// short chunks).
 static int64_t bx_chunk_cols(int64_t K, bool pub) {
-  static int64_t kc_env = -2;
-  if (kc_env == -2) {
-    const char *e = getenv("VIVIT_GEMM_SPLIT_KC");
-    kc_env = e ? atoll(e) / 16 * 16 : -1;
-    if (e && kc_env < 16) kc_env = 16;
-  }
-  const int64_t kc = kc_env > 0 ? kc_env : (pub ? (int64_t)bx_flush_tiles() * BK : 65536);
+  const int64_t kc = pub ? (int64_t)bx_flush_tiles * BK : 65536;
   return K < kc ? K : kc;
 }
 static bool bx_public_product();
@@ -2280,19 +2222,9 @@ static size_t bx_piece_bytes(int64_t M, int64_t N, int64_t K, bool same) {
   return (size_t)6 * (size_t)kc * (size_t)(same ? ra : ra + rb);
 }
 // pieces of one chunk + one range flag per chunk (BX_GATE)
-// XCD-group start barrier of the bf16-pipe kernel (experiment, VIVIT_BX_SYNC=1): counters per launch
-static bool bx_sync_enabled() {
-  static int on = -1;
-  if (on < 0) { const char *e = getenv("VIVIT_BX_SYNC"); on = e ? atoi(e) : 0; }
-  return on != 0;
-}
-static size_t bx_sync_ints(int64_t M, int64_t N) {   // upper bound of 8 x (number of super-blocks)
-  const int64_t tm = cdiv(M, B2), tn = cdiv(N, B2);
-  return (size_t)8 * (size_t)(tm * tn / 256 + tm + tn + 2);
-}
 static size_t bx_workspace_bytes(int64_t M, int64_t N, int64_t K, bool same) {
   const size_t nch = (size_t)cdiv(K, bx_chunk_cols(K, true));   // (the larger of the two counts)
-  return bx_piece_bytes(M, N, K, same) + 256 + 4 * nch + 256 + (bx_sync_enabled() ? 4 * nch * bx_sync_ints(M, N) + 256 : 0);
+  return bx_piece_bytes(M, N, K, same) + 256 + 4 * nch + 256;
 }
 
 // Which range flags send a chunk to the fp32 MFMA kernel.  The public products (vivit_gram_syrk_f32, vivit_gemm_*_f32)
@@ -2356,16 +2288,14 @@ static int gemm256_launch(int alay, int blay, GemmArgs p, bool syrk, void *works
   const int max_split = workspace ? (int)(workspace_bytes / slab1 < 32 ? workspace_bytes / slab1 : 32) : 1;
   gemm256_plan(p.M, p.N, p.K, syrk, &p.ksplit, &p.kchunk, max_split < 1 ? 1 : max_split);
   // the bf16-pipe kernel has no split-K: a last round of workgroups that is not full costs less than its 1.6x speed
-  const bool bx_same = p.A == p.B && p.lda == p.ldb && p.M == p.N && alay == blay;
-  if (gemm_split_mode() != 0 && workspace && workspace_bytes >= bx_workspace_bytes(p.M, p.N, p.K, bx_same)) {
+  const int bx = gemm_split_mode();
+  const bool same = p.A == p.B && p.lda == p.ldb && p.M == p.N && alay == blay;
+  const bool on_bx = bx != 0 && workspace && workspace_bytes >= bx_workspace_bytes(p.M, p.N, p.K, same);
+  if (on_bx) {
     p.ksplit = 1;
     p.kchunk = cdiv(p.K, BK) * BK;
   }
   p.slab = p.ksplit > 1 ? static_cast<float *>(workspace) : nullptr;
-  if (getenv("VIVIT_GEMM_DEBUG"))
-    fprintf(stderr, "gemm256: M=%lld N=%lld K=%lld syrk=%d ksplit=%d kchunk=%lld max_split=%d lay=%d%d bxws=%d\n", (long long)p.M,
-            (long long)p.N, (long long)p.K, (int)syrk, p.ksplit, (long long)p.kchunk, max_split, alay, blay,
-            (int)(workspace && workspace_bytes >= bx_workspace_bytes(p.M, p.N, p.K, bx_same)));
   p.tiles_m = (int)cdiv(p.M, B2);
   p.tiles_n = (int)cdiv(p.N, B2);
   p.syrk = syrk ? 1 : 0;
@@ -2380,12 +2310,9 @@ static int gemm256_launch(int alay, int blay, GemmArgs p, bool syrk, void *works
   dim3 grid((unsigned)(nsb * 256), (unsigned)p.ksplit, 1);
   const bool prof = syrk && p.A == p.B && prof_enabled() && bx_public_product();
   if (prof) prof_begin(0, (double)p.M * (double)(p.M + 1) * (double)p.K, stream);
-  const int bx = gemm_split_mode();
-  if (bx != 0 && p.ksplit == 1 && workspace &&
-      workspace_bytes >= bx_workspace_bytes(p.M, p.N, p.K, p.A == p.B && p.lda == p.ldb && p.M == p.N && alay == blay)) {
+  if (on_bx) {
     // fp32 product on the bf16 pipe: K in chunks of BX_KC columns, per chunk the operand pieces (bx_split_kernel)
     // and one pure-bf16 launch that accumulates into C (beta = 1 from the second chunk on)
-    const bool same = p.A == p.B && p.lda == p.ldb && p.M == p.N && alay == blay;
     const int64_t kc_max = bx_chunk_cols(p.K, bx_public_product());
     const int64_t nrbA = cdiv(p.M, 32), nrbB = cdiv(p.N, 32);
     unsigned short *PA = static_cast<unsigned short *>(workspace);
@@ -2393,11 +2320,7 @@ static int gemm256_launch(int alay, int blay, GemmArgs p, bool syrk, void *works
     unsigned short *PB = same ? PA : PA + 3 * strideA;
     int *flags = reinterpret_cast<int *>(align_up(reinterpret_cast<uintptr_t>(workspace) + bx_piece_bytes(p.M, p.N, p.K, same), 256));
     const int64_t nchunks = cdiv(p.K, kc_max);
-    int *sync = nullptr;
-    const size_t sync_ints = bx_sync_ints(p.M, p.N);
-    if (bx_sync_enabled()) sync = reinterpret_cast<int *>(align_up(reinterpret_cast<uintptr_t>(flags + nchunks), 256));
-    if (hipMemsetAsync(flags, 0, 4 * (size_t)nchunks + (sync ? 256 + 4 * (size_t)nchunks * sync_ints : 0), stream) != hipSuccess)
-      return VIVIT_E_LAUNCH;
+    if (hipMemsetAsync(flags, 0, 4 * (size_t)nchunks, stream) != hipSuccess) return VIVIT_E_LAUNCH;
     GemmBxArgs q;
     q.A = PA; q.B = PB; q.strideA = strideA; q.strideB = same ? strideA : strideB;
     q.nrbA = nrbA; q.nrbB = same ? nrbA : nrbB;
@@ -2407,8 +2330,8 @@ static int gemm256_launch(int alay, int blay, GemmArgs p, bool syrk, void *works
     q.gate_mask = tls_bx_gate_mask;
     // the eigensolver's own products (orthogonal factors: sums of random signs, nothing correlated) keep chains of 8192
     const bool internal = tls_bx_gate_mask == BX_GATE_RANGE;
-    q.flush_tiles = internal ? bx_flush_internal() : bx_flush_tiles();
-    q.flush_diag = internal ? bx_flush_internal() : bx_flush_diag();
+    q.flush_tiles = internal ? bx_flush_internal : bx_flush_tiles;
+    q.flush_diag = internal ? bx_flush_internal : bx_flush_diag;
     float beta0 = p.beta;
     if (beta0 != 0.f && beta0 != 1.f) {   // the in-loop flushes add into C: C <- beta C once, then beta = 1
       scale_c_kernel<<<(unsigned)cdiv(p.M * p.N, 256), 256, 0, stream>>>(p.C, p.M, p.N, p.ldc, beta0);
@@ -2420,22 +2343,18 @@ static int gemm256_launch(int alay, int blay, GemmArgs p, bool syrk, void *works
       const int64_t kc = (p.K - k0) < kc_max ? (p.K - k0) : kc_max;
       const unsigned gy = (unsigned)cdiv(kc / 16, 4);
       int *flag = flags + chunk;
-      if (alay == LAY_K)
-        bx_split_kernel<LAY_K><<<dim3((unsigned)nrbA, gy), 256, 0, stream>>>(p.A, p.M, p.lda, k0, kc, PA, strideA, nrbA, flag);
-      else
-        bx_split_kernel<LAY_M><<<dim3((unsigned)nrbA, gy), 256, 0, stream>>>(p.A, p.M, p.lda, k0, kc, PA, strideA, nrbA, flag);
-      if (!same) {
-        if (blay == LAY_K)
-          bx_split_kernel<LAY_K><<<dim3((unsigned)nrbB, gy), 256, 0, stream>>>(p.B, p.N, p.ldb, k0, kc, PB, strideB, nrbB, flag);
-        else
-          bx_split_kernel<LAY_M><<<dim3((unsigned)nrbB, gy), 256, 0, stream>>>(p.B, p.N, p.ldb, k0, kc, PB, strideB, nrbB, flag);
-      }
+      with_layout(alay, [&](auto L) {
+        bx_split_kernel<L><<<dim3((unsigned)nrbA, gy), 256, 0, stream>>>(p.A, p.M, p.lda, k0, kc, PA, strideA, nrbA, flag);
+      });
+      if (!same)
+        with_layout(blay, [&](auto L) {
+          bx_split_kernel<L><<<dim3((unsigned)nrbB, gy), 256, 0, stream>>>(p.B, p.N, p.ldb, k0, kc, PB, strideB, nrbB, flag);
+        });
       q.K = kc;
       q.beta = k0 == 0 ? beta0 : 1.f;
       // SYRK: only the last chunk mirrors the finished lower tiles into the upper triangle (2 = lower tiles, no mirror)
       q.syrk = (p.syrk == 1 && k0 + kc < p.K) ? 2 : p.syrk;
       q.gate = flag;
-      q.sync = sync ? sync + chunk * (int64_t)sync_ints : nullptr;
       if (bx == 6)
         bx_launch6(grid, q, stream);
       else if (bx == 9)
@@ -2453,14 +2372,7 @@ static int gemm256_launch(int alay, int blay, GemmArgs p, bool syrk, void *works
       f.a_vec = ((reinterpret_cast<uintptr_t>(f.A) & 15) == 0 && (f.lda & 3) == 0) ? 1 : 0;
       f.b_vec = ((reinterpret_cast<uintptr_t>(f.B) & 15) == 0 && (f.ldb & 3) == 0) ? 1 : 0;
       f.gate = flag; f.gate_mask = q.gate_mask;
-      if (alay == LAY_K && blay == LAY_K)
-        gemm256_kernel<LAY_K, LAY_K><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f);
-      else if (alay == LAY_K && blay == LAY_M)
-        gemm256_kernel<LAY_K, LAY_M><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f);
-      else if (alay == LAY_M && blay == LAY_K)
-        gemm256_kernel<LAY_M, LAY_K><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f);
-      else
-        gemm256_kernel<LAY_M, LAY_M><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f);
+      with_layouts(alay, blay, [&](auto LA, auto LB) { gemm256_kernel<LA, LB><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f); });
       st = launch_status();
     }
     if (st == VIVIT_OK && p.syrk == 1) {
@@ -2470,14 +2382,7 @@ static int gemm256_launch(int alay, int blay, GemmArgs p, bool syrk, void *works
     if (prof) prof_end(0, stream);
     return st;
   }
-  if (alay == LAY_K && blay == LAY_K)
-    gemm256_kernel<LAY_K, LAY_K><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(p);
-  else if (alay == LAY_K && blay == LAY_M)
-    gemm256_kernel<LAY_K, LAY_M><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(p);
-  else if (alay == LAY_M && blay == LAY_K)
-    gemm256_kernel<LAY_M, LAY_K><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(p);
-  else
-    gemm256_kernel<LAY_M, LAY_M><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(p);
+  with_layouts(alay, blay, [&](auto LA, auto LB) { gemm256_kernel<LA, LB><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(p); });
   int st = launch_status();
   if (st == VIVIT_OK && p.ksplit > 1) {
     gemm_reduce_kernel<<<(unsigned)cdiv(p.M * p.N, 256), 256, 0, stream>>>(p.slab, p.C, p.M, p.N, p.ldc, p.ksplit, p.alpha,
@@ -2553,16 +2458,13 @@ static int bx_splitk_launch(int alay, int blay, const GemmArgs &p, bool syrk, vo
   const bool prof = syrk && same && prof_enabled() && bx_public_product();
   if (prof) prof_begin(0, (double)p.M * (double)(p.M + 1) * (double)p.K, stream);
   const unsigned gy = (unsigned)cdiv(p.K / 16, 4);
-  if (alay == LAY_K)
-    bx_split_kernel<LAY_K><<<dim3((unsigned)nrbA, gy), 256, 0, stream>>>(p.A, p.M, p.lda, 0, p.K, PA, strideA, nrbA, flag);
-  else
-    bx_split_kernel<LAY_M><<<dim3((unsigned)nrbA, gy), 256, 0, stream>>>(p.A, p.M, p.lda, 0, p.K, PA, strideA, nrbA, flag);
-  if (!same) {
-    if (blay == LAY_K)
-      bx_split_kernel<LAY_K><<<dim3((unsigned)nrbB, gy), 256, 0, stream>>>(p.B, p.N, p.ldb, 0, p.K, PB, strideB, nrbB, flag);
-    else
-      bx_split_kernel<LAY_M><<<dim3((unsigned)nrbB, gy), 256, 0, stream>>>(p.B, p.N, p.ldb, 0, p.K, PB, strideB, nrbB, flag);
-  }
+  with_layout(alay, [&](auto L) {
+    bx_split_kernel<L><<<dim3((unsigned)nrbA, gy), 256, 0, stream>>>(p.A, p.M, p.lda, 0, p.K, PA, strideA, nrbA, flag);
+  });
+  if (!same)
+    with_layout(blay, [&](auto L) {
+      bx_split_kernel<L><<<dim3((unsigned)nrbB, gy), 256, 0, stream>>>(p.B, p.N, p.ldb, 0, p.K, PB, strideB, nrbB, flag);
+    });
   GemmBxArgs q;
   q.A = PA; q.B = PB; q.strideA = strideA; q.strideB = same ? strideA : strideB;
   q.nrbA = nrbA; q.nrbB = same ? nrbA : nrbB;
@@ -2573,9 +2475,8 @@ static int bx_splitk_launch(int alay, int blay, const GemmArgs &p, bool syrk, vo
   q.sbw = sbw;
   q.slab = slab; q.kt_split = kts;
   q.gate = flag; q.gate_mask = tls_bx_gate_mask;
-  q.flush_tiles = bx_flush_splitk();
-  q.flush_diag = bx_flush_diag();
-  q.sync = nullptr;
+  q.flush_tiles = bx_flush_splitk;
+  q.flush_diag = bx_flush_diag;
   const int64_t sbm = cdiv(q.tiles_m, sbh), sbn = cdiv(q.tiles_n, sbw);
   const int64_t nsb = syrk ? sbm * (sbm + 1) / 2 : sbm * sbn;
   dim3 grid((unsigned)(nsb * 256), (unsigned)nsplit);
@@ -2594,14 +2495,7 @@ static int bx_splitk_launch(int alay, int blay, const GemmArgs &p, bool syrk, vo
     f.tiles_m = q.tiles_m; f.tiles_n = q.tiles_n; f.syrk = q.syrk; f.sbw = q.sbw; f.desc = nullptr;
     f.a_vec = f.b_vec = 1;
     f.gate = flag; f.gate_mask = q.gate_mask;
-    if (alay == LAY_K && blay == LAY_K)
-      gemm256_kernel<LAY_K, LAY_K><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f);
-    else if (alay == LAY_K && blay == LAY_M)
-      gemm256_kernel<LAY_K, LAY_M><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f);
-    else if (alay == LAY_M && blay == LAY_K)
-      gemm256_kernel<LAY_M, LAY_K><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f);
-    else
-      gemm256_kernel<LAY_M, LAY_M><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f);
+    with_layouts(alay, blay, [&](auto LA, auto LB) { gemm256_kernel<LA, LB><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f); });
     st = launch_status();
     if (st != VIVIT_OK) return st;
   }
@@ -2727,21 +2621,12 @@ static int gemm64_launch(int alay, int blay, GemmArgs p, void *workspace, size_t
   p.desc = nullptr;
   dim3 grid((unsigned)p.tiles_n, (unsigned)p.ksplit, 1);
   auto launch_dma = [&](const GemmArgs &q) {
-    if (alay == LAY_K && blay == LAY_K)
-      gemm64_dma_kernel<LAY_K, LAY_K><<<grid, 256, GEMM64_LDS_BYTES, stream>>>(q);
-    else if (alay == LAY_K && blay == LAY_M)
-      gemm64_dma_kernel<LAY_K, LAY_M><<<grid, 256, GEMM64_LDS_BYTES, stream>>>(q);
-    else if (alay == LAY_M && blay == LAY_K)
-      gemm64_dma_kernel<LAY_M, LAY_K><<<grid, 256, GEMM64_LDS_BYTES, stream>>>(q);
-    else
-      gemm64_dma_kernel<LAY_M, LAY_M><<<grid, 256, GEMM64_LDS_BYTES, stream>>>(q);
+    with_layouts(alay, blay, [&](auto LA, auto LB) { gemm64_dma_kernel<LA, LB><<<grid, 256, GEMM64_LDS_BYTES, stream>>>(q); });
   };
   const unsigned kt = (unsigned)(p.K / BK);
   if (strict) {
-    if (alay == LAY_K) g64_split_a_kernel<LAY_K, true><<<kt, 128, 0, stream>>>(p.A, p.lda, p.M, apieces, flag);
-    else g64_split_a_kernel<LAY_M, true><<<kt, 128, 0, stream>>>(p.A, p.lda, p.M, apieces, flag);
-    if (blay == LAY_K) gemm64_bx_kernel<LAY_K, true><<<grid, 256, GEMM64X_LDS_BYTES, stream>>>(p, apieces, flag);
-    else gemm64_bx_kernel<LAY_M, true><<<grid, 256, GEMM64X_LDS_BYTES, stream>>>(p, apieces, flag);
+    with_layout(alay, [&](auto L) { g64_split_a_kernel<L, true><<<kt, 128, 0, stream>>>(p.A, p.lda, p.M, apieces, flag); });
+    with_layout(blay, [&](auto L) { gemm64_bx_kernel<L, true><<<grid, 256, GEMM64X_LDS_BYTES, stream>>>(p, apieces, flag); });
     int st = launch_status();
     if (st != VIVIT_OK) return st;
     GemmArgs f = p;
@@ -2749,10 +2634,8 @@ static int gemm64_launch(int alay, int blay, GemmArgs p, void *workspace, size_t
     f.gate_mask = tls_bx_gate_mask;
     launch_dma(f);
   } else if (bx) {   // products on the bf16 pipe: split the 64-row operand once, then stream
-    if (alay == LAY_K) g64_split_a_kernel<LAY_K><<<kt, 128, 0, stream>>>(p.A, p.lda, p.M, apieces, nullptr);
-    else g64_split_a_kernel<LAY_M><<<kt, 128, 0, stream>>>(p.A, p.lda, p.M, apieces, nullptr);
-    if (blay == LAY_K) gemm64_bx_kernel<LAY_K><<<grid, 256, GEMM64X_LDS_BYTES, stream>>>(p, apieces, nullptr);
-    else gemm64_bx_kernel<LAY_M><<<grid, 256, GEMM64X_LDS_BYTES, stream>>>(p, apieces, nullptr);
+    with_layout(alay, [&](auto L) { g64_split_a_kernel<L><<<kt, 128, 0, stream>>>(p.A, p.lda, p.M, apieces, nullptr); });
+    with_layout(blay, [&](auto L) { gemm64_bx_kernel<L><<<grid, 256, GEMM64X_LDS_BYTES, stream>>>(p, apieces, nullptr); });
   } else {
     launch_dma(p);
   }
@@ -2784,29 +2667,19 @@ int gemm_launch(int alay, int blay, const float *A, const float *B, float *C, in
   p.A = A; p.B = B; p.C = C;
   p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
   p.alpha = alpha; p.beta = beta;
-  {
-    const bool vec = (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (lda & 3) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0 &&
-                     (ldb & 3) == 0 && (alay == LAY_K || (M & 3) == 0) && (blay == LAY_K || (N & 3) == 0);
-    const int64_t Kmain = K / BK * BK;
-    if (vec && gemm256_plan(M, N, Kmain, syrk, nullptr, nullptr)) {
-      p.K = Kmain;
-      int st = gemm256_launch(alay, blay, p, syrk, workspace, workspace_bytes, stream);
-      if (st != VIVIT_OK || Kmain == K) return st;
-      // ragged K tail (< 16) through the small-tile kernel, accumulating
-      const float *At = A + (alay == LAY_K ? Kmain : Kmain * lda), *Bt = B + (blay == LAY_K ? Kmain : Kmain * ldb);
-      return gemm_launch(alay, blay, At, Bt, C, M, N, K - Kmain, lda, ldb, ldc, alpha, 1.f, syrk, workspace, workspace_bytes, stream);
-    }
-  }
-  {
+  {  // the 256-tile kernels (first the plain launch, then the bf16-pipe split-K) take K / BK whole tiles
     const bool vec = (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (lda & 3) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0 &&
                      (ldb & 3) == 0 && (alay == LAY_K || (M & 3) == 0) && (blay == LAY_K || (N & 3) == 0);
     const int64_t Kmain = K / BK * BK;
     const bool same = A == B && lda == ldb && M == N && alay == blay;
+    const bool on256 = vec && gemm256_plan(M, N, Kmain, syrk, nullptr, nullptr);
     size_t need = 0;
-    if (vec && bx_splitk_shape(M, N, Kmain, syrk, same, nullptr, nullptr, &need) && workspace && workspace_bytes >= need) {
+    if (on256 || (vec && bx_splitk_shape(M, N, Kmain, syrk, same, nullptr, nullptr, &need) && workspace && workspace_bytes >= need)) {
       p.K = Kmain;
-      int st = bx_splitk_launch(alay, blay, p, syrk, workspace, workspace_bytes, stream);
+      const int st = on256 ? gemm256_launch(alay, blay, p, syrk, workspace, workspace_bytes, stream)
+                           : bx_splitk_launch(alay, blay, p, syrk, workspace, workspace_bytes, stream);
       if (st != VIVIT_OK || Kmain == K) return st;
+      // ragged K tail (< 16) through the small-tile kernel, accumulating
       const float *At = A + (alay == LAY_K ? Kmain : Kmain * lda), *Bt = B + (blay == LAY_K ? Kmain : Kmain * ldb);
       return gemm_launch(alay, blay, At, Bt, C, M, N, K - Kmain, lda, ldb, ldc, alpha, 1.f, syrk, workspace, workspace_bytes, stream);
     }
@@ -2838,23 +2711,12 @@ int gemm_launch(int alay, int blay, const float *A, const float *B, float *C, in
   dim3 block(256, 1, 1);
   const bool prof = syrk && A == B && prof_enabled() && bx_public_product();  // only the caller's Gram SYRK is profiled as such
   if (prof) prof_begin(0, (double)M * (double)(M + 1) * (double)K, stream);
-  if (wm == 1) {
-    if (alay == LAY_K && blay == LAY_K)
-      gemm_kernel<LAY_K, LAY_K, 1><<<grid, block, 0, stream>>>(p);
-    else if (alay == LAY_K && blay == LAY_M)
-      gemm_kernel<LAY_K, LAY_M, 1><<<grid, block, 0, stream>>>(p);
-    else if (alay == LAY_M && blay == LAY_K)
-      gemm_kernel<LAY_M, LAY_K, 1><<<grid, block, 0, stream>>>(p);
+  with_layouts(alay, blay, [&](auto LA, auto LB) {
+    if (wm == 1)
+      gemm_kernel<LA, LB, 1><<<grid, block, 0, stream>>>(p);
     else
-      gemm_kernel<LAY_M, LAY_M, 1><<<grid, block, 0, stream>>>(p);
-  } else if (alay == LAY_K && blay == LAY_K)
-    gemm_kernel<LAY_K, LAY_K><<<grid, block, 0, stream>>>(p);
-  else if (alay == LAY_K && blay == LAY_M)
-    gemm_kernel<LAY_K, LAY_M><<<grid, block, 0, stream>>>(p);
-  else if (alay == LAY_M && blay == LAY_K)
-    gemm_kernel<LAY_M, LAY_K><<<grid, block, 0, stream>>>(p);
-  else
-    gemm_kernel<LAY_M, LAY_M><<<grid, block, 0, stream>>>(p);
+      gemm_kernel<LA, LB><<<grid, block, 0, stream>>>(p);
+  });
   if (prof) prof_end(0, stream);
   int st = launch_status();
   if (st != VIVIT_OK) return st;
@@ -2910,14 +2772,7 @@ int gemm_batched_launch(int alay, int blay, const GemmDesc *desc, int batch, int
   const int64_t nsb = cdiv(p.tiles_m, sbh) * cdiv(p.tiles_n, sbw);
   if (nsb * 256 > 0x7fffffffLL || batch > 65535) return VIVIT_E_UNSUPPORTED;
   dim3 grid((unsigned)(nsb * 256), 1, (unsigned)batch);
-  if (alay == LAY_K && blay == LAY_K)
-    gemm_kernel<LAY_K, LAY_K><<<grid, 256, 0, stream>>>(p);
-  else if (alay == LAY_K && blay == LAY_M)
-    gemm_kernel<LAY_K, LAY_M><<<grid, 256, 0, stream>>>(p);
-  else if (alay == LAY_M && blay == LAY_K)
-    gemm_kernel<LAY_M, LAY_K><<<grid, 256, 0, stream>>>(p);
-  else
-    gemm_kernel<LAY_M, LAY_M><<<grid, 256, 0, stream>>>(p);
+  with_layouts(alay, blay, [&](auto LA, auto LB) { gemm_kernel<LA, LB><<<grid, 256, 0, stream>>>(p); });
   return launch_status();
 }
 

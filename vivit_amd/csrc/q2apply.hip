@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void q2_prepare_kernel(Q2Step a, Q2Win win, fl
 // Everything is computed TRANSPOSED so that the slab never leaves the registers: with the 32x32x2
 // MFMA the accumulator of  X^T = A * B  (lane (r, h) holds X[row r][4h + (e&3) + 8(e>>2)]) is, with
 // the k index permuted accordingly, exactly the B operand of the next product.  A wave owns 32 rows
-// of Zt (lane (r, h) keeps S[row r][8q + 4h .. +3], q = 0..23, as loaded by float4) and runs
+// of Zt (lane (r, h) keeps S[row r][8q + 4h .. +3], q = 0..23, loaded element by element) and runs
 //     W2^T = (T V) S^T,   U^T = V^T W2^T,   S -= U
 // per block with V and T V (prepared per block by q2_prepare_kernel: (S V^T) T^T = S (T V)^T saves the
 // product with T) read from LDS as A operands.  Structurally zero 32x32 tiles of V (parallelogram) and
@@ -123,12 +123,12 @@ __global__ __launch_bounds__(256) void q2_prepare_kernel(Q2Step a, Q2Win win, fl
 // Pairing two levels reads/writes 192 instead of 2 x 128 columns of Zt per row (the kernel is close
 // to HBM-bound) and halves the number of launches.  A 512-thread workgroup (8 waves, 2 per SIMD)
 // keeps both blocks' V and T V in LDS (135 KB) and walks over several 256-row slabs.
+// This 32-row form takes the Zt that q2_apply16_kernel below cannot: rows not 16-byte aligned, or n not a multiple of 4.
 constexpr int LDS_V = QWIN + 4;    // 132: conflict-free ds_read_b128 fragments
 constexpr int Q2_THREADS = 512;
 constexpr int Q2_SLAB = 32 * (Q2_THREADS / 64);  // 256 rows per workgroup iteration
 constexpr int Q2_NQ = 24;                        // float4 per lane: 192 window columns
 
-template <bool VEC>
 __global__ __launch_bounds__(Q2_THREADS) void q2_apply_kernel(Q2Step a, const float *__restrict__ Tbuf,
                                                               float *__restrict__ Zt, int64_t ldz, int nrows) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -184,38 +184,23 @@ __global__ __launch_bounds__(Q2_THREADS) void q2_apply_kernel(Q2Step a, const fl
   __syncthreads();
 
   const int64_t colg = (int64_t)wstart + 4 * h;  // + 8 q
-  // FAST: window completely inside the matrix and float4-aligned: unguarded loads/stores at
-  // immediate offsets from one base pointer (rows past the end read row 0 and are not stored)
-  const bool fast = VEC && wstart + 8 * Q2_NQ <= a.n;
   float4 s[Q2_NQ];
   for (int slab = blockIdx.x; slab < nslab; slab += gridDim.x) {
     __asm__ volatile("" ::: "memory");  // keep the (slab-invariant) V/T fragment reads inside the loop
     const int64_t row = (int64_t)slab * Q2_SLAB + wave * 32 + r;
     const bool rok = row < nrows;
     float *base = Zt + (rok ? row * ldz : 0);
-    if (fast) {
-      const float4 *b4 = reinterpret_cast<const float4 *>(base + colg);
 #pragma unroll
-      for (int q = 0; q < Q2_NQ; ++q) s[q] = b4[2 * q];
-    } else {
+    for (int q = 0; q < Q2_NQ; ++q) {
+      const int64_t c = colg + 8 * q;
+      float e[4];
 #pragma unroll
-      for (int q = 0; q < Q2_NQ; ++q) {
-        const int64_t c = colg + 8 * q;
-        if constexpr (VEC) {
-          const bool ok = rok && c < a.n;  // n % 4 == 0 and c % 4 == 0: all four in or out
-          const float4 x = *reinterpret_cast<const float4 *>(ok ? base + c : Zt);
-          s[q] = ok ? x : make_float4(0.f, 0.f, 0.f, 0.f);
-        } else {
-          float e[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const bool ok = rok && c + u < a.n;
-            const float x = *(ok ? base + c + u : Zt);
-            e[u] = ok ? x : 0.f;
-          }
-          s[q] = make_float4(e[0], e[1], e[2], e[3]);
-        }
+      for (int u = 0; u < 4; ++u) {
+        const bool ok = rok && c + u < a.n;
+        const float x = *(ok ? base + c + u : Zt);
+        e[u] = ok ? x : 0.f;
       }
+      s[q] = make_float4(e[0], e[1], e[2], e[3]);
     }
 
     auto apply = [&](auto q0tag, const float *__restrict__ bV, const float *__restrict__ bTV) {
@@ -291,23 +276,13 @@ __global__ __launch_bounds__(Q2_THREADS) void q2_apply_kernel(Q2Step a, const fl
 
     // ---- store the slab back (same addresses as loaded)
     if (rok) {
-      if (fast) {
-        float4 *b4 = reinterpret_cast<float4 *>(base + colg);
 #pragma unroll
-        for (int q = 0; q < Q2_NQ; ++q) b4[2 * q] = s[q];
-      } else {
+      for (int q = 0; q < Q2_NQ; ++q) {
+        const int64_t c = colg + 8 * q;
+        const float e[4] = {s[q].x, s[q].y, s[q].z, s[q].w};
 #pragma unroll
-        for (int q = 0; q < Q2_NQ; ++q) {
-          const int64_t c = colg + 8 * q;
-          if constexpr (VEC) {
-            if (c < a.n) *reinterpret_cast<float4 *>(base + c) = s[q];
-          } else {
-            const float e[4] = {s[q].x, s[q].y, s[q].z, s[q].w};
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-              if (c + u < a.n) base[c + u] = e[u];
-          }
-        }
+        for (int u = 0; u < 4; ++u)
+          if (c + u < a.n) base[c + u] = e[u];
       }
     }
   }
@@ -481,8 +456,7 @@ int q2_apply_launch(float *Zt, int64_t ldz, int64_t nrows, int64_t n, const floa
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return VIVIT_E_LAUNCH;
     if (!(attr_done & (1ull << (dev & 63)))) {
-      if (!ensure_dynamic_lds(reinterpret_cast<const void *>(q2_apply_kernel<true>), Q2_LDS_BYTES, attr_done) ||
-          !ensure_dynamic_lds(reinterpret_cast<const void *>(q2_apply_kernel<false>), Q2_LDS_BYTES, attr_done) ||
+      if (!ensure_dynamic_lds(reinterpret_cast<const void *>(q2_apply_kernel), Q2_LDS_BYTES, attr_done) ||
           !ensure_dynamic_lds(reinterpret_cast<const void *>(q2_apply16_kernel), Q2_LDS_BYTES, attr_done))
         return VIVIT_E_LAUNCH;
       attr_done |= 1ull << (dev & 63);
@@ -540,14 +514,10 @@ int q2_apply_launch(float *Zt, int64_t ldz, int64_t nrows, int64_t n, const floa
           if (score > best + 1e-9) { best = score; gx = c; }
         }
       }
-      static int wave16 = -1;
-      if (wave16 < 0) { const char *e = getenv("VIVIT_Q2_WAVE16"); wave16 = e ? atoi(e) : 1; }   // (0: the 32-row form)
-      if (vec && wave16)
+      if (vec)
         q2_apply16_kernel<<<dim3((unsigned)gx, nblk), Q2W_THREADS, Q2_LDS_BYTES, stream>>>(a, TV, Zt, ldz, (int)nrows);
-      else if (vec)
-        q2_apply_kernel<true><<<dim3((unsigned)gx, nblk), Q2_THREADS, Q2_LDS_BYTES, stream>>>(a, TV, Zt, ldz, (int)nrows);
       else
-        q2_apply_kernel<false><<<dim3((unsigned)gx, nblk), Q2_THREADS, Q2_LDS_BYTES, stream>>>(a, TV, Zt, ldz, (int)nrows);
+        q2_apply_kernel<<<dim3((unsigned)gx, nblk), Q2_THREADS, Q2_LDS_BYTES, stream>>>(a, TV, Zt, ldz, (int)nrows);
     }
   }
   return launch_status();

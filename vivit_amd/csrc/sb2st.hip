@@ -391,13 +391,11 @@ __global__ __launch_bounds__(256) void sb2st_zero_kernel(float *__restrict__ tau
   if (i < nk) tau2[(int64_t)(n - 1) * nk + i] = 0.f;                       // control block
 }
 
-__global__ void sb2st_poison_kernel(const Sb2stCtl *ctl, int n, float *__restrict__ d, int *__restrict__ tmo) {
+__global__ void sb2st_poison_kernel(const Sb2stCtl *ctl, float *__restrict__ d, int *__restrict__ tmo) {
   if (ctl->dead) {
     d[0] = __builtin_nanf("");
     __hip_atomic_fetch_or(tmo, PERSIST_TMO_SB2ST, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  if (n < 0) printf("sb2st persist: mask 0x%x 0x%x dead %d tickets %d %d %d %d %d %d %d %d\n", ctl->mask[0], ctl->mask[1], ctl->dead, ctl->ticket[0], ctl->ticket[1],
-                    ctl->ticket[2], ctl->ticket[3], ctl->ticket[4], ctl->ticket[5], ctl->ticket[6], ctl->ticket[7]);
 }
 
 __global__ __launch_bounds__(256) void sb2st_extract_kernel(const float *__restrict__ AB, int n, float *__restrict__ d,
@@ -452,7 +450,7 @@ int sb2st_launch(float *AB, int64_t n, float *d, float *e, float *R2, int64_t ld
     for (int attempt = 0; attempt < 2; ++attempt)
       sb2st_persist_kernel<<<256, 256, 0, stream>>>(AB, ni, R2, ldr, tau2, nk, (int)r2rows, ctl, attempt, persist_fault());
     sb2st_extract_kernel<<<(unsigned)cdiv(n, 256), 256, 0, stream>>>(AB, ni, d, e);
-    sb2st_poison_kernel<<<1, 1, 0, stream>>>(ctl, getenv("VIVIT_SB2ST_DEBUG") ? -ni : ni, d, tmo);
+    sb2st_poison_kernel<<<1, 1, 0, stream>>>(ctl, d, tmo);
     return launch_status();
   }
   if (n >= 3) {

@@ -574,14 +574,9 @@ __global__ __launch_bounds__(256) void skinny64_kernel(Sk64Args p) {
 }
 
 // applicable: 16-byte aligned rows everywhere, K a multiple of 32, N a multiple of 4
-static bool skinny64_enabled() {
-  static int on = -1;
-  if (on < 0) { const char *e = getenv("VIVIT_SY2SB_FUSED"); on = e ? atoi(e) : 1; }
-  return on != 0;
-}
 static bool skinny64_launch(const float *Coef, int64_t ldcoef, const float *B, int64_t ldb, float *Out, int64_t ldo, int64_t N, int64_t K,
                             float alpha, float beta, hipStream_t stream) {
-  if (!skinny64_enabled() || K < 32 || K % 32 != 0 || K > 4096 || N % 4 != 0 || ldb % 4 != 0 || ldcoef % 4 != 0 ||
+  if (K < 32 || K % 32 != 0 || K > 4096 || N % 4 != 0 || ldb % 4 != 0 || ldcoef % 4 != 0 ||
       (reinterpret_cast<uintptr_t>(Coef) & 15) || (reinterpret_cast<uintptr_t>(B) & 15))
     return false;
   Sk64Args a;
@@ -793,7 +788,7 @@ int sy2sb_launch(float *A, int64_t n, int64_t lda, void *wsbase, float **tau1_ou
   // Row mode (16-byte aligned rows, n % 4 == 0): the pending updates of a group go to the block ROW that holds the next panel
   // (64 x (n - j0): the 64-row MFMA kernel; the tall 64-column form on the tile kernels took 60-100 us per panel) and the panel
   // is read from there; the block column below the band then keeps stale values that nothing reads.
-  const bool rowmode = skinny64_enabled() && (n % 4 == 0) && (lda % 4 == 0) && (reinterpret_cast<uintptr_t>(A) & 15) == 0;
+  const bool rowmode = (n % 4 == 0) && (lda % 4 == 0) && (reinterpret_cast<uintptr_t>(A) & 15) == 0;
   auto factor_panel = [&](int64_t j0, float *v1, float *v2) -> int {
     const int64_t mp = n - j0 - SNB, gi0 = j0 + SNB;
     const int ncol = (int)(mp < SNB ? mp : SNB);

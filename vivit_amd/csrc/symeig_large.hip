@@ -81,9 +81,6 @@ __global__ void bt_merge_desc_kernel(const float *S, float *T, float *X, int64_t
 }
 
 static int bt_nsub(int64_t n) {   // largest super-block (workspace sizing)
-  static int forced = -2;
-  if (forced == -2) { const char *e = getenv("VIVIT_BT_NSUB"); forced = e ? atoi(e) : -1; }
-  if (forced > 0 && n >= 2048) return forced;   // (power of two; experiments)
   return n >= 16384 ? 16 : (n >= 8192 ? 8 : (n >= 4096 ? 4 : (n >= 2048 ? 2 : 1)));
 }
 // Super-block actually used for `nrows` rows of Zt: the read-modify-write of Zt per super-block favours 2048

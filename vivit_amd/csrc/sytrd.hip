@@ -572,12 +572,7 @@ int sytrd_launch(float *A, int64_t n, int64_t lda, float *wsbase, SytrdWs *out, 
   prescale_launch(A, n, lda, ws.scal, scanpart, stream);
   if (sytrd_persist_ok(n)) return sytrd_persist_launch(A, n, lda, ws, stream);   // one persistent launch on one XCD
 
-  // Debug knob for counter collection (rocprofv3 --pmc dies on >10^4 dispatches): stop after this
-  // many columns.  The factorisation is then incomplete and its outputs meaningless.
-  const char *stop_env = getenv("VIVIT_SYTRD_STOP_AFTER");
-  const int64_t stop_after = stop_env ? atoll(stop_env) : -1;
   for (int64_t j0 = 0; j0 < n - 2; j0 += PB) {
-    if (stop_after >= 0 && j0 >= stop_after) break;
     const int bb = (int)((n - 2 - j0) < PB ? (n - 2 - j0) : PB);
     if (hipMemsetAsync(ws.vw, 0, sizeof(float) * 3 * PB * n, stream) != hipSuccess) return VIVIT_E_LAUNCH;
     for (int jj = 0; jj < bb; ++jj) {
