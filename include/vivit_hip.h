@@ -66,7 +66,7 @@ int vivit_persistent_kernels(int on);
 int vivit_take_persist_timeout(int32_t *info, void *stream);
 
 /* Library/ABI version (major*1000 + minor) and the gfx target it was compiled for. */
-int vivit_hip_abi_version(void);   /* 1007 in this release; _lib.py refuses any other library */
+int vivit_hip_abi_version(void);   /* 1008 in this release; _lib.py refuses any other library */
 const char *vivit_hip_target(void);
 /* Provenance: the content hash (32 hex digits, vivit_amd/_build.py:source_hash) of the csrc/ tree + this header the library
  * was compiled from ("unknown" for a build that did not go through _build.py).  _lib.load() compares it with the sources
@@ -252,6 +252,25 @@ int vivit_ce_sqrt_hessian_f32(const float *logits, const float *onehot, float *S
 size_t vivit_symeig_f32_workspace_bytes(int64_t n, int want_vectors);
 int vivit_symeig_f32(float *A, int64_t n, int64_t lda, float *w, float *Z, int64_t ldz,
                      void *workspace, size_t workspace_bytes, int32_t *info, void *stream);
+
+/* Eigenvalues of `batch` symmetric matrices of ONE size in one call (block-diagonal curvature: one spectrum per layer).
+ *   A: HOST array of `batch` device pointers, each [n, n] with the common lda >= n; every matrix is DESTROYED, only its
+ *      lower triangle is read.  The array itself is read before the call returns.
+ *   W: [batch][n] device, row b = eigenvalues of A[b], ascending.   info: device int32 [batch], per problem as above.
+ * Any batch >= 1: processed in waves of eight on the stream; the workspace is that of min(batch, 8) problems.
+ *   n <= 192: the single-workgroup solver, one workgroup per problem, one launch per wave (no workspace).
+ *   193 <= n <= 1280: the persistent tridiagonalisation with one problem per XCD in ONE launch -- a single solve of
+ *     this size keeps its matrix in the registers of one XCD's 32 CUs and leaves the other seven XCDs idle.  Every
+ *     problem has its own arrival gate, counters and exchange buffers; the failure word is the stream's, so if any
+ *     problem's persistent kernel gives up, EVERY info word of that wave is VIVIT_INFO_PERSIST_TIMEOUT.  With the
+ *     persistent kernels switched off (vivit_persistent_kernels(0), VIVIT_SYTRD_PERSIST=0): the single solve, problem
+ *     after problem.
+ *   n > 1280: VIVIT_E_UNSUPPORTED (those sizes use the whole chip per problem: call vivit_symeig_f32 in a loop).
+ * On every route row b of W holds exactly the bytes vivit_symeig_f32(A[b], Z = NULL) writes.
+ * Not in the reference, which solves one group at a time (vivit/linalg/eigvalsh.py:221). */
+size_t vivit_symeigvals_batched_f32_workspace_bytes(int64_t n, int64_t batch);
+int vivit_symeigvals_batched_f32(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, void *workspace,
+                                 size_t workspace_bytes, int32_t *info, void *stream);
 
 /* Row-range variant for the multi-GPU path: all n eigenvalues (ascending) plus the eigenvectors
  * row_begin .. row_end-1 (in that order) as ROWS of Zt: [row_end - row_begin, n], ldz >= n.  Reduction and

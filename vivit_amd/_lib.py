@@ -49,6 +49,8 @@ SIGNATURES = {
     "vivit_ce_sqrt_hessian_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _f32, _ptr]),
     "vivit_symeig_f32_workspace_bytes": (_sz, [_i64, _int]),
     "vivit_symeig_f32": (_int, [_ptr, _i64, _i64, _ptr, _ptr, _i64, _ptr, _sz, _ptr, _ptr]),
+    "vivit_symeigvals_batched_f32_workspace_bytes": (_sz, [_i64, _i64]),
+    "vivit_symeigvals_batched_f32": (_int, [_ptr, _i64, _i64, _i64, _ptr, _ptr, _sz, _ptr, _ptr]),
     "vivit_symeig_rows_f32": (_int, [_ptr, _i64, _i64, _ptr, _ptr, _i64, _i64, _i64, _ptr, _sz, _ptr, _ptr]),
     "vivit_symeig_reduce_f32_workspace_bytes": (_sz, [_i64]),
     "vivit_symeig_select_f32_workspace_bytes": (_sz, [_i64, _i64]),
@@ -82,7 +84,7 @@ SIGNATURES = {
     "vivit_unpack_lower_f32": (_int, [_ptr, _i64, _ptr, _i64, _ptr]),
 }
 
-ABI_VERSION = 1007  # include/vivit_hip.h of this checkout (vivit_hip_abi_version)
+ABI_VERSION = 1008  # include/vivit_hip.h of this checkout (vivit_hip_abi_version)
 
 _lib = None
 

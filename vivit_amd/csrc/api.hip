@@ -5,6 +5,11 @@ namespace vivit {
 constexpr int SMALL_N_MAX = 192;
 int symeig_small_launch(const float *A, int64_t lda, int n, float *w, float *Z, int64_t ldz, int32_t *info,
                         hipStream_t stream);
+int symeig_small_batched_launch(const float *const *A, int64_t batch, int64_t lda, int n, float *W, int32_t *info,
+                                hipStream_t stream);
+size_t symeigvals_batched_workspace_bytes(int64_t n, int64_t batch);
+int symeigvals_batched_launch(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, void *ws, size_t ws_bytes,
+                              int32_t *info, hipStream_t stream);
 size_t symeig_large_workspace_bytes(int64_t n, bool vectors);
 int symeig_large_launch(float *A, int64_t n, int64_t lda, float *w, float *Z, int64_t ldz, void *ws, size_t ws_bytes,
                         int32_t *info, hipStream_t stream);
@@ -26,7 +31,7 @@ extern "C" {
 // from the content hash of the tree AND the digest of the compile flags of every object it links, so a library relinked
 // from product objects plus a differently-compiled one (timing-only variants) cannot carry the product's hash.
 
-int vivit_hip_abi_version(void) { return 1007; }
+int vivit_hip_abi_version(void) { return 1008; }
 const char *vivit_hip_target(void) { return "gfx950"; }
 
 const char *vivit_hip_status_string(int status) {
@@ -54,6 +59,26 @@ int vivit_symeig_f32(float *A, int64_t n, int64_t lda, float *w, float *Z, int64
   if (!A || !w || lda < n || (Z && ldz < n)) return VIVIT_E_BADARG;
   if (n <= SMALL_N_MAX) return symeig_small_launch(A, lda, (int)n, w, Z, ldz, info, s);
   return symeig_large_launch(A, n, lda, w, Z, ldz, workspace, workspace_bytes, info, s);
+}
+
+constexpr int BATCHED_N_MAX = 1280;   // the sizes whose matrix fits the registers of one XCD (sytrd_persist.hip)
+
+size_t vivit_symeigvals_batched_f32_workspace_bytes(int64_t n, int64_t batch) {
+  if (n <= SMALL_N_MAX || n > BATCHED_N_MAX || batch < 1) return 0;
+  return symeigvals_batched_workspace_bytes(n, batch);
+}
+
+// Eigenvalues of `batch` matrices of one size: one workgroup per problem (n <= 192) or one XCD per problem (n <= 1280).
+int vivit_symeigvals_batched_f32(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, void *workspace,
+                                 size_t workspace_bytes, int32_t *info, void *stream) {
+  if (!A || !W || !info || batch < 1 || n < 1 || lda < n) return VIVIT_E_BADARG;
+  for (int64_t i = 0; i < batch; ++i)
+    if (!A[i]) return VIVIT_E_BADARG;
+  if (n > BATCHED_N_MAX) return VIVIT_E_UNSUPPORTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n <= SMALL_N_MAX) return symeig_small_batched_launch(A, batch, lda, (int)n, W, info, s);
+  if (!workspace || workspace_bytes < symeigvals_batched_workspace_bytes(n, batch)) return VIVIT_E_WORKSPACE;
+  return symeigvals_batched_launch(A, batch, n, lda, W, workspace, workspace_bytes, info, s);
 }
 
 // Eigenvalues (all n, ascending) and the eigenvectors row_begin .. row_end-1 as ROWS of Zt [row_end-row_begin][ldz].

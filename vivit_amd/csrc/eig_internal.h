@@ -21,10 +21,17 @@ struct SytrdWs {
 // sytrd.hip
 size_t sytrd_workspace_floats(int64_t n);
 int sytrd_launch(float *A, int64_t n, int64_t lda, float *wsbase, SytrdWs *out, hipStream_t stream);
+// the same for `batch` <= PERSIST_MAX_BATCH matrices of one size with the persistent reduction (sytrd_persist_ok(n), n <= 1280):
+// prescale per problem, then one batched persistent launch (A, wsbase, out: host arrays of `batch`)
+int sytrd_batched_launch(float *const *A, int batch, int64_t n, int64_t lda, float *const *wsbase, SytrdWs *out,
+                         hipStream_t stream);
 
 // sytrd_persist.hip: the same reduction as one persistent launch on the 32 CUs of one XCD (n <= 1280; after prescale_launch)
 bool sytrd_persist_ok(int64_t n);
 int sytrd_persist_launch(float *A, int64_t n, int64_t lda, const SytrdWs &ws, hipStream_t stream);
+// up to PERSIST_MAX_BATCH problems of one size n <= 1280 in ONE launch, problem q on XCD q (A, ws: host arrays of `batch`)
+constexpr int PERSIST_MAX_BATCH = 8;
+int sytrd_persist_batched_launch(float *const *A, int batch, int64_t n, int64_t lda, const SytrdWs *ws, hipStream_t stream);
 
 // stedc.hip
 size_t stedc_workspace_bytes(int64_t n, bool vectors);
@@ -97,5 +104,12 @@ int q2_slide_launch(float *Zt, int64_t ldz, int64_t nrows, int64_t n, const floa
 
 // info = n when the scan flagged non-finite input (scal[2] != 0)
 int info_finalize_launch(int32_t *info, int64_t n, const float *scal, hipStream_t stream);
+// the same for info[0 .. batch-1] (batch <= PERSIST_MAX_BATCH, scal: host array): the sticky failure word is one per
+// stream, so a set bit fails EVERY problem of the batch
+int info_finalize_batched_launch(int32_t *info, int batch, int64_t n, const float *const *scal, hipStream_t stream);
+// symeig_large.hip: eigenvalues of `batch` matrices of one size 193 <= n <= 1280, in waves of PERSIST_MAX_BATCH
+size_t symeigvals_batched_workspace_bytes(int64_t n, int64_t batch);
+int symeigvals_batched_launch(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, void *ws, size_t ws_bytes,
+                              int32_t *info, hipStream_t stream);
 
 } // namespace vivit

@@ -563,6 +563,22 @@ __global__ void finalize_info_kernel(int32_t *info, int n, const float *__restri
   }
 }
 
+struct ScalPtrs {
+  const float *p[PERSIST_MAX_BATCH];
+};
+
+// finalize_info_kernel for info[0 .. batch-1]: the sticky word belongs to the stream, not to a problem, so a persistent
+// kernel that gave up on ANY problem fails the whole batch (the host repeats all of it on the launch chains)
+__global__ void finalize_info_batched_kernel(int32_t *info, int batch, int n, ScalPtrs scal, int *__restrict__ tmo) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const bool gave_up = tmo && *tmo != 0;
+  for (int q = 0; q < batch; ++q) {
+    if (gave_up) info[q] = VIVIT_INFO_PERSIST_TIMEOUT;
+    else if (scal.p[q][2] != 0.f) info[q] = n;
+  }
+  if (gave_up) *tmo = 0;
+}
+
 // ------------------------------------------------------------------------------------------
 static int dc_num_leaves(int64_t n) {
   int64_t nl = 1;
@@ -672,6 +688,14 @@ int stebz_launch(const float *d, const float *e, int64_t n, float *w, const floa
 
 int info_finalize_launch(int32_t *info, int64_t n, const float *scal, hipStream_t stream) {
   finalize_info_kernel<<<1, 64, 0, stream>>>(info, (int)n, scal, persist_timeout_word(stream));
+  return launch_status();
+}
+
+int info_finalize_batched_launch(int32_t *info, int batch, int64_t n, const float *const *scal, hipStream_t stream) {
+  if (batch < 1 || batch > PERSIST_MAX_BATCH) return VIVIT_E_UNSUPPORTED;
+  ScalPtrs sp = {};
+  for (int q = 0; q < batch; ++q) sp.p[q] = scal[q];
+  finalize_info_batched_kernel<<<1, 64, 0, stream>>>(info, batch, (int)n, sp, persist_timeout_word(stream));
   return launch_status();
 }
 

@@ -567,6 +567,52 @@ int symeig_large_launch(float *A, int64_t n, int64_t lda, float *w, float *Z, in
   return symeig_large_impl(A, n, lda, w, Z, ldz, 0, -1, ws, ws_bytes, info, stream);
 }
 
+// ---- eigenvalues of `batch` matrices of one size 193 <= n <= 1280 (vivit_symeigvals_batched_f32) -------------------------
+// One slot of symeig_large_workspace_bytes(n, false) per problem of a wave; the waves of PERSIST_MAX_BATCH follow each other
+// on the stream and reuse the slots, so the size stops growing at eight.
+static size_t batched_slot_bytes(int64_t n) { return align_up(symeig_large_workspace_bytes(n, false), 256); }
+
+size_t symeigvals_batched_workspace_bytes(int64_t n, int64_t batch) {
+  const int64_t slots = batch < PERSIST_MAX_BATCH ? batch : PERSIST_MAX_BATCH;
+  return batched_slot_bytes(n) * (size_t)slots + 256;
+}
+
+// With the persistent reduction allowed a wave is: prescale per problem -> ONE persistent launch, problem q on XCD q ->
+// bisection per problem -> one status kernel for the wave.  Every per-problem kernel is the one the single solve launches,
+// on the same kind of workspace: the eigenvalues are those of vivit_symeig_f32, bit for bit.  Without the persistent kernels
+// (or with the two-stage reduction forced) the problems run one after the other through the single solve itself.
+int symeigvals_batched_launch(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, void *ws, size_t ws_bytes,
+                              int32_t *info, hipStream_t stream) {
+  if (!ws || ws_bytes < symeigvals_batched_workspace_bytes(n, batch)) return VIVIT_E_WORKSPACE;
+  char *base = reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
+  const size_t slot = batched_slot_bytes(n);
+  if (use_two_stage(n, false) || !sytrd_persist_ok(n)) {
+    for (int64_t i = 0; i < batch; ++i) {
+      const int st = symeig_large_impl(A[i], n, lda, W + i * n, nullptr, 0, 0, -1, base, slot, info + i, stream);
+      if (st != VIVIT_OK) return st;
+    }
+    return VIVIT_OK;
+  }
+  if (hipMemsetAsync(info, 0, sizeof(int32_t) * batch, stream) != hipSuccess) return VIVIT_E_LAUNCH;
+  for (int64_t i0 = 0; i0 < batch; i0 += PERSIST_MAX_BATCH) {
+    const int nb = (int)(batch - i0 < PERSIST_MAX_BATCH ? batch - i0 : PERSIST_MAX_BATCH);
+    float *trd_base[PERSIST_MAX_BATCH];
+    const float *scal[PERSIST_MAX_BATCH];
+    SytrdWs tw[PERSIST_MAX_BATCH];
+    for (int q = 0; q < nb; ++q) trd_base[q] = reinterpret_cast<float *>(base + slot * q);
+    int st = sytrd_batched_launch(A + i0, nb, n, lda, trd_base, tw, stream);
+    if (st != VIVIT_OK) return st;
+    for (int q = 0; q < nb; ++q) {
+      st = stebz_launch(tw[q].d, tw[q].e, n, W + (i0 + q) * n, tw[q].scal, stream);
+      if (st != VIVIT_OK) return st;
+      scal[q] = tw[q].scal;
+    }
+    st = info_finalize_batched_launch(info + i0, nb, n, scal, stream);
+    if (st != VIVIT_OK) return st;
+  }
+  return VIVIT_OK;
+}
+
 int symeig_large_rows_launch(float *A, int64_t n, int64_t lda, float *w, float *Zt, int64_t ldz, int64_t r0, int64_t r1,
                              void *ws, size_t ws_bytes, int32_t *info, hipStream_t stream) {
   if (!Zt || r0 < 0 || r1 < r0 || r1 > n) return VIVIT_E_BADARG;

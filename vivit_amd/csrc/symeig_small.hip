@@ -19,9 +19,19 @@
 
 namespace vivit {
 
-__global__ __launch_bounds__(256) void symeig_small_kernel(const float *__restrict__ Ag, int64_t lda, int n,
-                                                           float *__restrict__ wout, float *__restrict__ Zg,
-                                                           int64_t ldz, int32_t *__restrict__ info) {
+// One workgroup per problem: workgroup b solves A[b] into w + b n and info + b (vivit_symeigvals_batched_f32 launches up
+// to SMALL_MAX_BATCH of them at once; the single solve is the same kernel with one workgroup, the only one that may ask for Z).
+constexpr int SMALL_MAX_BATCH = 8;
+struct SmallBatch {
+  const float *A[SMALL_MAX_BATCH];
+};
+
+__global__ __launch_bounds__(256) void symeig_small_kernel(SmallBatch mats, int64_t lda, int n, float *__restrict__ wbase,
+                                                           float *__restrict__ Zg, int64_t ldz,
+                                                           int32_t *__restrict__ infobase) {
+  const float *__restrict__ const Ag = mats.A[blockIdx.x];
+  float *__restrict__ const wout = wbase + (int64_t)blockIdx.x * n;
+  int32_t *__restrict__ const info = infobase + blockIdx.x;
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int LD = n | 1;
   float *A = sm;
@@ -200,20 +210,39 @@ size_t symeig_small_lds_bytes(int n) {
   return (size_t)(n * LD + 4 * n + 4 * n + 3 * n + 4 + n) * sizeof(float);
 }
 
+// the kernel's dynamic-LDS limit, raised once per device
+static bool small_lds_ready() {
+  static unsigned long long attr_done = 0;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return false;
+  if (!(attr_done & (1ull << (dev & 63)))) {
+    if (!ensure_dynamic_lds(reinterpret_cast<const void *>(symeig_small_kernel), (int)symeig_small_lds_bytes(SMALL_N_MAX),
+                            attr_done))
+      return false;
+    attr_done |= 1ull << (dev & 63);
+  }
+  return true;
+}
+
 int symeig_small_launch(const float *A, int64_t lda, int n, float *w, float *Z, int64_t ldz, int32_t *info,
                         hipStream_t stream) {
-  static unsigned long long attr_done = 0;
-  {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return VIVIT_E_LAUNCH;
-    if (!(attr_done & (1ull << (dev & 63)))) {
-      if (!ensure_dynamic_lds(reinterpret_cast<const void *>(symeig_small_kernel), (int)symeig_small_lds_bytes(SMALL_N_MAX),
-                              attr_done))
-        return VIVIT_E_LAUNCH;
-      attr_done |= 1ull << (dev & 63);
-    }
+  if (!small_lds_ready()) return VIVIT_E_LAUNCH;
+  SmallBatch mats = {};
+  mats.A[0] = A;
+  symeig_small_kernel<<<1, 256, symeig_small_lds_bytes(n), stream>>>(mats, lda, n, w, Z, ldz, info);
+  return launch_status();
+}
+
+// values only, `batch` problems (A: host array of device pointers), W [batch][n], info [batch]: one launch per eight problems
+int symeig_small_batched_launch(const float *const *A, int64_t batch, int64_t lda, int n, float *W, int32_t *info,
+                                hipStream_t stream) {
+  if (!small_lds_ready()) return VIVIT_E_LAUNCH;
+  for (int64_t i0 = 0; i0 < batch; i0 += SMALL_MAX_BATCH) {
+    const int nb = (int)(batch - i0 < SMALL_MAX_BATCH ? batch - i0 : SMALL_MAX_BATCH);
+    SmallBatch mats = {};
+    for (int q = 0; q < nb; ++q) mats.A[q] = A[i0 + q];
+    symeig_small_kernel<<<nb, 256, symeig_small_lds_bytes(n), stream>>>(mats, lda, n, W + i0 * n, nullptr, 0, info + i0);
   }
-  symeig_small_kernel<<<1, 256, symeig_small_lds_bytes(n), stream>>>(A, lda, n, w, Z, ldz, info);
   return launch_status();
 }
 

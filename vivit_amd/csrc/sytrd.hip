@@ -559,6 +559,17 @@ int prescale_launch(float *A, int64_t n, int64_t lda, float *scal, float *part, 
   return launch_status();
 }
 
+int sytrd_batched_launch(float *const *A, int batch, int64_t n, int64_t lda, float *const *wsbase, SytrdWs *out,
+                         hipStream_t stream) {
+  if (batch < 1 || batch > PERSIST_MAX_BATCH) return VIVIT_E_UNSUPPORTED;
+  for (int q = 0; q < batch; ++q) {
+    float *scanpart;
+    out[q] = sytrd_carve(wsbase[q], n, &scanpart);
+    prescale_launch(A[q], n, lda, out[q].scal, scanpart, stream);
+  }
+  return sytrd_persist_batched_launch(A, batch, n, lda, out, stream);
+}
+
 // Tridiagonalise A (n x n, lda).  On return ws.d / ws.e / ws.tau hold T and the reflector
 // scalars, A's upper-triangle rows hold the reflectors, ws.scal[1] the applied scaling sigma
 // and ws.scal[2] the non-finite-input flag.

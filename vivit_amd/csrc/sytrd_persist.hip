@@ -18,7 +18,11 @@
 //   * w = tau y - (tau^2 y.v / 2) v, the rank-2 update of the own rows and of the replica of row j + 1 -- which is then
 //     the current row j + 1 in every workgroup: the next column starts without another exchange.
 // Workgroups find themselves on one XCD because the dispatcher deals workgroup b to XCD b % 8: the launch has 256
-// workgroups, 224 return at once.  The first exchange compares the XCC ids; should they ever differ the stores become
+// workgroups, and problem q of the launch -- up to eight of one size, PersistBatch -- is served by the 32 with b % 8 == q
+// (a single solve is a batch of one: 224 workgroups return at once, seven XCDs idle; the reduction is bound by its ~n
+// exchanges through ONE L2, so only independent problems can use them).  Problems share nothing but the sticky failure
+// word: each has its own matrix, outputs, exchange buffers, XCC ids, arrival gate and counters in its own workspace and
+// never waits for another.  The first exchange compares the XCC ids; should they ever differ the stores become
 // agent-scope atomic stores (write-through), which is correct anywhere (4 us per exchange).  Every spin is bounded (2 s):
 // the grid always drains.  Co-residency is decided once, atomically, by the arrival gate (device_utils.h:persist_arrive):
 // an attempt that does not get all its workgroups resident within 2 s aborts WITHOUT having written anything, and the
@@ -44,8 +48,23 @@ struct PersistWs {
   float *rowbuf;   // [2][NP]
   int *counter;    // [32]: per attempt a (0 | 1) at 8 a: monotonic arrival counter, arrival-gate state
   int *xcc;        // [32] XCC id of each workgroup
-  int *tmo;        // the sticky failure word (persist_timeout_word)
-  int attempt;     // 0: first launch; 1: the retry behind it (runs only if attempt 0 aborted at its arrival gate)
+};
+
+// One problem of a launch: everything that is its own -- matrix, outputs, exchange buffers, arrival gate, counters.
+struct PersistProblem {
+  float *A;
+  int64_t lda;
+  SytrdWs ws;
+  PersistWs pw;
+};
+
+// The kernel's one argument, by value.  Problem q is served by the workgroups with blockIdx.x % 8 == q, which the dispatcher
+// deals to XCD q: up to eight problems of one size, one per XCD, none of which ever reads a word of another's state.
+struct PersistBatch {
+  PersistProblem p[PERSIST_MAX_BATCH];
+  int batch;       // problems in this launch (1 .. 8; 1 when NWG = 256)
+  int *tmo;        // the sticky failure word (persist_timeout_word), one per (device, stream): shared by the batch
+  int attempt;     // 0: first launch; 1: the retry behind it (runs, per problem, only if ITS attempt 0 aborted at its arrival gate)
   int fault;       // VIVIT_PERSIST_FAULT (tests)
 };
 
@@ -56,11 +75,16 @@ __device__ __forceinline__ float ld_l2(const float *p) {
 }
 
 template <int KC, int RPW, int NWG>   // column chunks of 256: n <= 256 KC; rows per wave: n <= 8 NWG RPW; NWG = 32 (one XCD) or 256 (all)
-__global__ __launch_bounds__(TP_THREADS) void trd_persist_kernel(float *__restrict__ A, int64_t lda, int n, SytrdWs ws, PersistWs pw) {
-  if (NWG == TP_WG && (blockIdx.x & 7) != 0) return;
+__global__ __launch_bounds__(TP_THREADS) void trd_persist_kernel(int n, PersistBatch pb) {
+  const int prob = NWG == TP_WG ? (int)(blockIdx.x & 7) : 0;
+  if (prob >= pb.batch) return;
+  float *__restrict__ const A = pb.p[prob].A;
+  const int64_t lda = pb.p[prob].lda;
+  const SytrdWs ws = pb.p[prob].ws;
+  const PersistWs pw = pb.p[prob].pw;
   // the retry runs only when the first attempt aborted at its gate (that verdict is final once attempt 0 has drained)
-  if (pw.attempt == 1 && __hip_atomic_load(pw.counter + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != PERSIST_ABORT) return;
-  int *const cnt = pw.counter + 8 * pw.attempt;
+  if (pb.attempt == 1 && __hip_atomic_load(pw.counter + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != PERSIST_ABORT) return;
+  int *const cnt = pw.counter + 8 * pb.attempt;
   constexpr int NP = 256 * KC;
   const int w = NWG == TP_WG ? blockIdx.x >> 3 : blockIdx.x;
   const int tid = threadIdx.x, g = tid >> 6, l = tid & 63, lane = l;
@@ -93,7 +117,7 @@ __global__ __launch_bounds__(TP_THREADS) void trd_persist_kernel(float *__restri
     __asm__ volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
     if (NWG == TP_WG) __hip_atomic_store(pw.xcc + w, xcc & 15, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const bool go = persist_arrive(cnt, cnt + 1, NWG, ((pw.fault >> pw.attempt) & 1) ? 0ull : PERSIST_TIMEOUT_TICKS);
+    const bool go = persist_arrive(cnt, cnt + 1, NWG, ((pb.fault >> pb.attempt) & 1) ? 0ull : PERSIST_TIMEOUT_TICKS);
     const int dead = go ? 0 : 2;
     int slow = NWG != TP_WG;   // all XCDs: always the agent-scope stores
     const int x0 = __hip_atomic_load(pw.xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -104,8 +128,8 @@ __global__ __launch_bounds__(TP_THREADS) void trd_persist_kernel(float *__restri
   __syncthreads();
   const bool slow = s_flag[0] != 0;
   if (s_flag[1] == 2) {   // aborted at the gate: nothing has been written; the second abort fails the solve
-    if (tid == 0 && w == 0 && pw.attempt == 1) {
-      __hip_atomic_fetch_or(pw.tmo, PERSIST_TMO_SYTRD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0 && w == 0 && pb.attempt == 1) {
+      __hip_atomic_fetch_or(pb.tmo, PERSIST_TMO_SYTRD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       ws.scal[2] = 1.f;
     }
     return;
@@ -254,7 +278,7 @@ __global__ __launch_bounds__(TP_THREADS) void trd_persist_kernel(float *__restri
   }
   if (tid == 0 && s_flag[1]) {   // a stalled exchange: fail the solve, with the status of its own
     ws.scal[2] = 1.f;
-    __hip_atomic_fetch_or(pw.tmo, PERSIST_TMO_SYTRD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_or(pb.tmo, PERSIST_TMO_SYTRD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 #pragma unroll
   for (int q = 0; q < RPW; ++q) {
@@ -279,39 +303,52 @@ bool sytrd_persist_ok(int64_t n) {
   return on != 0 && n >= 64 && n <= (on == 2 ? 1280 : 2048) && device_cu_count() >= 256;
 }
 
-// workspace: 4 NP floats + 64 ints, carved from ws.vw (3 * 64 * n floats)
-int sytrd_persist_launch(float *A, int64_t n, int64_t lda, const SytrdWs &ws, hipStream_t stream) {
+// workspace per problem: 4 NP floats + 64 ints, carved from its ws.vw (3 * 64 * n floats).  batch > 1 needs n <= 1280 (the
+// one-XCD instantiations): problem q runs on XCD q, its own gate, counters and exchange buffers in its own workspace.
+int sytrd_persist_batched_launch(float *const *A, int batch, int64_t n, int64_t lda, const SytrdWs *ws, hipStream_t stream) {
   const int kc0 = (int)cdiv(n, 256);
   const int kc = kc0 <= 6 ? kc0 : (kc0 + 1) & ~1;   // the instantiated widths: 1..6, 8
   const int64_t NP = 256 * (int64_t)kc;
-  PersistWs pw;
-  pw.ybuf = ws.vw;
-  pw.rowbuf = ws.vw + 2 * NP;
-  pw.counter = reinterpret_cast<int *>(ws.vw + 4 * NP);
-  pw.xcc = pw.counter + 32;
-  pw.tmo = persist_timeout_word(stream);
-  pw.fault = persist_fault();
-  if (!pw.tmo) return VIVIT_E_LAUNCH;
+  if (batch < 1 || batch > PERSIST_MAX_BATCH || (batch > 1 && kc > 5)) return VIVIT_E_UNSUPPORTED;
   if (4 * NP + 64 > 3 * 64 * n) return VIVIT_E_WORKSPACE;
-  if (hipMemsetAsync(pw.counter, 0, 64 * sizeof(int), stream) != hipSuccess) return VIVIT_E_LAUNCH;
+  PersistBatch pb = {};
+  pb.batch = batch;
+  pb.tmo = persist_timeout_word(stream);
+  pb.fault = persist_fault();
+  if (!pb.tmo) return VIVIT_E_LAUNCH;
+  for (int q = 0; q < batch; ++q) {
+    PersistProblem &p = pb.p[q];
+    p.A = A[q];
+    p.lda = lda;
+    p.ws = ws[q];
+    p.pw.ybuf = ws[q].vw;
+    p.pw.rowbuf = ws[q].vw + 2 * NP;
+    p.pw.counter = reinterpret_cast<int *>(ws[q].vw + 4 * NP);
+    p.pw.xcc = p.pw.counter + 32;
+    if (hipMemsetAsync(p.pw.counter, 0, 64 * sizeof(int), stream) != hipSuccess) return VIVIT_E_LAUNCH;
+  }
   const dim3 grid(8 * TP_WG);
   const int ni = (int)n;
   // n <= 1280: the 32 workgroups of one XCD (2 us per exchange; <6, 6, 32> would spill 84 registers); above, all 256 CUs with
   // agent-scope exchanges (6.7 us: scripts/probe/grid_barrier.hip mode 3), a workgroup holds n / 256 rows
   for (int attempt = 0; attempt < 2; ++attempt) {
-    pw.attempt = attempt;
+    pb.attempt = attempt;
     switch (kc) {
-      case 1: trd_persist_kernel<1, 1, 32><<<grid, TP_THREADS, 0, stream>>>(A, lda, ni, ws, pw); break;
-      case 2: trd_persist_kernel<2, 2, 32><<<grid, TP_THREADS, 0, stream>>>(A, lda, ni, ws, pw); break;
-      case 3: trd_persist_kernel<3, 3, 32><<<grid, TP_THREADS, 0, stream>>>(A, lda, ni, ws, pw); break;
-      case 4: trd_persist_kernel<4, 4, 32><<<grid, TP_THREADS, 0, stream>>>(A, lda, ni, ws, pw); break;
-      case 5: trd_persist_kernel<5, 5, 32><<<grid, TP_THREADS, 0, stream>>>(A, lda, ni, ws, pw); break;
-      case 6: trd_persist_kernel<6, 1, 256><<<grid, TP_THREADS, 0, stream>>>(A, lda, ni, ws, pw); break;
-      case 8: trd_persist_kernel<8, 1, 256><<<grid, TP_THREADS, 0, stream>>>(A, lda, ni, ws, pw); break;
+      case 1: trd_persist_kernel<1, 1, 32><<<grid, TP_THREADS, 0, stream>>>(ni, pb); break;
+      case 2: trd_persist_kernel<2, 2, 32><<<grid, TP_THREADS, 0, stream>>>(ni, pb); break;
+      case 3: trd_persist_kernel<3, 3, 32><<<grid, TP_THREADS, 0, stream>>>(ni, pb); break;
+      case 4: trd_persist_kernel<4, 4, 32><<<grid, TP_THREADS, 0, stream>>>(ni, pb); break;
+      case 5: trd_persist_kernel<5, 5, 32><<<grid, TP_THREADS, 0, stream>>>(ni, pb); break;
+      case 6: trd_persist_kernel<6, 1, 256><<<grid, TP_THREADS, 0, stream>>>(ni, pb); break;
+      case 8: trd_persist_kernel<8, 1, 256><<<grid, TP_THREADS, 0, stream>>>(ni, pb); break;
       default: return VIVIT_E_UNSUPPORTED;
     }
-}
+  }
   return launch_status();
+}
+
+int sytrd_persist_launch(float *A, int64_t n, int64_t lda, const SytrdWs &ws, hipStream_t stream) {
+  return sytrd_persist_batched_launch(&A, 1, n, lda, &ws, stream);
 }
 
 }  // namespace vivit

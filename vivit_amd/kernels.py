@@ -5,6 +5,7 @@ gfx950 kernels behind the C ABI of ``include/vivit_hip.h``.  Every function rais
 ``RuntimeError`` for tensors that are not fp32 HIP-device tensors: there is deliberately no CPU
 path and no backend switch (host-logic tests monkeypatch these functions from ``tests/helpers.py``).
 """
+import ctypes
 import functools
 from typing import Optional, Tuple
 
@@ -627,6 +628,93 @@ def _retry_on_launch_chain(solve, intact: bool, G: Optional[torch.Tensor] = None
         warnings.warn("symeig: persistent kernel timed out; repeating the solve on the launch chains", RuntimeWarning)
         if backup is not None:
             G.copy_(backup)
+        with persistent_kernels(False):
+            return solve()
+
+
+SYMEIGVALS_BATCHED_MAX_N = 1280  # above: the whole chip per problem (vivit_symeigvals_batched_f32: VIVIT_E_UNSUPPORTED)
+
+
+def check_info_batched(info: torch.Tensor):
+    """:func:`check_info` for the ``[B]`` status vector of a batched solve: ONE device->host read; the error names the
+    failing problem."""
+    host = info.tolist()
+    for i, nfail in enumerate(host):
+        if nfail == _lib.VIVIT_INFO_PERSIST_TIMEOUT:
+            raise PersistentKernelTimeout(
+                f"symeigvals_batched: a persistent kernel could not become resident (two attempts of 2 s) or stalled "
+                f"(reported at problem {i}; the whole batch is void); "
+                "VIVIT_SYTRD_PERSIST=0 VIVIT_QR_PERSIST=0 VIVIT_SB2ST_PERSIST=0 select the launch chains")
+    for i, nfail in enumerate(host):
+        if nfail != 0:
+            raise RuntimeError(f"symeigvals_batched: problem {i}: {nfail} eigenvalues did not converge")
+
+
+@_launcher
+def symeigvals_batched(mats, overwrite: bool = False, info_out: Optional[list] = None) -> torch.Tensor:
+    """Eigenvalues (ascending, row ``b`` = problem ``b``) of ``B`` symmetric matrices of ONE size: a list of ``[n, n]``
+    tensors or a ``[B, n, n]`` tensor, fp32, on one device.  ``ValueError`` for mixed sizes.
+
+    For 193 <= n <= 1280 eight problems share one launch of the persistent tridiagonalisation, one per XCD (a single
+    ``symeig`` of that size occupies one XCD and idles seven); n <= 192 runs one workgroup per problem; n > 1280 is a loop
+    over :func:`symeig`.  Every row equals ``symeig(G_b, eigenvectors=False)[0]`` bit for bit.
+
+    Same contract as :func:`symeig`: the inputs are solved in place only with ``overwrite=True``; the ``[B]`` ``info``
+    vector is read once (``RuntimeError`` names the failing problem) unless a list is passed as ``info_out``, which then
+    receives it; a :class:`PersistentKernelTimeout` repeats the batch once on the launch chains when the inputs are
+    still there (copies, or backed up: :func:`_wants_backup`)."""
+    mats = list(mats.unbind(0)) if isinstance(mats, torch.Tensor) and mats.dim() == 3 else list(mats)
+    if not mats:
+        raise ValueError("symeigvals_batched needs at least one matrix")
+    _require_device(*mats)
+    for G in mats:
+        if G.dim() != 2 or G.shape[0] != G.shape[1]:
+            raise ValueError(f"Input must be a square matrix. Got shape {tuple(G.shape)}.")
+        if G.shape != mats[0].shape:
+            raise ValueError(f"symeigvals_batched needs matrices of one size, got {tuple(mats[0].shape)} and {tuple(G.shape)}")
+    n, B, dev = mats[0].shape[0], len(mats), mats[0].device
+    if n > SYMEIGVALS_BATCHED_MAX_N or n == 0:
+        infos = [] if info_out is not None else None
+        W = torch.stack([symeig(G, eigenvectors=False, overwrite=overwrite, info_out=infos)[0] for G in mats]) if n else \
+            torch.empty((B, 0), dtype=torch.float32, device=dev)
+        if info_out is not None:
+            info_out.append(torch.cat(infos) if infos else torch.zeros(B, dtype=torch.int32, device=dev))
+        return W
+    lib = _lib.load()
+
+    def solve():
+        work = []
+        for G in mats:
+            A = _as2d(G)
+            if _ld(A) != n:
+                A = A.contiguous()   # one leading dimension for the whole batch
+            if A.data_ptr() == G.data_ptr() and not overwrite:
+                A = A.clone()  # the solver destroys its inputs
+            work.append(A)
+        W = torch.empty((B, n), dtype=torch.float32, device=dev)
+        info = torch.zeros(B, dtype=torch.int32, device=dev)
+        ws, wsb = _workspace(lib.vivit_symeigvals_batched_f32_workspace_bytes(n, B), mats[0])
+        ptrs = (ctypes.c_void_p * B)(*[A.data_ptr() for A in work])
+        st = lib.vivit_symeigvals_batched_f32(ptrs, B, n, n, W.data_ptr(), ws, wsb, info.data_ptr(), _stream(mats[0]))
+        _lib.check(st, "vivit_symeigvals_batched_f32")
+        if info_out is not None:
+            info_out.append(info)
+        else:
+            check_info_batched(info)
+        return W
+
+    backups = [G.clone() for G in mats] if overwrite and all(_wants_backup(G) for G in mats) else None
+    try:
+        return solve()
+    except PersistentKernelTimeout:
+        if overwrite and backups is None:
+            raise
+        import warnings
+
+        warnings.warn("symeigvals_batched: persistent kernel timed out; repeating the batch on the launch chains", RuntimeWarning)
+        if backups is not None:
+            for G, b in zip(mats, backups):
+                G.copy_(b)
         with persistent_kernels(False):
             return solve()
 

@@ -1,6 +1,8 @@
 """GGN eigenvalues during backpropagation (API of ``vivit.linalg.eigvalsh``)."""
+import contextlib
 from typing import Any, Callable, Dict, List
 
+import torch
 from torch import Tensor
 from torch.nn import Module, Parameter
 
@@ -28,12 +30,24 @@ class EigvalshComputation:
     """
 
     def __init__(self, subsampling: List[int] = None, mc_samples: int = 0, verbose: bool = False, side: str = "gram",
-                 data_parallel: bool = False, process_group=None):
+                 data_parallel: bool = False, process_group=None, batched_solve: bool = False):
         """``side`` (not in the reference): ``"auto"`` solves a group on its parameter side (``P x P``) when it has
         fewer parameters than Gram rows, ``"gram"`` always decomposes the Gram matrix like the reference.
         ``data_parallel`` / ``process_group`` (not in the reference): every rank back-propagated ITS batch shard; the
         Gram matrix of the global batch is assembled across ranks (vivit_amd.distributed.BatchShardedGram), the
-        eigenvalues are those of the GGN of the mean loss over the global batch, identical on every rank."""
+        eigenvalues are those of the GGN of the mean loss over the global batch, identical on every rank.
+        ``batched_solve`` (not in the reference): for block-diagonal curvature with many groups of one Gram size.  A
+        group that is solved on the Gram side on one device is not solved in its hook; its Gram matrix is queued, and
+        the queue goes through ``kernels.symeigvals_batched`` -- eight matrices of 193 <= n <= 1280 share one launch,
+        one per XCD, where a single solve idles seven of the eight -- as soon as eight matrices of one size wait, and
+        for the remainder on the first ``get_result``.  The eigenvalues are those of ``batched_solve=False`` bit for
+        bit.  Parameter-side groups and ``data_parallel=True`` keep the immediate solve.
+        Streams: the hooks run on the backend's side stream (vivit_amd/backend/engine.py), so that is where a Gram
+        matrix is allocated and accumulated.  Each queue remembers the stream its matrices were queued on and EVERY
+        flush runs on that stream -- behind all accumulations by stream order, on memory that belongs to that stream
+        as far as the caching allocator is concerned (no ``record_stream`` is needed for the inputs).  When the flush
+        of ``get_result`` finds another stream current, that stream then waits for the flush and the result tensor is
+        recorded on it."""
         check_subsampling_unique(subsampling)
         use_parameter_side([], 1, side)  # validates ``side``
         if data_parallel and side != "gram":
@@ -47,9 +61,38 @@ class EigvalshComputation:
         # filled by side effect during backpropagation, keyed by id(group)
         self._batch_size: Dict[int, int] = {}
         self._evals: Dict[int, Tensor] = {}
+        self._batched_solve = bool(batched_solve) and not data_parallel
+        # (device, n, stream) -> [(gram, group_id, scale)]: Gram matrices waiting for a batched solve
+        self._pending: Dict[Any, List] = {}
+
+    _FLUSH_AT = 8  # matrices of one size that make a full launch (one per XCD)
+
+    def _flush(self, key):
+        """Solve the queue ``key`` in one batched call on the stream it was filled on, store the spectra."""
+        items = self._pending.pop(key, [])
+        if not items:
+            return
+        grams = [g for g, _, _ in items]
+        stream = key[2]
+        current = None if stream is None else torch.cuda.current_stream(grams[0].device)
+        foreign = stream is not None and current != stream
+        with torch.cuda.stream(stream) if foreign else contextlib.nullcontext():
+            W = kernels.symeigvals_batched(grams, overwrite=True)
+            for row, (_, group_id, scale) in zip(W.unbind(0), items):
+                # eigenvalues are homogeneous of degree one: the O(n) vector is scaled instead of the n x n Gram
+                if scale is not None:
+                    row *= scale
+                if self._verbose:
+                    print(f"Group {group_id}: Store 'gram_evals'")
+                self._evals[group_id] = row
+        if foreign:
+            current.wait_stream(stream)
+            W.record_stream(current)
 
     def get_result(self, group: Dict) -> Tensor:
         """Eigenvalues (ascending) of the group's GGN block; KeyError if unavailable."""
+        for key in list(self._pending):
+            self._flush(key)
         try:
             return self._evals[id(group)]
         except KeyError as e:
@@ -125,6 +168,7 @@ class EigvalshComputation:
     def get_group_hook(self) -> Callable[[ParameterGroupsHook, Tensor, Dict[str, Any]], None]:
         batch_sizes, subsampling = self._batch_size, self._subsampling
         evals, verbose, savefield = self._evals, self._verbose, self._savefield
+        batched, pending, flush, flush_at = self._batched_solve, self._pending, self._flush, self._FLUSH_AT
 
         def group_hook(self: ParameterGroupsHook, accumulation: Tensor, group: Dict):
             group_id = id(group)
@@ -143,6 +187,13 @@ class EigvalshComputation:
                     scale = batch_size / accumulation.N
                     accumulation = accumulation.finalize()
                 gram_mat = reshape_as_square(accumulation)
+                if batched:
+                    stream = torch.cuda.current_stream(gram_mat.device) if gram_mat.is_cuda else None
+                    key = (gram_mat.device, gram_mat.shape[0], stream)
+                    pending.setdefault(key, []).append((gram_mat, group_id, scale))
+                    if len(pending[key]) >= flush_at:
+                        flush(key)
+                    return
                 gram_evals, _ = kernels.symeig(gram_mat, eigenvectors=False, overwrite=True)
             # eigenvalues are homogeneous of degree one: the O(n) vector is scaled instead of the n x n Gram
             if scale is not None:
