@@ -306,6 +306,35 @@ int vivit_symeig_select_f32(const float *A, int64_t n, int64_t lda, const int32_
                             void *state, size_t state_bytes, void *workspace, size_t workspace_bytes, int32_t *info,
                             void *stream);
 
+/* The two phases for `batch` symmetric matrices of ONE size 193 <= n <= 1280 (block-diagonal curvature: one group per
+ * layer, each with its own criterion callback between the calls -- the per-group loop around vivit/linalg/eigh.py:248-253).
+ * Any batch >= 1, in waves of eight on the stream; the number of launches of a wave does not depend on how many problems
+ * it holds.  A, Zt, state, K: HOST arrays of `batch` entries, read before the call returns.
+ *   vivit_symeig_reduce_batched_f32: A[b] as in vivit_symeig_reduce_f32 (destroyed; keeps the reflectors).  W: [batch][n]
+ *     device, row b ascending.  state[b]: DEVICE block of state_bytes_each >= vivit_symeig_reduce_f32_workspace_bytes(n)
+ *     bytes.  One persistent tridiagonalisation launch (problem q on XCD q) and one Sturm multisection launch per wave.
+ *     Afterwards (A[b], state[b]) is exactly what vivit_symeig_reduce_f32 leaves and row b of W has its bytes: problem b may
+ *     be continued with vivit_symeig_select_f32.  info: device int32 [batch]; non-finite input fails only its own problem
+ *     (info[b] = n); a persistent kernel that gives up voids the wave (every word VIVIT_INFO_PERSIST_TIMEOUT).  With the
+ *     persistent kernels off or the two-stage reduction forced: vivit_symeig_reduce_f32 problem after problem.
+ *   vivit_symeig_select_batched_f32: idx: DEVICE int32, the selections of all problems one after the other (K[0], then K[1],
+ *     ... entries; strictly ascending within a problem); K[b] (HOST, 0 <= K[b] <= n) may differ, 0 is legal.  Zt[b]: DEVICE
+ *     [K[b]][ldz >= n], row k = unit eigenvector of problem b for W[b][idx_b[k]] (may be NULL when K[b] = 0).  Per wave:
+ *     three launches of inverse iteration over all (problem, eigenvalue) pairs and ONE launch that applies every problem's
+ *     Householder reflectors to its rows (one wavefront per row, reflector by reflector -- not the compact-WY products of
+ *     the single select, so the vectors agree with vivit_symeig_select_f32 to rounding, not bit for bit; a problem's rows do
+ *     not depend on what else is in the batch).  A problem with K[b] > 256 leaves the wave and goes through
+ *     vivit_symeig_select_f32.  workspace: vivit_symeig_select_batched_f32_workspace_bytes(n, batch, max K[b]) bytes, constant
+ *     beyond eight problems.
+ * n <= 192 and n > 1280: VIVIT_E_UNSUPPORTED (loop over the single entry points).  Not in the reference. */
+size_t vivit_symeig_select_batched_f32_workspace_bytes(int64_t n, int64_t batch, int64_t K_max);
+int vivit_symeig_reduce_batched_f32(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, void *const *state,
+                                    size_t state_bytes_each, int32_t *info, void *stream);
+int vivit_symeig_select_batched_f32(const float *const *A, int64_t batch, int64_t n, int64_t lda, const int32_t *idx,
+                                    const int64_t *K, float *const *Zt, int64_t ldz, void *const *state,
+                                    size_t state_bytes_each, void *workspace, size_t workspace_bytes, int32_t *info,
+                                    void *stream);
+
 /* Stage 1 of vivit_symeig_f32, exported for testing: Householder tridiagonalisation
  * A = Q T Q^T (lower triangle read).  d: [n], e: [n-1], tau: [n]; on return row j of A's upper
  * triangle, A[j][j+1:], holds reflector v_j (v_j[j+1] = 1), Q = H_0 ... H_{n-3},

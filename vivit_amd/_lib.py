@@ -56,6 +56,9 @@ SIGNATURES = {
     "vivit_symeig_select_f32_workspace_bytes": (_sz, [_i64, _i64]),
     "vivit_symeig_reduce_f32": (_int, [_ptr, _i64, _i64, _ptr, _ptr, _sz, _ptr, _ptr]),
     "vivit_symeig_select_f32": (_int, [_ptr, _i64, _i64, _ptr, _i64, _ptr, _i64, _ptr, _sz, _ptr, _sz, _ptr, _ptr]),
+    "vivit_symeig_select_batched_f32_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "vivit_symeig_reduce_batched_f32": (_int, [_ptr, _i64, _i64, _i64, _ptr, _ptr, _sz, _ptr, _ptr]),
+    "vivit_symeig_select_batched_f32": (_int, [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _sz, _ptr, _sz, _ptr, _ptr]),
     "vivit_sytrd_f32_workspace_bytes": (_sz, [_i64]),
     "vivit_sytrd_f32": (_int, [_ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
     "vivit_sy2sb_f32_workspace_bytes": (_sz, [_i64]),
@@ -84,7 +87,9 @@ SIGNATURES = {
     "vivit_unpack_lower_f32": (_int, [_ptr, _i64, _ptr, _i64, _ptr]),
 }
 
-ABI_VERSION = 1008  # include/vivit_hip.h of this checkout (vivit_hip_abi_version)
+# include/vivit_hip.h of this checkout (vivit_hip_abi_version).  The batched two-phase entry points only ADD exports: the
+# number stays; a library without them is refused by the symbol lookup in load() and by the source hash (_check_provenance).
+ABI_VERSION = 1008
 
 _lib = None
 

@@ -21,6 +21,12 @@ int symeig_reduce_launch(float *A, int64_t n, int64_t lda, float *w, void *ws, s
                          hipStream_t stream);
 int symeig_select_launch(const float *A, int64_t n, int64_t lda, const int *sel, int64_t K, float *Zt, int64_t ldz,
                          void *state, size_t state_bytes, void *ws, size_t ws_bytes, int32_t *info, hipStream_t stream);
+size_t symeig_select_batched_workspace_bytes(int64_t n, int64_t batch, int64_t kmax);
+int symeig_reduce_batched_launch(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, void *const *state,
+                                 size_t state_bytes_each, int32_t *info, hipStream_t stream);
+int symeig_select_batched_launch(const float *const *A, int64_t batch, int64_t n, int64_t lda, const int *idx, const int64_t *K,
+                                 float *const *Zt, int64_t ldz, void *const *state, size_t state_bytes_each, void *ws,
+                                 size_t ws_bytes, int32_t *info, hipStream_t stream);
 } // namespace vivit
 
 using namespace vivit;
@@ -120,6 +126,44 @@ int vivit_symeig_select_f32(const float *A, int64_t n, int64_t lda, const int32_
   if (n <= SMALL_N_MAX) return VIVIT_E_UNSUPPORTED;
   return symeig_select_launch(A, n, lda, idx, K, Zt, ldz, state, state_bytes, workspace, workspace_bytes, info,
                               static_cast<hipStream_t>(stream));
+}
+
+// The two phases for `batch` matrices of one size 193 <= n <= 1280 (the criterion callback of vivit/linalg/eigh.py:248-253 once
+// per group, between the two calls).  Everything is checked on the host before anything is enqueued.
+size_t vivit_symeig_select_batched_f32_workspace_bytes(int64_t n, int64_t batch, int64_t K_max) {
+  if (n <= SMALL_N_MAX || n > BATCHED_N_MAX || batch < 1 || K_max < 0) return 0;
+  return symeig_select_batched_workspace_bytes(n, batch, K_max);
+}
+
+int vivit_symeig_reduce_batched_f32(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, void *const *state,
+                                    size_t state_bytes_each, int32_t *info, void *stream) {
+  if (!A || !W || !info || !state || batch < 1 || n < 1 || lda < n) return VIVIT_E_BADARG;
+  for (int64_t i = 0; i < batch; ++i)
+    if (!A[i]) return VIVIT_E_BADARG;
+  if (n <= SMALL_N_MAX || n > BATCHED_N_MAX) return VIVIT_E_UNSUPPORTED;
+  if (state_bytes_each < symeig_reduce_workspace_bytes(n)) return VIVIT_E_WORKSPACE;
+  for (int64_t i = 0; i < batch; ++i)
+    if (!state[i]) return VIVIT_E_WORKSPACE;
+  return symeig_reduce_batched_launch(A, batch, n, lda, W, state, state_bytes_each, info, static_cast<hipStream_t>(stream));
+}
+
+int vivit_symeig_select_batched_f32(const float *const *A, int64_t batch, int64_t n, int64_t lda, const int32_t *idx,
+                                    const int64_t *K, float *const *Zt, int64_t ldz, void *const *state,
+                                    size_t state_bytes_each, void *workspace, size_t workspace_bytes, int32_t *info,
+                                    void *stream) {
+  if (!A || !K || !Zt || !state || !info || batch < 1 || n < 1 || lda < n || ldz < n) return VIVIT_E_BADARG;
+  int64_t kmax = 0;
+  for (int64_t i = 0; i < batch; ++i) {
+    if (!A[i] || K[i] < 0 || K[i] > n || (K[i] > 0 && (!Zt[i] || !idx))) return VIVIT_E_BADARG;
+    if (K[i] > kmax) kmax = K[i];
+  }
+  if (n <= SMALL_N_MAX || n > BATCHED_N_MAX) return VIVIT_E_UNSUPPORTED;
+  if (state_bytes_each < symeig_reduce_workspace_bytes(n)) return VIVIT_E_WORKSPACE;
+  for (int64_t i = 0; i < batch; ++i)
+    if (!state[i]) return VIVIT_E_WORKSPACE;
+  if (kmax > 0 && (!workspace || workspace_bytes < symeig_select_batched_workspace_bytes(n, batch, kmax))) return VIVIT_E_WORKSPACE;
+  return symeig_select_batched_launch(A, batch, n, lda, idx, K, Zt, ldz, state, state_bytes_each, workspace, workspace_bytes,
+                                      info, static_cast<hipStream_t>(stream));
 }
 
 } // extern "C"

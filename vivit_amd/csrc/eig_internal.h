@@ -41,10 +41,19 @@ int stedc_dc_launch(const float *d, const float *e, int64_t n, void *wsbase, flo
 // (w64, optional: the same eigenvalues in fp64, NOT divided by the scale)
 int stebz_launch(const float *d, const float *e, int64_t n, float *w, const float *scal, hipStream_t stream,
                  double *w64 = nullptr);
+// the same for `batch` <= PERSIST_MAX_BATCH tridiagonals of one size in one launch (host arrays of `batch`; scal / w64: null or
+// arrays without null entries): the kernel of stebz_launch with the problem as a grid dimension
+int stebz_batched_launch(int batch, int64_t n, const float *const *d, const float *const *e, float *const *w,
+                         const float *const *scal, hipStream_t stream, double *const *w64 = nullptr);
 // stein.hip: selected eigenvectors of the tridiagonal (d, e) by inverse iteration, rows of Zt
 size_t stein_workspace_bytes(int64_t n, int64_t K);
 int stein_launch(const float *d, const float *e, int64_t n, const double *lam64, const int *sel, int64_t K, float *Zt,
                  int64_t ldz, void *wsbase, int32_t *info, hipStream_t stream);
+// the same for `batch` <= PERSIST_MAX_BATCH tridiagonals of one size n: three launches for all (problem, eigenvalue) pairs.
+// Host arrays of `batch`; K[q] may differ, K[q] = 0 is legal (its other entries are not read); wsbase[q]: stein_workspace_bytes(n, K[q])
+int stein_batched_launch(int batch, int64_t n, const float *const *d, const float *const *e, const double *const *lam64,
+                         const int *const *sel, const int64_t *K, float *const *Zt, int64_t ldz, void *const *wsbase,
+                         int32_t *const *info, hipStream_t stream);
 // sytrd.hip: pointers into a workspace laid out by sytrd_launch (same base, same n) without launching anything
 void sytrd_layout(float *wsbase, int64_t n, SytrdWs *out);
 // two-phase eigensolver for criterion-selected eigenvectors (symeig_large.hip)
@@ -107,6 +116,13 @@ int info_finalize_launch(int32_t *info, int64_t n, const float *scal, hipStream_
 // the same for info[0 .. batch-1] (batch <= PERSIST_MAX_BATCH, scal: host array): the sticky failure word is one per
 // stream, so a set bit fails EVERY problem of the batch
 int info_finalize_batched_launch(int32_t *info, int batch, int64_t n, const float *const *scal, hipStream_t stream);
+// symeig_large.hip: the two-phase solver for `batch` matrices of one size 193 <= n <= 1280 (vivit_symeig_*_batched_f32)
+size_t symeig_select_batched_workspace_bytes(int64_t n, int64_t batch, int64_t kmax);
+int symeig_reduce_batched_launch(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, void *const *state,
+                                 size_t state_bytes_each, int32_t *info, hipStream_t stream);
+int symeig_select_batched_launch(const float *const *A, int64_t batch, int64_t n, int64_t lda, const int *idx, const int64_t *K,
+                                 float *const *Zt, int64_t ldz, void *const *state, size_t state_bytes_each, void *ws,
+                                 size_t ws_bytes, int32_t *info, hipStream_t stream);
 // symeig_large.hip: eigenvalues of `batch` matrices of one size 193 <= n <= 1280, in waves of PERSIST_MAX_BATCH
 size_t symeigvals_batched_workspace_bytes(int64_t n, int64_t batch);
 int symeigvals_batched_launch(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, void *ws, size_t ws_bytes,

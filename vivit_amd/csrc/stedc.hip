@@ -55,9 +55,20 @@ struct DcWs {
 // 256 CUs and cost 0.4 s at n = 40 960).  The bracket ends far below fp32 resolution: span * 9^-12 = 3.5e-12 span.
 constexpr int SB_LANES = 8;    // shifts per eigenvalue and round
 constexpr int SB_ROUNDS = 12;
-__global__ __launch_bounds__(256) void stebz_kernel(const float *__restrict__ d, const float *__restrict__ e, int n,
-                                                    float *__restrict__ w, double *__restrict__ w64) {
+// blockIdx.y = problem: up to PERSIST_MAX_BATCH tridiagonals of one size share the launch (pointers by value, as
+// PersistBatch); a single solve is a batch of one, so every route runs this one kernel and a problem's eigenvalues do not
+// depend on what else is in the launch.
+struct StebzBatch {
+  const float *d[PERSIST_MAX_BATCH], *e[PERSIST_MAX_BATCH];
+  float *w[PERSIST_MAX_BATCH];
+  double *w64[PERSIST_MAX_BATCH];        // all null or all set (the round count is the launch's)
+  const float *scal[PERSIST_MAX_BATCH];  // scale_w_kernel
+};
+__global__ __launch_bounds__(256) void stebz_kernel(int n, StebzBatch sb) {
   __shared__ float red[4];
+  const float *__restrict__ d = sb.d[blockIdx.y], *__restrict__ e = sb.e[blockIdx.y];
+  float *__restrict__ w = sb.w[blockIdx.y];
+  double *__restrict__ w64 = sb.w64[blockIdx.y];
   const int tid = threadIdx.x;
   // Gershgorin interval (every block recomputes it: O(n) reads, fixed order)
   float lo = 3.0e38f, hi = -3.0e38f;
@@ -546,7 +557,9 @@ __global__ __launch_bounds__(256) void dc_transpose_out_kernel(int n, const floa
   }
 }
 
-__global__ void scale_w_kernel(float *__restrict__ w, int n, const float *__restrict__ scal) {
+__global__ void scale_w_kernel(int n, StebzBatch sb) {
+  float *__restrict__ w = sb.w[blockIdx.y];
+  const float *__restrict__ scal = sb.scal[blockIdx.y];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) w[i] /= scal[1];
 }
@@ -679,11 +692,23 @@ int stedc_dc_launch(const float *d, const float *e, int64_t n, void *wsbase, flo
   return launch_status();
 }
 
+int stebz_batched_launch(int batch, int64_t n, const float *const *d, const float *const *e, float *const *w,
+                         const float *const *scal, hipStream_t stream, double *const *w64) {
+  if (batch < 1 || batch > PERSIST_MAX_BATCH) return VIVIT_E_UNSUPPORTED;
+  StebzBatch sb = {};
+  for (int q = 0; q < batch; ++q) {
+    sb.d[q] = d[q]; sb.e[q] = e[q]; sb.w[q] = w[q];
+    sb.w64[q] = w64 ? w64[q] : nullptr;
+    sb.scal[q] = scal ? scal[q] : nullptr;
+  }
+  stebz_kernel<<<dim3((unsigned)cdiv(n, 256 / SB_LANES), (unsigned)batch), 256, 0, stream>>>((int)n, sb);
+  if (scal) scale_w_kernel<<<dim3((unsigned)cdiv(n, 256), (unsigned)batch), 256, 0, stream>>>((int)n, sb);
+  return launch_status();
+}
+
 int stebz_launch(const float *d, const float *e, int64_t n, float *w, const float *scal, hipStream_t stream,
                  double *w64) {
-  stebz_kernel<<<(unsigned)cdiv(n, 256 / SB_LANES), 256, 0, stream>>>(d, e, (int)n, w, w64);
-  if (scal) scale_w_kernel<<<(unsigned)cdiv(n, 256), 256, 0, stream>>>(w, (int)n, scal);
-  return launch_status();
+  return stebz_batched_launch(1, n, &d, &e, &w, scal ? &scal : nullptr, stream, w64 ? &w64 : nullptr);
 }
 
 int info_finalize_launch(int32_t *info, int64_t n, const float *scal, hipStream_t stream) {

@@ -49,8 +49,8 @@ static SteinWs stein_carve(void *base, int64_t n, int64_t K) {
 }
 
 // span[0] = Gershgorin span of T, span[1] = max row sum (norm bound); one workgroup
-__global__ __launch_bounds__(256) void stein_span_kernel(const float *__restrict__ d, const float *__restrict__ e, int n,
-                                                         double *__restrict__ span) {
+__device__ __forceinline__ void stein_span_body(const float *__restrict__ d, const float *__restrict__ e, int n,
+                                                double *__restrict__ span) {
   __shared__ double slo[256], shi[256], snr[256];
   double lo = 1e300, hi = -1e300, nr = 0.0;
   for (int i = threadIdx.x; i < n; i += 256) {
@@ -75,12 +75,16 @@ __global__ __launch_bounds__(256) void stein_span_kernel(const float *__restrict
   }
 }
 
+__global__ __launch_bounds__(256) void stein_span_kernel(const float *__restrict__ d, const float *__restrict__ e, int n,
+                                                         double *__restrict__ span) {
+  stein_span_body(d, e, n, span);
+}
+
 // lane k: LU of T - lam_k I, then ST_ITERS solves from a pseudo-random start; y[:, k] is left with unit 2-norm.
 // `sel[k]` is the position of the wanted eigenvalue in the ascending list lam64 (strictly ascending in k).
-__global__ __launch_bounds__(64) void stein_iterate_kernel(const float *__restrict__ d, const float *__restrict__ e, int n,
-                                                           const double *__restrict__ lam64, const int *__restrict__ sel,
-                                                           int K, int Kp, SteinWs ws, int32_t *__restrict__ info) {
-  const int k = blockIdx.x * 64 + threadIdx.x;
+__device__ __forceinline__ void stein_iterate_body(const float *__restrict__ d, const float *__restrict__ e, int n,
+                                                   const double *__restrict__ lam64, const int *__restrict__ sel, int K, int Kp,
+                                                   const SteinWs &ws, int32_t *__restrict__ info, int k) {
   if (k >= K) return;
   const double tnorm = ws.span[1];
   const double tol = 2.3e-16 * tnorm;       // smallest pivot magnitude accepted in the back substitution
@@ -167,10 +171,16 @@ __global__ __launch_bounds__(64) void stein_iterate_kernel(const float *__restri
   if (tnorm > 1e-290 && (!(growth * tnorm >= 1e6) || !(growth < INFINITY))) atomicAdd(info, 1);
 }
 
+__global__ __launch_bounds__(64) void stein_iterate_kernel(const float *__restrict__ d, const float *__restrict__ e, int n,
+                                                           const double *__restrict__ lam64, const int *__restrict__ sel,
+                                                           int K, int Kp, SteinWs ws, int32_t *__restrict__ info) {
+  stein_iterate_body(d, e, n, lam64, sel, K, Kp, ws, info, blockIdx.x * 64 + threadIdx.x);
+}
+
 // One workgroup: modified Gram-Schmidt inside runs of numerically multiple selected eigenvalues (ascending order),
 // then Zt[k][i] = y[i][k] as fp32 (unit norm).  Vectors outside such runs are only converted.
-__global__ __launch_bounds__(256) void stein_finish_kernel(int n, const double *__restrict__ lam64, const int *__restrict__ sel,
-                                                           int K, int Kp, SteinWs ws, float *__restrict__ Zt, int64_t ldz) {
+__device__ __forceinline__ void stein_finish_body(int n, const double *__restrict__ lam64, const int *__restrict__ sel, int K,
+                                                  int Kp, const SteinWs &ws, float *__restrict__ Zt, int64_t ldz) {
   __shared__ double red[256];
   const int tid = threadIdx.x;
   const double tight = ST_TIGHT * ws.span[0];
@@ -211,6 +221,68 @@ __global__ __launch_bounds__(256) void stein_finish_kernel(int n, const double *
     }
     for (int i = tid; i < n; i += 256) Zt[(int64_t)k * ldz + i] = (float)yk[(int64_t)i * Kp];
   }
+}
+
+__global__ __launch_bounds__(256) void stein_finish_kernel(int n, const double *__restrict__ lam64, const int *__restrict__ sel,
+                                                           int K, int Kp, SteinWs ws, float *__restrict__ Zt, int64_t ldz) {
+  stein_finish_body(n, lam64, sel, K, Kp, ws, Zt, ldz);
+}
+
+// ---- the same three kernels for up to PERSIST_MAX_BATCH tridiagonals of one size n in one launch each: the problem is a grid
+// dimension, every problem has its own selection (K may differ, K = 0 is legal), workspace, output rows and status word, and
+// runs the bodies above unchanged -- shift of coincident eigenvalues and Gram-Schmidt of tight clusters stay per problem.
+struct SteinProblem {
+  const float *d, *e;
+  const double *lam64;
+  const int *sel;
+  int K, Kp;
+  SteinWs ws;
+  float *Zt;
+  int32_t *info;
+};
+struct SteinBatch {
+  SteinProblem p[PERSIST_MAX_BATCH];
+};
+
+__global__ __launch_bounds__(256) void stein_span_batched_kernel(int n, SteinBatch sb) {
+  const SteinProblem &p = sb.p[blockIdx.x];
+  if (p.K <= 0) return;
+  stein_span_body(p.d, p.e, n, p.ws.span);
+}
+
+__global__ __launch_bounds__(64) void stein_iterate_batched_kernel(int n, SteinBatch sb) {
+  const SteinProblem &p = sb.p[blockIdx.y];
+  stein_iterate_body(p.d, p.e, n, p.lam64, p.sel, p.K, p.Kp, p.ws, p.info, blockIdx.x * 64 + threadIdx.x);
+}
+
+__global__ __launch_bounds__(256) void stein_finish_batched_kernel(int n, int64_t ldz, SteinBatch sb) {
+  const SteinProblem &p = sb.p[blockIdx.x];
+  if (p.K <= 0) return;
+  stein_finish_body(n, p.lam64, p.sel, p.K, p.Kp, p.ws, p.Zt, ldz);
+}
+
+// Three launches for the whole wave, whatever `batch` is (grids are sized for PERSIST_MAX_BATCH problems and the largest
+// K; slots beyond `batch` carry K = 0).  wsbase[q]: stein_workspace_bytes(n, K[q]) bytes.
+int stein_batched_launch(int batch, int64_t n, const float *const *d, const float *const *e, const double *const *lam64,
+                         const int *const *sel, const int64_t *K, float *const *Zt, int64_t ldz, void *const *wsbase,
+                         int32_t *const *info, hipStream_t stream) {
+  if (batch < 1 || batch > PERSIST_MAX_BATCH) return VIVIT_E_UNSUPPORTED;
+  SteinBatch sb = {};
+  int64_t kmax = 0;
+  for (int q = 0; q < batch; ++q) {
+    if (K[q] <= 0) continue;
+    SteinProblem &p = sb.p[q];
+    p.d = d[q]; p.e = e[q]; p.lam64 = lam64[q]; p.sel = sel[q];
+    p.K = (int)K[q]; p.Kp = (int)stein_kp(K[q]);
+    p.ws = stein_carve(wsbase[q], n, K[q]);
+    p.Zt = Zt[q]; p.info = info[q];
+    if (K[q] > kmax) kmax = K[q];
+  }
+  if (kmax == 0) return VIVIT_OK;
+  stein_span_batched_kernel<<<PERSIST_MAX_BATCH, 256, 0, stream>>>((int)n, sb);
+  stein_iterate_batched_kernel<<<dim3((unsigned)cdiv(kmax, 64), PERSIST_MAX_BATCH), 64, 0, stream>>>((int)n, sb);
+  stein_finish_batched_kernel<<<PERSIST_MAX_BATCH, 256, 0, stream>>>((int)n, ldz, sb);
+  return launch_status();
 }
 
 // Zt[k][:] (k < K, ld ldz) = unit eigenvector of the tridiagonal (d, e) for the eigenvalue lam64[sel[k]].

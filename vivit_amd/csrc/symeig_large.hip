@@ -602,12 +602,209 @@ int symeigvals_batched_launch(float *const *A, int64_t batch, int64_t n, int64_t
     for (int q = 0; q < nb; ++q) trd_base[q] = reinterpret_cast<float *>(base + slot * q);
     int st = sytrd_batched_launch(A + i0, nb, n, lda, trd_base, tw, stream);
     if (st != VIVIT_OK) return st;
+    const float *dq[PERSIST_MAX_BATCH], *eq[PERSIST_MAX_BATCH];
+    float *wq[PERSIST_MAX_BATCH];
     for (int q = 0; q < nb; ++q) {
-      st = stebz_launch(tw[q].d, tw[q].e, n, W + (i0 + q) * n, tw[q].scal, stream);
-      if (st != VIVIT_OK) return st;
+      dq[q] = tw[q].d; eq[q] = tw[q].e; wq[q] = W + (i0 + q) * n;
       scal[q] = tw[q].scal;
     }
+    st = stebz_batched_launch(nb, n, dq, eq, wq, scal, stream);   // one bisection launch for the wave
+    if (st != VIVIT_OK) return st;
     st = info_finalize_batched_launch(info + i0, nb, n, scal, stream);
+    if (st != VIVIT_OK) return st;
+  }
+  return VIVIT_OK;
+}
+
+// ---- eigenpairs of `batch` matrices of one size 193 <= n <= 1280 in two phases (vivit_symeig_reduce_batched_f32 /
+// vivit_symeig_select_batched_f32): the batched reduction above with every problem's workspace inside ITS state block,
+// laid out by select_layout, so that state[b] + A[b] is what symeig_reduce_launch would have left (the single select accepts
+// it); then inverse iteration and the back-transformation of the few selected rows for the whole wave at once.
+
+// Zt_q[K_q x n] <- Zt_q Q_q^T = Zt_q H_{n-3} ... H_1 H_0 (H_j = I - tau_j v_j v_j^T, v_j = A_q[j][j+1:]) for all problems of a
+// wave in ONE launch.  The rows are independent: one wavefront keeps one row of Zt in registers (lane l: components l + 64 t)
+// and applies the reflectors one after the other, last first -- a dot product (wave butterfly, fixed order) and an axpy each.
+// The four waves of a workgroup share the reflector rows, staged BT_JB at a time in LDS.  Workgroup b serves problem b % 8:
+// with the round-robin placement of workgroups that is one XCD per problem, whose L2 then holds that problem's reflectors
+// for all of its rows.  No cross-problem data, no atomics; 2 K n^2 flop per problem where the compact-WY chain of
+// backtransform_launch pays 2 KB n^2 for the T factors alone (K ~ 10, KB = 128) in six launches per block.
+constexpr int BT_JB = 8;         // reflectors staged per round
+constexpr int BT_ROWS_WG = 4;    // rows of Zt (waves) per workgroup
+struct BtRowsProblem {
+  const float *A, *tau;
+  float *Zt;
+  int K;
+};
+struct BtRowsBatch {
+  BtRowsProblem p[PERSIST_MAX_BATCH];
+};
+
+template <int NT>   // n <= 64 NT
+__global__ __launch_bounds__(64 * BT_ROWS_WG) void bt_rows_batched_kernel(int n, int64_t lda, int64_t ldz, BtRowsBatch bb) {
+  __shared__ float sv[BT_JB][64 * NT];
+  __shared__ float stau[BT_JB];
+  const BtRowsProblem &p = bb.p[blockIdx.x % PERSIST_MAX_BATCH];
+  const int row0 = (int)(blockIdx.x / PERSIST_MAX_BATCH) * BT_ROWS_WG;
+  if (row0 >= p.K) return;   // (the whole workgroup: no barrier is missed)
+  const int tid = threadIdx.x, lane = tid & 63, row = row0 + (tid >> 6);
+  const bool active = row < p.K;
+  const float *__restrict__ A = p.A;
+  float z[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int i = lane + 64 * t;
+    z[t] = (active && i < n) ? p.Zt[(int64_t)row * ldz + i] : 0.f;
+  }
+  const int jmax = n - 3;
+  for (int jb = (jmax / BT_JB) * BT_JB; jb >= 0; jb -= BT_JB) {
+    __syncthreads();   // the previous round's readers are done
+    for (int idx = tid; idx < BT_JB * 64 * NT; idx += 64 * BT_ROWS_WG) {
+      const int jj = idx / (64 * NT), i = idx % (64 * NT), j = jb + jj;
+      sv[jj][i] = (j <= jmax && i > j && i < n) ? A[(int64_t)j * lda + i] : 0.f;
+    }
+    if (tid < BT_JB) stau[tid] = (jb + tid <= jmax) ? p.tau[jb + tid] : 0.f;
+    __syncthreads();
+    const int t0 = (jb + 1) / 64;   // tiles below hold no component of these reflectors
+    for (int jj = BT_JB - 1; jj >= 0; --jj) {
+      float dot = 0.f;
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+        if (t >= t0) dot += z[t] * sv[jj][lane + 64 * t];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) dot += __shfl_xor(dot, off, 64);
+      const float s = stau[jj] * dot;
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+        if (t >= t0) z[t] -= s * sv[jj][lane + 64 * t];
+    }
+  }
+  if (active) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int i = lane + 64 * t;
+      if (i < n) p.Zt[(int64_t)row * ldz + i] = z[t];
+    }
+  }
+}
+
+// A, tau, Zt, K: host arrays of `batch` <= PERSIST_MAX_BATCH (K[q] = 0: problem not touched); one launch
+static int bt_rows_batched_launch(int batch, int64_t n, int64_t lda, const float *const *A, const float *const *tau,
+                                  float *const *Zt, int64_t ldz, const int64_t *K, hipStream_t stream) {
+  if (batch < 1 || batch > PERSIST_MAX_BATCH || n > 64 * 20 || n < 3) return VIVIT_E_UNSUPPORTED;
+  BtRowsBatch bb = {};
+  int64_t kmax = 0;
+  for (int q = 0; q < batch; ++q) {
+    if (K[q] <= 0) continue;
+    bb.p[q].A = A[q]; bb.p[q].tau = tau[q]; bb.p[q].Zt = Zt[q]; bb.p[q].K = (int)K[q];
+    if (K[q] > kmax) kmax = K[q];
+  }
+  if (kmax == 0) return VIVIT_OK;
+  const dim3 grid((unsigned)(PERSIST_MAX_BATCH * cdiv(kmax, BT_ROWS_WG)));
+  const int ni = (int)n;
+  const int nt = (int)cdiv(n, 256) * 4;   // instantiated widths: 256, 512, 768, 1024, 1280 columns
+  switch (nt) {
+    case 4: bt_rows_batched_kernel<4><<<grid, 64 * BT_ROWS_WG, 0, stream>>>(ni, lda, ldz, bb); break;
+    case 8: bt_rows_batched_kernel<8><<<grid, 64 * BT_ROWS_WG, 0, stream>>>(ni, lda, ldz, bb); break;
+    case 12: bt_rows_batched_kernel<12><<<grid, 64 * BT_ROWS_WG, 0, stream>>>(ni, lda, ldz, bb); break;
+    case 16: bt_rows_batched_kernel<16><<<grid, 64 * BT_ROWS_WG, 0, stream>>>(ni, lda, ldz, bb); break;
+    case 20: bt_rows_batched_kernel<20><<<grid, 64 * BT_ROWS_WG, 0, stream>>>(ni, lda, ldz, bb); break;
+    default: return VIVIT_E_UNSUPPORTED;
+  }
+  return launch_status();
+}
+
+// the batched reduction needs the persistent kernel (one XCD per problem), the batched select only the one-stage state
+// layout; otherwise the entries loop over the single ones
+static bool batched_select_ok(int64_t n) { return !select_two_stage(n) && n <= 64 * 20; }
+static bool batched_pairs_ok(int64_t n) { return batched_select_ok(n) && sytrd_persist_ok(n); }
+
+int symeig_reduce_batched_launch(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, void *const *state,
+                                 size_t state_bytes_each, int32_t *info, hipStream_t stream) {
+  if (state_bytes_each < symeig_reduce_workspace_bytes(n)) return VIVIT_E_WORKSPACE;
+  if (!batched_pairs_ok(n)) {
+    for (int64_t i = 0; i < batch; ++i) {
+      const int st = symeig_reduce_launch(A[i], n, lda, W + i * n, state[i], state_bytes_each, info + i, stream);
+      if (st != VIVIT_OK) return st;
+    }
+    return VIVIT_OK;
+  }
+  if (hipMemsetAsync(info, 0, sizeof(int32_t) * batch, stream) != hipSuccess) return VIVIT_E_LAUNCH;
+  for (int64_t i0 = 0; i0 < batch; i0 += PERSIST_MAX_BATCH) {
+    const int nb = (int)(batch - i0 < PERSIST_MAX_BATCH ? batch - i0 : PERSIST_MAX_BATCH);
+    float *trd_base[PERSIST_MAX_BATCH], *wq[PERSIST_MAX_BATCH];
+    const float *dq[PERSIST_MAX_BATCH], *eq[PERSIST_MAX_BATCH], *scal[PERSIST_MAX_BATCH];
+    double *lam[PERSIST_MAX_BATCH];
+    SytrdWs tw[PERSIST_MAX_BATCH];
+    for (int q = 0; q < nb; ++q) {
+      const SelectLayout L = select_layout(state[i0 + q], n);
+      trd_base[q] = L.trd_base;
+      dq[q] = L.d; eq[q] = L.e; scal[q] = L.scal; lam[q] = L.lam64;
+      wq[q] = W + (i0 + q) * n;
+    }
+    int st = sytrd_batched_launch(A + i0, nb, n, lda, trd_base, tw, stream);
+    if (st != VIVIT_OK) return st;
+    st = stebz_batched_launch(nb, n, dq, eq, wq, scal, stream, lam);
+    if (st != VIVIT_OK) return st;
+    st = info_finalize_batched_launch(info + i0, nb, n, scal, stream);
+    if (st != VIVIT_OK) return st;
+  }
+  return VIVIT_OK;
+}
+
+// One slot of inverse-iteration scratch per problem of a wave (sized for the largest selection the batched kernels take);
+// a selection above SELECT_STEIN_MAX goes through the single select, whose scratch follows the slots.
+static int64_t batched_stein_k(int64_t kmax) { return kmax < 1 ? 1 : (kmax > SELECT_STEIN_MAX ? SELECT_STEIN_MAX : kmax); }
+
+size_t symeig_select_batched_workspace_bytes(int64_t n, int64_t batch, int64_t kmax) {
+  if (kmax > n) kmax = n;
+  const int64_t slots = batch < PERSIST_MAX_BATCH ? batch : PERSIST_MAX_BATCH;
+  size_t b = align_up(stein_workspace_bytes(n, batched_stein_k(kmax)), 256) * (size_t)slots;
+  if (kmax > SELECT_STEIN_MAX || !batched_select_ok(n)) b += align_up(symeig_select_workspace_bytes(n, kmax), 256);
+  return b + 256;
+}
+
+int symeig_select_batched_launch(const float *const *A, int64_t batch, int64_t n, int64_t lda, const int *idx, const int64_t *K,
+                                 float *const *Zt, int64_t ldz, void *const *state, size_t state_bytes_each, void *ws,
+                                 size_t ws_bytes, int32_t *info, hipStream_t stream) {
+  int64_t kmax = 0, ktot = 0;
+  for (int64_t i = 0; i < batch; ++i) kmax = K[i] > kmax ? K[i] : kmax;
+  if (state_bytes_each < symeig_reduce_workspace_bytes(n)) return VIVIT_E_WORKSPACE;
+  if (kmax > 0 && (!ws || ws_bytes < symeig_select_batched_workspace_bytes(n, batch, kmax))) return VIVIT_E_WORKSPACE;
+  if (hipMemsetAsync(info, 0, sizeof(int32_t) * batch, stream) != hipSuccess) return VIVIT_E_LAUNCH;
+  if (kmax == 0) return VIVIT_OK;
+  char *base = reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
+  const size_t slot = align_up(stein_workspace_bytes(n, batched_stein_k(kmax)), 256);
+  const int64_t slots = batch < PERSIST_MAX_BATCH ? batch : PERSIST_MAX_BATCH;
+  char *single_ws = base + slot * slots;
+  const size_t single_bytes = ws_bytes - (size_t)(single_ws - reinterpret_cast<char *>(ws));
+  const bool batched = batched_select_ok(n);
+  for (int64_t i0 = 0; i0 < batch; i0 += PERSIST_MAX_BATCH) {
+    const int nb = (int)(batch - i0 < PERSIST_MAX_BATCH ? batch - i0 : PERSIST_MAX_BATCH);
+    const float *dq[PERSIST_MAX_BATCH], *eq[PERSIST_MAX_BATCH], *tauq[PERSIST_MAX_BATCH];
+    const double *lam[PERSIST_MAX_BATCH];
+    const int *sel[PERSIST_MAX_BATCH];
+    int64_t Kq[PERSIST_MAX_BATCH];
+    void *stws[PERSIST_MAX_BATCH];
+    int32_t *infq[PERSIST_MAX_BATCH];
+    for (int q = 0; q < nb; ++q) {
+      const int64_t i = i0 + q;
+      const SelectLayout L = select_layout(state[i], n);
+      dq[q] = L.d; eq[q] = L.e; tauq[q] = L.tau1; lam[q] = L.lam64;
+      sel[q] = idx + ktot;
+      ktot += K[i];
+      stws[q] = base + slot * q;
+      infq[q] = info + i;
+      Kq[q] = K[i];
+      if (K[i] > 0 && (!batched || K[i] > SELECT_STEIN_MAX)) {   // out of the wave: the single select (divide & conquer route)
+        const int st = symeig_select_launch(A[i], n, lda, sel[q], K[i], Zt[i], ldz, state[i], state_bytes_each, single_ws,
+                                            single_bytes, info + i, stream);
+        if (st != VIVIT_OK) return st;
+        Kq[q] = 0;
+      }
+    }
+    int st = stein_batched_launch(nb, n, dq, eq, lam, sel, Kq, Zt + i0, ldz, stws, infq, stream);
+    if (st != VIVIT_OK) return st;
+    st = bt_rows_batched_launch(nb, n, lda, A + i0, tauq, Zt + i0, ldz, Kq, stream);
     if (st != VIVIT_OK) return st;
   }
   return VIVIT_OK;

@@ -635,19 +635,19 @@ def _retry_on_launch_chain(solve, intact: bool, G: Optional[torch.Tensor] = None
 SYMEIGVALS_BATCHED_MAX_N = 1280  # above: the whole chip per problem (vivit_symeigvals_batched_f32: VIVIT_E_UNSUPPORTED)
 
 
-def check_info_batched(info: torch.Tensor):
+def check_info_batched(info: torch.Tensor, what: str = "symeigvals_batched"):
     """:func:`check_info` for the ``[B]`` status vector of a batched solve: ONE device->host read; the error names the
     failing problem."""
     host = info.tolist()
     for i, nfail in enumerate(host):
         if nfail == _lib.VIVIT_INFO_PERSIST_TIMEOUT:
             raise PersistentKernelTimeout(
-                f"symeigvals_batched: a persistent kernel could not become resident (two attempts of 2 s) or stalled "
+                f"{what}: a persistent kernel could not become resident (two attempts of 2 s) or stalled "
                 f"(reported at problem {i}; the whole batch is void); "
                 "VIVIT_SYTRD_PERSIST=0 VIVIT_QR_PERSIST=0 VIVIT_SB2ST_PERSIST=0 select the launch chains")
     for i, nfail in enumerate(host):
         if nfail != 0:
-            raise RuntimeError(f"symeigvals_batched: problem {i}: {nfail} eigenvalues did not converge")
+            raise RuntimeError(f"{what}: problem {i}: {nfail} eigenvalues did not converge")
 
 
 @_launcher
@@ -712,6 +712,126 @@ def symeigvals_batched(mats, overwrite: bool = False, info_out: Optional[list] =
         import warnings
 
         warnings.warn("symeigvals_batched: persistent kernel timed out; repeating the batch on the launch chains", RuntimeWarning)
+        if backups is not None:
+            for G, b in zip(mats, backups):
+                G.copy_(b)
+        with persistent_kernels(False):
+            return solve()
+
+
+class SymeigBatchPlan:
+    """``B`` symmetric matrices of one size reduced together (:func:`symeig_reduce_batched`): ``evals`` is ``[B, n]``
+    (row ``b`` ascending), ``plans[b]`` an ordinary :class:`SymeigPlan` of problem ``b`` that can still be selected from
+    on its own, :meth:`select` the batched phase 2."""
+
+    def __init__(self, evals, n, plans, work=None, state=None):
+        self.evals, self.n, self.plans = evals, n, plans
+        self._work, self._state = work, state
+
+    @_launcher_method
+    def select(self, keeps):
+        """``keeps``: ``B`` index lists (rules of :meth:`SymeigPlan.select`: any order, repeats, negatives, ``IndexError``
+        out of range; the lists may differ in length and may be empty).  Returns a list of ``[n, K_b]`` tensors."""
+        n, B, dev = self.n, len(self.plans), self.evals.device
+        keeps = [[int(k) for k in (keep.tolist() if isinstance(keep, torch.Tensor) else keep)] for keep in keeps]
+        if len(keeps) != B:
+            raise ValueError(f"need one index list per problem: got {len(keeps)} for {B} problems")
+        keeps = [[k + n if k < 0 else k for k in keep] for keep in keeps]
+        if any(k < 0 or k >= n for keep in keeps for k in keep):
+            raise IndexError(f"eigenvector index out of range for n = {n}")
+        if self._state is None:  # sizes outside the batched range: problem after problem
+            return [plan.select(keep) for plan, keep in zip(self.plans, keeps)]
+        uniqs = [sorted(set(keep)) for keep in keeps]
+        Ks = [len(u) for u in uniqs]
+        if sum(Ks) == 0:
+            return [torch.empty((n, 0), dtype=torch.float32, device=dev) for _ in keeps]
+        idx = torch.tensor([k for u in uniqs for k in u], dtype=torch.int32, device=dev)
+        Zt = torch.empty((sum(Ks), n), dtype=torch.float32, device=dev)
+        rows = list(Zt.split(Ks))
+        info = torch.zeros(B, dtype=torch.int32, device=dev)
+        lib = _lib.load()
+        ws, wsb = _workspace(lib.vivit_symeig_select_batched_f32_workspace_bytes(n, B, max(Ks)), self.evals)
+        a_ptrs = (ctypes.c_void_p * B)(*[A.data_ptr() for A in self._work])
+        z_ptrs = (ctypes.c_void_p * B)(*[(r.data_ptr() if K else None) for r, K in zip(rows, Ks)])
+        s_ptrs = (ctypes.c_void_p * B)(*[s.data_ptr() for s in self._state])
+        k_arr = (ctypes.c_int64 * B)(*Ks)
+        st = lib.vivit_symeig_select_batched_f32(a_ptrs, B, n, n, idx.data_ptr(), k_arr, z_ptrs, n, s_ptrs,
+                                                 self._state[0].numel(), ws, wsb, info.data_ptr(), _stream(self.evals))
+        _lib.check(st, "vivit_symeig_select_batched_f32")
+        check_info_batched(info, "symeig_reduce_batched.select")
+        out = []
+        for r, uniq, keep in zip(rows, uniqs, keeps):
+            if uniq != keep:  # caller's order / repeated indices
+                pos = {k: i for i, k in enumerate(uniq)}
+                r = r[torch.tensor([pos[k] for k in keep], dtype=torch.long, device=dev)]
+            out.append(r.T)
+        return out
+
+
+@_launcher
+def symeig_reduce_batched(mats, overwrite: bool = False, info_out: Optional[list] = None) -> SymeigBatchPlan:
+    """Phase 1 of the selected-eigenvector solver for ``B`` symmetric matrices of ONE size (a list of ``[n, n]`` tensors or
+    a ``[B, n, n]`` tensor, fp32, one device; ``ValueError`` for mixed sizes or an empty list): all eigenvalues in
+    ``.evals`` ``[B, n]``, then ``.select(keeps)`` for only the wanted eigenvectors of every problem
+    (``vivit_symeig_reduce_batched_f32`` / ``vivit_symeig_select_batched_f32``).
+
+    For 193 <= n <= 1280 eight problems share one persistent tridiagonalisation launch (one per XCD), one bisection
+    launch, and -- in ``select`` -- the inverse iteration and one back-transformation launch; row ``b`` of ``evals`` and
+    ``plans[b].select(keep)`` equal ``symeig_reduce(G_b)`` bit for bit.  n < 193 and n > 1280 are loops over
+    :func:`symeig_reduce`.  Contract of :func:`symeigvals_batched`: inputs solved in place only with ``overwrite=True``,
+    one leading dimension per batch, ONE device->host read of the ``[B]`` ``info`` vector (``RuntimeError`` names the
+    failing problem; a list passed as ``info_out`` receives the vector instead), and a
+    :class:`PersistentKernelTimeout` repeats the batch once on the launch chains when the inputs are still there."""
+    mats = list(mats.unbind(0)) if isinstance(mats, torch.Tensor) and mats.dim() == 3 else list(mats)
+    if not mats:
+        raise ValueError("symeig_reduce_batched needs at least one matrix")
+    _require_device(*mats)
+    for G in mats:
+        if G.dim() != 2 or G.shape[0] != G.shape[1]:
+            raise ValueError(f"Input must be a square matrix. Got shape {tuple(G.shape)}.")
+        if G.shape != mats[0].shape:
+            raise ValueError(f"symeig_reduce_batched needs matrices of one size, got {tuple(mats[0].shape)} and {tuple(G.shape)}")
+    n, B, dev = mats[0].shape[0], len(mats), mats[0].device
+    if n < SYMEIG_ROWS_MIN_N or n > SYMEIGVALS_BATCHED_MAX_N:
+        plans = [symeig_reduce(G, overwrite=overwrite) for G in mats]
+        if info_out is not None:
+            info_out.append(torch.zeros(B, dtype=torch.int32, device=dev))
+        return SymeigBatchPlan(torch.stack([p.evals for p in plans]), n, plans)
+    lib = _lib.load()
+
+    def solve():
+        work = []
+        for G in mats:
+            A = _as2d(G)
+            if _ld(A) != n:
+                A = A.contiguous()   # one leading dimension for the whole batch
+            if A.data_ptr() == G.data_ptr() and not overwrite:
+                A = A.clone()  # the solver destroys its inputs
+            work.append(A)
+        W = torch.empty((B, n), dtype=torch.float32, device=dev)
+        info = torch.zeros(B, dtype=torch.int32, device=dev)
+        each = (lib.vivit_symeig_reduce_f32_workspace_bytes(n) + 256 + 255) // 256 * 256
+        state = list(torch.empty((B, each), dtype=torch.uint8, device=dev).unbind(0))
+        a_ptrs = (ctypes.c_void_p * B)(*[A.data_ptr() for A in work])
+        s_ptrs = (ctypes.c_void_p * B)(*[s.data_ptr() for s in state])
+        st = lib.vivit_symeig_reduce_batched_f32(a_ptrs, B, n, n, W.data_ptr(), s_ptrs, each, info.data_ptr(), _stream(mats[0]))
+        _lib.check(st, "vivit_symeig_reduce_batched_f32")
+        if info_out is not None:
+            info_out.append(info)
+        else:
+            check_info_batched(info, "symeig_reduce_batched")
+        plans = [SymeigPlan(W[b], n, A=work[b], state=state[b]) for b in range(B)]
+        return SymeigBatchPlan(W, n, plans, work=work, state=state)
+
+    backups = [G.clone() for G in mats] if overwrite and all(_wants_backup(G) for G in mats) else None
+    try:
+        return solve()
+    except PersistentKernelTimeout:
+        if overwrite and backups is None:
+            raise
+        import warnings
+
+        warnings.warn("symeig_reduce_batched: persistent kernel timed out; repeating the batch on the launch chains", RuntimeWarning)
         if backups is not None:
             for G, b in zip(mats, backups):
                 G.copy_(b)

@@ -1,7 +1,9 @@
 """GGN eigenpairs during backpropagation (API of ``vivit.linalg.eigh``)."""
+import contextlib
 from typing import Any, Callable, Dict, List, Tuple
 from warnings import warn
 
+import torch
 from torch import Tensor
 from torch.nn import Module, Parameter
 
@@ -37,12 +39,28 @@ class EighComputation:
         side: str = "gram",
         data_parallel: bool = False,
         process_group=None,
+        batched_solve: bool = False,
     ):
         """``side`` (not in the reference): ``"auto"`` solves a group on its parameter side (``P x P``, eigenvectors
         directly in parameter space) when it has fewer parameters than Gram rows; ``"gram"`` = reference path.
         ``data_parallel`` / ``process_group`` (not in the reference): batch-sharded ranks, see
         :class:`vivit_amd.linalg.EigvalshComputation`; the back-projection ``V e`` is summed over the ranks'
-        samples with one all-reduce of ``K P`` floats."""
+        samples with one all-reduce of ``K P`` floats.
+        ``batched_solve`` (not in the reference): for block-diagonal curvature with many groups of one Gram size.  A
+        group that is solved on the Gram side on one device is not solved in its hook: its Gram matrix is built as usual
+        and queued together with the group's ``V_mat_prod`` closures, and the queue goes through
+        ``kernels.symeig_reduce_batched`` -- reduction, bisection, inverse iteration and back-transformation of eight
+        matrices of 193 <= n <= 1280 in one launch each, where a loop of single solves leaves most of the chip idle --
+        as soon as eight matrices of one size wait, and for the remainder on the first ``get_result``.  A flush runs:
+        batched reduction, per group scaling and ``criterion``, batched select, per group back-projection, ``normalize``
+        and the small-eigenvalue warning.  The eigenvalues are those of ``batched_solve=False`` bit for bit; the
+        eigenvectors agree to rounding (another back-transformation kernel).  The save-fields are deleted in the hook
+        either way.  The price: the factors of up to eight queued groups (kept alive by the closures) and their Gram
+        matrices stay in memory until their flush, where the immediate path frees each group's factors in its hook.
+        Parameter-side groups and ``data_parallel=True`` keep the immediate solve.  Streams as in
+        :class:`vivit_amd.linalg.EigvalshComputation`: every flush runs on the stream its matrices were queued on;
+        when ``get_result`` finds another stream current, that stream waits for the flush and the results are
+        recorded on it."""
         check_subsampling_unique(subsampling)
         use_parameter_side([], 1, side)  # validates ``side``
         if data_parallel and side != "gram":
@@ -57,9 +75,56 @@ class EighComputation:
         self._batch_size: Dict[int, int] = {}
         self._evals: Dict[int, Tensor] = {}
         self._evecs: Dict[int, List[Tensor]] = {}
+        self._batched_solve = bool(batched_solve) and not data_parallel
+        # (device, n, stream) -> [(gram, group_id, scale, criterion, V_mat_prod closures, (C, N))]
+        self._pending: Dict[Any, List] = {}
+
+    _FLUSH_AT = 8  # matrices of one size that make a full launch (one per XCD)
+    _SMALL_WARNING = (
+        "Some eigenvectors have small eigenvalues."
+        + " Their parameter space transformation is numerically unstable."
+        + " This can spoil orthogonality of eigenvectors."
+        + " Maybe use a more restrictive eigenvalue filter criterion."
+    )
+
+    def _flush(self, key):
+        """Solve the queue ``key`` in one batched two-phase call on the stream it was filled on, store the eigenpairs."""
+        items = self._pending.pop(key, [])
+        if not items:
+            return
+        grams = [it[0] for it in items]
+        stream = key[2]
+        current = None if stream is None else torch.cuda.current_stream(grams[0].device)
+        foreign = stream is not None and current != stream
+        results = []
+        with torch.cuda.stream(stream) if foreign else contextlib.nullcontext():
+            plan = kernels.symeig_reduce_batched(grams, overwrite=True)
+            rows, keeps = list(plan.evals.unbind(0)), []
+            for row, (_, _, scale, criterion, _, _) in zip(rows, items):
+                if scale is not None:  # eigh.py:245-246; eigenvectors are scale invariant
+                    row *= scale
+                keeps.append(criterion(row))
+            all_evecs = plan.select(keeps)
+            del plan
+            for row, keep, gram_evecs, (_, group_id, _, _, v_mat_prods, (C, N)) in zip(rows, keeps, all_evecs, items):
+                gram_evals = row[keep]
+                if (gram_evals.abs() < self._warn_small_eigvals).any():
+                    warn(self._SMALL_WARNING)
+                gram_evecs = gram_evecs.transpose(0, 1).reshape(-1, C, N)  # [K, C, N] (eigh.py:265)
+                group_evecs = [v_mat_prod(gram_evecs) for v_mat_prod in v_mat_prods]
+                normalize(group_evecs)
+                self._evals[group_id] = gram_evals
+                self._evecs[group_id] = group_evecs
+                results += [gram_evals] + group_evecs
+        if foreign:
+            current.wait_stream(stream)
+            for t in results:
+                t.record_stream(current)
 
     def get_result(self, group: Dict) -> Tuple[Tensor, List[Tensor]]:
         """``(evals, evecs)`` of the group's GGN block; KeyError if unavailable."""
+        for key in list(self._pending):
+            self._flush(key)
         try:
             return self._evals[id(group)], self._evecs[id(group)]
         except KeyError as e:
@@ -104,12 +169,8 @@ class EighComputation:
         batch_sizes, subsampling, savefield = self._batch_size, self._subsampling, self._savefield
         evals, evecs, verbose = self._evals, self._evecs, self._verbose
         warn_small_eigvals, side, dp = self._warn_small_eigvals, self._side, self._dp
-        small_warning = (
-            "Some eigenvectors have small eigenvalues."
-            + " Their parameter space transformation is numerically unstable."
-            + " This can spoil orthogonality of eigenvectors."
-            + " Maybe use a more restrictive eigenvalue filter criterion."
-        )
+        small_warning = self._SMALL_WARNING
+        batched, pending, flush, flush_at = self._batched_solve, self._pending, self._flush, self._FLUSH_AT
 
         def group_hook(self: ParameterGroupsHook, accumulation: None, group: Dict[str, Any]) -> None:
             group_id = id(group)
@@ -120,8 +181,6 @@ class EighComputation:
             C, N = get_closures(group["params"][0], savefield)["shape_cn"]
             if use_parameter_side(group["params"], C * N, side):
                 # P x P block of the GGN: its eigenvectors are the parameter-space eigenvectors themselves
-                import torch
-
                 all_evals, Q, cols = parameter_side_symeig(group["params"], savefield, eigenvectors=True)
                 if subsampling is not None:
                     all_evals *= batch_size / len(subsampling)
@@ -161,6 +220,20 @@ class EighComputation:
                     gram_fn = get_closures(param, savefield)["gram_mat"]
                     gram_mat = gram_fn() if gram_mat is None else gram_fn(out=gram_mat, beta=1.0)
             C, N = gram_mat.shape[:2]
+
+            if batched and acc is None:  # queue for the batched two-phase solve (the closures keep the factors alive)
+                square = reshape_as_square(gram_mat)
+                scale = None if subsampling is None else batch_size / len(subsampling)
+                v_mat_prods = []
+                for param in group["params"]:
+                    v_mat_prods.append(get_closures(param, savefield)["V_mat_prod"])
+                    delete_savefield(param, savefield, verbose=verbose)
+                stream = torch.cuda.current_stream(square.device) if square.is_cuda else None
+                key = (square.device, square.shape[0], stream)
+                pending.setdefault(key, []).append((square, group_id, scale, group["criterion"], v_mat_prods, (C, N)))
+                if len(pending[key]) >= flush_at:
+                    flush(key)
+                return
 
             # two launches around the criterion callback: reduction + all eigenvalues, then only the kept eigenvectors
             # (inverse iteration + back-transformation of K rows; the reference computes all n and slices, eigh.py:248-253)
