@@ -196,7 +196,8 @@ int vivit_conv2d_weight_mjp_f32(const float *M, const float *x, float *V, int64_
  * ------------------------------------------------------------------------------------------- */
 /* out[v, e] = M[v, e] * f'(x[e]), e < per_v (= N * features).  kind: 0 ReLU, 1 Sigmoid, 2 Tanh, 3 LeakyReLU (param =
  * negative slope), 4 LogSigmoid, 5 ELU (param = alpha), 6 SELU.  Replaces SqrtGGN{ReLU,Sigmoid,Tanh,LeakyReLU,LogSigmoid,
- * ELU,SELU} (__init__.py:87-93). */
+ * ELU,SELU} (__init__.py:87-93).  A NaN in x: as torch's autograd of the module -- ReLU passes the factor unchanged and
+ * LeakyReLU scales it by the slope (the branch a failed comparison selects there), every other rule gives NaN. */
 int vivit_act_jac_t_f32(const float *M, const float *x, float *out, int64_t V, int64_t per_v, int kind, float param,
                         void *stream);
 /* out[r, c, l] = M[r, c, l] * scale[c]: BatchNorm in eval mode, scale = weight / sqrt(running_var + eps)
@@ -226,7 +227,9 @@ int vivit_row_dot_f32(const float *M, const float *X, float *out, int64_t rows, 
  * positions; X [rows_x = N C, L] the module's input): mx[r] = sum_l M[r, l] X[r % rows_x, l] and msum[r] = sum_l M[r, l]
  * (the weight rule sum_l M xhat = (mx - mean_c msum) rstd_c and the bias rule; batchnormnd.py:3 with
  * BatchNormNdDerivatives.param_mjp), out[r, l] = M[r, l] scale[r % C] (the input rule, scale = weight_c rstd_c).  Any of
- * out / mx / msum may be NULL.  Same summation order as vivit_row_dot_f32 (bit-identical sums).  wmean / wrstd ([C], both or
+ * out / mx / msum may be NULL.  Same summation order as vivit_row_dot_f32 (bit-identical sums whenever both take the same
+ * body: this kernel takes the 16-byte one when L % 4 == 0 and M, X and out are all 16-byte aligned, vivit_row_dot_f32 looks
+ * only at the operands it reads).  wmean / wrstd ([C], both or
  * neither): mx then holds the finished weight rule (mx - wmean_c msum) wrstd_c with wmean = running_mean, wrstd = 1/sqrt(var + eps). */
 int vivit_bn_eval_rules_f32(const float *M, const float *X, const float *scale, float *out, float *mx, float *msum, int64_t rows,
                             int64_t rows_x, int64_t C, int64_t L, const float *wmean, const float *wrstd, void *stream);

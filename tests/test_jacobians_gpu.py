@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+import epilogue_refs as R
 from oracle import vivit_oracle as oracle
 
 pytestmark = pytest.mark.gpu
@@ -41,7 +42,7 @@ def test_activation_rules(kind, module):
 
 
 @pytest.mark.parametrize("shape,k,s,p", [((64, 6, 28, 28), 2, 2, 0), ((9, 5, 13, 11), 3, 2, 1), ((4, 3, 8, 8), 3, 1, 1),
-                                         ((3, 2, 7, 9), (2, 3), (1, 2), (1, 0))])
+                                         ((3, 2, 7, 9), (2, 3), (1, 2), (1, 0))] + R.POOL_EDGE_GEOMS)
 def test_pooling_rules(shape, k, s, p):
     from vivit_amd import kernels
     from vivit_amd.backend.extensions import _pair
@@ -187,3 +188,167 @@ def test_pack_unpack_lower(n):
     big = torch.zeros(n, n + 3, device=DEV)
     big[:, :n] = Gm
     assert torch.equal(kernels.pack_lower(big[:, :n]), packed)
+
+
+# ---- edges of the factor rules (tests/epilogue_refs.py holds the grids; tests/test_epilogue_refs_host.py states what torch's
+# fp64 CPU autograd gives on them) ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["relu", "sigmoid", "tanh", "leaky_relu", "logsigmoid", "elu", "selu"])
+def test_activation_rules_edge_grid(kind):
+    """x on the grid {0, -0, +-1e-30 .. +-1e4, +-inf, NaN} against fp64 CPU autograd of the torch module: every entry in the
+    same class (finite, inf or NaN), an exactly zero reference exactly zero here, finite entries at the tolerance of
+    test_activation_rules.  (A zero class of its own cannot be asked of fp32: sigmoid'(20) = 2e-9 in fp64 is 0 in fp32
+    because 1 + e^-20 rounds to 1; the implication tested is reference == 0  =>  result == 0.)"""
+    from vivit_amd import kernels
+
+    g = torch.Generator().manual_seed(8)
+    x = R.act_grid_input()
+    M = torch.randn(3, *x.shape, generator=g) + 2.0 * torch.sign(torch.randn(3, *x.shape, generator=g))   # |M| away from 0
+    ref = R.act_reference(kind, x, M)
+    got = kernels.act_jac_t(M.to(DEV), x.to(DEV), kind, R.ACT_PARAM.get(kind, 0.0)).cpu().double()
+    assert torch.equal(got.isnan(), ref.isnan()), "NaN entries differ"
+    assert torch.equal(got.isinf(), ref.isinf()), "inf entries differ"
+    assert bool((got[ref == 0] == 0).all()), "a zero of the reference is not zero"
+    fin = ref.isfinite()
+    close(got[fin], ref[fin], rtol=2e-5, atol=1e-6)
+
+
+def test_activation_rule_grid_stride():
+    """More than 262 144 x 256 = 67 108 864 elements: the second trip of the grid-stride loop.  ReLU: bit-exact."""
+    from vivit_amd import kernels
+
+    V, per_v = 3, 22_400_000
+    assert V * per_v > 262144 * 256
+    g = torch.Generator(device=DEV).manual_seed(9)
+    x = torch.randn(per_v // 100, 100, generator=g, device=DEV)
+    M = torch.randn(V, *x.shape, generator=g, device=DEV)
+    got = kernels.act_jac_t(M, x, "relu")
+    ok = torch.equal(got, M * (x > 0))
+    del got, M
+    torch.cuda.empty_cache()
+    assert ok
+
+
+@pytest.mark.parametrize("V,N,C,sp", [(2, 3, 5, ()), (2, 3, 1, (4, 3)), (1, 1, 7, (13,)), (3, 2, 1, ())],
+                         ids=["L=1", "C=1", "prime-CL", "C=1-L=1"])
+def test_channel_scale_edges(V, N, C, sp):
+    from vivit_amd import kernels
+
+    g = torch.Generator(device=DEV).manual_seed(10)
+    M = torch.randn(V, N, C, *sp, generator=g, device=DEV)
+    scale = torch.randn(C, generator=g, device=DEV)
+    got = kernels.channel_scale(M, scale)
+    assert torch.equal(got, M * scale.view(1, 1, C, *([1] * len(sp))))
+
+
+@pytest.mark.parametrize("plane", ["constant", "neg-inf", "one-nan"])
+@pytest.mark.parametrize("shape,k,s,p", [((3, 2, 8, 8), 2, 2, 0), ((2, 3, 7, 9), 3, 2, 1)] + R.POOL_EDGE_GEOMS[:2])
+def test_pooling_rules_special_planes(shape, k, s, p, plane):
+    """A constant plane (every window tied: the first position in scan order takes the gradient), a plane of -inf and a plane
+    with one NaN (the NaN is its windows' maximum), against torch autograd on the same device; input positions outside every
+    window get exactly 0."""
+    from vivit_amd import kernels
+
+    g = torch.Generator(device=DEV).manual_seed(12)
+    x = torch.randn(*shape, generator=g, device=DEV)
+    if plane == "constant":
+        x[0, 0] = 0.75
+        x[1, 1] = 0.0
+    elif plane == "neg-inf":
+        x[0, 0] = float("-inf")
+        x[1, 1, 2:5, 1:4] = float("-inf")
+    else:
+        x[0, 0, 3, 3] = float("nan")
+        x[1, 1, 0, 0] = float("nan")
+    unc = R.pool_uncovered(shape[2], shape[3], k, s, p).to(DEV)
+    mod = nn.MaxPool2d(k, s, p)
+    y = mod(x)
+    M = torch.randn(2, *y.shape, generator=g, device=DEV)
+    ref = jac_t_by_autograd(mod, x, M)
+    got = kernels.maxpool2d_jac_t(M, x, R.pair(k), R.pair(s), R.pair(p))
+    close(got, ref)
+    assert bool((got[..., unc] == 0).all())
+    mod = nn.AvgPool2d(k, s, p)
+    got = kernels.avgpool2d_jac_t(M, x.shape[2:], R.pair(k), R.pair(s), R.pair(p))
+    close(got, jac_t_by_autograd(mod, x, M))
+    assert bool((got[..., unc] == 0).all())
+
+
+@pytest.mark.parametrize("shape,k,s,p", R.POOL_EDGE_GEOMS)
+def test_pooling_rules_uncovered_positions(shape, k, s, p):
+    from vivit_amd import kernels
+
+    g = torch.Generator(device=DEV).manual_seed(13)
+    x = torch.randn(*shape, generator=g, device=DEV)
+    unc = R.pool_uncovered(shape[2], shape[3], k, s, p).to(DEV)
+    y = nn.MaxPool2d(k, s, p)(x)
+    M = torch.randn(2, *y.shape, generator=g, device=DEV).abs() + 0.5
+    assert bool((kernels.maxpool2d_jac_t(M, x, R.pair(k), R.pair(s), R.pair(p))[..., unc] == 0).all())
+    avg = kernels.avgpool2d_jac_t(M, x.shape[2:], R.pair(k), R.pair(s), R.pair(p))
+    assert bool((avg[..., unc] == 0).all()) and bool((avg[..., ~unc] != 0).all())
+
+
+def _ce_checks(logits, N, C):
+    from vivit_amd import kernels
+
+    S = kernels.ce_sqrt_hessian(logits, 1.0 / math.sqrt(N))
+    ref = oracle.loss_hessian_sqrt_exact(logits.cpu().double(), "ce")
+    close(S.cpu().double(), ref, rtol=1e-4, atol=1e-6)
+    del ref
+    p = logits.double().softmax(1)
+    H = torch.einsum("vnc,vnd->ncd", S.double(), S.double())
+    close(H, (torch.diag_embed(p) - p.unsqueeze(2) * p.unsqueeze(1)) / N, rtol=1e-4, atol=1e-6)
+    del H
+    return S
+
+
+@pytest.mark.parametrize("C", [1, 2, 255, 256, 257, 15360])
+def test_cross_entropy_factor_class_counts(C):
+    """C around the workgroup size (256) and at the LDS limit C * 4 = 60 KiB."""
+    from vivit_amd import kernels
+
+    N = 1 if C > 1000 else 5
+    g = torch.Generator(device=DEV).manual_seed(14)
+    logits = torch.randn(N, C, generator=g, device=DEV) * 3
+    S = _ce_checks(logits, N, C)
+    del S
+    torch.cuda.empty_cache()
+    idx = torch.multinomial(logits.softmax(1), 3, replacement=True, generator=g)
+    onehot = F.one_hot(idx.t(), C).float()
+    Smc = kernels.ce_sqrt_hessian(logits, 1.0 / math.sqrt(3 * N), onehot=onehot)
+    close(Smc.cpu().double(), oracle.loss_hessian_sqrt_mc(logits.cpu().double(), onehot.cpu().double()), rtol=1e-4, atol=1e-6)
+
+
+def test_cross_entropy_factor_refuses_too_many_classes():
+    from vivit_amd import _lib, kernels
+
+    logits = torch.zeros(1, 15361, device=DEV)
+    onehot = torch.zeros(1, 1, 15361, device=DEV)
+    with pytest.raises(_lib.VivitHipError) as exc:
+        kernels.ce_sqrt_hessian(logits, 1.0, onehot=onehot)
+    assert exc.value.status == _lib.VIVIT_E_UNSUPPORTED
+
+
+@pytest.mark.parametrize("case", ["one-dominant", "all-equal", "masked", "all-very-negative"])
+@pytest.mark.parametrize("C", [10, 257])
+def test_cross_entropy_factor_logit_edges(C, case):
+    from vivit_amd import kernels
+
+    N = 6
+    g = torch.Generator(device=DEV).manual_seed(15)
+    logits = torch.randn(N, C, generator=g, device=DEV)
+    if case == "one-dominant":
+        logits[torch.arange(N), torch.arange(N) % C] = 1e4
+    elif case == "all-equal":
+        logits[:] = 2.5
+    elif case == "masked":
+        logits[:, 3] = float("-inf")
+    else:
+        logits -= 1e4
+    S = _ce_checks(logits, N, C)
+    assert bool(S.isfinite().all())
+    if case == "masked":   # a masked class: its slice and its column are exactly 0
+        assert bool((S[3] == 0).all()) and bool((S[:, :, 3] == 0).all())
+    idx = torch.multinomial(logits.softmax(1), 3, replacement=True, generator=g)
+    onehot = F.one_hot(idx.t(), C).float()
+    Smc = kernels.ce_sqrt_hessian(logits, 1.0 / math.sqrt(3 * N), onehot=onehot)
+    close(Smc.cpu().double(), oracle.loss_hessian_sqrt_mc(logits.cpu().double(), onehot.cpu().double()), rtol=1e-4, atol=1e-6)

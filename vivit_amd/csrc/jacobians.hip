@@ -15,9 +15,12 @@ namespace vivit {
 // ---- elementwise activations: out[v, n, e] = M[v, n, e] * f'(x[n, e]) ----------------------------------------------
 enum { ACT_RELU = 0, ACT_SIGMOID = 1, ACT_TANH = 2, ACT_LEAKY_RELU = 3, ACT_LOGSIGMOID = 4, ACT_ELU = 5, ACT_SELU = 6 };
 
+// A NaN input fails every comparison.  ReLU and LeakyReLU test what torch's backward kernels test (x <= 0 and x > 0), so the
+// factor passes unchanged through ReLU and with the negative slope through LeakyReLU, as in torch's autograd; every other
+// rule propagates the NaN (ELU and SELU through expf on the x <= 0 side, which a NaN takes here).
 __device__ __forceinline__ float act_derivative(int kind, float x, float a) {
   switch (kind) {
-    case ACT_RELU: return x > 0.f ? 1.f : 0.f;
+    case ACT_RELU: return x <= 0.f ? 0.f : 1.f;
     case ACT_SIGMOID: { const float s = 1.f / (1.f + expf(-x)); return s * (1.f - s); }
     case ACT_TANH: { const float t = tanhf(x); return 1.f - t * t; }
     case ACT_LEAKY_RELU: return x > 0.f ? 1.f : a;
@@ -388,6 +391,13 @@ static ConvJtPlan conv2d_jac_t_mfma_plan(const ConvGeom &g) {
 }
 
 // ---- reductions of the parameter rules --------------------------------------------------------------------------------
+// p . u of two float4 with ONE rounding sequence, spelled out: left to the compiler, the contraction of
+// (p.x u.x + p.y u.y) + (p.z u.z + p.w u.w) into fused multiply-adds came out differently in row_dot_kernel and
+// bn_eval_rules_kernel, and their sums, promised bit-identical, differed in the last bit.
+__device__ __forceinline__ float dot4(const float4 &p, const float4 &u) {
+  return fmaf(p.x, u.x, p.y * u.y) + fmaf(p.z, u.z, p.w * u.w);
+}
+
 // out[r] = sum_l M[r, l] * (X ? X[(r % rows_x), l] : 1): bias of a convolution / BatchNorm (X = null), BatchNorm weight
 // (X = normalised input, shared by the V slices).  One wave per row, fixed summation order.
 __global__ __launch_bounds__(256) void row_dot_kernel(const float *__restrict__ M, const float *__restrict__ X,
@@ -408,8 +418,8 @@ __global__ __launch_bounds__(256) void row_dot_kernel(const float *__restrict__ 
       const float4 p = m4[l], q = m4[l + 64];
       if (xr) {
         const float4 u = x4[l], v = x4[l + 64];
-        a0 += (p.x * u.x + p.y * u.y) + (p.z * u.z + p.w * u.w);
-        a1 += (q.x * v.x + q.y * v.y) + (q.z * v.z + q.w * v.w);
+        a0 += dot4(p, u);
+        a1 += dot4(q, v);
       } else {
         a0 += (p.x + p.y) + (p.z + p.w);
         a1 += (q.x + q.y) + (q.z + q.w);
@@ -419,7 +429,7 @@ __global__ __launch_bounds__(256) void row_dot_kernel(const float *__restrict__ 
       const float4 p = m4[l];
       if (xr) {
         const float4 u = x4[l];
-        a0 += (p.x * u.x + p.y * u.y) + (p.z * u.z + p.w * u.w);
+        a0 += dot4(p, u);
       } else {
         a0 += (p.x + p.y) + (p.z + p.w);
       }
@@ -460,8 +470,8 @@ __global__ __launch_bounds__(256) void bn_eval_rules_kernel(const float *__restr
     for (; l + 64 < L4; l += 128) {
       const float4 p = m4[l], q = m4[l + 64];
       const float4 u = x4[l], v = x4[l + 64];
-      a0 += (p.x * u.x + p.y * u.y) + (p.z * u.z + p.w * u.w);
-      a1 += (q.x * v.x + q.y * v.y) + (q.z * v.z + q.w * v.w);
+      a0 += dot4(p, u);
+      a1 += dot4(q, v);
       b0 += (p.x + p.y) + (p.z + p.w);
       b1 += (q.x + q.y) + (q.z + q.w);
       if (o) {
@@ -472,7 +482,7 @@ __global__ __launch_bounds__(256) void bn_eval_rules_kernel(const float *__restr
     if (l < L4) {
       const float4 p = m4[l];
       const float4 u = x4[l];
-      a0 += (p.x * u.x + p.y * u.y) + (p.z * u.z + p.w * u.w);
+      a0 += dot4(p, u);
       b0 += (p.x + p.y) + (p.z + p.w);
       if (o) o4[l] = make_float4(p.x * sc, p.y * sc, p.z * sc, p.w * sc);
     }
