@@ -426,6 +426,32 @@ int vivit_dir_curvature_f32(const float *GE, const float *evals, float *lambdas,
 int vivit_scale_cols_rsqrt_f32(float *X, const float *evals, int64_t rows, int64_t K, int64_t ldx,
                                float pre, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * K5 + K6 for `batch` per-layer groups of ONE Gram size in one launch: first- and second-order directional
+ * derivatives from the kept Gram eigenvectors, without G E in memory.  Per problem b, K = K[b]:
+ *   gammas[b][j, k]  = alpha_gamma * sum_i VtG[b][i, j] Zt[b][k, i] / sqrt(evals[b][k])
+ *   lambdas[b][m, k] = lambda_scale * sum_c ( alpha_gram * sum_i G[b][(c, m), i] Zt[b][k, i] )^2 / evals[b][k]
+ * G, Zt, evals, VtG, K, gammas, lambdas: HOST arrays of `batch` entries, read before the call returns.
+ *   G[b]: DEVICE [n, n], ldg >= n, symmetric, n = C * N; read in full, not modified.
+ *   Zt[b]: DEVICE [K[b]][ldz >= n], row k = unit eigenvector, as vivit_symeig_select_batched_f32 writes them.
+ *   evals[b]: DEVICE [K[b]], the kept eigenvalues, already scaled.  VtG[b]: DEVICE [n, M], ldv >= M (V_t_g_n flattened).
+ *   K[b]: HOST, 0 <= K[b] <= n, may differ between problems; with K[b] = 0 the problem's pointers may be NULL and
+ *     nothing of it is touched.  gammas[b]: DEVICE [M, K[b]], lambdas[b]: DEVICE [N, K[b]], both contiguous.
+ * Any batch >= 1 and any n >= 1; the problem index is in the grid (the descriptors travel as kernel arguments, 64 per
+ * launch, so a batch of up to 64 is ONE launch).  fp32 accumulation, fixed summation order, no atomics; a problem's
+ * results are bit-independent of the rest of the batch.  evals[k] <= 0 gives the IEEE class (inf / NaN) that
+ * vivit_scale_cols_rsqrt_f32 and vivit_dir_curvature_f32 give.  VIVIT_E_BADARG: null array or operand, negative size,
+ * C * N != n, K[b] outside 0..n, short leading dimension; nothing is launched then.
+ * Replaces, per group, "V_t_g_n contracted with evecs / evals.sqrt()" and "(V_n_T_V_e_d ** 2).sum(0) / evals" of
+ *   vivit/optim/directional_damped_newton.py:342,348-351 and vivit/optim/directional_derivatives.py:317,322-325 (K5/K6),
+ * i.e. the four launches vivit_gemm_tn_f32 + vivit_scale_cols_rsqrt_f32 + vivit_gemm_nn_f32 + vivit_dir_curvature_f32.
+ * ------------------------------------------------------------------------------------------- */
+int vivit_gram_directions_batched_f32(const float *const *G, int64_t batch, int64_t n, int64_t ldg,
+                                      const float *const *Zt, int64_t ldz, const float *const *evals,
+                                      const float *const *VtG, int64_t ldv, const int64_t *K, int64_t C, int64_t N,
+                                      int64_t M, float alpha_gram, float alpha_gamma, float lambda_scale,
+                                      float *const *gammas, float *const *lambdas, void *stream);
+
 /* K10  Squared 2-norms of K stacked vectors: acc[k] += sum_j X[k, j]^2, X: [K, len] contiguous;
  *      then vivit_scale_rows_f32 applies X[k, :] *= rsqrt(acc[k]).
  * Replaces normalize  vivit/linalg/utils.py:67-76. */

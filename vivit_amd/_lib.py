@@ -76,6 +76,8 @@ SIGNATURES = {
     "vivit_stedc_f32": (_int, [_ptr, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _sz, _ptr, _ptr]),
     "vivit_dir_curvature_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _f32, _ptr]),
     "vivit_scale_cols_rsqrt_f32": (_int, [_ptr, _ptr, _i64, _i64, _i64, _f32, _ptr]),
+    "vivit_gram_directions_batched_f32": (_int, [_ptr, _i64, _i64, _i64, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _i64, _i64, _i64,
+                                                 _f32, _f32, _f32, _ptr, _ptr, _ptr]),
     "vivit_row_sqnorm_workspace_bytes": (_sz, [_i64, _i64]),
     "vivit_row_sqnorm_acc_f32": (_int, [_ptr, _ptr, _i64, _i64, _ptr, _sz, _ptr]),
     "vivit_scale_rows_rsqrt_f32": (_int, [_ptr, _ptr, _i64, _i64, _ptr]),
@@ -87,7 +89,8 @@ SIGNATURES = {
     "vivit_unpack_lower_f32": (_int, [_ptr, _i64, _ptr, _i64, _ptr]),
 }
 
-# include/vivit_hip.h of this checkout (vivit_hip_abi_version).  The batched two-phase entry points only ADD exports: the
+# include/vivit_hip.h of this checkout (vivit_hip_abi_version).  The batched entry points (two-phase solve, Gram-space
+# directions) only ADD exports: the
 # number stays; a library without them is refused by the symbol lookup in load() and by the source hash (_check_provenance).
 ABI_VERSION = 1008
 

@@ -1052,6 +1052,70 @@ def scale_cols_rsqrt_(X, evals, pre: float = 1.0):
     return X
 
 
+def _one_ld(mats, cols):
+    """``mats`` as 2-d kernel operands that share ONE leading dimension: as they are when their strides agree,
+    contiguous copies otherwise."""
+    mats = [_as2d(t) for t in mats]
+    lds = {_ld(t) for t in mats if t.shape[0] > 1}
+    if len(lds) > 1:
+        mats = [t.contiguous() for t in mats]
+        lds = {max(cols, 1)}
+    return mats, (lds.pop() if lds else max(cols, 1))
+
+
+@_launcher
+def gram_directions_batched(grams, Zts, evals, VtGs, C: int, N: int, alpha_gram: float, alpha_gamma: float,
+                            lambda_scale: float):
+    """K5 + K6 of ``B`` groups of one Gram size in ONE launch (``vivit_gram_directions_batched_f32``), ``G E`` never
+    stored.  Per problem ``b``: ``grams[b] [n, n]`` (symmetric, ``n = C N``, left intact), ``Zts[b] [K_b, n]`` (rows = kept
+    unit eigenvectors, i.e. ``evecs.T``; ``K_b`` may differ and may be 0), ``evals[b] [K_b]`` (kept eigenvalues, already
+    scaled), ``VtGs[b] [n, M]``.  Returns ``(gammas, lambdas)``, two lists with
+
+      ``gammas[b][j, k]  = alpha_gamma * sum_i VtGs[b][i, j] Zts[b][k, i] / sqrt(evals[b][k])``            ``[M, K_b]``
+      ``lambdas[b][m, k] = lambda_scale * sum_c (alpha_gram * sum_i grams[b][(c, m), i] Zts[b][k, i])^2 / evals[b][k]``  ``[N, K_b]``
+
+    ``ValueError`` for mixed ``n`` or ``M``, for list lengths that differ and for an empty batch."""
+    grams, Zts, evals, VtGs = list(grams), list(Zts), list(evals), list(VtGs)
+    B = len(grams)
+    if B == 0:
+        raise ValueError("gram_directions_batched needs at least one problem")
+    if not (len(Zts) == len(evals) == len(VtGs) == B):
+        raise ValueError(f"need one entry per problem in every list: got {B}, {len(Zts)}, {len(evals)}, {len(VtGs)}")
+    _require_device(*grams, *Zts, *evals, *VtGs)
+    n, dev = C * N, grams[0].device
+    for G in grams:
+        if G.dim() != 2 or G.shape[0] != G.shape[1]:
+            raise ValueError(f"Input must be a square matrix. Got shape {tuple(G.shape)}.")
+        if G.shape[0] != n:
+            raise ValueError(f"gram_directions_batched needs Gram matrices of one size n = C N = {n}, got {tuple(G.shape)}")
+    if any(V.dim() != 2 or V.shape[0] != n for V in VtGs):
+        raise ValueError(f"every V^T g must be [{n}, M]")
+    M = VtGs[0].shape[1]
+    if any(V.shape[1] != M for V in VtGs):
+        raise ValueError(f"gram_directions_batched needs one M, got {sorted({V.shape[1] for V in VtGs})}")
+    Ks = [int(w.numel()) for w in evals]
+    for Zt, K in zip(Zts, Ks):
+        if Zt.dim() != 2 or tuple(Zt.shape) != (K, n):
+            raise ValueError(f"Zt must be [K, n] = [{K}, {n}] (one row per kept eigenvalue), got {tuple(Zt.shape)}")
+    grams, ldg = _one_ld(grams, n)
+    VtGs, ldv = _one_ld(VtGs, M)
+    Zts, ldz = _one_ld(Zts, n)
+    evals = [w.contiguous() for w in evals]
+    gam = torch.empty(M * sum(Ks), dtype=torch.float32, device=dev)
+    lam = torch.empty(N * sum(Ks), dtype=torch.float32, device=dev)
+    gammas = [g.view(M, K) for g, K in zip(gam.split([M * K for K in Ks]), Ks)]
+    lambdas = [l.view(N, K) for l, K in zip(lam.split([N * K for K in Ks]), Ks)]
+
+    def ptrs(ts):
+        return (ctypes.c_void_p * B)(*[(t.data_ptr() if t.numel() else None) for t in ts])
+
+    st = _lib.load().vivit_gram_directions_batched_f32(
+        ptrs(grams), B, n, ldg, ptrs(Zts), ldz, ptrs(evals), ptrs(VtGs), ldv, (ctypes.c_int64 * B)(*Ks), C, N, M,
+        alpha_gram, alpha_gamma, lambda_scale, ptrs(gammas), ptrs(lambdas), _stream(grams[0]))
+    _lib.check(st, "vivit_gram_directions_batched_f32")
+    return gammas, lambdas
+
+
 @_launcher
 def normalize_rows_(tensors):
     """Normalise ``K`` stacked vectors given in parameter-list format, in place (K10).

@@ -8,6 +8,7 @@ from torch.nn import Module
 from vivit_amd import kernels
 from vivit_amd.linalg.utils import get_hook_store_batch_size
 from vivit_amd.optim.directional_derivatives import (
+    GramDirectionsQueue,
     accumulate_dot_products,
     apply_factor,
     dot_products,
@@ -47,8 +48,9 @@ class DirectionalDampedNewtonComputation:
         factorised: bool = False,
         data_parallel: bool = False,
         process_group=None,
+        batched_solve: bool = False,
     ):
-        """Reference signature (vivit/optim/directional_damped_newton.py:39-83) plus three opt-in extensions:
+        """Reference signature (vivit/optim/directional_damped_newton.py:39-83) plus four opt-in extensions:
 
         ``factorised``: Linear weights keep ``V_t = s (x) z`` and ``grad_batch = delta (x) z`` factorised
           (vivit/extensions/secondorder/vivit/linear.py:41-42) -- same step, no ``[C, N, out, in]`` tensors (the only
@@ -58,6 +60,21 @@ class DirectionalDampedNewtonComputation:
           (:class:`vivit_amd.distributed.BatchShardedGram`), eigensolve / gammas / lambdas run replicated, each rank
           back-projects its own samples and one all-reduce of ``P`` floats sums the step
           (directional_damped_newton.py:370-373).  The batch size used for the scalings is the global one.
+        ``batched_solve``: for block-diagonal curvature with many groups of one Gram size (one group per layer).  A group
+          whose dot products are complete is not solved in its hook but queued under ``(device, n, C, N_grad, stream)``; a
+          queue goes through ``kernels.symeig_reduce_batched`` (eight matrices of 193 <= n <= 1280 share every launch of
+          the eigensolver), one batched ``select`` and ONE ``kernels.gram_directions_batched`` launch for all gammas and
+          lambdas -- where the immediate mode issues reduce, select and four small launches per group -- as soon as eight
+          groups wait, and for the remainder on the first ``get_result``.  Then, per group as in the immediate mode: the
+          small-eigenvalue warning, the ``damping`` callback, the coefficients and the back-projection through the factors
+          (:class:`vivit_amd.optim.directional_derivatives.GramDirectionsQueue`).  The save-fields are deleted in the hook
+          either way.  The price: the Gram matrices, ``V_t_g_n`` AND the factors ``V`` of up to eight queued groups per
+          size stay in memory until their flush, where the immediate mode frees each group's factors in its hook.  The
+          steps agree with the immediate mode to rounding (the eigenvalues bit for bit; the eigenvectors come from
+          another back-transformation kernel, their sign cancels in the step).  ``data_parallel=True`` keeps the
+          immediate path.  Streams as in :class:`vivit_amd.linalg.EighComputation`: a flush runs on the stream its groups
+          were queued on; when ``get_result`` finds another stream current, that stream waits for the flush and the
+          results are recorded on it.
         """
         check_subsampling_unique(subsampling_grad)
         check_subsampling_unique(subsampling_ggn)
@@ -74,8 +91,11 @@ class DirectionalDampedNewtonComputation:
         self._warn_small_eigvals = warn_small_eigvals
         self._batch_size: Dict[int, int] = {}
         self._newton_steps: Dict[int, Tuple[Tensor]] = {}
+        self._batched_solve = bool(batched_solve) and not data_parallel
+        self._queue = GramDirectionsQueue(self._finish_queued, warn_small_eigvals, _SMALL_EVALS_NEWTON, verbose)
 
     def get_result(self, group: Dict) -> Tuple[Tensor]:
+        self._queue.flush_all()
         try:
             return self._newton_steps[id(group)]
         except KeyError as e:
@@ -96,7 +116,8 @@ class DirectionalDampedNewtonComputation:
             lambda hook, param: self._param_computation(
                 hook, param, self._savefield_ggn, self._savefield_grad, self._verbose, self._dp
             ),
-            lambda hook, accumulation, group: self._group_hook(
+            lambda hook, accumulation, group: self._queue_group(accumulation, group)
+            if self._batched_solve else self._group_hook(
                 hook, accumulation, group, self._batch_size, self._savefield_ggn, self._newton_steps,
                 self._verbose, self._warn_small_eigvals,
             ),
@@ -121,6 +142,25 @@ class DirectionalDampedNewtonComputation:
         # V is kept for the back-projection of the step (directional_damped_newton.py:258)
         delete_savefield(param, savefield_grad, verbose=verbose)
         return result
+
+    def _queue_group(self, accumulation, group):
+        """``batched_solve``: queue the group with its factors (the queue keeps them alive), free the save-fields now."""
+        factors = []
+        for param in group["params"]:
+            factors.append(getattr(param, self._savefield_ggn))
+            delete_savefield(param, self._savefield_ggn, verbose=self._verbose)
+        self._queue.add(accumulation, group, self._batch_size.pop(id(group)), payload=factors)
+
+    def _finish_queued(self, group, factors, evals, evecs, gammas, lambdas, V_correction, C, N_ggn):
+        """The tail of :meth:`_group_hook` for a group that went through the queue."""
+        coefficients = (
+            -gammas.mean(0) / (lambdas.mean(0) + group["damping"](evals, evecs, gammas, lambdas)) / evals.sqrt()
+        )
+        v = kernels.gemm_nn(evecs, coefficients.reshape(-1, 1).contiguous(), alpha=V_correction)  # [n, 1]
+        coef = v.reshape(1, C, N_ggn)
+        steps = [apply_factor(V, coef)[0].view(param.shape) for V, param in zip(factors, group["params"])]
+        self._newton_steps[id(group)] = steps
+        return steps
 
     @staticmethod
     def _group_hook(hook, accumulation, group, batch_size, savefield_ggn, newton_steps, verbose,

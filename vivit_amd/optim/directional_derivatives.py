@@ -4,10 +4,12 @@ API of ``vivit.optim.directional_derivatives`` (vivit/optim/directional_derivati
 computed on the MI355X kernels.  The Gram-space part shared with the damped Newton step lives
 in :func:`gram_space_directions`.
 """
+import contextlib
 import math
 from typing import Callable, Dict, List, Optional, Tuple
 from warnings import warn
 
+import torch
 from torch import Tensor
 from torch.nn import Module
 
@@ -186,6 +188,94 @@ def gram_space_directions(accumulation: Dict[str, Tensor], group: Dict, N: int, 
     return evals, evecs, gammas, lambdas, V_correction, C, N_ggn, dp_acc
 
 
+class GramDirectionsQueue:
+    """The ``batched_solve=True`` mode of the two optim computations: groups whose dot products are complete wait here
+    instead of going through :func:`gram_space_directions` one by one (modelled on ``EighComputation._pending``).
+
+    Key ``(device, n, C, M, stream)``; a key is flushed when :attr:`FLUSH_AT` groups wait under it, everything else by
+    :meth:`flush_all` (the computations call it first thing in ``get_result``).  A flush runs, on the stream the groups
+    were queued on: ``kernels.symeig_reduce_batched`` on copies (the Gram matrices are needed again), per group the
+    eigenvalue scaling and ``criterion``, ONE batched ``select``, ONE ``kernels.gram_directions_batched``, then per group
+    the small-eigenvalue warning and ``finish(group, payload, evals, evecs, gammas, lambdas, V_correction, C, N_ggn)``, which
+    stores the group's result and returns its tensors (recorded on the current stream when that is another one).
+    Until its flush a queued group keeps its Gram matrix, ``V_t_g_n`` and whatever ``payload`` references alive."""
+
+    FLUSH_AT = 8  # matrices of one size that make a full launch of the batched eigensolver (one per XCD)
+
+    def __init__(self, finish: Callable, warn_small_eigvals: float, warning: str, verbose: bool):
+        self._finish, self._warn_small_eigvals, self._warning, self._verbose = finish, warn_small_eigvals, warning, verbose
+        # key -> [(gram [n, n], V_t_g_n [n, M], group, N, C, N_ggn, payload)]
+        self.pending: Dict[Tuple, List] = {}
+
+    def add(self, accumulation: Dict[str, Tensor], group: Dict, N: int, payload=None):
+        V_t_V = accumulation.pop("V_t_V")
+        C, N_ggn = V_t_V.shape[0], V_t_V.shape[1]
+        gram = reshape_as_square(V_t_V)
+        vtg = accumulation.pop("V_t_g_n").flatten(start_dim=0, end_dim=1)  # [n, N_grad]
+        stream = torch.cuda.current_stream(gram.device) if gram.is_cuda else None
+        key = (gram.device, gram.shape[0], C, vtg.shape[1], stream)
+        self.pending.setdefault(key, []).append((gram, vtg, group, N, C, N_ggn, payload))
+        if len(self.pending[key]) >= self.FLUSH_AT:
+            self.flush(key)
+
+    def flush_all(self):
+        for key in list(self.pending):
+            self.flush(key)
+
+    def flush(self, key):
+        items = self.pending.pop(key, [])
+        if not items:
+            return
+        stream = key[4]
+        current = None if stream is None else torch.cuda.current_stream(key[0])
+        foreign = stream is not None and current != stream
+        results = []
+        with torch.cuda.stream(stream) if foreign else contextlib.nullcontext():
+            results = self._solve(items)
+        if foreign:
+            current.wait_stream(stream)
+            for t in results:
+                t.record_stream(current)
+
+    def _solve(self, items) -> List[Tensor]:
+        verbose = self._verbose
+        grams = [it[0] for it in items]
+        if verbose:
+            print(f"Groups {[id(it[2]) for it in items]}: Eigen-decompose {len(items)} Gram matrices together")
+        plan = kernels.symeig_reduce_batched(grams)   # on copies: the directions kernel reads the Gram matrices again
+        rows, keeps, corrections = list(plan.evals.unbind(0)), [], []
+        for row, (_, _, group, N, _, N_ggn, _) in zip(rows, items):
+            V_correction = math.sqrt(N / N_ggn)  # compensates BackPACK's 1/sqrt(N) and the sub-sampling
+            row *= V_correction**2
+            keep = group["criterion"](row)
+            if verbose:
+                print(f"Group {id(group)}: Filter directions ({len(row)} → {len(keep)})")
+            keeps.append(keep)
+            corrections.append(V_correction)
+        all_evecs = plan.select(keeps)   # [n, K_b] each
+        del plan
+        all_evals = [row[keep] for row, keep in zip(rows, keeps)]
+        # the kernel's three scalars belong to a call: one call per (batch size N) -- one, in a single backward pass
+        gammas, lambdas = [None] * len(items), [None] * len(items)
+        for N in sorted({it[3] for it in items}):
+            sel = [i for i, it in enumerate(items) if it[3] == N]
+            _, _, _, _, C, N_ggn, _ = items[sel[0]]
+            V_correction = corrections[sel[0]]
+            gam, lam = kernels.gram_directions_batched(
+                [grams[i] for i in sel], [all_evecs[i].T for i in sel], [all_evals[i] for i in sel],
+                [items[i][1] for i in sel], C, N_ggn, alpha_gram=V_correction**2, alpha_gamma=V_correction * N,
+                lambda_scale=float(N_ggn))
+            for i, g, l in zip(sel, gam, lam):
+                gammas[i], lambdas[i] = g, l
+        results = []
+        for evals, evecs, gam, lam, V_correction, (_, _, group, _, C, N_ggn, payload) in zip(
+                all_evals, all_evecs, gammas, lambdas, corrections, items):
+            if (evals.abs() < self._warn_small_eigvals).any():
+                warn(self._warning)
+            results += self._finish(group, payload, evals, evecs, gam, lam, V_correction, C, N_ggn)
+        return results
+
+
 class DirectionalDerivativesComputation:
     """Provide extensions and the hook for 1st/2nd-order directional derivatives.
 
@@ -203,9 +293,13 @@ class DirectionalDerivativesComputation:
         factorised: bool = False,
         data_parallel: bool = False,
         process_group=None,
+        batched_solve: bool = False,
     ):
-        """``factorised``, ``data_parallel``, ``process_group`` are not in the reference: see
-        :class:`vivit_amd.optim.DirectionalDampedNewtonComputation`."""
+        """``factorised``, ``data_parallel``, ``process_group``, ``batched_solve`` are not in the reference: see
+        :class:`vivit_amd.optim.DirectionalDampedNewtonComputation`.  With ``batched_solve=True`` the Gram matrices and
+        ``V_t_g_n`` of up to eight queued groups per Gram size stay in memory until their flush (the factors are freed in
+        the hook as always); ``gammas`` may differ from the immediate mode in the sign of a column (another
+        back-transformation kernel), ``lambdas`` agree to rounding."""
         check_subsampling_unique(subsampling_grad)
         check_subsampling_unique(subsampling_ggn)
         self._mc_samples_ggn = mc_samples_ggn
@@ -222,8 +316,16 @@ class DirectionalDerivativesComputation:
         self._batch_size: Dict[int, int] = {}
         self._gammas: Dict[int, Tensor] = {}
         self._lambdas: Dict[int, Tensor] = {}
+        self._batched_solve = bool(batched_solve) and not data_parallel
+        self._queue = GramDirectionsQueue(self._store, warn_small_eigvals, _SMALL_EVALS_GAMMA, verbose)
+
+    def _store(self, group, payload, evals, evecs, gammas, lambdas, V_correction, C, N_ggn) -> List[Tensor]:
+        self._gammas[id(group)] = gammas
+        self._lambdas[id(group)] = lambdas
+        return [gammas, lambdas]
 
     def get_result(self, group: Dict) -> Tuple[Tensor, Tensor]:
+        self._queue.flush_all()
         try:
             return self._gammas[id(group)], self._lambdas[id(group)]
         except KeyError as e:
@@ -244,7 +346,8 @@ class DirectionalDerivativesComputation:
             lambda hook, param: self._param_computation(
                 hook, param, self._savefield_ggn, self._savefield_grad, self._verbose, self._dp
             ),
-            lambda hook, accumulation, group: self._group_hook(
+            lambda hook, accumulation, group: self._queue.add(accumulation, group, self._batch_size.pop(id(group)))
+            if self._batched_solve else self._group_hook(
                 hook, accumulation, group, self._batch_size, self._gammas, self._lambdas, self._verbose,
                 self._warn_small_eigvals,
             ),

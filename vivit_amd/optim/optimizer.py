@@ -19,7 +19,8 @@ class DirectionalDampedNewton(torch.optim.Optimizer):
     ``params``: iterable of parameters or of dicts with ``'params'`` (+ optional ``'criterion'``, ``'damping'``, ``'lr'``);
     ``backpack``: the context manager to use (``vivit_amd.backend.backpack`` or BackPACK's own);
     remaining keyword arguments go to :class:`DirectionalDampedNewtonComputation`
-    (``subsampling_grad``, ``subsampling_ggn``, ``mc_samples_ggn``, ``factorised``, ``data_parallel``, ...)."""
+    (``subsampling_grad``, ``subsampling_ggn``, ``mc_samples_ggn``, ``factorised``, ``data_parallel``,
+    ``batched_solve`` -- one group per layer: the groups' eigensolves and Gram-space epilogues share launches, ...)."""
 
     def __init__(self, params: Iterable, criterion: Callable, damping: Callable, backpack, lr: float = 1.0,
                  **computation_kwargs):
