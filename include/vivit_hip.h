@@ -195,9 +195,13 @@ int vivit_conv2d_weight_mjp_f32(const float *M, const float *x, float *V, int64_
  *   (base.py:84-92 -> param_mjp).  All tensors contiguous fp32, `V` slices outermost.
  * ------------------------------------------------------------------------------------------- */
 /* out[v, e] = M[v, e] * f'(x[e]), e < per_v (= N * features).  kind: 0 ReLU, 1 Sigmoid, 2 Tanh, 3 LeakyReLU (param =
- * negative slope), 4 LogSigmoid, 5 ELU (param = alpha), 6 SELU.  Replaces SqrtGGN{ReLU,Sigmoid,Tanh,LeakyReLU,LogSigmoid,
- * ELU,SELU} (__init__.py:87-93).  A NaN in x: as torch's autograd of the module -- ReLU passes the factor unchanged and
- * LeakyReLU scales it by the slope (the branch a failed comparison selects there), every other rule gives NaN. */
+ * negative slope), 4 LogSigmoid, 5 ELU (param = alpha), 6 SELU, 7 GELU (erf form: Phi(x) + x phi(x)), 8 GELU (tanh
+ * approximation, nn.GELU(approximate='tanh')), 9 SiLU (s (1 + x (1 - s)), s = sigmoid(x)).  Replaces SqrtGGN{ReLU,Sigmoid,Tanh,
+ * LeakyReLU,LogSigmoid,ELU,SELU} (__init__.py:87-93); 7 .. 9 have no counterpart in the reference.  A NaN in x: as torch's
+ * autograd of the module -- ReLU passes the factor unchanged and LeakyReLU scales it by the slope (the branch a failed
+ * comparison selects there), every other rule gives NaN.  GELU and SiLU at x = +-inf give NaN (the inf * 0 of torch's backward
+ * formulas, which are evaluated term by term here), at large finite |x| exactly 1 or (+-)0: no deliberate difference from
+ * torch. */
 int vivit_act_jac_t_f32(const float *M, const float *x, float *out, int64_t V, int64_t per_v, int kind, float param,
                         void *stream);
 /* out[r, c, l] = M[r, c, l] * scale[c]: BatchNorm in eval mode, scale = weight / sqrt(running_var + eps)
@@ -233,6 +237,29 @@ int vivit_row_dot_f32(const float *M, const float *X, float *out, int64_t rows, 
  * neither): mx then holds the finished weight rule (mx - wmean_c msum) wrstd_c with wmean = running_mean, wrstd = 1/sqrt(var + eps). */
 int vivit_bn_eval_rules_f32(const float *M, const float *X, const float *scale, float *out, float *mx, float *msum, int64_t rows,
                             int64_t rows_x, int64_t C, int64_t L, const float *wmean, const float *wrstd, void *stream);
+/* LayerNorm and GroupNorm (norm_rules.hip; no counterpart in the reference's module map).  A normalisation ROW is the set of L
+ * contiguous elements that share one mean and variance: nn.LayerNorm on [N, *extra, *D] has rows = N A (A = prod(extra)), L =
+ * prod(D); nn.GroupNorm(G, C) on [N, C, *spatial] has rows = N G, L = (C / G) S, S = prod(spatial).  Per row xhat = (x - mean) rstd,
+ * h = gamma o M (gamma = 1 when NULL); the index of gamma at position l of a row is (row % G) (L / S) + l / S (LayerNorm: G = S =
+ * 1).  All three launches: contiguous fp32, no atomics, fixed summation order; the bytes of a row's results depend on L, S and on
+ * the body only -- the 16-byte body is taken when L % 4 == 0 and every operand is 16-byte aligned, a scalar one otherwise.  Rows of
+ * L <= 1024 are held in the registers of one wavefront, longer ones by one workgroup. */
+/* mean[r] = sum_l X[r, l] / L,  rstd[r] = 1 / sqrt(sum_l (X[r, l] - mean[r])^2 / L + eps)  for X [rows, L]: two passes (never
+ * E[x^2] - mean^2).  The statistics nn.LayerNorm / nn.GroupNorm compute in their forward pass. */
+int vivit_norm_stats_f32(const float *X, float *mean, float *rstd, int64_t rows, int64_t L, float eps, void *stream);
+/* M [V rows, L], X [rows, L], mean / rstd [rows], gamma [G L / S] or NULL.  In one visit of each row:
+ *   out[r, l]   = rstd (h - mean_l(h) - xhat mean_l(h xhat))      the transposed input Jacobian of nn.LayerNorm / nn.GroupNorm
+ *   seg_w[r, j] = sum_{s < S} M[r, j S + s] xhat[j S + s]         j < L / S
+ *   seg_b[r, j] = sum_{s < S} M[r, j S + s]
+ * Any of out / seg_w / seg_b may be NULL (not all).  For GroupNorm seg_w / seg_b [V, N, C] are the finished weight and bias rules;
+ * for LayerNorm without extra dimensions (S = 1) they are the finished rules M xhat and M.  rows % G == 0, L % S == 0. */
+int vivit_norm_rules_f32(const float *M, const float *X, const float *gamma, const float *mean, const float *rstd, float *out,
+                         float *seg_w, float *seg_b, int64_t V, int64_t rows, int64_t L, int64_t G, int64_t S, void *stream);
+/* nn.LayerNorm with A > 1 positions per sample, M [V, N, A, D], X [N, A, D], mean / rstd [N A]:
+ *   pw[v, n, d] = sum_a M[v, n, a, d] (X[n, a, d] - mean[n, a]) rstd[n, a]   (weight rule),   pb[v, n, d] = sum_a M[v, n, a, d]   (bias rule)
+ * summed serially over a, one thread per d.  pw or pb may be NULL. */
+int vivit_norm_position_sums_f32(const float *M, const float *X, const float *mean, const float *rstd, float *pw, float *pb, int64_t V,
+                                 int64_t N, int64_t A, int64_t D, void *stream);
 /* Cross-entropy loss-Hessian square root from the logits [N, C]: p = softmax.  onehot == NULL (exact, V must equal C):
  * S[v, n, c] = sqrt(p_nv) (delta_vc - p_nc) scale;  onehot [V, N, C] (sampled): S[v, n, c] = (p_nc - onehot[v, n, c]) scale. */
 int vivit_ce_sqrt_hessian_f32(const float *logits, const float *onehot, float *S, int64_t N, int64_t C, int64_t V, float scale,

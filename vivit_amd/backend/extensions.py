@@ -25,6 +25,7 @@ DP_ROWS_MAX_COLUMNS = 4096  # data parallel: narrower materialised factors are a
                             # go through the all-to-all to parameter shards (vivit_amd.distributed.BatchShardedGram)
 _LOSSES = (nn.CrossEntropyLoss, nn.MSELoss)
 _BATCHNORM = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d)
+_NORMS = (nn.LayerNorm, nn.GroupNorm)   # normalisations over each sample's own elements: no train / eval distinction
 _CONVS = (nn.Conv1d, nn.Conv2d, nn.Conv3d, nn.ConvTranspose1d, nn.ConvTranspose2d, nn.ConvTranspose3d)
 
 
@@ -145,6 +146,61 @@ def _bn_eval_rules(module, M: Tensor, x: Tensor):
     return memo[1:]
 
 
+def _norm_geometry(module, x: Tensor):
+    """``(rows, G, S, A)`` of a LayerNorm / GroupNorm on the input ``x`` in the notation of csrc/norm_rules.hip: ``rows`` sets of
+    contiguous elements that share one mean and variance, ``G`` groups of gamma indices, segments of ``S`` elements that share one
+    gamma, ``A`` rows per sample."""
+    if isinstance(module, nn.LayerNorm):
+        rows = x.numel() // math.prod(module.normalized_shape)
+        return rows, 1, 1, rows // x.shape[0]
+    return x.shape[0] * module.num_groups, module.num_groups, math.prod(x.shape[2:]), module.num_groups
+
+
+def _norm_rules(module, M: Tensor, x: Tensor, input_rule: bool):
+    """``(input rule, weight rule, bias rule)`` of a LayerNorm / GroupNorm on the HIP kernels, remembered on the factor tensor as
+    :func:`_bn_eval_rules` does: the rules of one module are up to three calls on the same ``M``.  The statistics are computed once
+    (``vivit_norm_stats_f32``), then ONE launch visits every row of ``M`` for the input rule and the parameter rules that live
+    inside a row (``vivit_norm_rules_f32``: GroupNorm's sums over the spatial positions, LayerNorm's ``M xhat``); a LayerNorm with
+    extra dimensions sums over them in a launch of its own (``vivit_norm_position_sums_f32``).  Rules of parameters that are
+    absent or frozen are not computed (``None``), the input rule only when ``input_rule`` says that it will be asked for.
+    Nothing is remembered on the module."""
+    memo = getattr(M, "_vivit_norm_rules", None)
+    if memo is not None and memo[0] is module and (memo[1] is not None or not input_rule):
+        return memo[1:]
+    own = {name for name, _ in _own_params(module)}
+    rows, G, S, A = _norm_geometry(module, x)
+    gamma = module.weight.detach() if module.weight is not None else None
+    mean, rstd = kernels.norm_stats(x, rows, module.eps)
+    w = b = None
+    if isinstance(module, nn.LayerNorm):
+        shape = tuple(M.shape[:2]) + tuple(module.normalized_shape)
+        if A == 1:     # the rows are the samples: the weight rule is elementwise, the bias rule is the factor itself
+            out, w, _ = kernels.norm_rules(M, x, gamma, mean, rstd, want=(input_rule, "weight" in own, False))
+            w = w.view(shape) if w is not None else None
+            b = M.reshape(shape) if "bias" in own else None
+        else:
+            out = kernels.norm_rules(M, x, gamma, mean, rstd, want=(True, False, False))[0] if input_rule else None
+            if own:
+                D = math.prod(module.normalized_shape)
+                w, b = (t.view(shape) for t in kernels.norm_position_sums(M.reshape(M.shape[0], M.shape[1], A, D), x.reshape(-1, A, D), mean, rstd))
+    else:
+        out, w, b = kernels.norm_rules(M, x, gamma, mean, rstd, G, S, want=(input_rule, "weight" in own, "bias" in own))
+        w, b = (t.view(*M.shape[:2], module.num_channels) if t is not None else None for t in (w, b))
+    memo = (module, out, w, b)
+    try:
+        M._vivit_norm_rules = memo
+    except AttributeError:   # (tensor subclasses without a __dict__)
+        pass
+    return memo[1:]
+
+
+def _norm_xhat(module, x: Tensor) -> Tensor:
+    """The normalised input of a LayerNorm / GroupNorm without its affine part (plain torch: the rule of non-HIP tensors)."""
+    if isinstance(module, nn.LayerNorm):
+        return F.layer_norm(x, module.normalized_shape, None, None, module.eps)
+    return F.group_norm(x, module.num_groups, None, None, module.eps)
+
+
 def _param_factor(module, name: str, M: Tensor, x: Tensor) -> Tensor:
     """``param_mjp(..., sum_batch=False)``: ``M`` [V, N, *out] -> [V, N, *param.shape]."""
     if isinstance(module, nn.Linear):
@@ -185,6 +241,16 @@ def _param_factor(module, name: str, M: Tensor, x: Tensor) -> Tensor:
         shape = [1, -1] + [1] * (x.dim() - 2)
         xhat = (x - module.running_mean.view(shape)) * rstd.view(shape)
         return _spatial_sum(M * xhat.unsqueeze(0), 3)
+    if isinstance(module, _NORMS):
+        if M.is_cuda and M.dtype == torch.float32:
+            # (the input rule rides the same visit of M when the back-propagation goes on below this module)
+            _, Mw, Mb = _norm_rules(module, M, x, module.input0.requires_grad)
+            return Mb if name == "bias" else Mw
+        T = M if name == "bias" else M * _norm_xhat(module, x).unsqueeze(0)
+        if isinstance(module, nn.LayerNorm):   # weight [*D]: the extra dimensions between batch and D are summed
+            extra = tuple(range(2, M.dim() - len(module.normalized_shape)))
+            return T.sum(extra) if extra else T
+        return T.flatten(3).sum(3) if T.dim() > 3 else T
     raise NotImplementedError(f"no parameter rule for {type(module).__name__}")
 
 
@@ -390,7 +456,17 @@ def _conv_weight_factor(module, M: Tensor, x: Tensor) -> Tensor:
 
 _ACTIVATIONS = {nn.ReLU: ("relu", None), nn.Sigmoid: ("sigmoid", None), nn.Tanh: ("tanh", None),
                 nn.LeakyReLU: ("leaky_relu", "negative_slope"), nn.LogSigmoid: ("logsigmoid", None), nn.ELU: ("elu", "alpha"),
-                nn.SELU: ("selu", None)}
+                nn.SELU: ("selu", None), nn.GELU: ("gelu", None), nn.SiLU: ("silu", None)}   # (GELU: see _activation_kind)
+
+
+def _activation_kind(module):
+    """``(kind of kernels.act_jac_t, parameter)`` of an activation module, ``None`` for any other module."""
+    kind = _ACTIVATIONS.get(type(module))
+    if kind is None:
+        return None
+    if isinstance(module, nn.GELU) and module.approximate == "tanh":
+        return "gelu_tanh", 0.0
+    return kind[0], getattr(module, kind[1]) if kind[1] else 0.0
 
 
 def _pair(v):
@@ -402,13 +478,15 @@ def _single(v):
 
 
 def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor) -> Optional[Tensor]:
-    """The layer rules that have a HIP kernel (csrc/jacobians.hip): activations, Flatten / Identity / ActiveIdentity / Dropout(eval), ScaleModule,
+    """The layer rules that have a HIP kernel (csrc/jacobians.hip, csrc/norm_rules.hip): activations (ReLU, Sigmoid, Tanh, LeakyReLU,
+    LogSigmoid, ELU, SELU, GELU in both forms, SiLU), Flatten / Identity / ActiveIdentity / Dropout(eval), ScaleModule,
     Max/AvgPool1d/2d, Conv1d / Conv2d and ConvTranspose1d / 2d (any groups, zero padding), Pad / ZeroPad2d / Slicing,
-    BatchNorm (eval), and -- on the same two-dimensional kernels -- Conv3d, ConvTranspose3d, MaxPool3d, AvgPool3d.  ``None``: no
+    BatchNorm (eval), LayerNorm and GroupNorm (with or without affine parameters; the same visit of the factor serves their
+    parameter rules), and -- on the same two-dimensional kernels -- Conv3d, ConvTranspose3d, MaxPool3d, AvgPool3d.  ``None``: no
     kernel for this module (custom modules, unsupported options such as ceil_mode) -- the generic autograd rule takes over."""
-    kind = _ACTIVATIONS.get(type(module))
+    kind = _activation_kind(module)
     if kind is not None:
-        return kernels.act_jac_t(M, x, kind[0], getattr(module, kind[1]) if kind[1] else 0.0)
+        return kernels.act_jac_t(M, x, *kind)
     if isinstance(module, (nn.Flatten, nn.Identity, nn.Dropout, ActiveIdentity)):
         return M.reshape(M.shape[0], *x.shape)
     if isinstance(module, ScaleModule):   # SqrtGGNScaleModule (__init__.py:113-116): the Jacobian is ``weight * I``
@@ -489,6 +567,8 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor) -> Optional[Tensor]:
         g = _hip_pool3d_jac_t(module, M, x)
         if g is not None:
             return g
+    if isinstance(module, _NORMS):
+        return _norm_rules(module, M, x, True)[0]
     if isinstance(module, _BATCHNORM) and x.dim() >= 2:
         if _own_params(module):   # the parameter rules want the two row sums of the same pass
             return _bn_eval_rules(module, M, x)[0]

@@ -13,11 +13,14 @@
 namespace vivit {
 
 // ---- elementwise activations: out[v, n, e] = M[v, n, e] * f'(x[n, e]) ----------------------------------------------
-enum { ACT_RELU = 0, ACT_SIGMOID = 1, ACT_TANH = 2, ACT_LEAKY_RELU = 3, ACT_LOGSIGMOID = 4, ACT_ELU = 5, ACT_SELU = 6 };
+enum { ACT_RELU = 0, ACT_SIGMOID = 1, ACT_TANH = 2, ACT_LEAKY_RELU = 3, ACT_LOGSIGMOID = 4, ACT_ELU = 5, ACT_SELU = 6, ACT_GELU = 7,
+       ACT_GELU_TANH = 8, ACT_SILU = 9 };
 
 // A NaN input fails every comparison.  ReLU and LeakyReLU test what torch's backward kernels test (x <= 0 and x > 0), so the
 // factor passes unchanged through ReLU and with the negative slope through LeakyReLU, as in torch's autograd; every other
 // rule propagates the NaN (ELU and SELU through expf on the x <= 0 side, which a NaN takes here).
+// GELU (both forms) and SiLU evaluate the expressions of torch's backward kernels term by term, so x = +-inf gives the NaN of
+// their inf * 0 product as torch does, and large finite |x| gives exactly 1 or (+-)0.
 __device__ __forceinline__ float act_derivative(int kind, float x, float a) {
   switch (kind) {
     case ACT_RELU: return x <= 0.f ? 0.f : 1.f;
@@ -26,6 +29,18 @@ __device__ __forceinline__ float act_derivative(int kind, float x, float a) {
     case ACT_LEAKY_RELU: return x > 0.f ? 1.f : a;
     case ACT_LOGSIGMOID: return 1.f / (1.f + expf(x));
     case ACT_ELU: return x > 0.f ? 1.f : a * expf(x);
+    case ACT_GELU: {  // Phi(x) + x phi(x)
+      const float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752440f));
+      const float pdf = expf(-0.5f * x * x) * 0.39894228040143267794f;
+      return cdf + x * pdf;
+    }
+    case ACT_GELU_TANH: {  // d/dx 0.5 x (1 + tanh(u)), u = sqrt(2 / pi) (x + 0.044715 x^3)
+      const float beta = 0.79788456080286535588f, kappa = 0.044715f;
+      const float t = tanhf(beta * (x + kappa * (x * x * x)));
+      const float left = 0.5f * x, dtanh = 1.f - t * t, du = beta * (1.f + 3.f * kappa * (x * x));
+      return 0.5f * (1.f + t) + left * dtanh * du;
+    }
+    case ACT_SILU: { const float s = 1.f / (1.f + expf(-x)); return s * (1.f + x * (1.f - s)); }
     default: {  // SELU
       const float scale = 1.0507009873554804934193349852946f, alpha = 1.6732632423543772848170429916717f;
       return x > 0.f ? scale : scale * alpha * expf(x);
@@ -562,7 +577,7 @@ extern "C" {
 
 int vivit_act_jac_t_f32(const float *M, const float *x, float *out, int64_t Vd, int64_t per_v, int kind, float param,
                         void *stream) {
-  if (Vd < 0 || per_v < 0 || kind < 0 || kind > ACT_SELU) return VIVIT_E_BADARG;
+  if (Vd < 0 || per_v < 0 || kind < 0 || kind > ACT_SILU) return VIVIT_E_BADARG;
   if (Vd == 0 || per_v == 0) return VIVIT_OK;
   if (!M || !x || !out) return VIVIT_E_BADARG;
   act_jac_t_kernel<<<grid_for(Vd * per_v), 256, 0, static_cast<hipStream_t>(stream)>>>(M, x, out, Vd * per_v, per_v, kind, param);

@@ -321,13 +321,15 @@ def conv2d_weight_mjp(M, x, kernel_size, stride, padding, dilation):
     return out
 
 
-ACTIVATION_KINDS = {"relu": 0, "sigmoid": 1, "tanh": 2, "leaky_relu": 3, "logsigmoid": 4, "elu": 5, "selu": 6}
+ACTIVATION_KINDS = {"relu": 0, "sigmoid": 1, "tanh": 2, "leaky_relu": 3, "logsigmoid": 4, "elu": 5, "selu": 6, "gelu": 7,
+                    "gelu_tanh": 8, "silu": 9}
 
 
 @_launcher
 def act_jac_t(M, x, kind: str, param: float = 0.0):
     """``out[v, n, ...] = M[v, n, ...] * f'(x[n, ...])`` for an elementwise activation ``f`` (``kind`` in
-    :data:`ACTIVATION_KINDS`): the transposed input-Jacobian of SqrtGGN{ReLU,Sigmoid,Tanh,...}."""
+    :data:`ACTIVATION_KINDS`): the transposed input-Jacobian of SqrtGGN{ReLU,Sigmoid,Tanh,...} and of GELU (``"gelu"``: erf form,
+    ``"gelu_tanh"``: ``approximate='tanh'``) and SiLU."""
     _require_device(M, x)
     M, x = M.contiguous(), x.contiguous()
     if tuple(M.shape[1:]) != tuple(x.shape):
@@ -426,6 +428,75 @@ def bn_eval_rules(M, x, scale, mean=None, rstd=None):
                                             rstd.data_ptr() if rstd is not None else None, _stream(M))
     _lib.check(st, "vivit_bn_eval_rules_f32")
     return out, mx, ms
+
+
+@_launcher
+def norm_stats(x, rows: int, eps: float):
+    """``(mean [rows], rstd [rows])`` of the normalisation rows of ``x`` (``rows * L`` elements, ``vivit_norm_stats_f32``): the
+    biased variance, two passes, ``rstd = 1 / sqrt(var + eps)`` -- the statistics of ``nn.LayerNorm`` / ``nn.GroupNorm``."""
+    _require_device(x)
+    x = x.contiguous()
+    if rows <= 0 or x.numel() == 0 or x.numel() % rows != 0:
+        raise ValueError(f"x must hold {rows} rows of equal length, got {tuple(x.shape)}")
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    st = _lib.load().vivit_norm_stats_f32(x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows, x.numel() // rows, float(eps), _stream(x))
+    _lib.check(st, "vivit_norm_stats_f32")
+    return mean, rstd
+
+
+@_launcher
+def norm_rules(M, x, gamma, mean, rstd, groups: int = 1, seg: int = 1, want=(True, True, True)):
+    """The rules of a LayerNorm / GroupNorm in one visit of every normalisation row (``vivit_norm_rules_f32``): ``M [V, *x.shape]``,
+    ``x`` of ``rows = mean.numel()`` rows of ``L`` elements, ``gamma`` (``groups * L / seg`` values; ``None``: 1) ->
+    ``(out [like M], seg_w [V, rows, L / seg], seg_b [V, rows, L / seg])``: the transposed input Jacobian
+    ``rstd (h - mean(h) - xhat mean(h xhat))`` with ``h = gamma M``, and the sums of ``M xhat`` and of ``M`` over the ``L / seg``
+    segments of ``seg`` elements of a row.  ``want``: which of the three to compute (``None`` for the others)."""
+    _require_device(M, x, gamma, mean, rstd)
+    M, x, mean, rstd = M.contiguous(), x.contiguous(), mean.contiguous(), rstd.contiguous()
+    if M.dim() < 2 or tuple(M.shape[1:]) != tuple(x.shape):
+        raise ValueError(f"M must be [V, *x.shape], got {tuple(M.shape)} for x {tuple(x.shape)}")
+    rows = mean.numel()
+    if rows == 0 or rstd.numel() != rows or x.numel() == 0 or x.numel() % rows != 0:
+        raise ValueError(f"mean and rstd must hold one value per normalisation row of x, got {mean.numel()} and {rstd.numel()}")
+    L = x.numel() // rows
+    if groups <= 0 or seg <= 0 or L % seg != 0 or rows % groups != 0:
+        raise ValueError(f"rows of {L} elements do not split into segments of {seg}, or {rows} rows not into {groups} groups")
+    nseg = L // seg
+    if gamma is not None:
+        gamma = gamma.contiguous()
+        if gamma.numel() != groups * nseg:
+            raise ValueError(f"gamma must have {groups * nseg} elements, got {gamma.numel()}")
+    if not any(want):
+        raise ValueError("nothing to compute")
+    Vd = M.shape[0]
+    out = torch.empty_like(M) if want[0] else None
+    sw = torch.empty((Vd, rows, nseg), dtype=torch.float32, device=M.device) if want[1] else None
+    sb = torch.empty((Vd, rows, nseg), dtype=torch.float32, device=M.device) if want[2] else None
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    st = _lib.load().vivit_norm_rules_f32(M.data_ptr(), x.data_ptr(), ptr(gamma), mean.data_ptr(), rstd.data_ptr(), ptr(out), ptr(sw),
+                                         ptr(sb), Vd, rows, L, groups, seg, _stream(M))
+    _lib.check(st, "vivit_norm_rules_f32")
+    return out, sw, sb
+
+
+@_launcher
+def norm_position_sums(M, x, mean, rstd):
+    """Parameter rules of a LayerNorm with extra dimensions (``vivit_norm_position_sums_f32``): ``M [V, N, A, D]``, ``x [N, A, D]``,
+    ``mean`` / ``rstd`` of ``N * A`` values -> ``(sum_a M xhat, sum_a M)``, both ``[V, N, D]``."""
+    _require_device(M, x, mean, rstd)
+    M, x, mean, rstd = M.contiguous(), x.contiguous(), mean.contiguous(), rstd.contiguous()
+    if M.dim() != 4 or tuple(M.shape[1:]) != tuple(x.shape):
+        raise ValueError(f"M must be [V, N, A, D] and x [N, A, D], got {tuple(M.shape)} for x {tuple(x.shape)}")
+    Vd, N, A, D = M.shape
+    if mean.numel() != N * A or rstd.numel() != N * A:
+        raise ValueError(f"mean and rstd must have {N * A} elements, got {mean.numel()} and {rstd.numel()}")
+    pw = torch.empty((Vd, N, D), dtype=torch.float32, device=M.device)
+    pb = torch.empty((Vd, N, D), dtype=torch.float32, device=M.device)
+    st = _lib.load().vivit_norm_position_sums_f32(M.data_ptr(), x.data_ptr(), mean.data_ptr(), rstd.data_ptr(), pw.data_ptr(), pb.data_ptr(),
+                                                 Vd, N, A, D, _stream(M))
+    _lib.check(st, "vivit_norm_position_sums_f32")
+    return pw, pb
 
 
 @_launcher
