@@ -274,6 +274,18 @@ int vivit_ce_sqrt_hessian_f32(const float *logits, const float *onehot, float *S
  *   Z: [n, n] ldz >= n or NULL.  Z[:, i] is the unit eigenvector of w[i] (column-wise, as
  *      Tensor.symeig returned them: vivit/utils/eig.py:24-26).  NULL = values only.
  *   info: device int32; 0 on success, >0 = number of unconverged eigenvalues.
+ * INPUT RANGE (tests/test_symeig_scale_gpu.py, tests/test_symeig_degenerate_gpu.py; every entry point of this section, the
+ *   batched, row-range, banded and reduce / select ones included).  With amax = max |a_ij| inside 2^-20 .. 2^51 the matrix is
+ *   used as it is; outside, it is multiplied by a power of two (exact) -- the one that brings amax into [1, 2), limited to
+ *   2^-126 .. 2^127, so that a denormal amax ends below 1 and an amax of 2^127 or more in [2, 4) -- and the eigenvalues
+ *   are divided by it at the end (exact unless they leave the normal range).  The stated accuracy -- eigenvalues to 1e-5
+ *   ||A||_2, Z^T Z - I to 5e-5, A Z - Z diag(w) to 3e-5 ||A||_2 (2e-5, 2e-5, 5e-5 at n <= 192) -- is tested with amax at
+ *   2^-120, on both sides of 2^-51, of 2^-20 (the edge) and of 2^51, at 2^-10 and order n (unscaled) and at 2^100, for
+ *   ||A||_2 up to 2^126, each problem of a batch on its own scale, and on the zero matrix, c I (exact), diagonal,
+ *   tridiagonal, block-diagonal and rank-one input, with info = 0.  A matrix whose entries are all denormal
+ *   (amax = 2^-130) meets the same bounds plus n 2^-149, the spacing of its own entries.  An eigenvalue beyond FLT_MAX
+ *   comes back as +-inf with info = 0, the other eigenvalues and Z finite.  An entry above 3.0e38 or a non-finite one
+ *   gives info = n.  vivit_stedc_f32 on its own is tested for max(|d|, |e|) from 2^-50 to 2^50.
  * Replaces Tensor.symeig(eigenvectors=False)  vivit/linalg/eigvalsh.py:221 and
  *   Tensor.symeig(eigenvectors=True)  vivit/linalg/eigh.py:248-250,
  *   vivit/optim/directional_damped_newton.py:315, vivit/optim/directional_derivatives.py:291,

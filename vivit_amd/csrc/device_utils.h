@@ -107,6 +107,21 @@ __device__ inline int ql_implicit(float *d, float *e, int n, float *z, float nor
   int nfail = 0;
   float tn = norm_floor;
   for (int i = 0; i < n; ++i) tn = fmaxf(tn, fabsf(d[i]) + (i + 1 < n ? fabsf(e[i]) : 0.f));
+  // Below ||T|| = 2^-20 -- the smallest norm the solvers' own prescaling hands over; only a direct caller of the
+  // tridiagonal solver gets here -- work on T scaled by a power of two to ||T|| in [1, 2), exact and undone on d at the
+  // end, as LAPACK's ssteqr scales its blocks: the rotations square entries of T, and at ||T|| = 2^-50 the squares of
+  // everything below 2^-13 ||T|| leave the normal range: r = 0, and the recovery branch drops e.
+  int shift = 0;
+  if (tn > 0.f && tn < 0x1p-20f) {
+    (void)frexpf(tn, &shift);
+    shift = 1 - shift;
+    shift = shift > 126 ? 126 : shift;
+  }
+  if (shift != 0) {
+    const float up = ldexpf(1.f, shift);
+    for (int i = 0; i < n; ++i) { d[i] *= up; e[i] *= up; }
+    tn *= up;
+  }
   const float abs_tol = 0.5f * EPS32 * tn;
   for (int l = 0; l < n; ++l) {
     int iter = 0;
@@ -151,6 +166,10 @@ __device__ inline int ql_implicit(float *d, float *e, int n, float *z, float nor
       e[l] = g;
       e[m] = 0.f;
     }
+  }
+  if (shift != 0) {
+    const float down = ldexpf(1.f, -shift);
+    for (int i = 0; i < n; ++i) d[i] *= down;
   }
   return nfail;
 }

@@ -34,6 +34,7 @@ struct DcWs {
   float *dk, *zk;       // [n] compacted non-deflated poles / weights
   float *rot;           // [n][4]  (tp, tq) as ints in [0],[1]; c, s in [2],[3]
   float *rho, *tol;     // [nmerge]
+  float *tnorm;         // [1] norm of the whole tridiagonal matrix (written by the leaves)
   int *order;           // [n] sorted position -> local physical row
   int *ndpos, *dfpos;   // [n] sorted positions of the non-deflated / deflated poles, in output order
   int *kcount, *nrot;   // [nmerge]
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(256) void stebz_kernel(int n, StebzBatch sb) {
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void dc_leaf_kernel(const float *__restrict__ d, const float *__restrict__ e, int n, int nl,
                                                      float *__restrict__ dcur, float *__restrict__ Qt, int64_t ldq,
-                                                     int32_t *__restrict__ info) {
+                                                     int32_t *__restrict__ info, float *__restrict__ tnorm) {
   __shared__ float Z[LEAF * (LEAF + 1)];
   __shared__ float dl[LEAF], el[LEAF];
   const int lane = threadIdx.x;
@@ -159,6 +160,7 @@ __global__ __launch_bounds__(64) void dc_leaf_kernel(const float *__restrict__ d
     if (lane < s) Qt[(lo + c) * ldq + lo + lane] = Z[lane * (LEAF + 1) + c];
   if (lane < s) dcur[lo + lane] = dl[lane];
   if (lane == 0 && nfail > 0) atomicAdd(info, nfail);
+  if (lane == 0 && blockIdx.x == 0) *tnorm = tn;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -194,7 +196,11 @@ __global__ __launch_bounds__(256) void dc_setup_kernel(const float *__restrict__
   zmax = block_max(zmax, red, tid);
   if (tid == 0) {
     ws.rho[q] = fabsf(rho0) * ss;
-    ws.tol[q] = 8.f * EPS32 * fmaxf(dmax, zmax);
+    // LAPACK's slaed2 tolerance 8 eps max(|d|, |z|) is stated for a matrix scaled to norm one (sstedc does that first):
+    // the unit vector z is measured in units of ||T||.  Nothing is scaled here, and with |z| taken as it is the test is
+    // absolute: at ||T|| << 1 every pole deflates (at 1e-3 already an error of 1e-4 ||T||).  Below norm one the tolerance
+    // follows ||T|| as LAPACK's does; above, it stays at the tighter 8 eps max(|d|, |z|) (fewer deflations, no loss).
+    ws.tol[q] = 8.f * EPS32 * fmaxf(dmax, zmax * fminf(ws.tnorm[0], 1.f));
   }
 }
 
@@ -632,7 +638,7 @@ static DcWs dc_carve(void *base, int64_t n) {
   ws.zs = (float *)take(sizeof(float) * n);
   ws.dk = (float *)take(sizeof(float) * n);
   ws.zk = (float *)take(sizeof(float) * n);
-  take(sizeof(float) * n);
+  ws.tnorm = (float *)take(sizeof(float) * n);   // (one float of the spare block)
   ws.rot = (float *)take(sizeof(float) * 4 * n);
   ws.rho = (float *)take(sizeof(float) * nl);
   ws.tol = (float *)take(sizeof(float) * nl);
@@ -662,7 +668,7 @@ int stedc_dc_launch(const float *d, const float *e, int64_t n, void *wsbase, flo
   const int ni = (int)n;
   const int64_t ldq = n;
   float *Qcur = ws.Qt0, *Qnxt = ws.Qt1;
-  dc_leaf_kernel<<<nl, 64, 0, stream>>>(d, e, ni, nl, ws.dcur, Qcur, ldq, info);
+  dc_leaf_kernel<<<nl, 64, 0, stream>>>(d, e, ni, nl, ws.dcur, Qcur, ldq, info, ws.tnorm);
   int level = 0;
   for (int nm = nl / 2; nm >= 1; nm /= 2) {
     ++level;

@@ -71,7 +71,10 @@ __device__ __forceinline__ void stein_span_body(const float *__restrict__ d, con
   }
   if (threadIdx.x == 0) {
     span[0] = fmax(shi[0] - slo[0], 1e-300);
-    span[1] = fmax(snr[0], 1e-300);
+    // T = 0 exactly (any nonzero fp32 entry is >= 1e-45): every pivot of the solves is the floor `tol` = 2.3e-16 * this, and
+    // with 1e-300 here y / tol overflowed fp64 -- zero vectors for the zero matrix.  With 1e-100 the iterate is the
+    // normalised start vector, and the Gram-Schmidt pass of the cluster makes the set orthonormal.
+    span[1] = fmax(snr[0], 1e-100);
   }
 }
 
@@ -168,7 +171,8 @@ __device__ __forceinline__ void stein_iterate_body(const float *__restrict__ d, 
   // A converged inverse iteration amplifies a unit vector by ~ 1 / |lam - lam_true| >= 1 / (n eps64 |T|); a shift that is
   // not an eigenvalue (or a broken solve: zero / non-finite vector) shows as a small or non-finite growth factor.  The
   // caller's `info` word counts such vectors (kernels.check_info raises, like a non-converged Tensor.symeig).
-  if (tnorm > 1e-290 && (!(growth * tnorm >= 1e6) || !(growth < INFINITY))) atomicAdd(info, 1);
+  // (T = 0: tnorm is its floor 1e-100, every pivot the floor `tol`, so growth = 1 / tol = 4.3e115 and the test passes.)
+  if (!(growth * tnorm >= 1e6) || !(growth < INFINITY)) atomicAdd(info, 1);
 }
 
 __global__ __launch_bounds__(64) void stein_iterate_kernel(const float *__restrict__ d, const float *__restrict__ e, int n,

@@ -68,11 +68,19 @@ __global__ __launch_bounds__(256) void symeig_small_kernel(SmallBatch mats, int6
     if (tid == 0) *info = n;
     return;
   }
-  // LAPACK ssyev-style conditional scaling into [rmin, rmax].
-  const float rmin = 4.4408921e-16f, rmax = 2.2517998e15f;
+  // LAPACK ssyev-style conditional scaling, with two differences.  sigma is a power of two that brings amax into [1, 2), so
+  // that scaling and unscaling are exact.  And the window in which nothing is scaled starts at 2^-20, not at ssyev's
+  // rmin = 2^-51: ssyev may leave amax there because snrm2 / slapy2 never square an entry, while the Householder norms and
+  // the rotations here do -- at amax = 2^-51 the squares of the rounding-level entries (2^-24 amax) of a rank-deficient
+  // matrix are denormal, beta is wrong in its leading bits and the reflector is no longer orthogonal.
+  const float rmin = 9.5367432e-7f, rmax = 2.2517998e15f;
   float sigma = 1.f;
-  if (amax > 0.f && amax < rmin) sigma = rmin / amax;
-  else if (amax > rmax) sigma = rmax / amax;
+  if (amax > 0.f && (amax < rmin || amax > rmax)) {
+    int ex;
+    (void)frexpf(amax, &ex);
+    ex = 1 - ex;
+    sigma = ldexpf(1.f, ex > 127 ? 127 : (ex < -126 ? -126 : ex));   // (denormal amax: as far as fp32 goes)
+  }
   if (sigma != 1.f) {
     __syncthreads();
     for (int idx = tid; idx < n * n; idx += 256) A[(idx / n) * LD + idx % n] *= sigma;

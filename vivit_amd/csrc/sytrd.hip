@@ -53,10 +53,15 @@ __global__ __launch_bounds__(256) void trd_sigma_kernel(const float *__restrict_
   amax = block_max(amax, red, threadIdx.x);
   bad = block_max(bad, red, threadIdx.x);
   if (threadIdx.x == 0) {
-    const float rmin = 4.4408921e-16f, rmax = 2.2517998e15f;
+    // power-of-two sigma (exact) into [1, 2) outside [2^-20, 2^51]: see csrc/symeig_small.hip for the lower end
+    const float rmin = 9.5367432e-7f, rmax = 2.2517998e15f;
     float sigma = 1.f;
-    if (amax > 0.f && amax < rmin) sigma = rmin / amax;
-    else if (amax > rmax) sigma = rmax / amax;
+    if (amax > 0.f && (amax < rmin || amax > rmax)) {
+      int ex;
+      (void)frexpf(amax, &ex);
+      ex = 1 - ex;
+      sigma = ldexpf(1.f, ex > 127 ? 127 : (ex < -126 ? -126 : ex));   // (denormal amax: as far as fp32 goes)
+    }
     scal[1] = sigma; scal[2] = bad; scal[3] = amax;
   }
 }
