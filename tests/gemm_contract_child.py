@@ -20,15 +20,15 @@ LAYOUTS = ("nt", "nn", "tn")
 # One shape family per public route, in the order gemm_launch (vivit_amd/csrc/gemm_f32.hip) tries them with the default
 # VIVIT_GEMM_SPLIT=6.  route -> (the switch that turns it off, or None; cases (layout, M, N, K)).
 ROUTES = {
-    # gemm256_plan: >= 200 tiles of 256 x 256, M, N >= 512, K >= 512, one split -> bx_split_kernel + gemm256_bx_kernel with
+    # plan_tile256: >= 200 tiles of 256 x 256, M, N >= 512, K >= 512, one split -> bx_split_kernel + gemm256_bx_kernel with
     # the gated gemm256_kernel behind it; K = 2071: the ragged tail (7 k) goes through gemm_kernel
     "tile256": ("VIVIT_GEMM256", [(lay, 4096, 4096, k) for k in (2064, 2071) for lay in LAYOUTS]),
-    # bx_splitk_shape: M, N >= 256, at most 100 tiles, K >= 16384 -> bx_splitk_launch (gated gemm256_kernel behind it)
+    # plan_bx_splitk: M, N >= 256, at most 100 tiles, K >= 16384 -> launch_bx_splitk (gated gemm256_kernel behind it)
     "splitk": ("VIVIT_GEMM_BXSPLITK", [(lay, 1000, 1300, 20480) for lay in LAYOUTS]),
-    # use_gemm64: M <= 64, N >= 2048, K >= 2048, K % 16 == 0, aligned operands -> g64_split_a_kernel + gemm64_bx_kernel
+    # plan_gemm64: M <= 64, N >= 2048, K >= 2048, K % 16 == 0, aligned operands -> g64_split_a_kernel + gemm64_bx_kernel
     # (NN needs M > 16: skinny_applicable takes M <= 16 first; TN needs M % 4 == 0)
     "gemm64": ("VIVIT_GEMM64", [(lay, 64, 2304, 4096) for lay in LAYOUTS] + [("nt", 1, 2048, 2048)]),
-    # tsk_shape: M <= 64, N <= 1024, K >= 2048, both operands K-contiguous (NT only) -> gemm_tsk_kernel
+    # plan_tsk: M <= 64, N <= 1024, K >= 2048, both operands K-contiguous (NT only) -> gemm_tsk_kernel
     "tsk": ("VIVIT_GEMM_TSK", [("nt", 48, 700, 8192)]),
     # skinny_applicable: M <= 16 (vivit_gemm_nn_f32 only) -> skinny_nn_kernel
     "skinny": (None, [("nn", 8, 5000, 3000)]),

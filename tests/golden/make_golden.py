@@ -14,6 +14,7 @@ How the reference is made importable:
     driven exactly as BackPACK would drive them (``hook(module)`` per module).
 
 Usage:  python tests/golden/make_golden.py
+        python tests/golden/make_golden.py --gemm-workspace LIB   (gemm_workspace.json only, from the library LIB)
 """
 import os
 import sys
@@ -447,7 +448,70 @@ def run_eig_utils(vivit):
     return out
 
 
+# ---- workspace sizes of the GEMM routes (tests/test_gemm_plan_host.py): no reference involved, data recorded from a BUILT
+# libvivit_hip.so -- the one of the commit BEFORE a change to the launch planning of csrc/gemm_f32.hip, so that the change
+# can be held to "every query answers what it answered before".  Default environment (no VIVIT_GEMM* switch set).
+def _gemm_workspace_shapes():
+    """(m, n, k) of vivit_gemm_f32_workspace_bytes and (n, p) of vivit_gram_syrk_f32_workspace_bytes on both sides of every
+    route boundary of the planner (tile counts that are prime, such as 199 and 101, have no shape with M, N >= 256: the nearest
+    products stand in)."""
+    gemm, syrk = [], []
+    # 256-tile plan: 200 tiles (10 x 20, 8 x 25) against 198 (11 x 18), 196, 195; K 511 | 512; M, N 511 | 512; split-K depths
+    for m, n in ((2560, 5120), (2048, 6400), (2816, 4608), (3584, 3584), (3328, 3840), (511, 102400), (512, 102400), (4096, 4096)):
+        for k in (496, 511, 512, 527, 2064, 2071, 4096, 8192, 16384, 65536, 401408):
+            gemm.append((m, n, k))
+    for n in (4864, 4865, 5120, 40960):          # 19 | 20 tile rows: 190 | 210 lower tiles
+        for p in (511, 512, 2048, 4096, 4100, 65536, 401408):
+            syrk.append((n, p))
+    # bf16-pipe split-K: K 16368 | 16384, 100 tiles (10 x 10) | 102 (6 x 17) | 101 columns of one tile row, M, N 255 | 256
+    for m, n in ((2560, 2560), (1536, 4352), (256, 25600), (256, 25856), (255, 2560), (256, 2560), (2560, 255), (1000, 1300), (1280, 1280)):
+        for k in (16368, 16383, 16384, 20480, 131072, 401408):
+            gemm.append((m, n, k))
+    for n in (255, 256, 1280, 3328, 3329, 3584):   # 13 | 14 | 15 tile rows: 91 | 105 lower tiles
+        for p in (16368, 16384, 20480, 401408):
+            syrk.append((n, p))
+    # 64-row streaming route: M 64 | 65, N 2047 | 2048, K 2047 | 2048 and K % 16 != 0
+    for m in (1, 4, 17, 64, 65):
+        for n in (2047, 2048, 2304, 40960):
+            for k in (2032, 2047, 2048, 4096, 4100, 65536):
+                gemm.append((m, n, k))
+    # deep-K small-output route: N 1024 | 1025, K 2047 | 2048, K % 4 != 0
+    for m in (17, 48, 64, 65):
+        for n in (64, 700, 1024, 1025):
+            for k in (2047, 2048, 2050, 8190, 8192, 40960):
+                gemm.append((m, n, k))
+    # 128-tile split-K: fewer than 256 tiles with 63 | 64 K tiles; 256 tiles; one tile row
+    for m, n in ((300, 300), (128, 128), (2048, 2048), (1920, 2048), (64, 129), (17, 128)):
+        for k in (1008, 1009, 1024, 5001, 40960):
+            gemm.append((m, n, k))
+    # the route cases of tests/gemm_contract_child.py and the headline Gram build
+    gemm += [(4096, 4096, 2064), (4096, 4096, 2071), (1000, 1300, 20480), (64, 2304, 4096), (1, 2048, 2048), (48, 700, 8192),
+             (8, 5000, 3000), (300, 300, 5001)]
+    syrk += [(40960, 401408), (512, 2048), (300, 500)]
+    return sorted(set(gemm)), sorted(set(syrk))
+
+
+def gemm_workspace_table(lib_path):
+    import ctypes
+    import json
+
+    lib = ctypes.CDLL(lib_path)
+    for f in (lib.vivit_gemm_f32_workspace_bytes, lib.vivit_gram_syrk_f32_workspace_bytes):
+        f.restype = ctypes.c_size_t
+    lib.vivit_gemm_f32_workspace_bytes.argtypes = [ctypes.c_int64] * 3
+    lib.vivit_gram_syrk_f32_workspace_bytes.argtypes = [ctypes.c_int64] * 2
+    assert not [v for v in os.environ if v.startswith("VIVIT_GEMM") or v == "VIVIT_BX_ASM"], "default environment only"
+    gemm, syrk = _gemm_workspace_shapes()
+    table = {"gemm": [[m, n, k, lib.vivit_gemm_f32_workspace_bytes(m, n, k)] for m, n, k in gemm],
+             "syrk": [[n, p, lib.vivit_gram_syrk_f32_workspace_bytes(n, p)] for n, p in syrk]}
+    with open(os.path.join(OUT, "gemm_workspace.json"), "w") as f:
+        f.write("{\n" + ",\n".join('"%s": [\n%s\n]' % (k, ",\n".join(json.dumps(r) for r in v)) for k, v in table.items()) + "\n}\n")
+    print("gemm_workspace.json:", len(gemm), "GEMM shapes,", len(syrk), "SYRK shapes")
+
+
 def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--gemm-workspace":   # python make_golden.py --gemm-workspace path/to/libvivit_hip.so
+        return gemm_workspace_table(sys.argv[2])
     vivit = import_reference()
     for case in CASES:
         res = run_case(vivit, case)

@@ -183,6 +183,24 @@ def test_workspace_one_byte_short_is_refused():
     assert L.vivit_symeig_banded_rows_f32(P, nn, nn, Q, Q, R, R, nn, 0, 8, W, need - 1, P, None) == WORKSPACE
 
 
+def test_gemm_routes_refuse_a_missing_workspace_before_any_device_call():
+    """One shape per GEMM route that refuses (csrc/gemm_f32.hip: the route table; the bf16-pipe routes of the 256 tile fall
+    back instead), each needing a slab, each given none: the answer is VIVIT_E_WORKSPACE with or without a device -- a route
+    that set kernel attributes or cleared a flag first would answer VIVIT_E_LAUNCH on a box without one."""
+    L = lib()
+    gemm = lambda m, n, k, lda, ldb: L.vivit_gemm_nt_f32(P, Q, R, m, n, k, lda, ldb, n, 1.0, 0.0, None, 0, None)  # noqa: E731
+    assert L.vivit_gemm_f32_workspace_bytes(64, 2304, 4096) > 0
+    assert gemm(64, 2304, 4096, 4096, 4096) == WORKSPACE     # 64-row streaming route
+    assert L.vivit_gemm_f32_workspace_bytes(48, 700, 8192) > 0
+    assert gemm(48, 700, 8192, 8192, 8192) == WORKSPACE       # deep-K small-output route
+    assert L.vivit_gemm_f32_workspace_bytes(300, 300, 5001) > 0
+    assert gemm(300, 300, 5001, 5001, 5001) == WORKSPACE      # 128 tile with split-K (lda % 4 != 0 keeps it off the others)
+    assert L.vivit_gram_syrk_f32_workspace_bytes(512, 2048) > 0
+    assert L.vivit_gram_syrk_f32(P, 512, 2048, 2048, Q, 512, 1.0, 0.0, None, 0, None) == WORKSPACE
+    # (no one-byte-short cases: the query is the largest need over the routes a shape MAY take, so a buffer one byte short
+    # of it can still hold what the route taken needs, and the pointers here are fake)
+
+
 def test_unsupported_sizes_are_refused():
     L = lib()
     small = 192   # single-workgroup sizes: the row-range and two-phase entries send the caller to vivit_symeig_f32

@@ -145,8 +145,8 @@ LD = 4_500_000
 
 
 @pytest.mark.parametrize("route,M,N,K", [
-    ("gemm64", 64, 2048, 2048),   # use_gemm64: M <= 64, N >= 2048, K >= 2048 (B storage ~37 GB)
-    ("tsk", 64, 1024, 2048),      # tsk_shape: the next route a huge-ld NT product falls to (B storage ~18 GB)
+    ("gemm64", 64, 2048, 2048),   # plan_gemm64: M <= 64, N >= 2048, K >= 2048 (B storage ~37 GB)
+    ("tsk", 64, 1024, 2048),      # plan_tsk: the next route a huge-ld NT product falls to (B storage ~18 GB)
 ])
 def test_large_leading_dimension(route, M, N, K):
     from vivit_amd import kernels

@@ -1,4 +1,19 @@
-// fp32 MFMA GEMM / SYRK for gfx950 (MI355X).
+// fp32 GEMM / SYRK for gfx950 (MI355X): every large product of the library -- the Gram SYRK, the public
+// vivit_gemm_nt/nn/tn_f32 and the eigensolver's internal products.
+//
+// Kernel families, in file order (each with its own header comment):
+//   gemm_kernel                            128 x 128 (or 64 x 256) fp32 MFMA tile, every shape and layout; batched mode
+//   gemm256_kernel                         256 x 256 fp32 MFMA tile fed by global -> LDS DMA, for large outputs
+//   bx_split_kernel, gemm256_bx_kernel     the same tile on the bf16 pipe: exact three-way operand splits (bx_kloop_asm.inc:
+//                                          its hand-scheduled K loop); bx_sym_diag_kernel
+//   gemm64_dma_kernel, g64_split_a_kernel, 64-row streaming kernels (M <= 64, wide N) on the fp32 and the bf16 pipe
+//   gemm64_bx_kernel
+//   gemm_reduce_kernel                     fixed-order split-K reduction of the above
+//   gemm_tsk_kernel, gemm_tsk_reduce_kernel  deep-K products with a small output
+// then the host half: one planner and one launcher per route, the workspace query and the dispatcher built on them (see
+// the route table there), gemm_lower_launch, gemm_batched_launch, the fp64 diagonal of the public SYRK, the C entry points.
+//
+// The rest of this header describes the first family.
 //
 //   C[M,N] = alpha * op(A) op(B)^T + beta * C,   exact fp32 (v_mfma_f32_32x32x2_f32 is a
 //   k-ordered fmaf chain), accumulators flushed into a second accumulator every 2048 k so that
@@ -1610,7 +1625,7 @@ __device__ __forceinline__ int g64x_k(int h, int j) { return 8 * (j >> 2) + 4 * 
 // two bits of bx_split_kernel, gathered per lane as the largest 2|a| bit pattern (bit 0: >= 2 x 0x7F7F8000, NaN above it)
 // and the smallest 2|a| - 1 (bit 1: below 2 x 0x0D800000 - 1, i.e. 0 < |a| < 2^-100; an exact zero wraps to the top) --
 // three VALU instructions per value, no compare per value -- and ORed into one flag per launch.  A flagged product is
-// recomputed by gemm64_dma_kernel (fp32 MFMA) behind the bf16-pipe launch; see gemm64_launch.
+// recomputed by gemm64_dma_kernel (fp32 MFMA) behind the bf16-pipe launch; see launch_gemm64.
 struct G64Range {
   unsigned mx = 0u, mn = 0xffffffffu;
 };
@@ -1727,7 +1742,7 @@ __global__ __launch_bounds__(256, 1) void gemm64_bx_kernel(GemmArgs p, const uin
     }
   };
   // (STRICT: every split_raw call sees real B values of this workgroup -- the one after its last tile reads the stage of tile
-  // nt - 7, and every split has more than 40 K tiles (gemm64_workspace_bytes) -- so no uninitialised LDS reaches the flag)
+  // nt - 7, and every split has more than 40 K tiles (plan_gemm64) -- so no uninitialised LDS reaches the flag)
   G64Range rng;
   auto split_raw = [&](int par) __attribute__((always_inline)) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -1971,6 +1986,61 @@ __global__ __launch_bounds__(256) void gemm_tsk_reduce_kernel(const float *__res
   }
 }
 
+__global__ __launch_bounds__(256) void scale_c_kernel(float *__restrict__ C, int64_t M, int64_t N, int64_t ldc, float beta) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= M * N) return;
+  const int64_t i = idx / N, j = idx - i * N;
+  C[i * ldc + j] = beta == 0.f ? 0.f : beta * C[i * ldc + j];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Host half.  Every route has ONE plan_<route> (shape predicate, split heuristic, workspace carve) and ONE launch_<route>
+// that reads splits and offsets from the plan only; the workspace query and the dispatcher are both built on the plans.
+//
+// gemm_launch takes the first route of this table whose plan succeeds and whose extra conditions hold;
+// gemm_workspace_bytes is the largest plan.bytes over the routes whose plan succeeds (it knows neither pointers nor
+// layouts, so the extra conditions are the dispatcher's alone).  K of the first three routes is K / BK whole tiles; a
+// ragged tail (< 16 k) goes through Tile128, accumulating.
+//
+//   route      kernels                                        extra conditions                     workspace < plan.bytes
+//   Tile256Bx  bx_split_kernel, gemm256_bx_kernel,            16-byte operands (vec)               falls back to Tile256
+//              gated gemm256_kernel
+//   Tile256    gemm256_kernel                                 vec                                  fewer splits (down to one, which needs none)
+//   BxSplitK   bx_split_kernel, gemm256_bx_kernel,            vec                                  skipped
+//              gated gemm256_kernel, gemm_reduce_kernel
+//   Gemm64     g64_split_a_kernel, gemm64_bx_kernel,          VIVIT_GEMM64 != 0, vec, M >= 4 for   VIVIT_E_WORKSPACE
+//              gemm64_dma_kernel, gemm_reduce_kernel          row-major A, N >= 4 for row-major B
+//   Tsk        gemm_tsk_kernel, gemm_tsk_reduce_kernel        VIVIT_GEMM_TSK != 0, vec, both       VIVIT_E_WORKSPACE
+//                                                             operands K-contiguous
+//   Tile128    gemm_kernel, gemm_reduce_kernel                none                                 VIVIT_E_WORKSPACE
+//
+// The asymmetry of the last column is deliberate: callers size one workspace for their largest problem, and the bf16-pipe
+// routes of the 256 tile have an fp32 route of the same tile behind them that needs less; the last three routes have
+// nothing behind them whose result (summation order) would be the same.  Every launch_<route> finishes its argument and
+// workspace checks before its first HIP call.
+enum class GemmRoute { Tile256Bx, Tile256, BxSplitK, Gemm64, Tsk, Tile128 };
+
+struct GemmShape {
+  int64_t M, N, K;
+  bool syrk;   // lower tiles only, mirrored
+  bool same;   // A and B are one operand (one set of bf16 pieces)
+  bool pub;    // public product (BxStrictScope) or one of the eigensolver's own
+};
+
+struct GemmPlan {
+  GemmRoute route;
+  int ksplit;                    // parts of the contraction (1: no slab); nsplit of BxSplitK and Tsk
+  int64_t kchunk;                // columns of K per part; Tile256Bx: per chunk of operand pieces (one launch each)
+  int kt_split;                  // BxSplitK: K tiles per part
+  size_t slab_off, slab_bytes;   // partial sums [ksplit][M][N]
+  size_t a_off, b_off;           // bf16 pieces of the operands (b_off == a_off when they are one operand)
+  size_t flags_off;              // range flags (BX_GATE): one per chunk
+  size_t bytes;                  // all of it
+};
+
+template <class T>
+static T *ws_at(void *workspace, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(workspace) + off); }
+
 // Calls f with the operand layouts as std::integral_constant arguments, so that a launch can pass them on as template
 // arguments: with_layouts(alay, blay, [&](auto LA, auto LB) { kernel<LA, LB><<<...>>>(...); })
 template <class F>
@@ -1989,151 +2059,101 @@ static void with_layout(int lay, F &&f) {
   else f(std::integral_constant<int, LAY_M>{});
 }
 
-static bool tsk_shape(int64_t M, int64_t N, int64_t K) { return M <= 64 && N <= 1024 && K >= 2048 && (K & 3) == 0; }
+// 16-byte loads are legal for the operand
+static int operand_vec(const float *X, int64_t ld) { return ((reinterpret_cast<uintptr_t>(X) & 15) == 0 && (ld & 3) == 0) ? 1 : 0; }
 
-static void tsk_plan(int64_t N, int64_t K, int &nsplit, int64_t &kchunk) {
-  const int64_t nblk = cdiv(N, 64);
-  int64_t want = 512 / nblk, maxs = K / (2 * TSK_KC);   // two workgroups per CU; at least two steps per split
-  if (want < 1) want = 1;
-  int64_t s = want < maxs ? want : maxs;
-  if (s < 1) s = 1;
-  kchunk = cdiv(cdiv(K, s), TSK_KC) * TSK_KC;
-  nsplit = (int)cdiv(K, kchunk);
+// Super-block grid of a tile map (map_tile): *sbw = width of a super-block in tiles; returns the number of super-blocks
+// (256 workgroup slots each), or -1 when the slots do not fit a 32-bit grid dimension.
+static int64_t tile_grid(int64_t tiles_m, int64_t tiles_n, bool syrk, int *sbw) {
+  const int w = syrk ? 16 : sb_width((int)tiles_m, (int)tiles_n), h = 256 / w;
+  *sbw = w;
+  const int64_t sbm = cdiv(tiles_m, h), sbn = cdiv(tiles_n, w);
+  const int64_t nsb = syrk ? sbm * (sbm + 1) / 2 : sbm * sbn;
+  return nsb * 256 > 0x7fffffffLL ? -1 : nsb;
 }
 
-static size_t tsk_workspace_bytes(int64_t M, int64_t N, int64_t K) {
-  if (!tsk_shape(M, N, K)) return 0;
-  int ns;
-  int64_t kc;
-  tsk_plan(N, K, ns, kc);
-  return ns > 1 ? (size_t)ns * (size_t)M * (size_t)N * sizeof(float) : 0;
+// ---- the environment switches, each read once per process
+static int env_int(const char *name, int dflt) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+static bool gemm256_enabled() { static const int v = env_int("VIVIT_GEMM256", -1); return v != 0; }
+static bool bx_splitk_enabled() { static const int v = env_int("VIVIT_GEMM_BXSPLITK", -1); return v != 0; }
+static bool gemm64_enabled() { static const int v = env_int("VIVIT_GEMM64", -1); return v != 0; }
+static bool tsk_enabled() { static const int v = env_int("VIVIT_GEMM_TSK", -1); return v != 0; }
+// Which matrix pipe the 256-tile NT products (Gram SYRK, K-contiguous GEMMs) use: 6 (default) = bf16 pipe with exact
+// three-way operand splits and the 6 partial products that are >= 2^-16 of a product; 9 = all nine; 0 = fp32 MFMA
+// (gemm256_kernel); 3 = hi hi + hi mid + mid hi of the three-way split (per-product error 2^-16: experiments only).
+// VIVIT_GEMM_SPLIT overrides.
+static int gemm_split_mode() {
+  static const int v = env_int("VIVIT_GEMM_SPLIT", 6);
+  return (v == 0 || v == 3 || v == 6 || v == 9) ? v : 6;
+}
+// VIVIT_BX_ASM=1 / 0: the hand-scheduled K loop (gemm256_bx_kernel<6, true>) or the C++ loop (the reference implementation)
+static bool bx_asm_enabled() { static const int v = env_int("VIVIT_BX_ASM", 1); return v != 0; }
+// products of the 64-row streaming kernel on the bf16 pipe (exact three-way splits) unless the fp32 pipe is asked for
+// (VIVIT_GEMM_SPLIT=0 or VIVIT_GEMM64_BX=0)
+static bool gemm64_bx_enabled() { static const int v = env_int("VIVIT_GEMM64_BX", 1); return v != 0 && gemm_split_mode() != 0; }
+
+// Which range flags send a chunk to the fp32 MFMA kernel.  The public products (vivit_gram_syrk_f32, vivit_gemm_*_f32)
+// honour both bits and so keep fp32-MFMA semantics for every input; the eigensolver's internal products on orthogonal
+// factors only reroute non-finite / out-of-range chunks (a localised eigenvector has entries below 2^-100 whose
+// 2^-126-level piece is immaterial, and the reroute would cost that chunk the bf16 pipe's 2.7x).
+static thread_local int tls_bx_gate_mask = BX_GATE_RANGE;
+// true inside a public product (vivit_gram_syrk_f32 / vivit_gemm_*_f32): the profile (roofline.achieved of bench.py) counts
+// the Gram SYRKs of the caller, not the reflector Gram matrices the eigensolver's back-transformation builds internally
+static bool bx_public_product() { return (tls_bx_gate_mask & BX_GATE_TINY) != 0; }
+
+struct BxStrictScope {
+  int saved;
+  BxStrictScope() : saved(tls_bx_gate_mask) { tls_bx_gate_mask = BX_GATE_RANGE | BX_GATE_TINY; }
+  ~BxStrictScope() { tls_bx_gate_mask = saved; }
+};
+
+// hipFuncAttributeMaxDynamicSharedMemorySize of every GEMM kernel with dynamic LDS, once per device
+static bool gemm_attrs() {
+  static unsigned long long attr_done = 0;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return false;
+  if (attr_done & (1ull << (dev & 63))) return true;
+  const struct { const void *fn; int bytes; } kernels[] = {
+      {reinterpret_cast<const void *>(gemm256_kernel<LAY_K, LAY_K>), GEMM256_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm256_kernel<LAY_K, LAY_M>), GEMM256_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm256_kernel<LAY_M, LAY_K>), GEMM256_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm256_kernel<LAY_M, LAY_M>), GEMM256_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm256_bx_kernel<3>), GEMM256BX_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm256_bx_kernel<6>), GEMM256BX_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm256_bx_kernel<9>), GEMM256BX_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm256_bx_kernel<6, true>), GEMM256BX_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm64_dma_kernel<LAY_K, LAY_K>), GEMM64_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm64_dma_kernel<LAY_K, LAY_M>), GEMM64_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm64_dma_kernel<LAY_M, LAY_K>), GEMM64_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm64_dma_kernel<LAY_M, LAY_M>), GEMM64_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm64_bx_kernel<LAY_K>), GEMM64X_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm64_bx_kernel<LAY_M>), GEMM64X_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm64_bx_kernel<LAY_K, true>), GEMM64X_LDS_BYTES},
+      {reinterpret_cast<const void *>(gemm64_bx_kernel<LAY_M, true>), GEMM64X_LDS_BYTES}};
+  for (const auto &k : kernels)
+    if (!ensure_dynamic_lds(k.fn, k.bytes, attr_done)) return false;
+  attr_done |= 1ull << (dev & 63);
+  return true;
 }
 
-static bool use_tsk(int alay, int blay, const float *A, const float *B, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb,
-                    bool syrk) {
-  static int forced = -2;
-  if (forced == -2) {
-    const char *e = getenv("VIVIT_GEMM_TSK");
-    forced = e ? atoi(e) : -1;
-  }
-  if (forced == 0 || syrk || alay != LAY_K || blay != LAY_K || !tsk_shape(M, N, K)) return false;
-  return (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0 && (lda & 3) == 0 && (ldb & 3) == 0;
-}
-
-static int tsk_launch(const float *A, const float *B, float *C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc,
-                      float alpha, float beta, void *workspace, size_t workspace_bytes, hipStream_t stream) {
-  TskArgs p;
-  p.A = A; p.B = B; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.K = K; p.M = (int)M; p.N = (int)N;
-  p.alpha = alpha; p.beta = beta;
-  tsk_plan(N, K, p.nsplit, p.kchunk);
-  p.slab = nullptr;
-  if (p.nsplit > 1) {
-    if (!workspace || workspace_bytes < (size_t)p.nsplit * (size_t)M * (size_t)N * sizeof(float)) return VIVIT_E_WORKSPACE;
-    p.slab = static_cast<float *>(workspace);
-  }
-  gemm_tsk_kernel<<<dim3((unsigned)p.nsplit, (unsigned)cdiv(N, 64)), 256, 0, stream>>>(p);
-  int st = launch_status();
-  if (st != VIVIT_OK || p.nsplit == 1) return st;
-  gemm_tsk_reduce_kernel<<<(unsigned)cdiv(M * N, 32), 256, 0, stream>>>(p.slab, C, M * N, (int)N, ldc, p.nsplit, alpha, beta);
-  return launch_status();
-}
-
-// wave grid of the tile: 1 x 4 waves (64 x 256) when the output has at most 64 rows and is wide
-static int pick_wm(int64_t M, int64_t N, bool syrk) { return (!syrk && M <= 64 && N > 128) ? 1 : 2; }
-
-static void choose_split(int64_t M, int64_t N, int64_t K, bool syrk, int &ksplit, int64_t &kchunk) {
-  const int wm = pick_wm(M, N, syrk);
-  const int64_t tm = cdiv(M, 64 * wm), tn = cdiv(N, 256 / wm);
-  const int64_t tiles = syrk ? tm * (tm + 1) / 2 : tm * tn;
-  ksplit = 1;
-  kchunk = cdiv(K, BK) * BK;
-  if (kchunk < BK) kchunk = BK;
-  const int64_t ktiles = cdiv(K, BK);
-  // Fill at least ~2 workgroups per CU when the output has few tiles and K is deep; keep every
-  // split at least 32 K tiles long and the slab modest.
-  if (tiles < 256 && ktiles >= 64) {
-    // one resident round (2 workgroups per CU x 256 CUs) for compute-bound shapes; a one-tile-wide
-    // output streams its big operand once and is bandwidth-bound: more, shorter splits keep enough
-    // bytes in flight
-    int64_t want = (tm == 1 || tn == 1) ? 2048 / tiles : 512 / tiles;
-    int64_t maxs = (tm == 1 || tn == 1) ? ktiles / 8 : ktiles / 32;
-    int64_t s = want < maxs ? want : maxs;
-    // a single-tile output (the 64 x 64 Gram blocks of the band reduction's panels: both operands stream 64 rows
-    // x m) has nothing but split-K to spread over the chip (with the slot rotation of map_tile: before it every
-    // split's only valid workgroup sat on XCD 0 and more splits bought nothing); at most 64 splits for any output
-    if (s > 64) s = 64;
-    while (s > 1 && (size_t)s * (size_t)M * (size_t)N * 4 > ((size_t)1 << 30)) --s;
-    if (s > 1) {
-      kchunk = cdiv(ktiles, s) * BK;
-      ksplit = (int)cdiv(K, kchunk);
-    }
-  }
-}
-
-static size_t gemm64_workspace_bytes(int64_t M, int64_t N, int64_t K, int *ksplit_out, int64_t *kchunk_out, size_t *slab_out = nullptr);
-static bool gemm256_plan(int64_t M, int64_t N, int64_t K, bool syrk, int *ksplit_out, int64_t *kchunk_out, int max_split = 32);
-
-static int gemm_split_mode();
-static size_t bx_workspace_bytes(int64_t M, int64_t N, int64_t K, bool same);
-static bool bx_splitk_shape(int64_t M, int64_t N, int64_t K, bool syrk, bool same, int *nsplit_out, int *kt_split_out,
-                            size_t *bytes_out);
-size_t gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, bool syrk) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  int ksplit;
-  int64_t kchunk;
-  choose_split(M, N, K, syrk, ksplit, kchunk);
-  size_t b = ksplit > 1 ? (size_t)ksplit * (size_t)M * (size_t)N * sizeof(float) : 0;
-  {
-    int s256;
-    int64_t kc256;
-    if (gemm256_plan(M, N, K / BK * BK, syrk, &s256, &kc256)) {
-      if (s256 > 1) {
-        const size_t b256 = (size_t)s256 * (size_t)M * (size_t)N * sizeof(float);
-        if (b256 > b) b = b256;
-      }
-      if (gemm_split_mode() != 0) {  // operand pieces of the bf16-pipe path (gemm256_launch prefers it to split-K)
-        const size_t bb = bx_workspace_bytes(M, N, K / BK * BK, syrk);
-        if (bb > b) b = bb;
-      }
-    }
-  }
-  {  // bf16-pipe split-K for small outputs with a deep contraction (bx_splitk_launch)
-    size_t bs = 0;
-    if (bx_splitk_shape(M, N, K / BK * BK, syrk, syrk, nullptr, nullptr, &bs) && bs > b) b = bs;
-    if (!syrk && bx_splitk_shape(M, N, K / BK * BK, false, false, nullptr, nullptr, &bs) && bs > b) b = bs;
-  }
-  if (!syrk) {  // the deep-K small-output kernel may be chosen instead (tsk_launch)
-    const size_t bt = tsk_workspace_bytes(M, N, K);
-    if (bt > b) b = bt;
-  }
-  if (!syrk && M <= 64 && N >= 2048 && K >= 2048) {  // the streaming kernel may be chosen instead (gemm64_launch)
-    const size_t b64 = gemm64_workspace_bytes(M, N, K / BK * BK, nullptr, nullptr);
-    if (b64 > b) b = b64;
-  }
-  return b;
-}
-
-__global__ __launch_bounds__(256) void scale_c_kernel(float *__restrict__ C, int64_t M, int64_t N, int64_t ldc, float beta) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= M * N) return;
-  const int64_t i = idx / N, j = idx - i * N;
-  C[i * ldc + j] = beta == 0.f ? 0.f : beta * C[i * ldc + j];
-}
-
+// ---- Tile256: gemm256_kernel, split-K over blockIdx.y
 // The 256 x 256 tile pays off once the output has enough of them to fill the chip (one per CU).
 // Small outputs with a deep contraction stay on the 128 x 128 tile: measured with the 256 tile's split-K on the Gram
 // matrices of small batches (n = 1280, P = 4e5) the streamed K-major operand reached only 0.2 TB/s - 17 splits x 1280
 // row streams 1.6 MB apart - and the 128 x 128 tile with its 2 workgroups per CU was twice as fast (27 ms vs 59 ms).
-// Split-K here only fills the last round of workgroups of a large output (at most 4 splits).
-static bool gemm256_plan(int64_t M, int64_t N, int64_t K, bool syrk, int *ksplit_out, int64_t *kchunk_out, int max_split) {
-  static int forced = -2;
-  if (forced == -2) {
-    const char *e = getenv("VIVIT_GEMM256");
-    forced = e ? atoi(e) : -1;
-  }
-  if (ksplit_out) *ksplit_out = 1;
-  if (kchunk_out) *kchunk_out = cdiv(K, BK) * BK;
-  if (forced == 0 || K < 512) return false;
+// Split-K here only fills the last round of workgroups of a large output (at most 4 splits, and never more than
+// `max_split`: gemm_launch passes what the caller's workspace holds).
+static bool plan_tile256(const GemmShape &sh, GemmPlan &pl, int max_split = 4) {
+  const int64_t M = sh.M, N = sh.N, K = sh.K;
+  const bool syrk = sh.syrk;
+  pl = GemmPlan{};
+  pl.route = GemmRoute::Tile256;
+  pl.ksplit = 1;
+  pl.kchunk = cdiv(K, BK) * BK;
+  if (!gemm256_enabled() || K < 512) return false;
   const int64_t tm = cdiv(M, B2), tn = cdiv(N, B2);
   const int64_t tiles = syrk ? tm * (tm + 1) / 2 : tm * tn;
   // one workgroup per CU: prologue (first DMA round trip) and epilogue (256 KB of C) are not overlapped with
@@ -2156,28 +2176,43 @@ static bool gemm256_plan(int64_t M, int64_t N, int64_t K, bool syrk, int *ksplit
     if (eff > best + 1e-9) { best = eff; best_s = s; }
   }
   if (best_s == 0 || best < 0.6) return false;
-  if (ksplit_out && best_s > 1) {
-    const int64_t kchunk = cdiv(ktiles, best_s) * BK;
-    *kchunk_out = kchunk;
-    *ksplit_out = (int)cdiv(K, kchunk);
+  if (best_s > 1) {
+    pl.kchunk = cdiv(ktiles, best_s) * BK;
+    pl.ksplit = (int)cdiv(K, pl.kchunk);
+    pl.slab_bytes = (size_t)pl.ksplit * (size_t)M * (size_t)N * sizeof(float);
   }
+  pl.bytes = pl.slab_bytes;
   return true;
 }
 
-// Which matrix pipe the 256-tile NT products (Gram SYRK, K-contiguous GEMMs) use: 6 (default) = bf16 pipe with exact
-// three-way operand splits and the 6 partial products that are >= 2^-16 of a product; 9 = all nine; 0 = fp32 MFMA
-// (gemm256_kernel); 3 = hi hi + hi mid + mid hi of the three-way split (per-product error 2^-16: experiments only).
-// VIVIT_GEMM_SPLIT overrides.
-static int gemm_split_mode() {
-  static int mode = -1;
-  if (mode < 0) {
-    const char *e = getenv("VIVIT_GEMM_SPLIT");
-    mode = e ? atoi(e) : 6;
-    if (mode != 0 && mode != 3 && mode != 6 && mode != 9) mode = 6;
+static int launch_tile256(const GemmPlan &pl, const GemmShape &sh, int alay, int blay, GemmArgs p, void *workspace, hipStream_t stream) {
+  p.ksplit = pl.ksplit;
+  p.kchunk = pl.kchunk;
+  p.slab = pl.ksplit > 1 ? ws_at<float>(workspace, pl.slab_off) : nullptr;
+  p.tiles_m = (int)cdiv(p.M, B2);
+  p.tiles_n = (int)cdiv(p.N, B2);
+  p.syrk = sh.syrk ? 1 : 0;
+  p.a_vec = operand_vec(p.A, p.lda);
+  p.b_vec = operand_vec(p.B, p.ldb);
+  p.desc = nullptr;
+  const int64_t nsb = tile_grid(p.tiles_m, p.tiles_n, sh.syrk, &p.sbw);
+  if (nsb < 0) return VIVIT_E_UNSUPPORTED;
+  if (!gemm_attrs()) return VIVIT_E_LAUNCH;
+  dim3 grid((unsigned)(nsb * 256), (unsigned)p.ksplit, 1);
+  const bool prof = sh.syrk && p.A == p.B && prof_enabled() && sh.pub;
+  if (prof) prof_begin(0, (double)p.M * (double)(p.M + 1) * (double)p.K, stream);
+  with_layouts(alay, blay, [&](auto LA, auto LB) { gemm256_kernel<LA, LB><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(p); });
+  int st = launch_status();
+  if (st == VIVIT_OK && p.ksplit > 1) {
+    gemm_reduce_kernel<<<(unsigned)cdiv(p.M * p.N, 256), 256, 0, stream>>>(p.slab, p.C, p.M, p.N, p.ldc, p.ksplit, p.alpha,
+                                                                           p.beta, p.syrk, B2);
+    st = launch_status();
   }
-  return mode;
+  if (prof) prof_end(0, stream);
+  return st;
 }
 
+// ---- the bf16 pipe of the 256 tile (Tile256Bx, BxSplitK)
 // Length of one MFMA accumulation chain of the bf16-pipe kernel, in K tiles.  v_mfma_f32_32x32x16_bf16 is NOT a chain
 // of correctly rounded fmas: it adds the accumulator and two 8-product group sums after aligning them to the largest
 // exponent with about one guard bit, and what is shifted out is TRUNCATED (scripts/probe/mfma_round.hip: c = 1 plus
@@ -2213,202 +2248,144 @@ static int64_t bx_chunk_cols(int64_t K, bool pub) {
   const int64_t kc = pub ? (int64_t)bx_flush_tiles * BK : 65536;
   return K < kc ? K : kc;
 }
-static bool bx_public_product();
-static size_t bx_piece_bytes(int64_t M, int64_t N, int64_t K, bool same) {
-  // (the public workspace queries run inside a BxStrictScope like the public launches: 1 GB of pieces instead of 16 GB at
-  // n = 40 960; the eigensolver's own queries and launches see the long chunk)
-  const int64_t kc = bx_chunk_cols(K, bx_public_product());
-  const int64_t ra = cdiv(M, 32) * 32, rb = cdiv(N, 32) * 32;
-  return (size_t)6 * (size_t)kc * (size_t)(same ? ra : ra + rb);
-}
-// pieces of one chunk + one range flag per chunk (BX_GATE)
-static size_t bx_workspace_bytes(int64_t M, int64_t N, int64_t K, bool same) {
-  const size_t nch = (size_t)cdiv(K, bx_chunk_cols(K, true));   // (the larger of the two counts)
-  return bx_piece_bytes(M, N, K, same) + 256 + 4 * nch + 256;
+
+// bytes of the three bf16 pieces of `cols` columns of the operands (32-row blocks); *b_off: where B's pieces start
+static size_t bx_carve_pieces(const GemmShape &sh, int64_t cols, size_t *b_off) {
+  const int64_t ra = cdiv(sh.M, 32) * 32, rb = cdiv(sh.N, 32) * 32;
+  *b_off = sh.same ? 0 : (size_t)6 * (size_t)cols * (size_t)ra;
+  return (size_t)6 * (size_t)cols * (size_t)(sh.same ? ra : ra + rb);
 }
 
-// Which range flags send a chunk to the fp32 MFMA kernel.  The public products (vivit_gram_syrk_f32, vivit_gemm_*_f32)
-// honour both bits and so keep fp32-MFMA semantics for every input; the eigensolver's internal products on orthogonal
-// factors only reroute non-finite / out-of-range chunks (a localised eigenvector has entries below 2^-100 whose
-// 2^-126-level piece is immaterial, and the reroute would cost that chunk the bf16 pipe's 2.7x).
-static thread_local int tls_bx_gate_mask = BX_GATE_RANGE;
-// true inside a public product (vivit_gram_syrk_f32 / vivit_gemm_*_f32): the profile (roofline.achieved of bench.py) counts
-// the Gram SYRKs of the caller, not the reflector Gram matrices the eigensolver's back-transformation builds internally
-static bool bx_public_product() { return (tls_bx_gate_mask & BX_GATE_TINY) != 0; }
-
-struct BxStrictScope {
-  int saved;
-  BxStrictScope() : saved(tls_bx_gate_mask) { tls_bx_gate_mask = BX_GATE_RANGE | BX_GATE_TINY; }
-  ~BxStrictScope() { tls_bx_gate_mask = saved; }
-};
-
-// VIVIT_BX_ASM=1 / 0: the hand-scheduled K loop (gemm256_bx_kernel<6, true>) or the C++ loop (the reference implementation)
-static bool bx_asm_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char *e = getenv("VIVIT_BX_ASM");
-    on = e ? (atoi(e) != 0) : 1;
-  }
-  return on != 0;
-}
-static void bx_launch6(dim3 grid, const GemmBxArgs &q, hipStream_t stream) {
-  if (bx_asm_enabled())
-    gemm256_bx_kernel<6, true><<<grid, 256, GEMM256BX_LDS_BYTES, stream>>>(q);
-  else
-    gemm256_bx_kernel<6><<<grid, 256, GEMM256BX_LDS_BYTES, stream>>>(q);
-}
-
-static bool gemm256_attrs() {
-  static unsigned long long attr_done = 0;
-  {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    if (!(attr_done & (1ull << (dev & 63)))) {
-      const void *fns[4] = {reinterpret_cast<const void *>(gemm256_kernel<LAY_K, LAY_K>),
-                            reinterpret_cast<const void *>(gemm256_kernel<LAY_K, LAY_M>),
-                            reinterpret_cast<const void *>(gemm256_kernel<LAY_M, LAY_K>),
-                            reinterpret_cast<const void *>(gemm256_kernel<LAY_M, LAY_M>)};
-      for (const void *f : fns)
-        if (!ensure_dynamic_lds(f, GEMM256_LDS_BYTES, attr_done)) return false;
-      const void *bx[4] = {reinterpret_cast<const void *>(gemm256_bx_kernel<3>), reinterpret_cast<const void *>(gemm256_bx_kernel<6>),
-                           reinterpret_cast<const void *>(gemm256_bx_kernel<9>), reinterpret_cast<const void *>(gemm256_bx_kernel<6, true>)};
-      for (const void *f : bx)
-        if (!ensure_dynamic_lds(f, GEMM256BX_LDS_BYTES, attr_done)) return false;
-      attr_done |= 1ull << (dev & 63);
-    }
-  }
+// Tile256Bx: the shapes of Tile256, K in chunks of pl.kchunk columns, per chunk the operand pieces (bx_split_kernel) and one
+// pure-bf16 launch that accumulates into C.  No split-K: a last round of workgroups that is not full costs less than the
+// bf16 pipe's 1.6x speed.  Workspace: the pieces of one chunk + one range flag per chunk (BX_GATE).
+// (the public workspace queries run inside a BxStrictScope like the public launches: 1 GB of pieces instead of 16 GB at
+// n = 40 960; the eigensolver's own queries and launches see the long chunk)
+static bool plan_tile256_bx(const GemmShape &sh, GemmPlan &pl) {
+  if (gemm_split_mode() == 0 || !plan_tile256(sh, pl)) return false;
+  pl.route = GemmRoute::Tile256Bx;
+  pl.ksplit = 1;
+  pl.kchunk = bx_chunk_cols(sh.K, sh.pub);
+  pl.slab_bytes = 0;
+  const size_t pieces = bx_carve_pieces(sh, pl.kchunk, &pl.b_off);
+  pl.flags_off = align_up(pieces, 256);
+  const size_t nch = (size_t)cdiv(sh.K, bx_chunk_cols(sh.K, true));   // (the larger of the two counts)
+  pl.bytes = pieces + 256 + 4 * nch + 256;
   return true;
 }
 
-static int gemm256_launch(int alay, int blay, GemmArgs p, bool syrk, void *workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!gemm256_attrs()) return VIVIT_E_LAUNCH;
-  // never more splits than the caller's workspace holds (callers size it for their largest problem; the plan
-  // of a smaller one may differ)
-  const size_t slab1 = (size_t)p.M * (size_t)p.N * sizeof(float);
-  const int max_split = workspace ? (int)(workspace_bytes / slab1 < 32 ? workspace_bytes / slab1 : 32) : 1;
-  gemm256_plan(p.M, p.N, p.K, syrk, &p.ksplit, &p.kchunk, max_split < 1 ? 1 : max_split);
-  // the bf16-pipe kernel has no split-K: a last round of workgroups that is not full costs less than its 1.6x speed
+// Splits columns [k0, k0 + kc) of the operands into their bf16 pieces (piece rows of `kcap` columns at pl.a_off / pl.b_off,
+// range bits ORed into *flag) and launches the bf16-pipe kernel on them.  The caller has filled what differs between the
+// routes: alpha, beta, syrk, sbw, slab, kt_split and the chain lengths of q.
+static int launch_bx(const GemmPlan &pl, const GemmShape &sh, int alay, int blay, const GemmArgs &p, void *workspace, int64_t k0,
+                     int64_t kc, int64_t kcap, int *flag, GemmBxArgs q, dim3 grid, hipStream_t stream) {
+  const int64_t nrbA = cdiv(p.M, 32), nrbB = sh.same ? nrbA : cdiv(p.N, 32);
+  const int64_t strideA = nrbA * 32 * kcap, strideB = nrbB * 32 * kcap;
+  unsigned short *PA = ws_at<unsigned short>(workspace, pl.a_off), *PB = ws_at<unsigned short>(workspace, pl.b_off);
+  const unsigned gy = (unsigned)cdiv(kc / 16, 4);
+  with_layout(alay, [&](auto L) {
+    bx_split_kernel<L><<<dim3((unsigned)nrbA, gy), 256, 0, stream>>>(p.A, p.M, p.lda, k0, kc, PA, strideA, nrbA, flag);
+  });
+  if (!sh.same)
+    with_layout(blay, [&](auto L) {
+      bx_split_kernel<L><<<dim3((unsigned)nrbB, gy), 256, 0, stream>>>(p.B, p.N, p.ldb, k0, kc, PB, strideB, nrbB, flag);
+    });
+  q.A = PA; q.B = PB; q.strideA = strideA; q.strideB = strideB;
+  q.nrbA = nrbA; q.nrbB = nrbB;
+  q.C = p.C; q.M = p.M; q.N = p.N; q.K = kc; q.ldc = p.ldc;
+  q.tiles_m = p.tiles_m; q.tiles_n = p.tiles_n;
+  q.gate = flag; q.gate_mask = tls_bx_gate_mask;
   const int bx = gemm_split_mode();
-  const bool same = p.A == p.B && p.lda == p.ldb && p.M == p.N && alay == blay;
-  const bool on_bx = bx != 0 && workspace && workspace_bytes >= bx_workspace_bytes(p.M, p.N, p.K, same);
-  if (on_bx) {
-    p.ksplit = 1;
-    p.kchunk = cdiv(p.K, BK) * BK;
-  }
-  p.slab = p.ksplit > 1 ? static_cast<float *>(workspace) : nullptr;
+  if (bx == 6 && bx_asm_enabled())
+    gemm256_bx_kernel<6, true><<<grid, 256, GEMM256BX_LDS_BYTES, stream>>>(q);
+  else if (bx == 6)
+    gemm256_bx_kernel<6><<<grid, 256, GEMM256BX_LDS_BYTES, stream>>>(q);
+  else if (bx == 9)
+    gemm256_bx_kernel<9><<<grid, 256, GEMM256BX_LDS_BYTES, stream>>>(q);
+  else
+    gemm256_bx_kernel<3><<<grid, 256, GEMM256BX_LDS_BYTES, stream>>>(q);
+  return launch_status();
+}
+
+// BX_GATE: the fp32 MFMA kernel on the grid of the bf16-pipe launch it stands in for; every workgroup returns at once unless
+// the range flag of the chunk is set
+static int launch_fp32_standin(int alay, int blay, GemmArgs f, dim3 grid, const int *flag, hipStream_t stream) {
+  f.a_vec = operand_vec(f.A, f.lda);
+  f.b_vec = operand_vec(f.B, f.ldb);
+  f.gate = flag; f.gate_mask = tls_bx_gate_mask;
+  with_layouts(alay, blay, [&](auto LA, auto LB) { gemm256_kernel<LA, LB><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f); });
+  return launch_status();
+}
+
+static int launch_tile256_bx(const GemmPlan &pl, const GemmShape &sh, int alay, int blay, GemmArgs p, void *workspace, hipStream_t stream) {
+  p.ksplit = 1;
+  p.kchunk = cdiv(p.K, BK) * BK;
+  p.slab = nullptr;
   p.tiles_m = (int)cdiv(p.M, B2);
   p.tiles_n = (int)cdiv(p.N, B2);
-  p.syrk = syrk ? 1 : 0;
-  p.a_vec = ((reinterpret_cast<uintptr_t>(p.A) & 15) == 0 && (p.lda & 3) == 0) ? 1 : 0;
-  p.b_vec = ((reinterpret_cast<uintptr_t>(p.B) & 15) == 0 && (p.ldb & 3) == 0) ? 1 : 0;
+  p.syrk = sh.syrk ? 1 : 0;
   p.desc = nullptr;
-  const int sbw = syrk ? 16 : sb_width(p.tiles_m, p.tiles_n), sbh = 256 / sbw;
-  p.sbw = sbw;
-  const int64_t sbm = cdiv(p.tiles_m, sbh), sbn = cdiv(p.tiles_n, sbw);
-  const int64_t nsb = syrk ? sbm * (sbm + 1) / 2 : sbm * sbn;
-  if (nsb * 256 > 0x7fffffffLL) return VIVIT_E_UNSUPPORTED;
-  dim3 grid((unsigned)(nsb * 256), (unsigned)p.ksplit, 1);
-  const bool prof = syrk && p.A == p.B && prof_enabled() && bx_public_product();
+  const int64_t nsb = tile_grid(p.tiles_m, p.tiles_n, sh.syrk, &p.sbw);
+  if (nsb < 0) return VIVIT_E_UNSUPPORTED;
+  if (!gemm_attrs()) return VIVIT_E_LAUNCH;
+  dim3 grid((unsigned)(nsb * 256), 1, 1);
+  const bool prof = sh.syrk && p.A == p.B && prof_enabled() && sh.pub;
   if (prof) prof_begin(0, (double)p.M * (double)(p.M + 1) * (double)p.K, stream);
-  if (on_bx) {
-    // fp32 product on the bf16 pipe: K in chunks of BX_KC columns, per chunk the operand pieces (bx_split_kernel)
-    // and one pure-bf16 launch that accumulates into C (beta = 1 from the second chunk on)
-    const int64_t kc_max = bx_chunk_cols(p.K, bx_public_product());
-    const int64_t nrbA = cdiv(p.M, 32), nrbB = cdiv(p.N, 32);
-    unsigned short *PA = static_cast<unsigned short *>(workspace);
-    const int64_t strideA = nrbA * 32 * kc_max, strideB = nrbB * 32 * kc_max;
-    unsigned short *PB = same ? PA : PA + 3 * strideA;
-    int *flags = reinterpret_cast<int *>(align_up(reinterpret_cast<uintptr_t>(workspace) + bx_piece_bytes(p.M, p.N, p.K, same), 256));
-    const int64_t nchunks = cdiv(p.K, kc_max);
-    if (hipMemsetAsync(flags, 0, 4 * (size_t)nchunks, stream) != hipSuccess) return VIVIT_E_LAUNCH;
-    GemmBxArgs q;
-    q.A = PA; q.B = PB; q.strideA = strideA; q.strideB = same ? strideA : strideB;
-    q.nrbA = nrbA; q.nrbB = same ? nrbA : nrbB;
-    q.C = p.C; q.M = p.M; q.N = p.N; q.ldc = p.ldc; q.alpha = p.alpha;
-    q.tiles_m = p.tiles_m; q.tiles_n = p.tiles_n; q.syrk = p.syrk; q.sbw = p.sbw;
-    q.slab = nullptr; q.kt_split = 0;
-    q.gate_mask = tls_bx_gate_mask;
-    // the eigensolver's own products (orthogonal factors: sums of random signs, nothing correlated) keep chains of 8192
-    const bool internal = tls_bx_gate_mask == BX_GATE_RANGE;
-    q.flush_tiles = internal ? bx_flush_internal : bx_flush_tiles;
-    q.flush_diag = internal ? bx_flush_internal : bx_flush_diag;
-    float beta0 = p.beta;
-    if (beta0 != 0.f && beta0 != 1.f) {   // the in-loop flushes add into C: C <- beta C once, then beta = 1
-      scale_c_kernel<<<(unsigned)cdiv(p.M * p.N, 256), 256, 0, stream>>>(p.C, p.M, p.N, p.ldc, beta0);
-      beta0 = 1.f;
-    }
-    int st = VIVIT_OK;
-    int64_t chunk = 0;
-    for (int64_t k0 = 0; k0 < p.K && st == VIVIT_OK; k0 += kc_max, ++chunk) {
-      const int64_t kc = (p.K - k0) < kc_max ? (p.K - k0) : kc_max;
-      const unsigned gy = (unsigned)cdiv(kc / 16, 4);
-      int *flag = flags + chunk;
-      with_layout(alay, [&](auto L) {
-        bx_split_kernel<L><<<dim3((unsigned)nrbA, gy), 256, 0, stream>>>(p.A, p.M, p.lda, k0, kc, PA, strideA, nrbA, flag);
-      });
-      if (!same)
-        with_layout(blay, [&](auto L) {
-          bx_split_kernel<L><<<dim3((unsigned)nrbB, gy), 256, 0, stream>>>(p.B, p.N, p.ldb, k0, kc, PB, strideB, nrbB, flag);
-        });
-      q.K = kc;
-      q.beta = k0 == 0 ? beta0 : 1.f;
-      // SYRK: only the last chunk mirrors the finished lower tiles into the upper triangle (2 = lower tiles, no mirror)
-      q.syrk = (p.syrk == 1 && k0 + kc < p.K) ? 2 : p.syrk;
-      q.gate = flag;
-      if (bx == 6)
-        bx_launch6(grid, q, stream);
-      else if (bx == 9)
-        gemm256_bx_kernel<9><<<grid, 256, GEMM256BX_LDS_BYTES, stream>>>(q);
-      else
-        gemm256_bx_kernel<3><<<grid, 256, GEMM256BX_LDS_BYTES, stream>>>(q);
-      st = launch_status();
-      if (st != VIVIT_OK) break;
-      // BX_GATE: the same chunk on the fp32 MFMA kernel; every workgroup returns at once unless the chunk is flagged
-      GemmArgs f = p;
-      f.A = p.A + (alay == LAY_K ? k0 : k0 * p.lda);
-      f.B = p.B + (blay == LAY_K ? k0 : k0 * p.ldb);
-      f.K = kc; f.kchunk = kc; f.ksplit = 1; f.slab = nullptr;
-      f.beta = q.beta; f.syrk = q.syrk;
-      f.a_vec = ((reinterpret_cast<uintptr_t>(f.A) & 15) == 0 && (f.lda & 3) == 0) ? 1 : 0;
-      f.b_vec = ((reinterpret_cast<uintptr_t>(f.B) & 15) == 0 && (f.ldb & 3) == 0) ? 1 : 0;
-      f.gate = flag; f.gate_mask = q.gate_mask;
-      with_layouts(alay, blay, [&](auto LA, auto LB) { gemm256_kernel<LA, LB><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f); });
-      st = launch_status();
-    }
-    if (st == VIVIT_OK && p.syrk == 1) {
-      bx_sym_diag_kernel<<<(unsigned)p.tiles_m, 256, 0, stream>>>(p.C, p.M, p.ldc);
-      st = launch_status();
-    }
-    if (prof) prof_end(0, stream);
-    return st;
+  const int64_t kc_max = pl.kchunk;
+  int *flags = ws_at<int>(workspace, pl.flags_off);
+  if (hipMemsetAsync(flags, 0, 4 * (size_t)cdiv(p.K, kc_max), stream) != hipSuccess) return VIVIT_E_LAUNCH;
+  GemmBxArgs q;
+  q.alpha = p.alpha; q.sbw = p.sbw;
+  q.slab = nullptr; q.kt_split = 0;
+  // the eigensolver's own products (orthogonal factors: sums of random signs, nothing correlated) keep chains of 8192
+  q.flush_tiles = sh.pub ? bx_flush_tiles : bx_flush_internal;
+  q.flush_diag = sh.pub ? bx_flush_diag : bx_flush_internal;
+  float beta0 = p.beta;
+  if (beta0 != 0.f && beta0 != 1.f) {   // the in-loop flushes add into C: C <- beta C once, then beta = 1
+    scale_c_kernel<<<(unsigned)cdiv(p.M * p.N, 256), 256, 0, stream>>>(p.C, p.M, p.N, p.ldc, beta0);
+    beta0 = 1.f;
   }
-  with_layouts(alay, blay, [&](auto LA, auto LB) { gemm256_kernel<LA, LB><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(p); });
-  int st = launch_status();
-  if (st == VIVIT_OK && p.ksplit > 1) {
-    gemm_reduce_kernel<<<(unsigned)cdiv(p.M * p.N, 256), 256, 0, stream>>>(p.slab, p.C, p.M, p.N, p.ldc, p.ksplit, p.alpha,
-                                                                           p.beta, p.syrk, B2);
+  int st = VIVIT_OK;
+  int *flag = flags;
+  for (int64_t k0 = 0; k0 < p.K && st == VIVIT_OK; k0 += kc_max, ++flag) {
+    const int64_t kc = (p.K - k0) < kc_max ? (p.K - k0) : kc_max;
+    q.beta = k0 == 0 ? beta0 : 1.f;
+    // SYRK: only the last chunk mirrors the finished lower tiles into the upper triangle (2 = lower tiles, no mirror)
+    q.syrk = (p.syrk == 1 && k0 + kc < p.K) ? 2 : p.syrk;
+    st = launch_bx(pl, sh, alay, blay, p, workspace, k0, kc, kc_max, flag, q, grid, stream);
+    if (st != VIVIT_OK) break;
+    GemmArgs f = p;   // the same chunk on the fp32 MFMA kernel
+    f.A = p.A + (alay == LAY_K ? k0 : k0 * p.lda);
+    f.B = p.B + (blay == LAY_K ? k0 : k0 * p.ldb);
+    f.K = kc; f.kchunk = kc;
+    f.beta = q.beta; f.syrk = q.syrk;
+    st = launch_fp32_standin(alay, blay, f, grid, flag, stream);
+  }
+  if (st == VIVIT_OK && p.syrk == 1) {
+    bx_sym_diag_kernel<<<(unsigned)p.tiles_m, 256, 0, stream>>>(p.C, p.M, p.ldc);
     st = launch_status();
   }
   if (prof) prof_end(0, stream);
   return st;
 }
 
-// ---- bf16-pipe split-K for SMALL outputs with a deep contraction (Gram matrices of small batches: n = 1280,
+// ---- BxSplitK: bf16-pipe split-K for SMALL outputs with a deep contraction (Gram matrices of small batches: n = 1280,
 // P = 4e5 has 15 lower 256-tiles).  The whole operand is split into its three bf16 pieces once (blocked layout: a k
 // tile of a 256-row block is 8 KB contiguous per piece, so a K split streams long runs, unlike the 1280 row streams
 // 1.6 MB apart of the fp32 operand), one launch with the k tiles divided over blockIdx.y writes partial tiles to a slab,
 // and the fixed-order reduce mirrors the lower tiles of a SYRK.
-static bool bx_splitk_shape(int64_t M, int64_t N, int64_t K, bool syrk, bool same, int *nsplit_out, int *kt_split_out,
-                            size_t *bytes_out) {
-  static int forced = -2;
-  if (forced == -2) { const char *e = getenv("VIVIT_GEMM_BXSPLITK"); forced = e ? atoi(e) : -1; }
-  if (forced == 0 || gemm_split_mode() != 6) return false;
+// Workspace: whole-K pieces, the slab, one range flag.
+static bool plan_bx_splitk(const GemmShape &sh, GemmPlan &pl) {
+  const int64_t M = sh.M, N = sh.N, K = sh.K;
+  const bool syrk = sh.syrk;
+  if (!bx_splitk_enabled() || gemm_split_mode() != 6) return false;
   if (K < 16384 || (K % BK) != 0 || M < 256 || N < 256) return false;
   const int64_t tm = cdiv(M, B2), tn = cdiv(N, B2);
   const int64_t tiles = syrk ? tm * (tm + 1) / 2 : tm * tn;
   if (tiles > 100) return false;                       // enough tiles: the plain bf16-pipe launch fills the chip
-  const int64_t ra = cdiv(M, 32) * 32, rb = cdiv(N, 32) * 32;
-  const size_t pieces = (size_t)6 * (size_t)K * (size_t)(same ? ra : ra + rb);
+  pl = GemmPlan{};
+  pl.route = GemmRoute::BxSplitK;
+  const size_t pieces = bx_carve_pieces(sh, K, &pl.b_off);
   if (pieces > ((size_t)8 << 30)) return false;        // whole-K pieces: bounded scratch
   const int64_t nt = K / BK;
   int64_t s = 512 / tiles;                             // ~2 rounds of one workgroup per CU
@@ -2419,9 +2396,8 @@ static bool bx_splitk_shape(int64_t M, int64_t N, int64_t K, bool syrk, bool sam
     // number of splits is 8 g, and what counts is the busiest XCD -- ceil(tiles g / 32) rounds of ceil(nt / 8 g) K tiles on its 32
     // CUs -- plus the slab the reduce has to read back.  (34 splits of 15 tiles gave two XCDs 75 workgroups and six 60: three
     // rounds where the others needed two.)
-    const int sbw = syrk ? 16 : sb_width((int)tm, (int)tn), sbh = 256 / sbw;
-    const int64_t nsb = syrk ? cdiv(tm, sbh) * (cdiv(tm, sbh) + 1) / 2 : cdiv(tm, sbh) * cdiv(tn, sbw);
-    if (nsb == 1) {
+    int sbw;
+    if (tile_grid(tm, tn, syrk, &sbw) == 1) {
       double best = 0.0;
       int64_t gbest = 0;
       for (int64_t g = 1; g <= 16 && nt / (8 * g) >= 64; ++g) {
@@ -2434,108 +2410,68 @@ static bool bx_splitk_shape(int64_t M, int64_t N, int64_t K, bool syrk, bool sam
   }
   const int64_t kts = cdiv(nt, s);
   s = cdiv(nt, kts);
-  if (nsplit_out) *nsplit_out = (int)s;
-  if (kt_split_out) *kt_split_out = (int)kts;
-  if (bytes_out) *bytes_out = pieces + 256 + (size_t)s * (size_t)M * (size_t)N * sizeof(float) + 256 + 256;  // + range flag
+  pl.ksplit = (int)s;
+  pl.kt_split = (int)kts;
+  pl.kchunk = kts * BK;
+  pl.slab_off = align_up(pieces, 256);
+  pl.slab_bytes = (size_t)s * (size_t)M * (size_t)N * sizeof(float);
+  pl.flags_off = align_up(pl.slab_off + pl.slab_bytes, 256);
+  pl.bytes = pieces + 256 + pl.slab_bytes + 256 + 256;  // + range flag
   return true;
 }
 
-static int bx_splitk_launch(int alay, int blay, const GemmArgs &p, bool syrk, void *workspace, size_t workspace_bytes, hipStream_t stream) {
-  if (!gemm256_attrs()) return VIVIT_E_LAUNCH;
-  const bool same = p.A == p.B && p.lda == p.ldb && p.M == p.N && alay == blay;
-  int nsplit, kts;
-  size_t need;
-  if (!bx_splitk_shape(p.M, p.N, p.K, syrk, same, &nsplit, &kts, &need)) return VIVIT_E_UNSUPPORTED;
-  if (!workspace || workspace_bytes < need) return VIVIT_E_WORKSPACE;
-  const int64_t nrbA = cdiv(p.M, 32), nrbB = cdiv(p.N, 32);
-  const int64_t strideA = nrbA * 32 * p.K, strideB = nrbB * 32 * p.K;
-  unsigned short *PA = static_cast<unsigned short *>(workspace);
-  unsigned short *PB = same ? PA : PA + 3 * strideA;
-  const size_t pieces = (size_t)6 * (size_t)p.K * (size_t)(same ? nrbA * 32 : (nrbA + nrbB) * 32);
-  float *slab = reinterpret_cast<float *>(align_up(reinterpret_cast<uintptr_t>(workspace) + pieces, 256));
-  int *flag = reinterpret_cast<int *>(align_up(reinterpret_cast<uintptr_t>(slab) + (size_t)nsplit * (size_t)p.M * (size_t)p.N * sizeof(float), 256));
-  if (hipMemsetAsync(flag, 0, 4, stream) != hipSuccess) return VIVIT_E_LAUNCH;
-  const bool prof = syrk && same && prof_enabled() && bx_public_product();
-  if (prof) prof_begin(0, (double)p.M * (double)(p.M + 1) * (double)p.K, stream);
-  const unsigned gy = (unsigned)cdiv(p.K / 16, 4);
-  with_layout(alay, [&](auto L) {
-    bx_split_kernel<L><<<dim3((unsigned)nrbA, gy), 256, 0, stream>>>(p.A, p.M, p.lda, 0, p.K, PA, strideA, nrbA, flag);
-  });
-  if (!same)
-    with_layout(blay, [&](auto L) {
-      bx_split_kernel<L><<<dim3((unsigned)nrbB, gy), 256, 0, stream>>>(p.B, p.N, p.ldb, 0, p.K, PB, strideB, nrbB, flag);
-    });
+static int launch_bx_splitk(const GemmPlan &pl, const GemmShape &sh, int alay, int blay, GemmArgs p, void *workspace, hipStream_t stream) {
+  const int nsplit = pl.ksplit;
+  float *slab = ws_at<float>(workspace, pl.slab_off);
+  int *flag = ws_at<int>(workspace, pl.flags_off);
+  p.tiles_m = (int)cdiv(p.M, B2);
+  p.tiles_n = (int)cdiv(p.N, B2);
+  p.desc = nullptr;
   GemmBxArgs q;
-  q.A = PA; q.B = PB; q.strideA = strideA; q.strideB = same ? strideA : strideB;
-  q.nrbA = nrbA; q.nrbB = same ? nrbA : nrbB;
-  q.C = p.C; q.M = p.M; q.N = p.N; q.K = p.K; q.ldc = p.ldc; q.alpha = 1.f; q.beta = 0.f;
-  q.tiles_m = (int)cdiv(p.M, B2); q.tiles_n = (int)cdiv(p.N, B2);
-  q.syrk = syrk ? 2 : 0;   // lower tiles only; the reduce mirrors
-  const int sbw = syrk ? 16 : sb_width(q.tiles_m, q.tiles_n), sbh = 256 / sbw;
-  q.sbw = sbw;
-  q.slab = slab; q.kt_split = kts;
-  q.gate = flag; q.gate_mask = tls_bx_gate_mask;
+  q.alpha = 1.f; q.beta = 0.f;
+  q.syrk = sh.syrk ? 2 : 0;   // lower tiles only; the reduce mirrors
+  const int64_t nsb = tile_grid(p.tiles_m, p.tiles_n, sh.syrk, &q.sbw);
+  if (nsb < 0) return VIVIT_E_UNSUPPORTED;
+  q.slab = slab; q.kt_split = pl.kt_split;
   q.flush_tiles = bx_flush_splitk;
   q.flush_diag = bx_flush_diag;
-  const int64_t sbm = cdiv(q.tiles_m, sbh), sbn = cdiv(q.tiles_n, sbw);
-  const int64_t nsb = syrk ? sbm * (sbm + 1) / 2 : sbm * sbn;
   dim3 grid((unsigned)(nsb * 256), (unsigned)nsplit);
   if (nsb == 1) {   // one (partial) super-block: the compact grid of map_tile_z, all tiles of a split on one XCD
-    const int64_t d = q.tiles_m < q.tiles_n ? q.tiles_m : q.tiles_n;
-    const int64_t v = syrk ? d * (d + 1) / 2 : (int64_t)q.tiles_m * q.tiles_n;
+    const int64_t d = p.tiles_m < p.tiles_n ? p.tiles_m : p.tiles_n;
+    const int64_t v = sh.syrk ? d * (d + 1) / 2 : (int64_t)p.tiles_m * p.tiles_n;
     grid = dim3((unsigned)(8 * v * cdiv(nsplit, 8)), 1);
-    q.sbw = -sbw;
+    q.sbw = -q.sbw;
   }
-  bx_launch6(grid, q, stream);
-  int st = launch_status();
+  if (!gemm_attrs()) return VIVIT_E_LAUNCH;
+  if (hipMemsetAsync(flag, 0, 4, stream) != hipSuccess) return VIVIT_E_LAUNCH;
+  const bool prof = sh.syrk && sh.same && prof_enabled() && sh.pub;
+  if (prof) prof_begin(0, (double)p.M * (double)(p.M + 1) * (double)p.K, stream);
+  int st = launch_bx(pl, sh, alay, blay, p, workspace, 0, p.K, p.K, flag, q, grid, stream);
   if (st != VIVIT_OK) return st;
-  {  // BX_GATE: the fp32 MFMA kernel with the same K split and slab; returns at once unless the operand is flagged
-    GemmArgs f = p;
-    f.ksplit = nsplit; f.kchunk = (int64_t)kts * BK; f.slab = slab;
-    f.tiles_m = q.tiles_m; f.tiles_n = q.tiles_n; f.syrk = q.syrk; f.sbw = q.sbw; f.desc = nullptr;
-    f.a_vec = f.b_vec = 1;
-    f.gate = flag; f.gate_mask = q.gate_mask;
-    with_layouts(alay, blay, [&](auto LA, auto LB) { gemm256_kernel<LA, LB><<<grid, 256, GEMM256_LDS_BYTES, stream>>>(f); });
-    st = launch_status();
-    if (st != VIVIT_OK) return st;
-  }
+  GemmArgs f = p;   // the fp32 MFMA kernel with the same K split and slab
+  f.ksplit = nsplit; f.kchunk = pl.kchunk; f.slab = slab;
+  f.syrk = q.syrk; f.sbw = q.sbw;
+  st = launch_fp32_standin(alay, blay, f, grid, flag, stream);
+  if (st != VIVIT_OK) return st;
   gemm_reduce_kernel<<<(unsigned)cdiv(p.M * p.N, 256), 256, 0, stream>>>(slab, p.C, p.M, p.N, p.ldc, nsplit, p.alpha, p.beta,
-                                                                       syrk ? 1 : 0, B2);
+                                                                       sh.syrk ? 1 : 0, B2);
   st = launch_status();
-  if (st == VIVIT_OK && syrk) {
-    bx_sym_diag_kernel<<<(unsigned)q.tiles_m, 256, 0, stream>>>(p.C, p.M, p.ldc);
+  if (st == VIVIT_OK && sh.syrk) {
+    bx_sym_diag_kernel<<<(unsigned)p.tiles_m, 256, 0, stream>>>(p.C, p.M, p.ldc);
     st = launch_status();
   }
   if (prof) prof_end(0, stream);
   return st;
 }
 
-// 64-row streaming kernel: split-K so that ~2 workgroups per CU exist (one resident at a time: 140 KB LDS)
-static bool use_gemm64(int alay, int blay, const float *A, const float *B, int64_t M, int64_t N, int64_t K, int64_t lda,
-                       int64_t ldb) {
-  static int forced = -2;
-  if (forced == -2) {
-    const char *e = getenv("VIVIT_GEMM64");
-    forced = e ? atoi(e) : -1;
-  }
-  if (forced == 0) return false;
-  const bool vec = (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (lda & 3) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0 &&
-                   (ldb & 3) == 0 && (alay == LAY_K || ((M & 3) == 0 && M >= 4)) && (blay == LAY_K || ((N & 3) == 0 && N >= 4));
-  return vec && M <= 64 && N >= 2048 && K >= 2048 && (K % BK) == 0;
-}
-
-// products of the 64-row streaming kernel on the bf16 pipe (exact three-way splits) unless the fp32 pipe is asked for
-// (VIVIT_GEMM_SPLIT=0 or VIVIT_GEMM64_BX=0)
-static bool gemm64_bx_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char *e = getenv("VIVIT_GEMM64_BX");
-    on = (e ? atoi(e) != 0 : true) && gemm_split_mode() != 0;
-  }
-  return on != 0;
-}
-
-static size_t gemm64_workspace_bytes(int64_t M, int64_t N, int64_t K, int *ksplit_out, int64_t *kchunk_out, size_t *slab_out) {
+// ---- Gemm64: the 64-row streaming kernels, split-K so that ~2 workgroups per CU exist (one resident at a time: 140 KB LDS)
+// Workspace: the slab, behind it the bf16 pieces of the 64-row operand (gemm64_bx_kernel: 6 KB per K tile), behind them
+// the range flag of a public product.
+static bool plan_gemm64(const GemmShape &sh, GemmPlan &pl) {
+  const int64_t M = sh.M, N = sh.N, K = sh.K;
+  if (sh.syrk || !(M <= 64 && N >= 2048 && K >= 2048 && (K % BK) == 0)) return false;
+  pl = GemmPlan{};
+  pl.route = GemmRoute::Gemm64;
   const int64_t tiles = cdiv(N, 256), ktiles = K / BK;
   // one workgroup per CU: pick the split count (>= 2 rounds of work, every split >= 64 K tiles) whose last
   // round of 256 workgroups is fullest
@@ -2548,18 +2484,18 @@ static size_t gemm64_workspace_bytes(int64_t M, int64_t N, int64_t K, int *kspli
     const double score = wgs >= 512 ? fill : fill * 0.5 * (double)wgs / 512.0;  // too few workgroups: latency-bound
     if (score > best + 1e-9) { best = score; s = c; }
   }
-  const int64_t kchunk = cdiv(ktiles, s) * BK;
-  const int ksplit = (int)cdiv(K, kchunk);
-  if (ksplit_out) *ksplit_out = ksplit;
-  if (kchunk_out) *kchunk_out = kchunk;
+  pl.kchunk = cdiv(ktiles, s) * BK;
+  pl.ksplit = (int)cdiv(K, pl.kchunk);
   // a public product on the bf16 pipe always goes through the slab (its gated fp32 stand-in may replace the partial sums)
-  const bool strict = gemm64_bx_enabled() && bx_public_product();
-  const size_t slab = (ksplit > 1 || strict) ? (size_t)ksplit * (size_t)M * (size_t)N * sizeof(float) : 0;
-  if (slab_out) *slab_out = slab;
-  if (!gemm64_bx_enabled()) return slab;
-  // + the bf16 pieces of the 64-row operand (gemm64_bx_kernel): 6 KB per K tile, after the slab; + the range flag
-  const size_t pieces_end = align_up(slab, 256) + (size_t)ktiles * 6144;
-  return strict ? align_up(pieces_end, 256) + 256 : pieces_end;
+  const bool strict = gemm64_bx_enabled() && sh.pub;
+  pl.slab_bytes = (pl.ksplit > 1 || strict) ? (size_t)pl.ksplit * (size_t)M * (size_t)N * sizeof(float) : 0;
+  pl.bytes = pl.slab_bytes;
+  if (!gemm64_bx_enabled()) return true;
+  pl.a_off = align_up(pl.slab_bytes, 256);
+  const size_t pieces_end = pl.a_off + (size_t)ktiles * 6144;
+  pl.flags_off = align_up(pieces_end, 256);
+  pl.bytes = strict ? pl.flags_off + 256 : pieces_end;
+  return true;
 }
 
 // gemm64_bx_kernel addresses B as a scalar base + a 32-bit byte offset per lane: up to 255 rows of ldb floats (K-contiguous B)
@@ -2569,28 +2505,10 @@ static bool gemm64_bx_reach(int blay, int64_t ldb) {
   return (int64_t)(blay == LAY_K ? 255 : 15) * ldb * 4 + 1024 < ((int64_t)1 << 32);
 }
 
-static int gemm64_launch(int alay, int blay, GemmArgs p, void *workspace, size_t workspace_bytes, hipStream_t stream) {
-  static unsigned long long attr_done = 0;
-  {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return VIVIT_E_LAUNCH;
-    if (!(attr_done & (1ull << (dev & 63)))) {
-      const void *fns[4] = {reinterpret_cast<const void *>(gemm64_dma_kernel<LAY_K, LAY_K>),
-                            reinterpret_cast<const void *>(gemm64_dma_kernel<LAY_K, LAY_M>),
-                            reinterpret_cast<const void *>(gemm64_dma_kernel<LAY_M, LAY_K>),
-                            reinterpret_cast<const void *>(gemm64_dma_kernel<LAY_M, LAY_M>)};
-      for (int f = 0; f < 4; ++f)
-        if (!ensure_dynamic_lds(fns[f], GEMM64_LDS_BYTES, attr_done)) return VIVIT_E_LAUNCH;
-      if (!ensure_dynamic_lds(reinterpret_cast<const void *>(gemm64_bx_kernel<LAY_K>), GEMM64X_LDS_BYTES, attr_done) ||
-          !ensure_dynamic_lds(reinterpret_cast<const void *>(gemm64_bx_kernel<LAY_M>), GEMM64X_LDS_BYTES, attr_done) ||
-          !ensure_dynamic_lds(reinterpret_cast<const void *>(gemm64_bx_kernel<LAY_K, true>), GEMM64X_LDS_BYTES, attr_done) ||
-          !ensure_dynamic_lds(reinterpret_cast<const void *>(gemm64_bx_kernel<LAY_M, true>), GEMM64X_LDS_BYTES, attr_done))
-        return VIVIT_E_LAUNCH;
-      attr_done |= 1ull << (dev & 63);
-    }
-  }
-  size_t slab_bytes = 0;
-  const size_t need = gemm64_workspace_bytes(p.M, p.N, p.K, &p.ksplit, &p.kchunk, &slab_bytes);
+static int launch_gemm64(const GemmPlan &pl, const GemmShape &sh, int alay, int blay, GemmArgs p, void *workspace, size_t workspace_bytes,
+                         hipStream_t stream) {
+  p.ksplit = pl.ksplit;
+  p.kchunk = pl.kchunk;
   // Which kernel runs depends on SHAPE (leading dimensions included) and ENVIRONMENT only (results are bit-identical from call
   // to call, include/vivit_hip.h): a workspace smaller than the query's answer is refused -- it is never a silent switch to the
   // fp32 kernel, whose summation order (and speed) differs.
@@ -2598,23 +2516,21 @@ static int gemm64_launch(int alay, int blay, GemmArgs p, void *workspace, size_t
   // Public products on the bf16 pipe (INPUT RANGE CONTRACT): both split kernels OR the range bits of their operand into a flag,
   // the bf16-pipe product writes the slab, gemm64_dma_kernel on the same grid returns at once unless the flag is set and
   // otherwise rewrites the whole slab in fp32, and the reduce applies alpha and beta once.  No host synchronisation.
-  const bool strict = bx && bx_public_product();
+  const bool strict = bx && sh.pub;
   p.slab = nullptr;
   if (p.ksplit > 1 || strict) {
-    if (!workspace || workspace_bytes < slab_bytes) return VIVIT_E_WORKSPACE;
-    p.slab = static_cast<float *>(workspace);
+    if (!workspace || workspace_bytes < pl.slab_bytes) return VIVIT_E_WORKSPACE;
+    p.slab = ws_at<float>(workspace, pl.slab_off);
   }
   uint4 *apieces = nullptr;
   int *flag = nullptr;
   if (bx) {   // the pieces of A behind the slab, the range flag behind them
-    if (!workspace || workspace_bytes < need) return VIVIT_E_WORKSPACE;
-    const size_t off = align_up(slab_bytes, 256);
-    apieces = reinterpret_cast<uint4 *>(static_cast<char *>(workspace) + off);
-    if (strict) {
-      flag = reinterpret_cast<int *>(static_cast<char *>(workspace) + align_up(off + (size_t)(p.K / BK) * 6144, 256));
-      if (hipMemsetAsync(flag, 0, sizeof(int), stream) != hipSuccess) return VIVIT_E_LAUNCH;
-    }
+    if (!workspace || workspace_bytes < pl.bytes) return VIVIT_E_WORKSPACE;
+    apieces = ws_at<uint4>(workspace, pl.a_off);
+    if (strict) flag = ws_at<int>(workspace, pl.flags_off);
   }
+  if (!gemm_attrs()) return VIVIT_E_LAUNCH;
+  if (flag && hipMemsetAsync(flag, 0, sizeof(int), stream) != hipSuccess) return VIVIT_E_LAUNCH;
   p.tiles_m = 1;
   p.tiles_n = (int)cdiv(p.N, 256);
   p.syrk = 0;
@@ -2649,6 +2565,139 @@ static int gemm64_launch(int alay, int blay, GemmArgs p, void *workspace, size_t
   return st;
 }
 
+// ---- Tsk: gemm_tsk_kernel, one 64 x 64 output block and a K range per workgroup
+static bool plan_tsk(const GemmShape &sh, GemmPlan &pl) {
+  const int64_t M = sh.M, N = sh.N, K = sh.K;
+  if (sh.syrk || !(M <= 64 && N <= 1024 && K >= 2048 && (K & 3) == 0)) return false;
+  pl = GemmPlan{};
+  pl.route = GemmRoute::Tsk;
+  const int64_t nblk = cdiv(N, 64);
+  int64_t want = 512 / nblk, maxs = K / (2 * TSK_KC);   // two workgroups per CU; at least two steps per split
+  if (want < 1) want = 1;
+  int64_t s = want < maxs ? want : maxs;
+  if (s < 1) s = 1;
+  pl.kchunk = cdiv(cdiv(K, s), TSK_KC) * TSK_KC;
+  pl.ksplit = (int)cdiv(K, pl.kchunk);
+  pl.slab_bytes = pl.ksplit > 1 ? (size_t)pl.ksplit * (size_t)M * (size_t)N * sizeof(float) : 0;
+  pl.bytes = pl.slab_bytes;
+  return true;
+}
+
+static int launch_tsk(const GemmPlan &pl, const GemmArgs &g, void *workspace, size_t workspace_bytes, hipStream_t stream) {
+  TskArgs p;
+  p.A = g.A; p.B = g.B; p.C = g.C; p.lda = g.lda; p.ldb = g.ldb; p.ldc = g.ldc; p.K = g.K; p.M = (int)g.M; p.N = (int)g.N;
+  p.alpha = g.alpha; p.beta = g.beta;
+  p.nsplit = pl.ksplit;
+  p.kchunk = pl.kchunk;
+  p.slab = nullptr;
+  if (p.nsplit > 1) {
+    if (!workspace || workspace_bytes < pl.bytes) return VIVIT_E_WORKSPACE;
+    p.slab = ws_at<float>(workspace, pl.slab_off);
+  }
+  gemm_tsk_kernel<<<dim3((unsigned)p.nsplit, (unsigned)cdiv(g.N, 64)), 256, 0, stream>>>(p);
+  int st = launch_status();
+  if (st != VIVIT_OK || p.nsplit == 1) return st;
+  gemm_tsk_reduce_kernel<<<(unsigned)cdiv(g.M * g.N, 32), 256, 0, stream>>>(p.slab, g.C, g.M * g.N, (int)g.N, g.ldc, p.nsplit,
+                                                                            g.alpha, g.beta);
+  return launch_status();
+}
+
+// ---- Tile128: gemm_kernel, every shape
+// wave grid of the tile: 1 x 4 waves (64 x 256) when the output has at most 64 rows and is wide
+static int pick_wm(int64_t M, int64_t N, bool syrk) { return (!syrk && M <= 64 && N > 128) ? 1 : 2; }
+
+static bool plan_tile128(const GemmShape &sh, GemmPlan &pl) {
+  const int64_t M = sh.M, N = sh.N, K = sh.K;
+  const bool syrk = sh.syrk;
+  pl = GemmPlan{};
+  pl.route = GemmRoute::Tile128;
+  const int wm = pick_wm(M, N, syrk);
+  const int64_t tm = cdiv(M, 64 * wm), tn = cdiv(N, 256 / wm);
+  const int64_t tiles = syrk ? tm * (tm + 1) / 2 : tm * tn;
+  pl.ksplit = 1;
+  pl.kchunk = cdiv(K, BK) * BK;
+  if (pl.kchunk < BK) pl.kchunk = BK;
+  const int64_t ktiles = cdiv(K, BK);
+  // Fill at least ~2 workgroups per CU when the output has few tiles and K is deep; keep every
+  // split at least 32 K tiles long and the slab modest.
+  if (tiles < 256 && ktiles >= 64) {
+    // one resident round (2 workgroups per CU x 256 CUs) for compute-bound shapes; a one-tile-wide
+    // output streams its big operand once and is bandwidth-bound: more, shorter splits keep enough
+    // bytes in flight
+    int64_t want = (tm == 1 || tn == 1) ? 2048 / tiles : 512 / tiles;
+    int64_t maxs = (tm == 1 || tn == 1) ? ktiles / 8 : ktiles / 32;
+    int64_t s = want < maxs ? want : maxs;
+    // a single-tile output (the 64 x 64 Gram blocks of the band reduction's panels: both operands stream 64 rows
+    // x m) has nothing but split-K to spread over the chip (with the slot rotation of map_tile: before it every
+    // split's only valid workgroup sat on XCD 0 and more splits bought nothing); at most 64 splits for any output
+    if (s > 64) s = 64;
+    while (s > 1 && (size_t)s * (size_t)M * (size_t)N * 4 > ((size_t)1 << 30)) --s;
+    if (s > 1) {
+      pl.kchunk = cdiv(ktiles, s) * BK;
+      pl.ksplit = (int)cdiv(K, pl.kchunk);
+    }
+  }
+  pl.slab_bytes = pl.ksplit > 1 ? (size_t)pl.ksplit * (size_t)M * (size_t)N * sizeof(float) : 0;
+  pl.bytes = pl.slab_bytes;
+  return true;
+}
+
+static int launch_tile128(const GemmPlan &pl, const GemmShape &sh, int alay, int blay, GemmArgs p, void *workspace, size_t workspace_bytes,
+                          hipStream_t stream) {
+  p.ksplit = pl.ksplit;
+  p.kchunk = pl.kchunk;
+  p.slab = nullptr;
+  if (p.ksplit > 1) {
+    if (!workspace || workspace_bytes < pl.bytes) return VIVIT_E_WORKSPACE;
+    p.slab = ws_at<float>(workspace, pl.slab_off);
+  }
+  const int wm = pick_wm(p.M, p.N, sh.syrk);
+  p.tiles_m = (int)cdiv(p.M, 64 * wm);
+  p.tiles_n = (int)cdiv(p.N, 256 / wm);
+  p.syrk = sh.syrk ? 1 : 0;
+  p.a_vec = operand_vec(p.A, p.lda);
+  p.b_vec = operand_vec(p.B, p.ldb);
+  p.desc = nullptr;
+  const int64_t nsb = tile_grid(p.tiles_m, p.tiles_n, sh.syrk, &p.sbw);
+  if (nsb < 0) return VIVIT_E_UNSUPPORTED;
+  dim3 grid((unsigned)(nsb * 256), (unsigned)p.ksplit, 1);
+  dim3 block(256, 1, 1);
+  const bool prof = sh.syrk && p.A == p.B && prof_enabled() && sh.pub;  // only the caller's Gram SYRK is profiled as such
+  if (prof) prof_begin(0, (double)p.M * (double)(p.M + 1) * (double)p.K, stream);
+  with_layouts(alay, blay, [&](auto LA, auto LB) {
+    if (wm == 1)
+      gemm_kernel<LA, LB, 1><<<grid, block, 0, stream>>>(p);
+    else
+      gemm_kernel<LA, LB><<<grid, block, 0, stream>>>(p);
+  });
+  if (prof) prof_end(0, stream);
+  int st = launch_status();
+  if (st != VIVIT_OK) return st;
+  if (p.ksplit > 1) {
+    gemm_reduce_kernel<<<(unsigned)cdiv(p.M * p.N, 256), 256, 0, stream>>>(p.slab, p.C, p.M, p.N, p.ldc, p.ksplit, p.alpha,
+                                                                           p.beta, p.syrk);
+    st = launch_status();
+  }
+  return st;
+}
+
+// ---- the two callers of the plans
+size_t gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, bool syrk) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  const GemmShape sh{M, N, K, syrk, syrk, bx_public_product()};
+  GemmShape whole = sh;   // the routes of the 256 tile and the 64-row route take K / BK whole tiles
+  whole.K = K / BK * BK;
+  size_t b = 0;
+  GemmPlan pl;
+  if (plan_tile256_bx(whole, pl) && pl.bytes > b) b = pl.bytes;
+  if (plan_tile256(whole, pl) && pl.bytes > b) b = pl.bytes;
+  if (plan_bx_splitk(whole, pl) && pl.bytes > b) b = pl.bytes;
+  if (plan_gemm64(whole, pl) && pl.bytes > b) b = pl.bytes;
+  if (plan_tsk(sh, pl) && pl.bytes > b) b = pl.bytes;
+  if (plan_tile128(sh, pl) && pl.bytes > b) b = pl.bytes;
+  return b;
+}
+
 int gemm_launch(int alay, int blay, const float *A, const float *B, float *C, int64_t M, int64_t N,
                 int64_t K, int64_t lda, int64_t ldb, int64_t ldc, float alpha, float beta, bool syrk,
                 void *workspace, size_t workspace_bytes, hipStream_t stream) {
@@ -2667,65 +2716,46 @@ int gemm_launch(int alay, int blay, const float *A, const float *B, float *C, in
   p.A = A; p.B = B; p.C = C;
   p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
   p.alpha = alpha; p.beta = beta;
-  {  // the 256-tile kernels (first the plain launch, then the bf16-pipe split-K) take K / BK whole tiles
-    const bool vec = (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (lda & 3) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0 &&
-                     (ldb & 3) == 0 && (alay == LAY_K || (M & 3) == 0) && (blay == LAY_K || (N & 3) == 0);
-    const int64_t Kmain = K / BK * BK;
-    const bool same = A == B && lda == ldb && M == N && alay == blay;
-    const bool on256 = vec && gemm256_plan(M, N, Kmain, syrk, nullptr, nullptr);
-    size_t need = 0;
-    if (on256 || (vec && bx_splitk_shape(M, N, Kmain, syrk, same, nullptr, nullptr, &need) && workspace && workspace_bytes >= need)) {
-      p.K = Kmain;
-      const int st = on256 ? gemm256_launch(alay, blay, p, syrk, workspace, workspace_bytes, stream)
-                           : bx_splitk_launch(alay, blay, p, syrk, workspace, workspace_bytes, stream);
-      if (st != VIVIT_OK || Kmain == K) return st;
+  const GemmShape sh{M, N, K, syrk, A == B && lda == ldb && M == N && alay == blay, bx_public_product()};
+  const bool ptr_vec = operand_vec(A, lda) && operand_vec(B, ldb);
+  const auto holds = [&](const GemmPlan &q) { return workspace && workspace_bytes >= q.bytes; };
+  GemmPlan pl;
+  // the 256-tile kernels take K / BK whole tiles
+  if (ptr_vec && (alay == LAY_K || (M & 3) == 0) && (blay == LAY_K || (N & 3) == 0)) {
+    GemmShape whole = sh;
+    whole.K = p.K = K / BK * BK;
+    bool on256 = true;
+    int st = VIVIT_OK;
+    if (plan_tile256_bx(whole, pl) && holds(pl)) {
+      st = launch_tile256_bx(pl, whole, alay, blay, p, workspace, stream);
+    } else if (plan_tile256(whole, pl)) {
+      // never more splits than the caller's workspace holds (callers size it for their largest problem; the plan
+      // of a smaller one may differ)
+      if (pl.ksplit > 1 && !holds(pl)) {
+        const size_t fit = workspace ? workspace_bytes / ((size_t)M * (size_t)N * sizeof(float)) : 1;
+        plan_tile256(whole, pl, fit < 1 ? 1 : (int)(fit < 4 ? fit : 4));
+      }
+      st = launch_tile256(pl, whole, alay, blay, p, workspace, stream);
+    } else if (plan_bx_splitk(whole, pl) && holds(pl)) {
+      st = launch_bx_splitk(pl, whole, alay, blay, p, workspace, stream);
+    } else {
+      on256 = false;
+      p.K = K;
+    }
+    if (on256) {
+      if (st != VIVIT_OK || whole.K == K) return st;
       // ragged K tail (< 16) through the small-tile kernel, accumulating
-      const float *At = A + (alay == LAY_K ? Kmain : Kmain * lda), *Bt = B + (blay == LAY_K ? Kmain : Kmain * ldb);
-      return gemm_launch(alay, blay, At, Bt, C, M, N, K - Kmain, lda, ldb, ldc, alpha, 1.f, syrk, workspace, workspace_bytes, stream);
+      const float *At = A + (alay == LAY_K ? whole.K : whole.K * lda), *Bt = B + (blay == LAY_K ? whole.K : whole.K * ldb);
+      return gemm_launch(alay, blay, At, Bt, C, M, N, K - whole.K, lda, ldb, ldc, alpha, 1.f, syrk, workspace, workspace_bytes, stream);
     }
   }
-  if (!syrk && use_gemm64(alay, blay, A, B, M, N, K, lda, ldb)) return gemm64_launch(alay, blay, p, workspace, workspace_bytes, stream);
-  if (use_tsk(alay, blay, A, B, M, N, K, lda, ldb, syrk))
-    return tsk_launch(A, B, C, M, N, K, lda, ldb, ldc, alpha, beta, workspace, workspace_bytes, stream);
-  choose_split(M, N, K, syrk, p.ksplit, p.kchunk);
-  p.slab = nullptr;
-  if (p.ksplit > 1) {
-    const size_t need = (size_t)p.ksplit * (size_t)M * (size_t)N * sizeof(float);
-    if (!workspace || workspace_bytes < need) return VIVIT_E_WORKSPACE;
-    p.slab = static_cast<float *>(workspace);
-  }
-  const int wm = pick_wm(M, N, syrk);
-  p.tiles_m = (int)cdiv(M, 64 * wm);
-  p.tiles_n = (int)cdiv(N, 256 / wm);
-  p.syrk = syrk ? 1 : 0;
-  p.a_vec = ((reinterpret_cast<uintptr_t>(A) & 15) == 0 && (lda & 3) == 0) ? 1 : 0;
-  p.b_vec = ((reinterpret_cast<uintptr_t>(B) & 15) == 0 && (ldb & 3) == 0) ? 1 : 0;
-  p.desc = nullptr;
-
-  const int sbw = syrk ? 16 : sb_width(p.tiles_m, p.tiles_n), sbh = 256 / sbw;
-  p.sbw = sbw;
-  const int64_t sbm = cdiv(p.tiles_m, sbh), sbn = cdiv(p.tiles_n, sbw);
-  const int64_t nsb = syrk ? sbm * (sbm + 1) / 2 : sbm * sbn;
-  if (nsb * 256 > 0x7fffffffLL) return VIVIT_E_UNSUPPORTED;
-  dim3 grid((unsigned)(nsb * 256), (unsigned)p.ksplit, 1);
-  dim3 block(256, 1, 1);
-  const bool prof = syrk && A == B && prof_enabled() && bx_public_product();  // only the caller's Gram SYRK is profiled as such
-  if (prof) prof_begin(0, (double)M * (double)(M + 1) * (double)K, stream);
-  with_layouts(alay, blay, [&](auto LA, auto LB) {
-    if (wm == 1)
-      gemm_kernel<LA, LB, 1><<<grid, block, 0, stream>>>(p);
-    else
-      gemm_kernel<LA, LB><<<grid, block, 0, stream>>>(p);
-  });
-  if (prof) prof_end(0, stream);
-  int st = launch_status();
-  if (st != VIVIT_OK) return st;
-  if (p.ksplit > 1) {
-    gemm_reduce_kernel<<<(unsigned)cdiv(M * N, 256), 256, 0, stream>>>(p.slab, C, M, N, ldc, p.ksplit, alpha,
-                                                                       beta, p.syrk);
-    st = launch_status();
-  }
-  return st;
+  if (gemm64_enabled() && ptr_vec && (alay == LAY_K || ((M & 3) == 0 && M >= 4)) && (blay == LAY_K || ((N & 3) == 0 && N >= 4)) &&
+      plan_gemm64(sh, pl))
+    return launch_gemm64(pl, sh, alay, blay, p, workspace, workspace_bytes, stream);
+  if (tsk_enabled() && ptr_vec && alay == LAY_K && blay == LAY_K && plan_tsk(sh, pl))
+    return launch_tsk(pl, p, workspace, workspace_bytes, stream);
+  plan_tile128(sh, pl);
+  return launch_tile128(pl, sh, alay, blay, p, workspace, workspace_bytes, stream);
 }
 
 int gemm_lower_launch(const float *A, const float *B, float *C, int64_t n, int64_t K, int64_t lda, int64_t ldb,
@@ -2741,8 +2771,8 @@ int gemm_lower_launch(const float *A, const float *B, float *C, int64_t n, int64
   p.slab = nullptr;
   p.tiles_m = p.tiles_n = (int)cdiv(n, BM);
   p.syrk = 2;
-  p.a_vec = ((reinterpret_cast<uintptr_t>(A) & 15) == 0 && (lda & 3) == 0) ? 1 : 0;
-  p.b_vec = ((reinterpret_cast<uintptr_t>(B) & 15) == 0 && (ldb & 3) == 0) ? 1 : 0;
+  p.a_vec = operand_vec(A, lda);
+  p.b_vec = operand_vec(B, ldb);
   p.desc = nullptr;
   p.sbw = SB;
   const int64_t sbm = cdiv(p.tiles_m, SB);
@@ -2767,10 +2797,8 @@ int gemm_batched_launch(int alay, int blay, const GemmDesc *desc, int batch, int
   p.syrk = 0;
   p.a_vec = p.b_vec = 0;
   p.desc = desc;
-  const int sbw = sb_width(p.tiles_m, p.tiles_n), sbh = 256 / sbw;
-  p.sbw = sbw;
-  const int64_t nsb = cdiv(p.tiles_m, sbh) * cdiv(p.tiles_n, sbw);
-  if (nsb * 256 > 0x7fffffffLL || batch > 65535) return VIVIT_E_UNSUPPORTED;
+  const int64_t nsb = tile_grid(p.tiles_m, p.tiles_n, false, &p.sbw);
+  if (nsb < 0 || batch > 65535) return VIVIT_E_UNSUPPORTED;
   dim3 grid((unsigned)(nsb * 256), 1, (unsigned)batch);
   with_layouts(alay, blay, [&](auto LA, auto LB) { gemm_kernel<LA, LB><<<grid, 256, 0, stream>>>(p); });
   return launch_status();
@@ -2872,8 +2900,7 @@ int vivit_gram_syrk_f32(const float *A, int64_t n, int64_t p, int64_t lda, float
   float *diag = nullptr;
   if (fix_diag) {
     diag = reinterpret_cast<float *>(align_up(reinterpret_cast<uintptr_t>(workspace), 256));
-    const bool vec = (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (lda & 3) == 0;
-    if (vec) syrk_diag_kernel<true><<<(unsigned)n, 256, 0, s>>>(A, p, lda, G, ldg, alpha, beta, diag);
+    if (operand_vec(A, lda)) syrk_diag_kernel<true><<<(unsigned)n, 256, 0, s>>>(A, p, lda, G, ldg, alpha, beta, diag);
     else syrk_diag_kernel<false><<<(unsigned)n, 256, 0, s>>>(A, p, lda, G, ldg, alpha, beta, diag);
     workspace = reinterpret_cast<char *>(workspace) + syrk_diag_bytes(n);
     workspace_bytes -= syrk_diag_bytes(n);
