@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Generator of the hand-scheduled K loop of gemm256_bx_kernel<6, true> (vivit_amd/csrc/gemm_f32.hip) as an inline-asm block.
+"""Generator of the hand-scheduled K loop of gemm256_bx_kernel<6, true> (vivit_amd/csrc/gemm_tile256_bx.hip) as an inline-asm block.
 
     python scripts/gen_bx_kloop.py            # writes vivit_amd/csrc/bx_kloop_asm.inc (committed: the build never runs this)
 
 VERDICT r03-r05 asked for the loop body in assembly: fixed register map, the global -> LDS requests of a K tile placed by
-hand between the MFMAs.  The block runs `ntiles` K tiles (16 k each) of the pipeline the C++ loop runs (gemm_f32.hip,
+hand between the MFMAs.  The block runs `ntiles` K tiles (16 k each) of the pipeline the C++ loop runs (gemm_tile256_bx.hip,
 "Pipeline (tile t lives in stage t % 3)") and is entered / left in that loop's invariant:
 
     entry: tile t has landed in stage st and is published (every wave is past the barrier that followed its wait), the
@@ -63,7 +63,7 @@ class Emitter:
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# The v_mfma_f32_16x16x32_bf16 form (gemm_f32.hip "S16").  One instruction adds TWO partial products: its K = 32 is the tile's 16 k
+# The v_mfma_f32_16x16x32_bf16 form (gemm_tile256_bx.hip "S16").  One instruction adds TWO partial products: its K = 32 is the tile's 16 k
 # twice, with a different pair of pieces each time (the lanes of k blocks 0, 1 read one piece, those of blocks 2, 3 the other -- the
 # per-lane piece offset is folded into the fragment address the C++ side passes in).  Per 16 x 16 accumulator (rt, ct) and K tile
 # three instructions in this order (smallest terms first; mfma_row of the C++ loop):

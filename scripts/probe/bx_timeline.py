@@ -1,4 +1,4 @@
-"""Per-CU timeline of the bf16-pipe Gram SYRK (diagnostic build scripts/probe/libstamp2.so: scripts/probe/variants.sh gemm_f32 stamp2
+"""Per-CU timeline of the bf16-pipe Gram SYRK (diagnostic build scripts/probe/libstamp2.so: scripts/probe/variants.sh gemm_tile256_bx stamp2
 -DBX_STAMP=2): every workgroup of the last non-mirroring chunk launch stamps s_memrealtime (100 MHz) at entry, at the start and the
 end of its K loop and behind its flush, together with the CU it ran on.  Prints the medians of prologue / K loop / flush and of the
 gap between consecutive workgroups of a CU.   usage: python bx_timeline.py [randn|half]"""

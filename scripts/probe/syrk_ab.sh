@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box timing of the headline-shaped Gram SYRK (n = 40 960, P = 131 072 of N(0,1) and of half-zero data) with the product
-# library and with variant libraries scripts/probe/lib<tag>.so (scripts/probe/variants.sh gemm_f32 <tag> -D...), interleaved.
-#   scripts/probe/variants.sh gemm_f32 stamp2 -DBX_STAMP=2 && scripts/probe/syrk_ab.sh stamp2
+# library and with variant libraries scripts/probe/lib<tag>.so (scripts/probe/variants.sh gemm_tile256_bx <tag> -D...), interleaved.
+#   scripts/probe/variants.sh gemm_tile256_bx stamp2 -DBX_STAMP=2 && scripts/probe/syrk_ab.sh stamp2
 cd "$(dirname "$0")/../.."
 run() { VIVIT_HIP_ALLOW_STALE=1 VIVIT_HIP_LIB=$1 python - <<'PY' 2>&1 | grep -v "amdgpu.ids\|arn"
 import os, sys, time

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Diagnostic builds of one translation unit with extra defines, as separate libraries scripts/probe/lib<tag>.so (select
 # one with VIVIT_HIP_LIB; such a library is not the product's build).  Run on the CPU box (hipcc cross-compiles).
-#   scripts/probe/variants.sh gemm_f32 stamp2 -DBX_STAMP=2
+#   scripts/probe/variants.sh gemm_tile256_bx stamp2 -DBX_STAMP=2
 set -e
 cd "$(dirname "$0")/../.."
 unit=$1; tag=$2; shift 2

@@ -17,7 +17,7 @@ from vivit_amd import kernels  # noqa: E402
 DEV = torch.device("cuda:0")
 LAYOUTS = ("nt", "nn", "tn")
 
-# One shape family per public route, in the order gemm_launch (vivit_amd/csrc/gemm_f32.hip) tries them with the default
+# One shape family per public route, in the order gemm_launch (vivit_amd/csrc/gemm_f32.hip; the routes: gemm_plan.h) tries them with the default
 # VIVIT_GEMM_SPLIT=6.  route -> (the switch that turns it off, or None; cases (layout, M, N, K)).
 ROUTES = {
     # plan_tile256: >= 200 tiles of 256 x 256, M, N >= 512, K >= 512, one split -> bx_split_kernel + gemm256_bx_kernel with

@@ -449,7 +449,7 @@ def run_eig_utils(vivit):
 
 
 # ---- workspace sizes of the GEMM routes (tests/test_gemm_plan_host.py): no reference involved, data recorded from a BUILT
-# libvivit_hip.so -- the one of the commit BEFORE a change to the launch planning of csrc/gemm_f32.hip, so that the change
+# libvivit_hip.so -- the one of the commit BEFORE a change to the launch planning of the GEMM routes (csrc/gemm_plan.h), so that the change
 # can be held to "every query answers what it answered before".  Default environment (no VIVIT_GEMM* switch set).
 def _gemm_workspace_shapes():
     """(m, n, k) of vivit_gemm_f32_workspace_bytes and (n, p) of vivit_gram_syrk_f32_workspace_bytes on both sides of every

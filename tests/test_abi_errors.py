@@ -184,7 +184,7 @@ def test_workspace_one_byte_short_is_refused():
 
 
 def test_gemm_routes_refuse_a_missing_workspace_before_any_device_call():
-    """One shape per GEMM route that refuses (csrc/gemm_f32.hip: the route table; the bf16-pipe routes of the 256 tile fall
+    """One shape per GEMM route that refuses (csrc/gemm_plan.h: the route table; the bf16-pipe routes of the 256 tile fall
     back instead), each needing a slab, each given none: the answer is VIVIT_E_WORKSPACE with or without a device -- a route
     that set kernel attributes or cleared a flag first would answer VIVIT_E_LAUNCH on a box without one."""
     L = lib()

@@ -1,7 +1,7 @@
 """Bit-reproducibility of the hot path (include/vivit_hip.h: "results are deterministic").  The multi-GPU design rests on
 it -- every rank runs the replicated eigensolver stages on the same matrix and nothing is broadcast (DESIGN.md section 6;
 SURVEY.md 8e "deterministic kernel => identical results, no broadcast") -- and the bf16-pipe tile product ends its
-accumulation chains with float atomics (single writer per element; gemm_f32.hip:bx_flush_tiles), so it is tested where
+accumulation chains with float atomics (single writer per element; gemm_tile256_bx.hip:bx_flush_tiles), so it is tested where
 that runs: the 256-tile SYRK at K = 65 552 and at the headline K = 401 408, `gram += gram_p`, the split-K products, the
 band reduction's streaming panel product on the bf16 pipe, the convolution rules of the factor provider, the
 two-stage eigensolver with vectors (persistent band reduction panels, persistent bulge chase, Q2, Q1 on the bf16 pipe) at

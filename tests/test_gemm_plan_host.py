@@ -1,4 +1,4 @@
-"""Workspace queries of the GEMM planner (csrc/gemm_f32.hip: plan_<route>) against a recorded table.  Host only, no device.
+"""Workspace queries of the GEMM planner (csrc/gemm_plan.h: plan_<route>) against a recorded table.  Host only, no device.
 
 tests/golden/gemm_workspace.json holds what vivit_gemm_f32_workspace_bytes(m, n, k) and vivit_gram_syrk_f32_workspace_bytes(n, p)
 answered BEFORE the per-route planners replaced the separately written query, at shapes on both sides of every route boundary

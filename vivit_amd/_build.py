@@ -19,7 +19,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvivit_hip.so")
-SOURCES = ["gemm_f32.hip", "symeig_small.hip", "sytrd.hip", "sytrd_persist.hip", "sy2sb.hip", "sb2st.hip", "q2apply.hip", "q2slide.hip", "stedc.hip", "stein.hip", "symeig_large.hip", "elementwise.hip", "gram_directions.hip", "factors.hip", "jacobians.hip", "norm_rules.hip", "skinny.hip", "profile.hip", "api.hip"]
+SOURCES = ["gemm_tile256.hip", "gemm_tile256_bx.hip", "gemm_tile128.hip", "gemm64.hip", "gemm_tsk.hip", "gemm_f32.hip", "symeig_small.hip", "sytrd.hip", "sytrd_persist.hip", "sy2sb.hip", "sb2st.hip", "q2apply.hip", "q2slide.hip", "stedc.hip", "stein.hip", "symeig_large.hip", "elementwise.hip", "gram_directions.hip", "factors.hip", "jacobians.hip", "norm_rules.hip", "skinny.hip", "profile.hip", "api.hip"]
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function"]
 
 
@@ -95,39 +95,46 @@ def _stamp_stale(obj, stamp):
         return True
 
 
-def build(force=False, verbose=True):
-    """Compile every HIP source to an object, link the shared library. Returns the library path."""
-    headers = _headers()
-    objdir = os.path.join(CSRC, "obj")
+def _compile_stale(objdir, flags, force=False, echo=False):
+    """Compile, in parallel, every source whose object under ``objdir`` is missing or was built from other (source, headers,
+    ``flags``); stamp each object that compiled.  Returns (objs, results): the object path of every source, and
+    (source, succeeded, compiler output) of each one that was compiled."""
     os.makedirs(objdir, exist_ok=True)
-    objs = []
-    procs = []
+    headers = _headers()
+    objs, procs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(o)
-        flags = FLAGS
         stamp = _digest([s] + headers, flags)
         if force or _stamp_stale(o, stamp):
             cmd = [_hipcc()] + flags + ["-c", s, "-o", o]
-            if verbose:
+            if echo:
                 print(" ".join(cmd), flush=True)
             procs.append((src, o, stamp, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
-    failed = False
+    results = []
     for src, o, stamp, p in procs:
         out, _ = p.communicate()
-        if out.strip() and verbose:
-            print(out)
-        if p.returncode != 0:
-            failed = True
-            print(f"hipcc failed on {src}", file=sys.stderr)
-        else:
+        if p.returncode == 0:
             with open(o + ".stamp", "w") as f:
                 f.write(stamp + "\n")
-    if failed:
+        results.append((src, p.returncode == 0, out))
+    return objs, results
+
+
+def build(force=False, verbose=True):
+    """Compile every HIP source to an object, link the shared library. Returns the library path."""
+    objdir = os.path.join(CSRC, "obj")
+    objs, results = _compile_stale(objdir, FLAGS, force, echo=verbose)
+    for src, ok, out in results:
+        if out.strip() and verbose:
+            print(out)
+        if not ok:
+            print(f"hipcc failed on {src}", file=sys.stderr)
+    if not all(ok for _, ok, _ in results):
         raise RuntimeError("hipcc compilation failed")
     info, fresh = _buildinfo_object(objdir, FLAGS)
-    if force or procs or fresh or _stale(LIB, objs):
+    if force or results or fresh or _stale(LIB, objs):
         cmd = [_hipcc(), "-shared", "-fPIC", "--offload-arch=gfx950", "-o", LIB] + objs + [info]
         if verbose:
             print(" ".join(cmd), flush=True)
@@ -151,28 +158,15 @@ def build_host_sanitized(verbose=False):
     source with AddressSanitizer + UndefinedBehaviorSanitizer, for the CPU box: GPU sanitizers are not available on the
     pool.  The result can refuse calls and plan launches; any kernel launch through it fails.  Returns the library path."""
     objdir = os.path.join(CSRC, "obj_asan")
-    os.makedirs(objdir, exist_ok=True)
     flags = ASAN_FLAGS
-    headers = _headers()
-    objs, procs = [], []
-    for src in SOURCES:
-        s = os.path.join(CSRC, src)
-        o = os.path.join(objdir, src.replace(".hip", ".o"))
-        objs.append(o)
-        fl = flags
-        stamp = _digest([s] + headers, fl)
-        if _stamp_stale(o, stamp):
-            procs.append((src, o, stamp, subprocess.Popen([_hipcc()] + fl + ["-c", s, "-o", o], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
-    for src, o, stamp, p in procs:
-        out, _ = p.communicate()
-        if p.returncode != 0:
+    objs, results = _compile_stale(objdir, flags)
+    for src, ok, out in results:
+        if not ok:
             raise RuntimeError(f"hipcc (host sanitizer build) failed on {src}:\n{out}")
-        with open(o + ".stamp", "w") as f:
-            f.write(stamp + "\n")
         if verbose and out.strip():
             print(out)
     info, fresh = _buildinfo_object(objdir, flags)
-    if procs or fresh or _stale(ASAN_LIB, objs):
+    if results or fresh or _stale(ASAN_LIB, objs):
         # a host-only object still refers to its (absent) device fat binary: define each of those symbols as an EMPTY
         # clang offload bundle (magic + zero entries), which the HIP runtime registers and never finds a kernel in
         undef = subprocess.run(["nm", "-u"] + objs, stdout=subprocess.PIPE, text=True).stdout.split()

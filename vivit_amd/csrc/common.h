@@ -63,7 +63,7 @@ struct GemmArgs {
   int gate_mask = 0;
 };
 
-// Generic launcher (gemm_f32.hip).  alay/blay in {LAY_K, LAY_M}.
+// Generic launcher (gemm_f32.hip; the routes behind it: gemm_plan.h).  alay/blay in {LAY_K, LAY_M}.
 int gemm_launch(int alay, int blay, const float *A, const float *B, float *C, int64_t M, int64_t N,
                 int64_t K, int64_t lda, int64_t ldb, int64_t ldc, float alpha, float beta, bool syrk,
                 void *workspace, size_t workspace_bytes, hipStream_t stream);

@@ -9,7 +9,7 @@
 // Block (g, k) touches the 64-column units g + k and g + k + 1, so inside a pass the three-unit window slides LEFT by one
 // unit per group: per two blocks one unit is loaded and one is stored -- a third of the traffic (2.1 TB) -- and the slab
 // never leaves the registers between blocks.  The products run on v_mfma_f32_16x16x32_bf16 with the exact three-way bf16
-// split of both operands and six partial products (the arithmetic of gemm_f32.hip:gemm256_bx_kernel; chains are at most
+// split of both operands and six partial products (the arithmetic of gemm_tile256_bx.hip:gemm256_bx_kernel; chains are at most
 // 128 long here): a wave owns 16 rows, lane (n16, kq) keeps S[row n16][16 q + 4 kq .. + 3] as float4 q = 0..11, and per
 // block
 //     W2^T = (T V) S^T     (A operand: T V tile from LDS,  B operand: the slab, split in registers)
