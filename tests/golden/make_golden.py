@@ -15,6 +15,7 @@ How the reference is made importable:
 
 Usage:  python tests/golden/make_golden.py
         python tests/golden/make_golden.py --gemm-workspace LIB   (gemm_workspace.json only, from the library LIB)
+        python tests/golden/make_golden.py --eig-workspace LIB    (eig_workspace.json only, from the library LIB)
 """
 import os
 import sys
@@ -509,7 +510,78 @@ def gemm_workspace_table(lib_path):
     print("gemm_workspace.json:", len(gemm), "GEMM shapes,", len(syrk), "SYRK shapes")
 
 
+# ---- workspace sizes of the eigensolver entries (tests/test_eig_workspace_host.py): recorded, like the GEMM table, from the
+# BUILT library of the commit before the eigensolver workspaces got one layout function each.  The route switches are read
+# once per process, so every environment is asked in a process of its own.
+EIG_WORKSPACE_ENVS = {"unset": None, "0": "0", "1": "1"}   # VIVIT_TWO_STAGE, each with VIVIT_SYTRD_PERSIST=0
+_EIG_QUERY_ARGS = {"vivit_symeig_f32": 2, "vivit_symeigvals_batched_f32": 2, "vivit_symeig_reduce_f32": 1, "vivit_symeig_select_f32": 2,
+                   "vivit_symeig_select_batched_f32": 3, "vivit_sytrd_f32": 1, "vivit_stedc_f32": 2, "vivit_sy2sb_f32": 1,
+                   "vivit_sy2sb_panel_qr_f32": 1, "vivit_sb2st_f32": 1, "vivit_q2_apply_f32": 1}
+
+
+def _eig_workspace_rows():
+    """[entry, args...] of every public eigensolver query on both sides of every boundary the layouts branch on."""
+    sizes = [128, 129, 192, 193, 200, 300, 512, 1280, 1281, 2047, 2048, 2049, 4095, 4096, 4097, 4100, 8191, 8192, 16383, 16384,
+             40960]
+    rows = []
+    for n in sizes:
+        rows += [["vivit_symeig_f32", n, 0], ["vivit_symeig_f32", n, 1], ["vivit_symeig_reduce_f32", n], ["vivit_sytrd_f32", n],
+                 ["vivit_stedc_f32", n, 0], ["vivit_stedc_f32", n, 1], ["vivit_sy2sb_f32", n], ["vivit_sy2sb_panel_qr_f32", n],
+                 ["vivit_sb2st_f32", n], ["vivit_q2_apply_f32", n]]
+        for K in (1, 256, 257, n):
+            rows.append(["vivit_symeig_select_f32", n, K])
+        for batch in (1, 7, 8, 9):
+            rows.append(["vivit_symeigvals_batched_f32", n, batch])
+            for K in (1, 256, 257, n):
+                rows.append(["vivit_symeig_select_batched_f32", n, batch, K])
+    rows.append(["vivit_sy2sb_panel_qr_f32", 100])
+    return rows
+
+
+def eig_workspace_answers(lib_path, rows):
+    """rows with the library's answer appended (this process's environment)."""
+    import ctypes
+
+    lib = ctypes.CDLL(lib_path)
+    out = []
+    for name, *args in rows:
+        f = getattr(lib, name + "_workspace_bytes")
+        f.restype = ctypes.c_size_t
+        f.argtypes = [ctypes.c_int64] * _EIG_QUERY_ARGS[name]
+        if name in ("vivit_symeig_f32", "vivit_stedc_f32"):
+            f.argtypes = [ctypes.c_int64, ctypes.c_int]
+        out.append([name] + args + [f(*args)])
+    return out
+
+
+def eig_workspace_env(two_stage):
+    env = {k: v for k, v in os.environ.items() if not k.startswith("VIVIT_")}
+    env["VIVIT_SYTRD_PERSIST"] = "0"
+    if two_stage is not None:
+        env["VIVIT_TWO_STAGE"] = two_stage
+    return env
+
+
+def eig_workspace_table(lib_path):
+    import json
+    import subprocess
+
+    table = {}
+    for key, two_stage in EIG_WORKSPACE_ENVS.items():
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--eig-workspace-rows", lib_path], env=eig_workspace_env(two_stage),
+                             stdout=subprocess.PIPE, check=True, text=True).stdout
+        table[key] = json.loads(out.strip().splitlines()[-1])
+    with open(os.path.join(OUT, "eig_workspace.json"), "w") as f:
+        f.write("{\n" + ",\n".join('"%s": [\n%s\n]' % (k, ",\n".join(json.dumps(r) for r in v)) for k, v in table.items()) + "\n}\n")
+    print("eig_workspace.json:", len(table), "environments,", len(table["unset"]), "queries each")
+
+
 def main():
+    if len(sys.argv) == 3 and sys.argv[1] == "--eig-workspace":   # python make_golden.py --eig-workspace path/to/libvivit_hip.so
+        return eig_workspace_table(sys.argv[2])
+    if len(sys.argv) == 3 and sys.argv[1] == "--eig-workspace-rows":   # (the child of --eig-workspace: one environment)
+        import json
+        return print(json.dumps(eig_workspace_answers(sys.argv[2], _eig_workspace_rows())))
     if len(sys.argv) == 3 and sys.argv[1] == "--gemm-workspace":   # python make_golden.py --gemm-workspace path/to/libvivit_hip.so
         return gemm_workspace_table(sys.argv[2])
     vivit = import_reference()

@@ -5,6 +5,45 @@
 
 namespace vivit {
 
+// One workspace, handed out front to back.  Built from (base, bytes) it returns regions; built without memory it only
+// measures, so the function that lays a workspace out is also the one that sizes it.  Regions start on `align` bytes,
+// the first at `base` rounded up.  A region that would end past base + bytes sets overflow(): its pointer is still
+// returned, so every entry point checks the flag after laying out and before its first HIP call.
+class Arena {
+ public:
+  explicit Arena(size_t align = 256) : align_(align) {}
+  Arena(void *base, size_t bytes, size_t align = 256)
+      : align_(align), real_(true), begin_(align_up(reinterpret_cast<uintptr_t>(base), align)), at_(begin_),
+        end_(reinterpret_cast<uintptr_t>(base) + bytes) {
+    overflow_ = at_ > end_;
+  }
+  template <class T> T *take(size_t count) {
+    const uintptr_t r = at_;
+    if (real_ && r + sizeof(T) * count > end_) overflow_ = true;   // (the region itself: the padding behind the last one is not used)
+    at_ += align_up(sizeof(T) * count, align_);
+    return reinterpret_cast<T *>(r);
+  }
+  // the next `bytes` as an arena of their own: the block of a stage that carries its own alignment and slack
+  Arena sub(size_t bytes, size_t align = 256) {
+    Arena s = real_ ? Arena(reinterpret_cast<void *>(at_), bytes, align) : Arena(align);
+    take<char>(bytes);
+    s.overflow_ |= overflow_;
+    return s;
+  }
+  void absorb(const Arena &s) { overflow_ |= s.overflow_; }   // a sub-arena's overflow is this one's too
+  size_t used() const { return at_ - begin_; }
+  size_t left() const { return end_ > at_ ? end_ - at_ : 0; }
+  bool overflow() const { return overflow_; }
+  // position, to hand a finished stage's regions to the next one: p = mark() ... rewind(p)
+  void *mark() const { return reinterpret_cast<void *>(at_); }
+  void rewind(void *m) { at_ = reinterpret_cast<uintptr_t>(m); }
+
+ private:
+  size_t align_;
+  bool real_ = false, overflow_ = false;
+  uintptr_t begin_ = 0, at_ = 0, end_ = 0;
+};
+
 struct SytrdWs {
   float *vw;        // [3*PB][n]: V (PB rows) | W (PB rows) | V again  (so [V;W] and [W;V] are both contiguous)
   float *xbuf;      // [n]
@@ -18,13 +57,18 @@ struct SytrdWs {
   float *d, *e, *tau;
 };
 
-// sytrd.hip
+struct SytrdLayout {
+  SytrdWs ws;
+  float *scanpart;  // [2n] partials of the prescale scan
+};
+
+// sytrd.hip: the block is sytrd_workspace_floats(n) floats, laid out on an arena of 16-byte regions
+SytrdLayout sytrd_layout(Arena &a, int64_t n);
 size_t sytrd_workspace_floats(int64_t n);
-int sytrd_launch(float *A, int64_t n, int64_t lda, float *wsbase, SytrdWs *out, hipStream_t stream);
+int sytrd_launch(float *A, int64_t n, int64_t lda, const SytrdLayout &L, hipStream_t stream);
 // the same for `batch` <= PERSIST_MAX_BATCH matrices of one size with the persistent reduction (sytrd_persist_ok(n), n <= 1280):
-// prescale per problem, then one batched persistent launch (A, wsbase, out: host arrays of `batch`)
-int sytrd_batched_launch(float *const *A, int batch, int64_t n, int64_t lda, float *const *wsbase, SytrdWs *out,
-                         hipStream_t stream);
+// prescale per problem, then one batched persistent launch (A, L: host arrays of `batch`)
+int sytrd_batched_launch(float *const *A, int batch, int64_t n, int64_t lda, const SytrdLayout *L, hipStream_t stream);
 
 // sytrd_persist.hip: the same reduction as one persistent launch on the 32 CUs of one XCD (n <= 1280; after prescale_launch)
 bool sytrd_persist_ok(int64_t n);
@@ -33,9 +77,30 @@ int sytrd_persist_launch(float *A, int64_t n, int64_t lda, const SytrdWs &ws, hi
 constexpr int PERSIST_MAX_BATCH = 8;
 int sytrd_persist_batched_launch(float *const *A, int batch, int64_t n, int64_t lda, const SytrdWs *ws, hipStream_t stream);
 
+struct DcWs {
+  float *dcur, *dnew;   // [n] eigenvalues of the current / next level (physical row order)
+  float *z;             // [n] rank-one vector
+  float *ds, *zs;       // [n] sorted copies (modified by the deflation scan)
+  float *dk, *zk;       // [n] compacted non-deflated poles / weights
+  float *rot;           // [n][4]  (tp, tq) as ints in [0],[1]; c, s in [2],[3]
+  float *rho, *tol;     // [nmerge]
+  float *tnorm;         // [1] norm of the whole tridiagonal matrix (written by the leaves)
+  int *order;           // [n] sorted position -> local physical row
+  int *ndpos, *dfpos;   // [n] sorted positions of the non-deflated / deflated poles, in output order
+  int *kcount, *nrot;   // [nmerge]
+  int *org;             // [n] origin pole of each secular root
+  double *mu, *zhat;    // [n]
+  float **rowptr;       // [n] destination row of each sorted position (after gather)
+  GemmDesc *desc;       // [nmerge]
+  float *Qt0, *Qt1;     // [n][n] eigenvectors (rows), block diagonal per node, ping-pong
+  float *G;             // [n][n] gathered non-deflated rows
+  float *U;             // [n * smax] secular eigenvectors, U_q[j * s + i]
+};
+
 // stedc.hip
+DcWs dc_layout(Arena &a, int64_t n);
 size_t stedc_workspace_bytes(int64_t n, bool vectors);
-int stedc_dc_launch(const float *d, const float *e, int64_t n, void *wsbase, float **Qt_out, float **d_out,
+int stedc_dc_launch(const float *d, const float *e, int64_t n, DcWs ws, float **Qt_out, float **d_out,
                     int **order_scratch, int32_t *info, hipStream_t stream);
 // w[m] = m-th smallest eigenvalue of (d, e) by bisection, divided by scal[1] when scal != nullptr
 // (w64, optional: the same eigenvalues in fp64, NOT divided by the scale)
@@ -46,16 +111,20 @@ int stebz_launch(const float *d, const float *e, int64_t n, float *w, const floa
 int stebz_batched_launch(int batch, int64_t n, const float *const *d, const float *const *e, float *const *w,
                          const float *const *scal, hipStream_t stream, double *const *w64 = nullptr);
 // stein.hip: selected eigenvectors of the tridiagonal (d, e) by inverse iteration, rows of Zt
+struct SteinWs {
+  double *a, *b, *c, *d2, *y;  // [n][Kp]
+  unsigned char *piv;          // [n][Kp]
+  double *span;                // [2]: Gershgorin span, norm bound
+};
+SteinWs stein_layout(Arena &a, int64_t n, int64_t K);
 size_t stein_workspace_bytes(int64_t n, int64_t K);
 int stein_launch(const float *d, const float *e, int64_t n, const double *lam64, const int *sel, int64_t K, float *Zt,
-                 int64_t ldz, void *wsbase, int32_t *info, hipStream_t stream);
+                 int64_t ldz, const SteinWs &ws, int32_t *info, hipStream_t stream);
 // the same for `batch` <= PERSIST_MAX_BATCH tridiagonals of one size n: three launches for all (problem, eigenvalue) pairs.
-// Host arrays of `batch`; K[q] may differ, K[q] = 0 is legal (its other entries are not read); wsbase[q]: stein_workspace_bytes(n, K[q])
+// Host arrays of `batch`; K[q] may differ, K[q] = 0 is legal (its other entries are not read); ws[q]: stein_layout(., n, K[q])
 int stein_batched_launch(int batch, int64_t n, const float *const *d, const float *const *e, const double *const *lam64,
-                         const int *const *sel, const int64_t *K, float *const *Zt, int64_t ldz, void *const *wsbase,
+                         const int *const *sel, const int64_t *K, float *const *Zt, int64_t ldz, const SteinWs *ws,
                          int32_t *const *info, hipStream_t stream);
-// sytrd.hip: pointers into a workspace laid out by sytrd_launch (same base, same n) without launching anything
-void sytrd_layout(float *wsbase, int64_t n, SytrdWs *out);
 // two-phase eigensolver for criterion-selected eigenvectors (symeig_large.hip)
 size_t symeig_reduce_workspace_bytes(int64_t n);
 size_t symeig_select_workspace_bytes(int64_t n, int64_t K);
@@ -76,8 +145,29 @@ int dc_output_launch(int64_t n, const float *dcur, const float *Qt, int64_t ldq,
                      int64_t ldz, const float *scal, int32_t *info, hipStream_t stream);
 
 // sy2sb.hip / sb2st.hip (two-stage tridiagonalisation)
+struct QrPart {
+  float *u;     // [2][nwg][SNB]
+  float *diag;  // [2][SNB]
+};
+
+struct Sy2sbWs {
+  float *pan;      // [n][SNB]   compact copy of the current panel block
+  float *stackA;   // [2*SGRP*SNB][n]  V1 | W1 | V2 | W2 ...  (k-major, ld = n)
+  float *stackB;   // [2*SGRP*SNB][n]  W1 | V1 | W2 | V2 ...
+  float *xt;       // [SNB][n]    scratch (X^T)
+  float *G12;      // [SNB][2*SNB*(SGRP-1)]
+  float *S, *T, *Y3, *S2;  // [SNB*SNB] each
+  float *tau1;     // [n]
+  float *betas;    // [SNB] diagonal of R of the current panel
+  QrPart qp;       // partials of the fused panel QR
+  void *qpw;       // exchange buffers of the persistent panel QR
+  void *gws;       // split-K workspace
+  size_t gws_bytes;
+};
+Sy2sbWs sy2sb_layout(Arena &a, int64_t n);
 size_t sy2sb_workspace_bytes(int64_t n);
-int sy2sb_launch(float *A, int64_t n, int64_t lda, void *wsbase, float **tau1_out, hipStream_t stream);
+// (the reflector scalars are left in ws.tau1)
+int sy2sb_launch(float *A, int64_t n, int64_t lda, const Sy2sbWs &ws, hipStream_t stream);
 // Row stride of the band array INSIDE the library: the 2 NB + 1 = 129 entries of a band row + 3 floats of padding, so that the
 // bulge chase can write a row's [E | D] segment with 16-byte stores (what such a store writes beyond the diagonal entry lands in
 // the padding).  The public entry points (vivit_sy2sb_f32, vivit_sb2st_f32) keep rows of 129.

@@ -27,26 +27,6 @@ __host__ __device__ inline int64_t node_bound(int64_t q, int level, int64_t n, i
   return ((q << level) * n) / nl;  // first row of node q at `level` (level 0 = leaves)
 }
 
-struct DcWs {
-  float *dcur, *dnew;   // [n] eigenvalues of the current / next level (physical row order)
-  float *z;             // [n] rank-one vector
-  float *ds, *zs;       // [n] sorted copies (modified by the deflation scan)
-  float *dk, *zk;       // [n] compacted non-deflated poles / weights
-  float *rot;           // [n][4]  (tp, tq) as ints in [0],[1]; c, s in [2],[3]
-  float *rho, *tol;     // [nmerge]
-  float *tnorm;         // [1] norm of the whole tridiagonal matrix (written by the leaves)
-  int *order;           // [n] sorted position -> local physical row
-  int *ndpos, *dfpos;   // [n] sorted positions of the non-deflated / deflated poles, in output order
-  int *kcount, *nrot;   // [nmerge]
-  int *org;             // [n] origin pole of each secular root
-  double *mu, *zhat;    // [n]
-  float **rowptr;       // [n] destination row of each sorted position (after gather)
-  GemmDesc *desc;       // [nmerge]
-  float *Qt0, *Qt1;     // [n][n] eigenvectors (rows), block diagonal per node, ping-pong
-  float *G;             // [n][n] gathered non-deflated rows
-  float *U;             // [n * smax] secular eigenvectors, U_q[j * s + i]
-};
-
 // ------------------------------------------------------------------------------------------
 // values only: bisection on the Sturm count (thread m finds the m-th smallest eigenvalue)
 // ------------------------------------------------------------------------------------------
@@ -605,66 +585,49 @@ static int dc_num_leaves(int64_t n) {
   return (int)nl;
 }
 
-size_t stedc_workspace_bytes(int64_t n, bool vectors) {
-  if (!vectors) return 256;
+DcWs dc_layout(Arena &a, int64_t n) {
   const int64_t nl = dc_num_leaves(n);
-  size_t b = 0;
-  b += align_up(sizeof(float) * n, 256) * 8;                // dcur dnew z ds zs dk zk + spare
-  b += align_up(sizeof(float) * 4 * n, 256);                // rot
-  b += align_up(sizeof(float) * nl, 256) * 2;               // rho tol
-  b += align_up(sizeof(int) * n, 256) * 4;                  // order org ndpos dfpos
-  b += align_up(sizeof(int) * nl, 256) * 2;                 // kcount nrot
-  b += align_up(sizeof(double) * n, 256) * 2;               // mu zhat
-  b += align_up(sizeof(float *) * n, 256);                  // rowptr
-  b += align_up(sizeof(GemmDesc) * nl, 256);                // desc
-  b += align_up(sizeof(float) * n * n, 256) * 4;            // Qt0 Qt1 G U
-  return b + 1024;
+  DcWs ws;
+  ws.dcur = a.take<float>(n);
+  ws.dnew = a.take<float>(n);
+  ws.z = a.take<float>(n);
+  ws.ds = a.take<float>(n);
+  ws.zs = a.take<float>(n);
+  ws.dk = a.take<float>(n);
+  ws.zk = a.take<float>(n);
+  ws.tnorm = a.take<float>(n);   // (one float of a spare block)
+  ws.rot = a.take<float>(4 * n);
+  ws.rho = a.take<float>(nl);
+  ws.tol = a.take<float>(nl);
+  ws.order = a.take<int>(n);
+  ws.org = a.take<int>(n);
+  ws.ndpos = a.take<int>(n);
+  ws.dfpos = a.take<int>(n);
+  ws.kcount = a.take<int>(nl);
+  ws.nrot = a.take<int>(nl);
+  ws.mu = a.take<double>(n);
+  ws.zhat = a.take<double>(n);
+  ws.rowptr = a.take<float *>(n);
+  ws.desc = a.take<GemmDesc>(nl);
+  ws.Qt0 = a.take<float>(n * n);
+  ws.Qt1 = a.take<float>(n * n);
+  ws.G = a.take<float>(n * n);
+  ws.U = a.take<float>(n * n);
+  return ws;
 }
 
-static DcWs dc_carve(void *base, int64_t n) {
-  const int64_t nl = dc_num_leaves(n);
-  char *p = static_cast<char *>(base);
-  p = reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(p), 256));
-  auto take = [&](size_t bytes) {
-    char *r = p;
-    p += align_up(bytes, 256);
-    return r;
-  };
-  DcWs ws;
-  ws.dcur = (float *)take(sizeof(float) * n);
-  ws.dnew = (float *)take(sizeof(float) * n);
-  ws.z = (float *)take(sizeof(float) * n);
-  ws.ds = (float *)take(sizeof(float) * n);
-  ws.zs = (float *)take(sizeof(float) * n);
-  ws.dk = (float *)take(sizeof(float) * n);
-  ws.zk = (float *)take(sizeof(float) * n);
-  ws.tnorm = (float *)take(sizeof(float) * n);   // (one float of the spare block)
-  ws.rot = (float *)take(sizeof(float) * 4 * n);
-  ws.rho = (float *)take(sizeof(float) * nl);
-  ws.tol = (float *)take(sizeof(float) * nl);
-  ws.order = (int *)take(sizeof(int) * n);
-  ws.org = (int *)take(sizeof(int) * n);
-  ws.ndpos = (int *)take(sizeof(int) * n);
-  ws.dfpos = (int *)take(sizeof(int) * n);
-  ws.kcount = (int *)take(sizeof(int) * nl);
-  ws.nrot = (int *)take(sizeof(int) * nl);
-  ws.mu = (double *)take(sizeof(double) * n);
-  ws.zhat = (double *)take(sizeof(double) * n);
-  ws.rowptr = (float **)take(sizeof(float *) * n);
-  ws.desc = (GemmDesc *)take(sizeof(GemmDesc) * nl);
-  ws.Qt0 = (float *)take(sizeof(float) * n * n);
-  ws.Qt1 = (float *)take(sizeof(float) * n * n);
-  ws.G = (float *)take(sizeof(float) * n * n);
-  ws.U = (float *)take(sizeof(float) * n * n);
-  return ws;
+size_t stedc_workspace_bytes(int64_t n, bool vectors) {
+  if (!vectors) return 256;
+  Arena m;
+  dc_layout(m, n);
+  return m.used() + 1024;
 }
 
 // Divide and conquer.  On return *Qt_out points at the (unsorted, row = eigenvector) matrix and
 // *d_out at the matching eigenvalues, both inside the workspace.
-int stedc_dc_launch(const float *d, const float *e, int64_t n, void *wsbase, float **Qt_out, float **d_out,
+int stedc_dc_launch(const float *d, const float *e, int64_t n, DcWs ws, float **Qt_out, float **d_out,
                     int **order_scratch, int32_t *info, hipStream_t stream) {
   const int nl = dc_num_leaves(n);
-  DcWs ws = dc_carve(wsbase, n);
   const int ni = (int)n;
   const int64_t ldq = n;
   float *Qcur = ws.Qt0, *Qnxt = ws.Qt1;
@@ -807,12 +770,16 @@ int vivit_stedc_f32(float *d, float *e, int64_t n, float *w, float *Z, int64_t l
   if (n > 0 && (!d || !w || (n > 1 && !e) || (Z && ldz < n))) return VIVIT_E_BADARG;
   if (n > 0x7fffffffLL / 4) return VIVIT_E_UNSUPPORTED;
   if (n > 0 && Z && (!workspace || workspace_bytes < stedc_workspace_bytes(n, true))) return VIVIT_E_WORKSPACE;
+  Arena a(workspace, workspace_bytes);
+  DcWs ws = {};
+  if (n > 0 && Z) ws = dc_layout(a, n);
+  if (a.overflow()) return VIVIT_E_WORKSPACE;
   if (hipMemsetAsync(info, 0, sizeof(int32_t), s) != hipSuccess) return VIVIT_E_LAUNCH;
   if (n == 0) return VIVIT_OK;
   if (!Z) return stebz_launch(d, e, n, w, nullptr, s);
   float *Qt, *dd;
   int *order;
-  int st = stedc_dc_launch(d, e, n, workspace, &Qt, &dd, &order, info, s);
+  int st = stedc_dc_launch(d, e, n, ws, &Qt, &dd, &order, info, s);
   if (st != VIVIT_OK) return st;
   return dc_output_launch(n, dd, Qt, n, order, w, Z, ldz, nullptr, info, s);
 }

@@ -16,36 +16,25 @@ namespace vivit {
 constexpr int ST_ITERS = 4;          // inverse-iteration steps (2 would do for isolated eigenvalues)
 constexpr double ST_TIGHT = 1e-9;    // eigenvalues closer than this fraction of the span are orthogonalised explicitly
 
-struct SteinWs {
-  double *a, *b, *c, *d2, *y;  // [n][Kp]
-  unsigned char *piv;          // [n][Kp]
-  double *span;                // [2]: Gershgorin span, norm bound
-};
-
 static inline int64_t stein_kp(int64_t K) { return (K + 63) / 64 * 64; }
 
-size_t stein_workspace_bytes(int64_t n, int64_t K) {
+SteinWs stein_layout(Arena &a, int64_t n, int64_t K) {
   const int64_t Kp = stein_kp(K);
-  return (size_t)align_up(sizeof(double) * n * Kp, 256) * 5 + align_up((size_t)n * Kp, 256) + 256 + 512;
+  SteinWs ws;
+  ws.a = a.take<double>(n * Kp);
+  ws.b = a.take<double>(n * Kp);
+  ws.c = a.take<double>(n * Kp);
+  ws.d2 = a.take<double>(n * Kp);
+  ws.y = a.take<double>(n * Kp);
+  ws.piv = a.take<unsigned char>(n * Kp);
+  ws.span = a.take<double>(256 / sizeof(double));
+  return ws;
 }
 
-static SteinWs stein_carve(void *base, int64_t n, int64_t K) {
-  const int64_t Kp = stein_kp(K);
-  char *p = reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(base), 256));
-  auto take = [&](size_t bytes) {
-    char *r = p;
-    p += align_up(bytes, 256);
-    return r;
-  };
-  SteinWs ws;
-  ws.a = (double *)take(sizeof(double) * n * Kp);
-  ws.b = (double *)take(sizeof(double) * n * Kp);
-  ws.c = (double *)take(sizeof(double) * n * Kp);
-  ws.d2 = (double *)take(sizeof(double) * n * Kp);
-  ws.y = (double *)take(sizeof(double) * n * Kp);
-  ws.piv = (unsigned char *)take((size_t)n * Kp);
-  ws.span = (double *)take(256);
-  return ws;
+size_t stein_workspace_bytes(int64_t n, int64_t K) {
+  Arena m;
+  stein_layout(m, n, K);
+  return m.used() + 512;
 }
 
 // span[0] = Gershgorin span of T, span[1] = max row sum (norm bound); one workgroup
@@ -266,9 +255,9 @@ __global__ __launch_bounds__(256) void stein_finish_batched_kernel(int n, int64_
 }
 
 // Three launches for the whole wave, whatever `batch` is (grids are sized for PERSIST_MAX_BATCH problems and the largest
-// K; slots beyond `batch` carry K = 0).  wsbase[q]: stein_workspace_bytes(n, K[q]) bytes.
+// K; slots beyond `batch` carry K = 0).  ws[q]: stein_layout(., n, K[q]).
 int stein_batched_launch(int batch, int64_t n, const float *const *d, const float *const *e, const double *const *lam64,
-                         const int *const *sel, const int64_t *K, float *const *Zt, int64_t ldz, void *const *wsbase,
+                         const int *const *sel, const int64_t *K, float *const *Zt, int64_t ldz, const SteinWs *ws,
                          int32_t *const *info, hipStream_t stream) {
   if (batch < 1 || batch > PERSIST_MAX_BATCH) return VIVIT_E_UNSUPPORTED;
   SteinBatch sb = {};
@@ -278,7 +267,7 @@ int stein_batched_launch(int batch, int64_t n, const float *const *d, const floa
     SteinProblem &p = sb.p[q];
     p.d = d[q]; p.e = e[q]; p.lam64 = lam64[q]; p.sel = sel[q];
     p.K = (int)K[q]; p.Kp = (int)stein_kp(K[q]);
-    p.ws = stein_carve(wsbase[q], n, K[q]);
+    p.ws = ws[q];
     p.Zt = Zt[q]; p.info = info[q];
     if (K[q] > kmax) kmax = K[q];
   }
@@ -292,9 +281,8 @@ int stein_batched_launch(int batch, int64_t n, const float *const *d, const floa
 // Zt[k][:] (k < K, ld ldz) = unit eigenvector of the tridiagonal (d, e) for the eigenvalue lam64[sel[k]].
 // sel: device int32 [K], strictly ascending positions in the ascending eigenvalue list lam64 [n] (fp64).
 int stein_launch(const float *d, const float *e, int64_t n, const double *lam64, const int *sel, int64_t K, float *Zt,
-                 int64_t ldz, void *wsbase, int32_t *info, hipStream_t stream) {
+                 int64_t ldz, const SteinWs &ws, int32_t *info, hipStream_t stream) {
   if (K <= 0) return VIVIT_OK;
-  SteinWs ws = stein_carve(wsbase, n, K);
   const int Kp = (int)stein_kp(K);
   stein_span_kernel<<<1, 256, 0, stream>>>(d, e, (int)n, ws.span);
   stein_iterate_kernel<<<(unsigned)cdiv(K, 64), 64, 0, stream>>>(d, e, (int)n, lam64, sel, (int)K, Kp, ws, info);

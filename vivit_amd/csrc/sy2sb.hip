@@ -32,26 +32,6 @@ constexpr int SGRP = 8;     // panels per delayed trailing-matrix update (measur
                             // P^T corrections: 4 -> 1.127 s, 6 -> 1.122, 8 -> 1.094 (other box: 8 -> 1.113, 12 -> 1.117,
                             // 16 -> 1.134): the rank-1024 update spends a fifth instead of a third of a tile on C)
 
-struct QrPart {
-  float *u;     // [2][nwg][SNB]
-  float *diag;  // [2][SNB]
-};
-
-struct Sy2sbWs {
-  float *pan;      // [n][SNB]   compact copy of the current panel block
-  float *stackA;   // [2*SGRP*SNB][n]  V1 | W1 | V2 | W2 ...  (k-major, ld = n)
-  float *stackB;   // [2*SGRP*SNB][n]  W1 | V1 | W2 | V2 ...
-  float *xt;       // [SNB][n]    scratch (X^T)
-  float *G12;      // [SNB][2*SNB*(SGRP-1)]
-  float *S, *T, *Y3, *S2;  // [SNB*SNB] each
-  float *tau1;     // [n]
-  float *betas;    // [SNB] diagonal of R of the current panel
-  QrPart qp;       // partials of the fused panel QR
-  void *qpw;       // exchange buffers of the persistent panel QR
-  void *gws;       // split-K workspace
-  size_t gws_bytes;
-};
-
 __global__ __launch_bounds__(256) void sb_panel_load_kernel(const float *__restrict__ A, int64_t lda, int64_t j0, int64_t mp,
                                                             float *__restrict__ pan) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -736,51 +716,36 @@ static size_t sy2sb_gemm_ws_bytes(int64_t n) {
   return m * 2;  // generous: shapes between the sampled mp values
 }
 
-size_t sy2sb_workspace_bytes(int64_t n) {
-  const int64_t nwg = cdiv(n, QT) + 1;
-  size_t b = 0;
-  b += align_up(sizeof(float) * n * SNB, 256);          // pan
-  b += align_up(sizeof(float) * 2 * SGRP * SNB * n, 256) * 2;  // stackA, stackB
-  b += align_up(sizeof(float) * SNB * n, 256);          // xt
-  b += align_up(sizeof(float) * SNB * 2 * SNB * SGRP, 256);    // G12
-  b += align_up(sizeof(float) * 2 * nwg * SNB, 256);    // QR partials u (double-buffered)
-  b += align_up(sizeof(float) * 2 * SNB, 256);          // QR diagonal row
-  b += align_up(QR_PERSIST_WS_BYTES, 256);              // persistent panel QR
-  b += align_up(sizeof(float) * SNB * SNB, 256) * 4;    // S T Y3 S2
-  b += align_up(sizeof(float) * n, 256);                // tau1
-  b += align_up(sizeof(float) * SNB, 256);              // betas
-  b += align_up(sy2sb_gemm_ws_bytes(n), 256);
-  return b + 1024;
-}
-
-// Reduce A (n x n, FULL symmetric storage, lda) to band form in place.  tau1_out receives the pointer
-// to the reflector scalars (inside the workspace).
-int sy2sb_launch(float *A, int64_t n, int64_t lda, void *wsbase, float **tau1_out, hipStream_t stream) {
-  char *p = reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(wsbase), 256));
-  auto take = [&](size_t bytes) {
-    char *r = p;
-    p += align_up(bytes, 256);
-    return r;
-  };
+Sy2sbWs sy2sb_layout(Arena &a, int64_t n) {
   const int64_t nwg = cdiv(n, QT) + 1;
   Sy2sbWs ws;
-  ws.pan = (float *)take(sizeof(float) * n * SNB);
-  ws.stackA = (float *)take(sizeof(float) * 2 * SGRP * SNB * n);
-  ws.stackB = (float *)take(sizeof(float) * 2 * SGRP * SNB * n);
-  ws.xt = (float *)take(sizeof(float) * SNB * n);
-  ws.G12 = (float *)take(sizeof(float) * SNB * 2 * SNB * SGRP);
-  ws.qp.u = (float *)take(sizeof(float) * 2 * nwg * SNB);
-  ws.qp.diag = (float *)take(sizeof(float) * 2 * SNB);
-  ws.qpw = take(QR_PERSIST_WS_BYTES);
-  ws.S = (float *)take(sizeof(float) * SNB * SNB);
-  ws.T = (float *)take(sizeof(float) * SNB * SNB);
-  ws.Y3 = (float *)take(sizeof(float) * SNB * SNB);
-  ws.S2 = (float *)take(sizeof(float) * SNB * SNB);
-  ws.tau1 = (float *)take(sizeof(float) * n);
-  ws.betas = (float *)take(sizeof(float) * SNB);
+  ws.pan = a.take<float>(n * SNB);
+  ws.stackA = a.take<float>(2 * SGRP * SNB * n);
+  ws.stackB = a.take<float>(2 * SGRP * SNB * n);
+  ws.xt = a.take<float>(SNB * n);
+  ws.G12 = a.take<float>(SNB * 2 * SNB * SGRP);
+  ws.qp.u = a.take<float>(2 * nwg * SNB);   // QR partials (double-buffered)
+  ws.qp.diag = a.take<float>(2 * SNB);      // QR diagonal row
+  ws.qpw = a.take<char>(QR_PERSIST_WS_BYTES);
+  ws.S = a.take<float>(SNB * SNB);
+  ws.T = a.take<float>(SNB * SNB);
+  ws.Y3 = a.take<float>(SNB * SNB);
+  ws.S2 = a.take<float>(SNB * SNB);
+  ws.tau1 = a.take<float>(n);
+  ws.betas = a.take<float>(SNB);
   ws.gws_bytes = sy2sb_gemm_ws_bytes(n);
-  ws.gws = take(ws.gws_bytes);
-  *tau1_out = ws.tau1;
+  ws.gws = a.take<char>(ws.gws_bytes);
+  return ws;
+}
+
+size_t sy2sb_workspace_bytes(int64_t n) {
+  Arena m;
+  sy2sb_layout(m, n);
+  return m.used() + 1024;
+}
+
+// Reduce A (n x n, FULL symmetric storage, lda) to band form in place.  The reflector scalars are left in ws.tau1.
+int sy2sb_launch(float *A, int64_t n, int64_t lda, const Sy2sbWs &ws, hipStream_t stream) {
   if (hipMemsetAsync(ws.tau1, 0, sizeof(float) * n, stream) != hipSuccess) return VIVIT_E_LAUNCH;
 
   const int64_t ldn = n;
@@ -903,29 +868,41 @@ int sy2sb_launch(float *A, int64_t n, int64_t lda, void *wsbase, float **tau1_ou
 // the broadcast panel itself, the trailing matrix is sharded).  pan: [mp][SNB] row-major, factored in place (R above the
 // diagonal of its first SNB rows, diagonal in betas); Vt: [SNB][ldv] k-major reflectors (row c = v_c, v_c[c] = 1, zeros
 // before); tau: [SNB]; T: [SNB][SNB] upper triangular, Q = I - V T V^T.
-size_t sy2sb_panel_qr_workspace_bytes(int64_t mp) {
+struct PanelQrWs {
+  QrPart qp;
+  float *S;
+  void *qpw, *gws;
+  size_t gws_bytes;
+};
+
+static PanelQrWs panel_qr_layout(Arena &a, int64_t mp) {
   const int64_t nwg = cdiv(mp, QT) + 1;
-  return align_up(sizeof(float) * 2 * nwg * SNB, 256) + align_up(sizeof(float) * 2 * SNB, 256) + align_up(sizeof(float) * SNB * SNB, 256) +
-         align_up(QR_PERSIST_WS_BYTES, 256) + align_up(gemm_workspace_bytes(SNB, SNB, mp, false), 256) + 1024;
+  PanelQrWs ws;
+  ws.qp.u = a.take<float>(2 * nwg * SNB);
+  ws.qp.diag = a.take<float>(2 * SNB);
+  ws.S = a.take<float>(SNB * SNB);
+  ws.qpw = a.take<char>(QR_PERSIST_WS_BYTES);
+  ws.gws_bytes = gemm_workspace_bytes(SNB, SNB, mp, false);
+  ws.gws = a.take<char>(ws.gws_bytes);
+  return ws;
+}
+
+size_t sy2sb_panel_qr_workspace_bytes(int64_t mp) {
+  Arena m;
+  panel_qr_layout(m, mp);
+  return m.used() + 1024;
 }
 
 int sy2sb_panel_qr_launch(float *pan, int64_t mp, float *Vt, int64_t ldv, float *tau, float *betas, float *T, void *wsbase,
                           size_t ws_bytes, hipStream_t stream) {
   if (ws_bytes < sy2sb_panel_qr_workspace_bytes(mp)) return VIVIT_E_WORKSPACE;
-  char *p = reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(wsbase), 256));
-  auto take = [&](size_t bytes) {
-    char *r = p;
-    p += align_up(bytes, 256);
-    return r;
-  };
-  const int64_t nwg = cdiv(mp, QT) + 1;
-  QrPart qp;
-  qp.u = (float *)take(sizeof(float) * 2 * nwg * SNB);
-  qp.diag = (float *)take(sizeof(float) * 2 * SNB);
-  float *S = (float *)take(sizeof(float) * SNB * SNB);
-  void *qpw = take(QR_PERSIST_WS_BYTES);
-  const size_t gws_bytes = gemm_workspace_bytes(SNB, SNB, mp, false);
-  void *gws = take(gws_bytes);
+  Arena a(wsbase, ws_bytes);
+  const PanelQrWs ws = panel_qr_layout(a, mp);
+  if (a.overflow()) return VIVIT_E_WORKSPACE;
+  const QrPart qp = ws.qp;
+  float *S = ws.S;
+  void *qpw = ws.qpw, *gws = ws.gws;
+  const size_t gws_bytes = ws.gws_bytes;
   const int ncol = (int)(mp < SNB ? mp : SNB);
   const int g = (int)cdiv(mp, QT);
   if (hipMemsetAsync(tau, 0, sizeof(float) * SNB, stream) != hipSuccess) return VIVIT_E_LAUNCH;
@@ -961,12 +938,14 @@ int vivit_sy2sb_f32(float *A, int64_t n, int64_t lda, float *AB, float *tau1, vo
   if (n < 1 || !A || !AB || !tau1 || lda < n) return VIVIT_E_BADARG;
   if (!workspace || workspace_bytes < sy2sb_workspace_bytes(n)) return VIVIT_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  float *t1;
-  int st = sy2sb_launch(A, n, lda, workspace, &t1, s);
+  Arena a(workspace, workspace_bytes);
+  const Sy2sbWs ws = sy2sb_layout(a, n);
+  if (a.overflow()) return VIVIT_E_WORKSPACE;
+  int st = sy2sb_launch(A, n, lda, ws, s);
   if (st != VIVIT_OK) return st;
   st = sy2sb_extract_band_launch(A, lda, n, AB, 2 * SNB + 1, s);
   if (st != VIVIT_OK) return st;
-  if (hipMemcpyAsync(tau1, t1, sizeof(float) * n, hipMemcpyDeviceToDevice, s) != hipSuccess) return VIVIT_E_LAUNCH;
+  if (hipMemcpyAsync(tau1, ws.tau1, sizeof(float) * n, hipMemcpyDeviceToDevice, s) != hipSuccess) return VIVIT_E_LAUNCH;
   return VIVIT_OK;
 }
 

@@ -103,35 +103,48 @@ static size_t bt_gemm_ws_bytes(int64_t n) {
   return b > bound ? b : bound;
 }
 
-static size_t bt_workspace_bytes(int64_t n) {
+struct BtWs {
+  float *Yt, *W1, *W2;   // [KS][n], [n][KS] x 2
+  float *S, *T, *X;      // [KS][KS]
+  GemmDesc *mdesc;       // merge-tree descriptors
+  void *gws;
+  size_t gws_bytes;
+};
+
+// (sized for the largest super-block, bt_nsub(n), whatever bt_nsub_rows picks for a call)
+static BtWs bt_layout(Arena &a, int64_t n) {
   const int64_t KS = (int64_t)KB * bt_nsub(n);
-  size_t b = 0;
-  b += align_up(sizeof(float) * KS * n, 256);      // Yt
-  b += align_up(sizeof(float) * n * KS, 256) * 2;  // W1, W2
-  b += align_up(sizeof(float) * KS * KS, 256) * 3; // S, T, X
-  b += align_up(sizeof(GemmDesc) * BT_MAX_DESC, 256);   // merge-tree descriptors
-  b += align_up(bt_gemm_ws_bytes(n), 256);
-  return b + 512;
+  BtWs ws;
+  ws.Yt = a.take<float>(KS * n);
+  ws.W1 = a.take<float>(n * KS);
+  ws.W2 = a.take<float>(n * KS);
+  ws.S = a.take<float>(KS * KS);
+  ws.T = a.take<float>(KS * KS);
+  ws.X = a.take<float>(KS * KS);
+  ws.mdesc = a.take<GemmDesc>(BT_MAX_DESC);
+  ws.gws_bytes = bt_gemm_ws_bytes(n);
+  ws.gws = a.take<char>(ws.gws_bytes);
+  return ws;
+}
+
+static size_t bt_workspace_bytes(int64_t n) {
+  Arena m;
+  bt_layout(m, n);
+  return m.used() + 512;
 }
 
 // Zt[nrows x n] (ld ldq) <- Zt * Q^T for Q = H_0 H_1 ... (reflector j in row j of A, support i >= j + shift,
 // j <= jmax), compact-WY super-blocks, last one first.  Every row is transformed independently (nrows = n for
 // the full eigenvector matrix, a slice of the rows when the back-transformation is sharded over GPUs).
-template <class Take>
 static int backtransform_launch(const float *A, int64_t n, int64_t lda, const float *tau, int shift, int64_t jmax,
-                                float *Qt, int64_t ldq, int64_t nrows, Take &take, hipStream_t stream) {
+                                float *Qt, int64_t ldq, int64_t nrows, const BtWs &ws, hipStream_t stream) {
   const int ni = (int)n;
   const int nsub = bt_nsub_rows(n, nrows);
-  const int64_t KS = (int64_t)KB * nsub, KSmax = (int64_t)KB * bt_nsub(n);   // (buffers are carved for the largest)
-  float *Yt = (float *)take(sizeof(float) * KSmax * n);
-  float *W1 = (float *)take(sizeof(float) * n * KSmax);
-  float *W2 = (float *)take(sizeof(float) * n * KSmax);
-  float *S = (float *)take(sizeof(float) * KSmax * KSmax);
-  float *T = (float *)take(sizeof(float) * KSmax * KSmax);
-  float *X = (float *)take(sizeof(float) * KSmax * KSmax);
-  GemmDesc *mdesc = (GemmDesc *)take(sizeof(GemmDesc) * BT_MAX_DESC);
-  const size_t gws_bytes = bt_gemm_ws_bytes(n);
-  void *gws = take(gws_bytes);
+  const int64_t KS = (int64_t)KB * nsub;
+  float *const Yt = ws.Yt, *const W1 = ws.W1, *const W2 = ws.W2, *const S = ws.S, *const T = ws.T, *const X = ws.X;
+  GemmDesc *const mdesc = ws.mdesc;
+  void *const gws = ws.gws;
+  const size_t gws_bytes = ws.gws_bytes;
   if (jmax < 0 || nrows <= 0) return VIVIT_OK;
   static unsigned long long tf_done = 0;
   {
@@ -185,209 +198,222 @@ static int backtransform_launch(const float *A, int64_t n, int64_t lda, const fl
 // ---- two-stage reduction (sy2sb + sb2st) --------------------------------------------------------
 constexpr int TS_NB = 64;
 
-// 1 = use the two-stage tridiagonalisation.  Values-only solves switch at n >= 2048 (the band
-// reduction is MFMA-bound, the one-stage reduction HBM-bound; 53.1 / 53.6 ms at the crossover).  With eigenvectors the
-// second back-transformation (Q2, q2apply.hip) has to be paid for: measured at the end of round 2 (one-stage /
-// two-stage, ms) n = 2048: 58 / 63, 3072: 92 / 95, 4096: 137 / 130, 6144: 259 / 199, 8192: 420 / 272, 40960: 16400 / 4500
-// (round 1 had the crossover at 8192: bulge chasing, band reduction and Q2 have since become 1.5-2x faster).
-// VIVIT_TWO_STAGE=0/1 overrides.
-static bool use_two_stage(int64_t n, bool vectors) {
+// 1 = use the two-stage tridiagonalisation, with or without eigenvectors: where the persistent one-stage reduction
+// applies (sytrd_persist_ok, n <= 2048) it wins (n = 2048: 24.9 / 31.1 ms against 37 / ~47 for the two stages), above
+// it the two stages do (one-stage chain / two-stage, ms, eigvalsh | symeig: n = 2304: 61 / 43 | 65 / 52, 4096: 129 / 79
+// | 136 / 96 -- scripts/probe/crossover2.py; earlier crossovers: profiles/HISTORY.md).  VIVIT_TWO_STAGE=0/1 overrides.
+static bool use_two_stage(int64_t n) {
   static int forced = -2;
   if (forced == -2) {
     const char *e = getenv("VIVIT_TWO_STAGE");
     forced = e ? atoi(e) : -1;
   }
   if (forced >= 0) return forced != 0 && n > 2 * TS_NB;
-  (void)vectors;
-  // Round 3: the persistent one-stage reduction (n <= 2048) beats the two stages with and without vectors (n = 2048: 24.9 /
-  // 31.1 ms against 37 / ~47); above it the two stages win everywhere now that their launch chains are persistent kernels
-  // (one-stage chain / two-stage, ms, eigvalsh | symeig: n = 2304: 61 / 43 | 65 / 52, 3072: 85 / 58 | 91 / 72, 4096: 129 / 79 |
-  // 136 / 96 -- scripts/probe/crossover2.py).
   if (sytrd_persist_ok(n)) return false;
   return n >= 2048;
 }
 
+// What the users of the two-stage front half differ in.
+struct TsMode {
+  bool band_here;   // prescale, mirror and band reduction run here (false: the caller did them and gives tau1 and scal)
+  bool keep_q2;     // R2 of n rows and tau2 cleared, for the Q2 back-transformation (false: the ring of a values-only solve)
+  bool own_tau1;    // tau1 copied out of the band reduction's block (the reduce phase keeps it in its state)
+};
+constexpr TsMode TS_VALUES = {true, false, false}, TS_VECTORS = {true, true, false}, TS_STATE = {true, true, true},
+                 TS_BANDED = {false, true, false};
+
+struct TwoStageWs {
+  TsMode mode;
+  float *scal, *part;   // scaling record [16], scan partials [2n]
+  Sy2sbWs sb;
+  float *AB, *R2, *tau2, *tau1, *d, *e;
+  int64_t r2rows;
+};
+
+static TwoStageWs two_stage_layout(Arena &a, int64_t n, TsMode m) {
+  TwoStageWs L = {};
+  L.mode = m;
+  L.scal = a.take<float>(16);
+  if (m.band_here) {
+    L.part = a.take<float>(2 * n);
+    Arena s = a.sub(sy2sb_workspace_bytes(n));
+    L.sb = sy2sb_layout(s, n);
+    a.absorb(s);
+    L.tau1 = L.sb.tau1;
+  }
+  L.AB = a.take<float>(n * SB2ST_LDP);
+  L.r2rows = m.keep_q2 ? n : sb2st_ring_rows(n);
+  L.R2 = a.take<float>(L.r2rows * n);
+  L.tau2 = a.take<float>(n * sb2st_num_levels(n));
+  if (m.own_tau1) L.tau1 = a.take<float>(n);
+  L.d = a.take<float>(n);
+  L.e = a.take<float>(n);
+  return L;
+}
+
+// [prescale -> mirror -> band] -> band extract -> tridiagonal (d, e; the Q2 reflectors in R2, tau2 when they are kept)
+static int two_stage_reduce(float *A, int64_t n, int64_t lda, const TwoStageWs &L, hipStream_t stream) {
+  prof_mark(PROF_STAGE_BEGIN, stream);
+  int st;
+  if (L.mode.band_here) {
+    st = prescale_launch(A, n, lda, L.scal, L.part, stream);
+    if (st != VIVIT_OK) return st;
+    st = symmetrize_launch(A, n, lda, stream);
+    if (st != VIVIT_OK) return st;
+    prof_mark(PROF_STAGE_PREP, stream);
+    st = sy2sb_launch(A, n, lda, L.sb, stream);
+    if (st != VIVIT_OK) return st;
+    if (L.mode.own_tau1 && hipMemcpyAsync(L.tau1, L.sb.tau1, sizeof(float) * n, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+      return VIVIT_E_LAUNCH;
+  }
+  st = sy2sb_extract_band_launch(A, lda, n, L.AB, SB2ST_LDP, stream);
+  if (st != VIVIT_OK) return st;
+  prof_mark(PROF_STAGE_SY2SB, stream);
+  if (L.mode.keep_q2 && hipMemsetAsync(L.tau2, 0, sizeof(float) * n * sb2st_num_levels(n), stream) != hipSuccess)
+    return VIVIT_E_LAUNCH;
+  st = sb2st_launch(L.AB, n, L.d, L.e, L.R2, n, L.r2rows, L.tau2, stream);
+  if (st != VIVIT_OK) return st;
+  prof_mark(PROF_STAGE_SB2ST, stream);
+  return VIVIT_OK;
+}
+
+// ---- one-stage reduction: the sytrd block on 16-byte regions inside the 256-byte ones of its caller
+static SytrdLayout one_stage_layout(Arena &a, int64_t n) {
+  Arena s = a.sub(sizeof(float) * sytrd_workspace_floats(n), 16);
+  const SytrdLayout L = sytrd_layout(s, n);
+  a.absorb(s);
+  return L;
+}
+
+static int one_stage_reduce(float *A, int64_t n, int64_t lda, const SytrdLayout &L, hipStream_t stream) {
+  prof_mark(PROF_STAGE_BEGIN, stream);
+  const int st = sytrd_launch(A, n, lda, L, stream);
+  if (st != VIVIT_OK) return st;
+  prof_mark(PROF_STAGE_SYTRD, stream);
+  return VIVIT_OK;
+}
+
+static size_t one_stage_workspace_bytes(int64_t n) {
+  Arena m;
+  one_stage_layout(m, n);
+  return m.used() + 512;
+}
+
 static size_t two_stage_workspace_bytes(int64_t n, bool vectors) {
-  size_t b = 0;
-  b += align_up(sizeof(float) * 16, 256) + align_up(sizeof(float) * 2 * n, 256);       // scal, scan partials
-  b += align_up(sy2sb_workspace_bytes(n), 256);
-  b += align_up(sizeof(float) * n * SB2ST_LDP, 256);                              // AB
-  b += align_up(sizeof(float) * (vectors ? n : sb2st_ring_rows(n)) * n, 256);           // R2
-  b += align_up(sizeof(float) * n * sb2st_num_levels(n), 256);                          // tau2
-  b += align_up(sizeof(float) * n, 256) * 2;                                            // d, e
-  return b + 1024;
+  Arena m;
+  two_stage_layout(m, n, vectors ? TS_VECTORS : TS_VALUES);
+  return m.used() + 1024;
+}
+
+// What either reduction leaves for the rest of a solve: the tridiagonal, the scaling record and the reflectors
+// (those of sytrd / sy2sb are in A, scalars tau1; R2 != nullptr: two-stage, the bulge-chasing reflectors).
+struct Reduced {
+  const float *d, *e, *scal, *tau1, *R2, *tau2;
+};
+static Reduced reduced_of(const TwoStageWs &L) { return {L.d, L.e, L.scal, L.tau1, L.R2, L.tau2}; }
+static Reduced reduced_of(const SytrdLayout &L) { return {L.ws.d, L.ws.e, L.ws.scal, L.ws.tau, nullptr, nullptr}; }
+
+// Zt[nrows x n] <- Zt Q2^T (two-stage only) Q1^T
+static int back_transform_rows(const float *A, int64_t n, int64_t lda, const Reduced &R, float *Zt, int64_t ldz, int64_t nrows,
+                               void *q2ws, const BtWs &bt, hipStream_t stream) {
+  int st;
+  if (R.R2) {
+    st = q2_apply_launch(Zt, ldz, nrows, n, R.R2, n, R.tau2, q2ws, stream);
+    if (st != VIVIT_OK) return st;
+    prof_mark(PROF_STAGE_Q2, stream);
+    st = backtransform_launch(A, n, lda, R.tau1, TS_NB, n - TS_NB - 1, Zt, ldz, nrows, bt, stream);
+  } else {
+    st = backtransform_launch(A, n, lda, R.tau1, 1, n - 3, Zt, ldz, nrows, bt, stream);
+  }
+  if (st != VIVIT_OK) return st;
+  prof_mark(PROF_STAGE_Q1, stream);
+  return VIVIT_OK;
+}
+
+// ---- the back half of a solve with eigenvectors: divide & conquer, then the back-transformations
+struct BackWs {
+  DcWs dc;
+  void *q2ws;
+  BtWs bt;
+};
+
+static BackWs back_layout(Arena &a, int64_t n, bool two_stage) {
+  BackWs B;
+  Arena s = a.sub(stedc_workspace_bytes(n, true));
+  B.dc = dc_layout(s, n);
+  a.absorb(s);
+  B.q2ws = two_stage ? a.take<char>(q2_workspace_bytes(n, n)) : nullptr;
+  B.bt = bt_layout(a, n);
+  return B;
+}
+
+// T = Q_T diag(w) Q_T^T by divide and conquer (Qt = Q_T^T, rows unsorted), then Zt = Qt Q2^T Q1^T on the rows of Qt.
+// r1 < 0: all of them, Z = column eigenvectors.  Rows mode (r1 >= 0): Z receives the eigenvectors r0 .. r1-1 (ascending
+// eigenvalue order) as ROWS, [r1-r0][ldz], and only those rows are back-transformed (rows of Zt are independent: this is
+// what the multi-GPU path shards).
+static int eigvec_back_half(const float *A, int64_t n, int64_t lda, const Reduced &R, const BackWs &B, float *w, float *Z,
+                            int64_t ldz, int64_t r0, int64_t r1, int32_t *info, hipStream_t stream) {
+  float *Qt, *dd;
+  int *order;
+  int st = stedc_dc_launch(R.d, R.e, n, B.dc, &Qt, &dd, &order, info, stream);
+  if (st != VIVIT_OK) return st;
+  if (r1 >= 0) {
+    st = dc_rows_launch(n, dd, Qt, n, order, w, Z, ldz, r0, r1, R.scal, stream);
+    if (st != VIVIT_OK) return st;
+    prof_mark(PROF_STAGE_TRIDIAG, stream);
+    st = back_transform_rows(A, n, lda, R, Z, ldz, r1 - r0, B.q2ws, B.bt, stream);
+    if (st != VIVIT_OK) return st;
+    return info_scal_launch(info, n, R.scal, stream);
+  }
+  prof_mark(PROF_STAGE_TRIDIAG, stream);
+  st = back_transform_rows(A, n, lda, R, Qt, n, n, B.q2ws, B.bt, stream);
+  if (st != VIVIT_OK) return st;
+  // sort ascending, undo the scaling, deliver column eigenvectors
+  st = dc_output_launch(n, dd, Qt, n, order, w, Z, ldz, R.scal, info, stream);
+  prof_mark(PROF_STAGE_OUTPUT, stream);
+  return st;
+}
+
+// values only: bisection, undo the scaling (lam64, optional: the eigenvalues in fp64)
+static int values_launch(const Reduced &R, int64_t n, float *w, double *lam64, int32_t *info, hipStream_t stream) {
+  int st = stebz_launch(R.d, R.e, n, w, R.scal, stream, lam64);
+  if (st != VIVIT_OK) return st;
+  st = info_finalize_launch(info, n, R.scal, stream);
+  prof_mark(PROF_STAGE_TRIDIAG, stream);
+  return st;
 }
 
 size_t symeig_large_workspace_bytes(int64_t n, bool vectors) {
-  size_t one = align_up(sizeof(float) * sytrd_workspace_floats(n), 256) + 512;
-  size_t two = two_stage_workspace_bytes(n, vectors);
+  const size_t one = one_stage_workspace_bytes(n), two = two_stage_workspace_bytes(n, vectors);
   size_t b = one > two ? one : two;   // either reduction may be selected at run time
   b += stedc_workspace_bytes(n, vectors);
   if (vectors) b += bt_workspace_bytes(n) + q2_workspace_bytes(n, n) + 512;
   return b;
 }
 
-// values only: prescale -> mirror -> band -> tridiagonal -> bisection
-static int symeig_two_stage_values(float *A, int64_t n, int64_t lda, float *w, void *ws, int32_t *info,
-                                   hipStream_t stream) {
-  char *p = reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
-  auto take = [&](size_t bytes) {
-    char *r = p;
-    p += align_up(bytes, 256);
-    return r;
-  };
-  float *scal = (float *)take(sizeof(float) * 16);
-  float *part = (float *)take(sizeof(float) * 2 * n);
-  void *sbws = take(sy2sb_workspace_bytes(n));
-  float *AB = (float *)take(sizeof(float) * n * SB2ST_LDP);
-  const int64_t rrows = sb2st_ring_rows(n);
-  float *R2 = (float *)take(sizeof(float) * rrows * n);
-  float *tau2 = (float *)take(sizeof(float) * n * sb2st_num_levels(n));
-  float *d = (float *)take(sizeof(float) * n);
-  float *e = (float *)take(sizeof(float) * n);
-  prof_mark(PROF_STAGE_BEGIN, stream);
-  int st = prescale_launch(A, n, lda, scal, part, stream);
-  if (st != VIVIT_OK) return st;
-  st = symmetrize_launch(A, n, lda, stream);
-  if (st != VIVIT_OK) return st;
-  prof_mark(PROF_STAGE_PREP, stream);
-  float *tau1;
-  st = sy2sb_launch(A, n, lda, sbws, &tau1, stream);
-  if (st != VIVIT_OK) return st;
-  st = sy2sb_extract_band_launch(A, lda, n, AB, SB2ST_LDP, stream);
-  if (st != VIVIT_OK) return st;
-  prof_mark(PROF_STAGE_SY2SB, stream);
-  st = sb2st_launch(AB, n, d, e, R2, n, rrows, tau2, stream);
-  if (st != VIVIT_OK) return st;
-  prof_mark(PROF_STAGE_SB2ST, stream);
-  st = stebz_launch(d, e, n, w, scal, stream);
-  if (st != VIVIT_OK) return st;
-  st = info_finalize_launch(info, n, scal, stream);
-  prof_mark(PROF_STAGE_TRIDIAG, stream);
-  return st;
-}
-
-// rows mode (r1 >= 0): Z receives the eigenvectors r0 .. r1-1 (ascending eigenvalue order) as ROWS, [r1-r0][ldz];
-// reduction and divide & conquer are done in full, only the back-transformations are restricted to those rows
-// (rows of Zt are independent: this is what the multi-GPU path shards).  Default mode: Z = column eigenvectors.
+// Z == nullptr: eigenvalues only; otherwise eigenvectors as for eigvec_back_half.
 static int symeig_large_impl(float *A, int64_t n, int64_t lda, float *w, float *Z, int64_t ldz, int64_t r0, int64_t r1,
                              void *ws, size_t ws_bytes, int32_t *info, hipStream_t stream) {
   const bool vectors = Z != nullptr;
-  const bool rows_mode = r1 >= 0;
   if (n > 0x7fffffffLL / 8) return VIVIT_E_UNSUPPORTED;
   if (!ws || ws_bytes < symeig_large_workspace_bytes(n, vectors)) return VIVIT_E_WORKSPACE;
+  const bool two_stage = use_two_stage(n);
+  Arena a(ws, ws_bytes);
+  TwoStageWs ts = {};
+  SytrdLayout trd = {};
+  if (two_stage) ts = two_stage_layout(a, n, vectors ? TS_VECTORS : TS_VALUES);
+  else trd = one_stage_layout(a, n);
+  BackWs back = {};
+  if (vectors) back = back_layout(a, n, two_stage);
+  if (a.overflow()) return VIVIT_E_WORKSPACE;
   if (hipMemsetAsync(info, 0, sizeof(int32_t), stream) != hipSuccess) return VIVIT_E_LAUNCH;
-  char *p = reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
-  auto take = [&](size_t bytes) {
-    char *r = p;
-    p += align_up(bytes, 256);
-    return r;
-  };
 
-  if (!vectors && use_two_stage(n, false)) return symeig_two_stage_values(A, n, lda, w, ws, info, stream);
-
-  if (vectors && use_two_stage(n, true)) {
-    // ---- two-stage with vectors: A = Q1 B Q1^T (band), B = Q2 T Q2^T, T = Q_T diag(w) Q_T^T;
-    //      Zt = Q_T^T Q2^T Q1^T, applied right to left on the rows of Qt
-    float *scal = (float *)take(sizeof(float) * 16);
-    float *part = (float *)take(sizeof(float) * 2 * n);
-    void *sbws = take(sy2sb_workspace_bytes(n));
-    float *AB = (float *)take(sizeof(float) * n * SB2ST_LDP);
-    float *R2 = (float *)take(sizeof(float) * n * n);
-    const size_t tau2_bytes = sizeof(float) * n * sb2st_num_levels(n);
-    float *tau2 = (float *)take(tau2_bytes);
-    float *d = (float *)take(sizeof(float) * n);
-    float *e = (float *)take(sizeof(float) * n);
-    prof_mark(PROF_STAGE_BEGIN, stream);
-    int st = prescale_launch(A, n, lda, scal, part, stream);
-    if (st != VIVIT_OK) return st;
-    st = symmetrize_launch(A, n, lda, stream);
-    if (st != VIVIT_OK) return st;
-    prof_mark(PROF_STAGE_PREP, stream);
-    float *tau1;
-    st = sy2sb_launch(A, n, lda, sbws, &tau1, stream);
-    if (st != VIVIT_OK) return st;
-    st = sy2sb_extract_band_launch(A, lda, n, AB, SB2ST_LDP, stream);
-    if (st != VIVIT_OK) return st;
-    prof_mark(PROF_STAGE_SY2SB, stream);
-    if (hipMemsetAsync(tau2, 0, tau2_bytes, stream) != hipSuccess) return VIVIT_E_LAUNCH;
-    st = sb2st_launch(AB, n, d, e, R2, n, n, tau2, stream);
-    if (st != VIVIT_OK) return st;
-    prof_mark(PROF_STAGE_SB2ST, stream);
-    void *dc_base = take(stedc_workspace_bytes(n, true));
-    float *Qt, *dd;
-    int *order;
-    st = stedc_dc_launch(d, e, n, dc_base, &Qt, &dd, &order, info, stream);
-    if (st != VIVIT_OK) return st;
-    void *q2ws = take(q2_workspace_bytes(n, n));
-    if (rows_mode) {
-      st = dc_rows_launch(n, dd, Qt, n, order, w, Z, ldz, r0, r1, scal, stream);
-      if (st != VIVIT_OK) return st;
-      prof_mark(PROF_STAGE_TRIDIAG, stream);
-      st = q2_apply_launch(Z, ldz, r1 - r0, n, R2, n, tau2, q2ws, stream);
-      if (st != VIVIT_OK) return st;
-      prof_mark(PROF_STAGE_Q2, stream);
-      st = backtransform_launch(A, n, lda, tau1, TS_NB, n - TS_NB - 1, Z, ldz, r1 - r0, take, stream);
-      if (st != VIVIT_OK) return st;
-      prof_mark(PROF_STAGE_Q1, stream);
-      return info_scal_launch(info, n, scal, stream);
-    }
-    prof_mark(PROF_STAGE_TRIDIAG, stream);
-    st = q2_apply_launch(Qt, n, n, n, R2, n, tau2, q2ws, stream);
-    if (st != VIVIT_OK) return st;
-    prof_mark(PROF_STAGE_Q2, stream);
-    st = backtransform_launch(A, n, lda, tau1, TS_NB, n - TS_NB - 1, Qt, n, n, take, stream);
-    if (st != VIVIT_OK) return st;
-    prof_mark(PROF_STAGE_Q1, stream);
-    st = dc_output_launch(n, dd, Qt, n, order, w, Z, ldz, scal, info, stream);
-    prof_mark(PROF_STAGE_OUTPUT, stream);
-    return st;
-  }
-
-  // ---- stage 1: A = Q_H T Q_H^T
-  SytrdWs tw;
-  float *trd_base = (float *)take(sizeof(float) * sytrd_workspace_floats(n));
-  prof_mark(PROF_STAGE_BEGIN, stream);
-  int st = sytrd_launch(A, n, lda, trd_base, &tw, stream);
+  // A = Q1 B Q1^T (band), B = Q2 T Q2^T  |  A = Q_H T Q_H^T
+  const int st = two_stage ? two_stage_reduce(A, n, lda, ts, stream) : one_stage_reduce(A, n, lda, trd, stream);
   if (st != VIVIT_OK) return st;
-  prof_mark(PROF_STAGE_SYTRD, stream);
-
-  if (!vectors) {
-    // ---- stage 2 (values only): bisection, undo the scaling
-    st = stebz_launch(tw.d, tw.e, n, w, tw.scal, stream);
-    if (st != VIVIT_OK) return st;
-    st = info_finalize_launch(info, n, tw.scal, stream);
-    prof_mark(PROF_STAGE_TRIDIAG, stream);
-    return st;
-  }
-
-  // ---- stage 2: T = Q_T diag(w) Q_T^T by divide and conquer (Qt = Q_T^T, rows unsorted)
-  void *dc_base = take(stedc_workspace_bytes(n, true));
-  float *Qt, *dd;
-  int *order;
-  st = stedc_dc_launch(tw.d, tw.e, n, dc_base, &Qt, &dd, &order, info, stream);
-  if (st != VIVIT_OK) return st;
-
-  if (rows_mode) {
-    st = dc_rows_launch(n, dd, Qt, n, order, w, Z, ldz, r0, r1, tw.scal, stream);
-    if (st != VIVIT_OK) return st;
-    prof_mark(PROF_STAGE_TRIDIAG, stream);
-    st = backtransform_launch(A, n, lda, tw.tau, 1, n - 3, Z, ldz, r1 - r0, take, stream);
-    if (st != VIVIT_OK) return st;
-    prof_mark(PROF_STAGE_Q1, stream);
-    return info_scal_launch(info, n, tw.scal, stream);
-  }
-  prof_mark(PROF_STAGE_TRIDIAG, stream);
-
-  // ---- stage 3: Zt = Qt * Q_H^T
-  st = backtransform_launch(A, n, lda, tw.tau, 1, n - 3, Qt, n, n, take, stream);
-  if (st != VIVIT_OK) return st;
-  prof_mark(PROF_STAGE_Q1, stream);
-
-  // ---- sort ascending, undo the scaling, deliver column eigenvectors
-  st = dc_output_launch(n, dd, Qt, n, order, w, Z, ldz, tw.scal, info, stream);
-  prof_mark(PROF_STAGE_OUTPUT, stream);
-  return st;
+  const Reduced R = two_stage ? reduced_of(ts) : reduced_of(trd);
+  if (!vectors) return values_launch(R, n, w, nullptr, info, stream);
+  return eigvec_back_half(A, n, lda, R, back, w, Z, ldz, r0, r1, info, stream);
 }
 
 // ---- two-phase solver: reduction + all eigenvalues, host-side criterion, then only the selected eigenvectors --------
@@ -399,75 +425,38 @@ constexpr int64_t SELECT_STEIN_MAX = 256;
 
 struct SelectLayout {
   bool two_stage;
-  // two-stage
-  float *scal, *part;
-  void *sbws;
-  float *AB, *R2, *tau2, *tau1, *d, *e;
-  // one-stage
-  float *trd_base;
-  SytrdWs tw;
+  TwoStageWs ts;     // two-stage
+  SytrdLayout trd;   // one-stage
+  Reduced R;
   double *lam64;
-  int *order_id;  // [n] identity permutation (rows mode of the D&C output wants an order array)
-  char *rest;     // phase-2 scratch (stein | stedc, q2, back-transformation)
 };
 
-static bool select_two_stage(int64_t n) { return use_two_stage(n, false); }
-
-static SelectLayout select_layout(void *ws, int64_t n) {
-  char *p = reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
-  auto take = [&](size_t bytes) {
-    char *r = p;
-    p += align_up(bytes, 256);
-    return r;
-  };
-  SelectLayout L;
-  L.two_stage = select_two_stage(n);
+static SelectLayout select_layout(Arena &a, int64_t n) {
+  SelectLayout L = {};
+  L.two_stage = use_two_stage(n);
   if (L.two_stage) {
-    L.scal = (float *)take(sizeof(float) * 16);
-    L.part = (float *)take(sizeof(float) * 2 * n);
-    L.sbws = take(sy2sb_workspace_bytes(n));
-    L.AB = (float *)take(sizeof(float) * n * SB2ST_LDP);
-    L.R2 = (float *)take(sizeof(float) * n * n);
-    L.tau2 = (float *)take(sizeof(float) * n * sb2st_num_levels(n));
-    L.tau1 = (float *)take(sizeof(float) * n);
-    L.d = (float *)take(sizeof(float) * n);
-    L.e = (float *)take(sizeof(float) * n);
-    L.trd_base = nullptr;
+    L.ts = two_stage_layout(a, n, TS_STATE);
+    L.R = reduced_of(L.ts);
   } else {
-    L.trd_base = (float *)take(sizeof(float) * sytrd_workspace_floats(n));
-    sytrd_layout(L.trd_base, n, &L.tw);
-    L.scal = L.tw.scal;
-    L.d = L.tw.d;
-    L.e = L.tw.e;
-    L.tau1 = L.tw.tau;
+    L.trd = one_stage_layout(a, n);
+    L.R = reduced_of(L.trd);
   }
-  L.lam64 = (double *)take(sizeof(double) * n);
-  L.rest = p;
+  L.lam64 = a.take<double>(n);
   return L;
 }
 
 // state workspace (phase 1 writes it, phase 2 reads it)
 size_t symeig_reduce_workspace_bytes(int64_t n) {
-  size_t b = 0;
-  if (select_two_stage(n)) {
-    b += align_up(sizeof(float) * 16, 256) + align_up(sizeof(float) * 2 * n, 256);
-    b += align_up(sy2sb_workspace_bytes(n), 256);
-    b += align_up(sizeof(float) * n * SB2ST_LDP, 256);
-    b += align_up(sizeof(float) * n * n, 256);
-    b += align_up(sizeof(float) * n * sb2st_num_levels(n), 256);
-    b += align_up(sizeof(float) * n, 256) * 3;
-  } else {
-    b += align_up(sizeof(float) * sytrd_workspace_floats(n), 256);
-  }
-  b += align_up(sizeof(double) * n, 256);
-  return b + 1024;
+  Arena m;
+  select_layout(m, n);
+  return m.used() + 1024;
 }
 
 // scratch workspace of phase 2 for K selected eigenvectors
 size_t symeig_select_workspace_bytes(int64_t n, int64_t K) {
   if (K < 1) K = 1;
   if (K > n) K = n;
-  size_t b = select_two_stage(n) ? q2_workspace_bytes(n, K) + 512 : 0;
+  size_t b = use_two_stage(n) ? q2_workspace_bytes(n, K) + 512 : 0;
   const size_t after = bt_workspace_bytes(n);
   if (K > SELECT_STEIN_MAX) {  // D&C buffers, reused by the back-transformations afterwards
     const size_t dc = align_up(stedc_workspace_bytes(n, true), 256);
@@ -482,84 +471,58 @@ int symeig_reduce_launch(float *A, int64_t n, int64_t lda, float *w, void *ws, s
                          hipStream_t stream) {
   if (n > 0x7fffffffLL / 8) return VIVIT_E_UNSUPPORTED;
   if (!ws || ws_bytes < symeig_reduce_workspace_bytes(n)) return VIVIT_E_WORKSPACE;
+  Arena a(ws, ws_bytes);
+  const SelectLayout L = select_layout(a, n);
+  if (a.overflow()) return VIVIT_E_WORKSPACE;
   if (hipMemsetAsync(info, 0, sizeof(int32_t), stream) != hipSuccess) return VIVIT_E_LAUNCH;
-  SelectLayout L = select_layout(ws, n);
-  prof_mark(PROF_STAGE_BEGIN, stream);
-  int st;
-  if (L.two_stage) {
-    st = prescale_launch(A, n, lda, L.scal, L.part, stream);
-    if (st != VIVIT_OK) return st;
-    st = symmetrize_launch(A, n, lda, stream);
-    if (st != VIVIT_OK) return st;
-    prof_mark(PROF_STAGE_PREP, stream);
-    float *tau1;
-    st = sy2sb_launch(A, n, lda, L.sbws, &tau1, stream);
-    if (st != VIVIT_OK) return st;
-    if (hipMemcpyAsync(L.tau1, tau1, sizeof(float) * n, hipMemcpyDeviceToDevice, stream) != hipSuccess) return VIVIT_E_LAUNCH;
-    st = sy2sb_extract_band_launch(A, lda, n, L.AB, SB2ST_LDP, stream);
-    if (st != VIVIT_OK) return st;
-    prof_mark(PROF_STAGE_SY2SB, stream);
-    if (hipMemsetAsync(L.tau2, 0, sizeof(float) * n * sb2st_num_levels(n), stream) != hipSuccess) return VIVIT_E_LAUNCH;
-    st = sb2st_launch(L.AB, n, L.d, L.e, L.R2, n, n, L.tau2, stream);
-    if (st != VIVIT_OK) return st;
-    prof_mark(PROF_STAGE_SB2ST, stream);
-  } else {
-    SytrdWs tw;
-    st = sytrd_launch(A, n, lda, L.trd_base, &tw, stream);
-    if (st != VIVIT_OK) return st;
-    prof_mark(PROF_STAGE_SYTRD, stream);
-  }
-  st = stebz_launch(L.d, L.e, n, w, L.scal, stream, L.lam64);
+  const int st = L.two_stage ? two_stage_reduce(A, n, lda, L.ts, stream) : one_stage_reduce(A, n, lda, L.trd, stream);
   if (st != VIVIT_OK) return st;
-  st = info_finalize_launch(info, n, L.scal, stream);
-  prof_mark(PROF_STAGE_TRIDIAG, stream);
-  return st;
+  return values_launch(L.R, n, w, L.lam64, info, stream);
 }
 
-// order[i] = sel[i] for i < K (device copy with the identity elsewhere is not needed: dc_rows_launch sorts itself)
 int symeig_select_launch(const float *A, int64_t n, int64_t lda, const int *sel, int64_t K, float *Zt, int64_t ldz,
                          void *state, size_t state_bytes, void *ws, size_t ws_bytes, int32_t *info, hipStream_t stream) {
   if (K < 0 || K > n || (K > 0 && (!sel || !Zt || ldz < n))) return VIVIT_E_BADARG;
   if (!state || state_bytes < symeig_reduce_workspace_bytes(n)) return VIVIT_E_WORKSPACE;
   if (K == 0) return VIVIT_OK;
   if (!ws || ws_bytes < symeig_select_workspace_bytes(n, K)) return VIVIT_E_WORKSPACE;
-  SelectLayout L = select_layout(state, n);
-  char *p = reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
-  auto take = [&](size_t bytes) {
-    char *r = p;
-    p += align_up(bytes, 256);
-    return r;
-  };
+  Arena sa(state, state_bytes), a(ws, ws_bytes);
+  const SelectLayout L = select_layout(sa, n);
+  const bool dc_route = K > SELECT_STEIN_MAX;   // many eigenvectors: divide & conquer for all of them, keep the selected rows
+  SteinWs stw = {};
+  DcWs dc = {};
+  float *wscratch = nullptr;
+  if (dc_route) {
+    wscratch = a.take<float>(n);
+    void *dc_base = a.mark();
+    Arena s = a.sub(stedc_workspace_bytes(n, true));
+    dc = dc_layout(s, n);
+    a.absorb(s);
+    a.rewind(dc_base);   // once the selected rows are in Zt the D&C block is free for the back-transformations
+  } else {
+    Arena s = a.sub(stein_workspace_bytes(n, K));
+    stw = stein_layout(s, n, K);
+    a.absorb(s);
+  }
+  void *q2ws = L.two_stage ? a.take<char>(q2_workspace_bytes(n, K)) : nullptr;
+  const BtWs bt = bt_layout(a, n);
+  if (sa.overflow() || a.overflow()) return VIVIT_E_WORKSPACE;
+  // (not eigvec_back_half: the selection is a gather by index without eigenvalues, scaling or status, and the
+  // back-transformations run on the D&C block's memory instead of behind it)
   prof_mark(PROF_STAGE_BEGIN, stream);
   int st;
-  if (K <= SELECT_STEIN_MAX) {
-    void *stws = take(stein_workspace_bytes(n, K));
-    st = stein_launch(L.d, L.e, n, L.lam64, sel, K, Zt, ldz, stws, info, stream);
-    if (st != VIVIT_OK) return st;
-  } else {  // many eigenvectors: divide & conquer for all of them, keep the selected rows
-    float *wscratch = (float *)take(sizeof(float) * n);
-    void *dc_base = take(stedc_workspace_bytes(n, true));
+  if (dc_route) {
     float *Qt, *dd;
     int *order;
-    st = stedc_dc_launch(L.d, L.e, n, dc_base, &Qt, &dd, &order, info, stream);
+    st = stedc_dc_launch(L.R.d, L.R.e, n, dc, &Qt, &dd, &order, info, stream);
     if (st != VIVIT_OK) return st;
     st = dc_select_launch(n, dd, Qt, n, order, wscratch, sel, K, Zt, ldz, stream);
-    if (st != VIVIT_OK) return st;
-    p = reinterpret_cast<char *>(dc_base);  // the D&C buffers are free again for the back-transformations
-  }
-  prof_mark(PROF_STAGE_TRIDIAG, stream);
-  if (L.two_stage) {
-    void *q2ws = take(q2_workspace_bytes(n, K));
-    st = q2_apply_launch(Zt, ldz, K, n, L.R2, n, L.tau2, q2ws, stream);
-    if (st != VIVIT_OK) return st;
-    prof_mark(PROF_STAGE_Q2, stream);
-    st = backtransform_launch(A, n, lda, L.tau1, TS_NB, n - TS_NB - 1, Zt, ldz, K, take, stream);
   } else {
-    st = backtransform_launch(A, n, lda, L.tau1, 1, n - 3, Zt, ldz, K, take, stream);
+    st = stein_launch(L.R.d, L.R.e, n, L.lam64, sel, K, Zt, ldz, stw, info, stream);
   }
   if (st != VIVIT_OK) return st;
-  prof_mark(PROF_STAGE_Q1, stream);
-  return VIVIT_OK;
+  prof_mark(PROF_STAGE_TRIDIAG, stream);
+  return back_transform_rows(A, n, lda, L.R, Zt, ldz, K, q2ws, bt, stream);
 }
 
 int symeig_large_launch(float *A, int64_t n, int64_t lda, float *w, float *Z, int64_t ldz, void *ws, size_t ws_bytes,
@@ -577,43 +540,64 @@ size_t symeigvals_batched_workspace_bytes(int64_t n, int64_t batch) {
   return batched_slot_bytes(n) * (size_t)slots + 256;
 }
 
-// With the persistent reduction allowed a wave is: prescale per problem -> ONE persistent launch, problem q on XCD q ->
-// bisection per problem -> one status kernel for the wave.  Every per-problem kernel is the one the single solve launches,
-// on the same kind of workspace: the eigenvalues are those of vivit_symeig_f32, bit for bit.  Without the persistent kernels
-// (or with the two-stage reduction forced) the problems run one after the other through the single solve itself.
+// A wave of both batched reductions: prescale per problem -> ONE persistent launch, problem q on XCD q -> one bisection
+// launch -> one status kernel.  Every per-problem kernel is the one the single solve launches, on the same kind of
+// workspace: the eigenvalues are those of vivit_symeig_f32, bit for bit.  slot_of(i, q): where problem i, the q-th of its
+// wave, has its sytrd block, and its fp64 eigenvalues if they are kept (all problems or none).
+struct WaveSlot {
+  SytrdLayout trd;
+  double *lam64;
+};
+
+template <class SlotOf>
+static int reduce_waves(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, SlotOf slot_of, int32_t *info,
+                        hipStream_t stream) {
+  if (hipMemsetAsync(info, 0, sizeof(int32_t) * batch, stream) != hipSuccess) return VIVIT_E_LAUNCH;
+  for (int64_t i0 = 0; i0 < batch; i0 += PERSIST_MAX_BATCH) {
+    const int nb = (int)(batch - i0 < PERSIST_MAX_BATCH ? batch - i0 : PERSIST_MAX_BATCH);
+    SytrdLayout trd[PERSIST_MAX_BATCH];
+    const float *dq[PERSIST_MAX_BATCH], *eq[PERSIST_MAX_BATCH], *scal[PERSIST_MAX_BATCH];
+    float *wq[PERSIST_MAX_BATCH];
+    double *lam[PERSIST_MAX_BATCH];
+    for (int q = 0; q < nb; ++q) {
+      const WaveSlot s = slot_of(i0 + q, q);
+      trd[q] = s.trd;
+      dq[q] = s.trd.ws.d; eq[q] = s.trd.ws.e; scal[q] = s.trd.ws.scal; lam[q] = s.lam64;
+      wq[q] = W + (i0 + q) * n;
+    }
+    int st = sytrd_batched_launch(A + i0, nb, n, lda, trd, stream);
+    if (st != VIVIT_OK) return st;
+    st = stebz_batched_launch(nb, n, dq, eq, wq, scal, stream, lam[0] ? lam : nullptr);   // one bisection launch for the wave
+    if (st != VIVIT_OK) return st;
+    st = info_finalize_batched_launch(info + i0, nb, n, scal, stream);
+    if (st != VIVIT_OK) return st;
+  }
+  return VIVIT_OK;
+}
+
+// Without the persistent kernels (or with the two-stage reduction forced) the problems run one after the other through
+// the single solve itself.
 int symeigvals_batched_launch(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, void *ws, size_t ws_bytes,
                               int32_t *info, hipStream_t stream) {
   if (!ws || ws_bytes < symeigvals_batched_workspace_bytes(n, batch)) return VIVIT_E_WORKSPACE;
-  char *base = reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
+  Arena a(ws, ws_bytes);
   const size_t slot = batched_slot_bytes(n);
-  if (use_two_stage(n, false) || !sytrd_persist_ok(n)) {
+  WaveSlot slots[PERSIST_MAX_BATCH] = {};
+  void *base = a.mark();
+  for (int q = 0; q < PERSIST_MAX_BATCH && q < batch; ++q) {
+    Arena s = a.sub(slot);
+    slots[q].trd = one_stage_layout(s, n);
+    a.absorb(s);
+  }
+  if (a.overflow()) return VIVIT_E_WORKSPACE;
+  if (use_two_stage(n) || !sytrd_persist_ok(n)) {
     for (int64_t i = 0; i < batch; ++i) {
       const int st = symeig_large_impl(A[i], n, lda, W + i * n, nullptr, 0, 0, -1, base, slot, info + i, stream);
       if (st != VIVIT_OK) return st;
     }
     return VIVIT_OK;
   }
-  if (hipMemsetAsync(info, 0, sizeof(int32_t) * batch, stream) != hipSuccess) return VIVIT_E_LAUNCH;
-  for (int64_t i0 = 0; i0 < batch; i0 += PERSIST_MAX_BATCH) {
-    const int nb = (int)(batch - i0 < PERSIST_MAX_BATCH ? batch - i0 : PERSIST_MAX_BATCH);
-    float *trd_base[PERSIST_MAX_BATCH];
-    const float *scal[PERSIST_MAX_BATCH];
-    SytrdWs tw[PERSIST_MAX_BATCH];
-    for (int q = 0; q < nb; ++q) trd_base[q] = reinterpret_cast<float *>(base + slot * q);
-    int st = sytrd_batched_launch(A + i0, nb, n, lda, trd_base, tw, stream);
-    if (st != VIVIT_OK) return st;
-    const float *dq[PERSIST_MAX_BATCH], *eq[PERSIST_MAX_BATCH];
-    float *wq[PERSIST_MAX_BATCH];
-    for (int q = 0; q < nb; ++q) {
-      dq[q] = tw[q].d; eq[q] = tw[q].e; wq[q] = W + (i0 + q) * n;
-      scal[q] = tw[q].scal;
-    }
-    st = stebz_batched_launch(nb, n, dq, eq, wq, scal, stream);   // one bisection launch for the wave
-    if (st != VIVIT_OK) return st;
-    st = info_finalize_batched_launch(info + i0, nb, n, scal, stream);
-    if (st != VIVIT_OK) return st;
-  }
-  return VIVIT_OK;
+  return reduce_waves(A, batch, n, lda, W, [&](int64_t, int q) { return slots[q]; }, info, stream);
 }
 
 // ---- eigenpairs of `batch` matrices of one size 193 <= n <= 1280 in two phases (vivit_symeig_reduce_batched_f32 /
@@ -715,8 +699,18 @@ static int bt_rows_batched_launch(int batch, int64_t n, int64_t lda, const float
 
 // the batched reduction needs the persistent kernel (one XCD per problem), the batched select only the one-stage state
 // layout; otherwise the entries loop over the single ones
-static bool batched_select_ok(int64_t n) { return !select_two_stage(n) && n <= 64 * 20; }
+static bool batched_select_ok(int64_t n) { return !use_two_stage(n) && n <= 64 * 20; }
 static bool batched_pairs_ok(int64_t n) { return batched_select_ok(n) && sytrd_persist_ok(n); }
+
+// every state block holds its layout (the blocks may sit differently against a 256-byte boundary)
+static bool states_fit(void *const *state, int64_t batch, size_t state_bytes_each, int64_t n) {
+  for (int64_t i = 0; i < batch; ++i) {
+    Arena s(state[i], state_bytes_each);
+    select_layout(s, n);
+    if (s.overflow()) return false;
+  }
+  return true;
+}
 
 int symeig_reduce_batched_launch(float *const *A, int64_t batch, int64_t n, int64_t lda, float *W, void *const *state,
                                  size_t state_bytes_each, int32_t *info, hipStream_t stream) {
@@ -728,27 +722,13 @@ int symeig_reduce_batched_launch(float *const *A, int64_t batch, int64_t n, int6
     }
     return VIVIT_OK;
   }
-  if (hipMemsetAsync(info, 0, sizeof(int32_t) * batch, stream) != hipSuccess) return VIVIT_E_LAUNCH;
-  for (int64_t i0 = 0; i0 < batch; i0 += PERSIST_MAX_BATCH) {
-    const int nb = (int)(batch - i0 < PERSIST_MAX_BATCH ? batch - i0 : PERSIST_MAX_BATCH);
-    float *trd_base[PERSIST_MAX_BATCH], *wq[PERSIST_MAX_BATCH];
-    const float *dq[PERSIST_MAX_BATCH], *eq[PERSIST_MAX_BATCH], *scal[PERSIST_MAX_BATCH];
-    double *lam[PERSIST_MAX_BATCH];
-    SytrdWs tw[PERSIST_MAX_BATCH];
-    for (int q = 0; q < nb; ++q) {
-      const SelectLayout L = select_layout(state[i0 + q], n);
-      trd_base[q] = L.trd_base;
-      dq[q] = L.d; eq[q] = L.e; scal[q] = L.scal; lam[q] = L.lam64;
-      wq[q] = W + (i0 + q) * n;
-    }
-    int st = sytrd_batched_launch(A + i0, nb, n, lda, trd_base, tw, stream);
-    if (st != VIVIT_OK) return st;
-    st = stebz_batched_launch(nb, n, dq, eq, wq, scal, stream, lam);
-    if (st != VIVIT_OK) return st;
-    st = info_finalize_batched_launch(info + i0, nb, n, scal, stream);
-    if (st != VIVIT_OK) return st;
-  }
-  return VIVIT_OK;
+  if (!states_fit(state, batch, state_bytes_each, n)) return VIVIT_E_WORKSPACE;
+  auto slot_of = [&](int64_t i, int) {
+    Arena s(state[i], state_bytes_each);
+    const SelectLayout L = select_layout(s, n);
+    return WaveSlot{L.trd, L.lam64};
+  };
+  return reduce_waves(A, batch, n, lda, W, slot_of, info, stream);
 }
 
 // One slot of inverse-iteration scratch per problem of a wave (sized for the largest selection the batched kernels take);
@@ -770,13 +750,24 @@ int symeig_select_batched_launch(const float *const *A, int64_t batch, int64_t n
   for (int64_t i = 0; i < batch; ++i) kmax = K[i] > kmax ? K[i] : kmax;
   if (state_bytes_each < symeig_reduce_workspace_bytes(n)) return VIVIT_E_WORKSPACE;
   if (kmax > 0 && (!ws || ws_bytes < symeig_select_batched_workspace_bytes(n, batch, kmax))) return VIVIT_E_WORKSPACE;
+  Arena slots[PERSIST_MAX_BATCH];
+  void *single_ws = nullptr;
+  size_t single_bytes = 0;
+  if (kmax > 0) {
+    Arena a(ws, ws_bytes);
+    const size_t slot = align_up(stein_workspace_bytes(n, batched_stein_k(kmax)), 256);
+    for (int q = 0; q < PERSIST_MAX_BATCH && q < batch; ++q) {
+      slots[q] = a.sub(slot);
+      Arena s = slots[q];
+      stein_layout(s, n, batched_stein_k(kmax));   // (the largest layout a slot is asked for)
+      a.absorb(s);
+    }
+    single_ws = a.mark();
+    single_bytes = a.left();
+    if (a.overflow() || !states_fit(state, batch, state_bytes_each, n)) return VIVIT_E_WORKSPACE;
+  }
   if (hipMemsetAsync(info, 0, sizeof(int32_t) * batch, stream) != hipSuccess) return VIVIT_E_LAUNCH;
   if (kmax == 0) return VIVIT_OK;
-  char *base = reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
-  const size_t slot = align_up(stein_workspace_bytes(n, batched_stein_k(kmax)), 256);
-  const int64_t slots = batch < PERSIST_MAX_BATCH ? batch : PERSIST_MAX_BATCH;
-  char *single_ws = base + slot * slots;
-  const size_t single_bytes = ws_bytes - (size_t)(single_ws - reinterpret_cast<char *>(ws));
   const bool batched = batched_select_ok(n);
   for (int64_t i0 = 0; i0 < batch; i0 += PERSIST_MAX_BATCH) {
     const int nb = (int)(batch - i0 < PERSIST_MAX_BATCH ? batch - i0 : PERSIST_MAX_BATCH);
@@ -784,15 +775,16 @@ int symeig_select_batched_launch(const float *const *A, int64_t batch, int64_t n
     const double *lam[PERSIST_MAX_BATCH];
     const int *sel[PERSIST_MAX_BATCH];
     int64_t Kq[PERSIST_MAX_BATCH];
-    void *stws[PERSIST_MAX_BATCH];
+    SteinWs stws[PERSIST_MAX_BATCH];
     int32_t *infq[PERSIST_MAX_BATCH];
     for (int q = 0; q < nb; ++q) {
       const int64_t i = i0 + q;
-      const SelectLayout L = select_layout(state[i], n);
-      dq[q] = L.d; eq[q] = L.e; tauq[q] = L.tau1; lam[q] = L.lam64;
+      Arena sa(state[i], state_bytes_each), s = slots[q];
+      const SelectLayout L = select_layout(sa, n);
+      dq[q] = L.R.d; eq[q] = L.R.e; tauq[q] = L.R.tau1; lam[q] = L.lam64;
       sel[q] = idx + ktot;
       ktot += K[i];
-      stws[q] = base + slot * q;
+      stws[q] = stein_layout(s, n, K[i]);
       infq[q] = info + i;
       Kq[q] = K[i];
       if (K[i] > 0 && (!batched || K[i] > SELECT_STEIN_MAX)) {   // out of the wave: the single select (divide & conquer route)
@@ -817,10 +809,12 @@ int symeig_large_rows_launch(float *A, int64_t n, int64_t lda, float *w, float *
 }
 
 // ---- the two-stage solver in two halves, for a band reduction done elsewhere (multi-GPU: vivit_amd/distributed.py).
-// prepare: LAPACK-style scaling + mirror (what symeig_large_impl does in front of sy2sb_launch); scal: device [16].
+// prepare: LAPACK-style scaling + mirror (what two_stage_reduce does in front of sy2sb_launch); scal: device [16].
 int symeig_prepare_launch(float *A, int64_t n, int64_t lda, float *scal, void *ws, size_t ws_bytes, hipStream_t stream) {
   if (ws_bytes < sizeof(float) * 2 * (size_t)n + 256) return VIVIT_E_WORKSPACE;
-  float *part = reinterpret_cast<float *>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
+  Arena a(ws, ws_bytes);
+  float *part = a.take<float>(2 * n);
+  if (a.overflow()) return VIVIT_E_WORKSPACE;
   int st = prescale_launch(A, n, lda, scal, part, stream);
   if (st != VIVIT_OK) return st;
   return symmetrize_launch(A, n, lda, stream);
@@ -830,45 +824,16 @@ int symeig_banded_rows_launch(float *A, int64_t n, int64_t lda, const float *tau
                               int64_t ldz, int64_t r0, int64_t r1, void *ws, size_t ws_bytes, int32_t *info, hipStream_t stream) {
   if (!Zt || r0 < 0 || r1 < r0 || r1 > n || n <= 2 * TS_NB) return VIVIT_E_BADARG;
   if (!ws || ws_bytes < symeig_large_workspace_bytes(n, true)) return VIVIT_E_WORKSPACE;
+  Arena a(ws, ws_bytes);
+  TwoStageWs ts = two_stage_layout(a, n, TS_BANDED);
+  ts.tau1 = const_cast<float *>(tau1);
+  const BackWs back = back_layout(a, n, true);
+  if (a.overflow()) return VIVIT_E_WORKSPACE;
   if (hipMemsetAsync(info, 0, sizeof(int32_t), stream) != hipSuccess) return VIVIT_E_LAUNCH;
-  char *p = reinterpret_cast<char *>(align_up(reinterpret_cast<uintptr_t>(ws), 256));
-  auto take = [&](size_t bytes) {
-    char *r = p;
-    p += align_up(bytes, 256);
-    return r;
-  };
-  float *scal = (float *)take(sizeof(float) * 16);
-  float *AB = (float *)take(sizeof(float) * n * SB2ST_LDP);
-  float *R2 = (float *)take(sizeof(float) * n * n);
-  const size_t tau2_bytes = sizeof(float) * n * sb2st_num_levels(n);
-  float *tau2 = (float *)take(tau2_bytes);
-  float *d = (float *)take(sizeof(float) * n);
-  float *e = (float *)take(sizeof(float) * n);
-  if (hipMemcpyAsync(scal, scal_in, sizeof(float) * 16, hipMemcpyDeviceToDevice, stream) != hipSuccess) return VIVIT_E_LAUNCH;
-  prof_mark(PROF_STAGE_BEGIN, stream);
-  int st = sy2sb_extract_band_launch(A, lda, n, AB, SB2ST_LDP, stream);
+  if (hipMemcpyAsync(ts.scal, scal_in, sizeof(float) * 16, hipMemcpyDeviceToDevice, stream) != hipSuccess) return VIVIT_E_LAUNCH;
+  const int st = two_stage_reduce(A, n, lda, ts, stream);
   if (st != VIVIT_OK) return st;
-  prof_mark(PROF_STAGE_SY2SB, stream);
-  if (hipMemsetAsync(tau2, 0, tau2_bytes, stream) != hipSuccess) return VIVIT_E_LAUNCH;
-  st = sb2st_launch(AB, n, d, e, R2, n, n, tau2, stream);
-  if (st != VIVIT_OK) return st;
-  prof_mark(PROF_STAGE_SB2ST, stream);
-  void *dc_base = take(stedc_workspace_bytes(n, true));
-  float *Qt, *dd;
-  int *order;
-  st = stedc_dc_launch(d, e, n, dc_base, &Qt, &dd, &order, info, stream);
-  if (st != VIVIT_OK) return st;
-  void *q2ws = take(q2_workspace_bytes(n, n));
-  st = dc_rows_launch(n, dd, Qt, n, order, w, Zt, ldz, r0, r1, scal, stream);
-  if (st != VIVIT_OK) return st;
-  prof_mark(PROF_STAGE_TRIDIAG, stream);
-  st = q2_apply_launch(Zt, ldz, r1 - r0, n, R2, n, tau2, q2ws, stream);
-  if (st != VIVIT_OK) return st;
-  prof_mark(PROF_STAGE_Q2, stream);
-  st = backtransform_launch(A, n, lda, tau1, TS_NB, n - TS_NB - 1, Zt, ldz, r1 - r0, take, stream);
-  if (st != VIVIT_OK) return st;
-  prof_mark(PROF_STAGE_Q1, stream);
-  return info_scal_launch(info, n, scal, stream);
+  return eigvec_back_half(A, n, lda, reduced_of(ts), back, w, Zt, ldz, r0, r1, info, stream);
 }
 
 } // namespace vivit
@@ -893,7 +858,7 @@ int vivit_symeig_banded_rows_f32(float *A, int64_t n, int64_t lda, const float *
 
 size_t vivit_sytrd_f32_workspace_bytes(int64_t n) {
   if (n <= 0) return 0;
-  return align_up(sizeof(float) * sytrd_workspace_floats(n), 256) + 512;
+  return one_stage_workspace_bytes(n);
 }
 
 int vivit_sytrd_f32(float *A, int64_t n, int64_t lda, float *d, float *e, float *tau, void *workspace,
@@ -901,9 +866,11 @@ int vivit_sytrd_f32(float *A, int64_t n, int64_t lda, float *d, float *e, float 
   if (n < 3 || !A || !d || !e || !tau || lda < n) return VIVIT_E_BADARG;
   if (!workspace || workspace_bytes < vivit_sytrd_f32_workspace_bytes(n)) return VIVIT_E_WORKSPACE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  float *base = reinterpret_cast<float *>(align_up(reinterpret_cast<uintptr_t>(workspace), 256));
-  SytrdWs tw;
-  int st = sytrd_launch(A, n, lda, base, &tw, s);
+  Arena a(workspace, workspace_bytes);
+  const SytrdLayout L = one_stage_layout(a, n);
+  if (a.overflow()) return VIVIT_E_WORKSPACE;
+  const SytrdWs &tw = L.ws;
+  int st = sytrd_launch(A, n, lda, L, s);
   if (st != VIVIT_OK) return st;
   if (hipMemcpyAsync(d, tw.d, sizeof(float) * n, hipMemcpyDeviceToDevice, s) != hipSuccess) return VIVIT_E_LAUNCH;
   if (hipMemcpyAsync(e, tw.e, sizeof(float) * (n - 1), hipMemcpyDeviceToDevice, s) != hipSuccess) return VIVIT_E_LAUNCH;

@@ -513,47 +513,32 @@ __global__ void trd_tail_kernel(const float *__restrict__ A, int64_t lda, int n,
 }
 
 // ------------------------------------------------------------------------------------------
+// The block's buffers, in order.  The arena of a launch hands out 16-byte regions; sytrd_workspace_floats measures the
+// plain lengths and its slack of 64 floats covers the 13 roundings (3 floats each at most).
+SytrdLayout sytrd_layout(Arena &a, int64_t n) {
+  const int64_t nct = cdiv(n, TC), nrt = cdiv(n, 32), nwg = cdiv(n, 64) + 1;
+  SytrdLayout L;
+  SytrdWs &ws = L.ws;
+  ws.vw = a.take<float>(3 * PB * n);
+  ws.xbuf = a.take<float>(n);
+  ws.rowpart = a.take<float>(nct * n);
+  ws.colpart = a.take<float>(nrt * n);
+  ws.dotpart = a.take<float>(NAUX * 2 * PB);
+  ws.cvw = a.take<float>(2 * PB);
+  ws.ssqpart = a.take<float>(nwg);
+  ws.wdotpart = a.take<float>(nwg);
+  ws.scal = a.take<float>(16);
+  ws.d = a.take<float>(n);
+  ws.e = a.take<float>(n);
+  ws.tau = a.take<float>(n);
+  L.scanpart = a.take<float>(2 * n);
+  return L;
+}
+
 size_t sytrd_workspace_floats(int64_t n) {
-  const int64_t nct = cdiv(n, TC), nrt = cdiv(n, 32), nwg = cdiv(n, 64) + 1;
-  int64_t f = 0;
-  f += 3 * PB * n;                 // vw
-  f += n;                          // xbuf
-  f += nct * n + nrt * n;          // rowpart, colpart
-  f += NAUX * 2 * PB + 2 * PB;     // dotpart, cvw
-  f += 2 * nwg + 16;               // ssqpart, wdotpart, scal
-  f += 3 * n;                      // d, e, tau
-  f += 2 * n;                      // scan partials
-  return (size_t)(f + 64) / 4 * 4 + 64;
-}
-
-// Carve the workspace (all sub-buffers 16-byte aligned).
-static SytrdWs sytrd_carve(float *base, int64_t n, float **scanpart) {
-  const int64_t nct = cdiv(n, TC), nrt = cdiv(n, 32), nwg = cdiv(n, 64) + 1;
-  auto take = [&](int64_t count) {
-    float *p = base;
-    base += (count + 3) / 4 * 4;
-    return p;
-  };
-  SytrdWs ws;
-  ws.vw = take(3 * PB * n);
-  ws.xbuf = take(n);
-  ws.rowpart = take(nct * n);
-  ws.colpart = take(nrt * n);
-  ws.dotpart = take(NAUX * 2 * PB);
-  ws.cvw = take(2 * PB);
-  ws.ssqpart = take(nwg);
-  ws.wdotpart = take(nwg);
-  ws.scal = take(16);
-  ws.d = take(n);
-  ws.e = take(n);
-  ws.tau = take(n);
-  *scanpart = take(2 * n);
-  return ws;
-}
-
-void sytrd_layout(float *wsbase, int64_t n, SytrdWs *out) {
-  float *scanpart;
-  *out = sytrd_carve(wsbase, n, &scanpart);
+  Arena m(sizeof(float));
+  sytrd_layout(m, n);
+  return (m.used() / sizeof(float) + 64) / 4 * 4 + 64;
 }
 
 int prescale_launch(float *A, int64_t n, int64_t lda, float *scal, float *part, hipStream_t stream) {
@@ -564,28 +549,25 @@ int prescale_launch(float *A, int64_t n, int64_t lda, float *scal, float *part, 
   return launch_status();
 }
 
-int sytrd_batched_launch(float *const *A, int batch, int64_t n, int64_t lda, float *const *wsbase, SytrdWs *out,
-                         hipStream_t stream) {
+int sytrd_batched_launch(float *const *A, int batch, int64_t n, int64_t lda, const SytrdLayout *L, hipStream_t stream) {
   if (batch < 1 || batch > PERSIST_MAX_BATCH) return VIVIT_E_UNSUPPORTED;
+  SytrdWs ws[PERSIST_MAX_BATCH];
   for (int q = 0; q < batch; ++q) {
-    float *scanpart;
-    out[q] = sytrd_carve(wsbase[q], n, &scanpart);
-    prescale_launch(A[q], n, lda, out[q].scal, scanpart, stream);
+    ws[q] = L[q].ws;
+    prescale_launch(A[q], n, lda, ws[q].scal, L[q].scanpart, stream);
   }
-  return sytrd_persist_batched_launch(A, batch, n, lda, out, stream);
+  return sytrd_persist_batched_launch(A, batch, n, lda, ws, stream);
 }
 
 // Tridiagonalise A (n x n, lda).  On return ws.d / ws.e / ws.tau hold T and the reflector
 // scalars, A's upper-triangle rows hold the reflectors, ws.scal[1] the applied scaling sigma
 // and ws.scal[2] the non-finite-input flag.
-int sytrd_launch(float *A, int64_t n, int64_t lda, float *wsbase, SytrdWs *out, hipStream_t stream) {
-  float *scanpart;
-  SytrdWs ws = sytrd_carve(wsbase, n, &scanpart);
-  *out = ws;
+int sytrd_launch(float *A, int64_t n, int64_t lda, const SytrdLayout &L, hipStream_t stream) {
+  const SytrdWs ws = L.ws;
   const int ni = (int)n;
   const bool vec = ((reinterpret_cast<uintptr_t>(A) & 15) == 0) && (lda % 4 == 0) && (n % 4 == 0);
 
-  prescale_launch(A, n, lda, ws.scal, scanpart, stream);
+  prescale_launch(A, n, lda, ws.scal, L.scanpart, stream);
   if (sytrd_persist_ok(n)) return sytrd_persist_launch(A, n, lda, ws, stream);   // one persistent launch on one XCD
 
   for (int64_t j0 = 0; j0 < n - 2; j0 += PB) {

@@ -558,6 +558,51 @@ def unpack_lower_(packed: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
     return G
 
 
+def _square_batch(mats, who: str):
+    """``B`` square matrices of one size on one device, from a list or a ``[B, n, n]`` tensor, as a list (``who``: the calling
+    function, named in the errors)."""
+    mats = list(mats.unbind(0)) if isinstance(mats, torch.Tensor) and mats.dim() == 3 else list(mats)
+    if not mats:
+        raise ValueError(f"{who} needs at least one matrix")
+    _require_device(*mats)
+    for G in mats:
+        if G.dim() != 2 or G.shape[0] != G.shape[1]:
+            raise ValueError(f"Input must be a square matrix. Got shape {tuple(G.shape)}.")
+        if G.shape != mats[0].shape:
+            raise ValueError(f"{who} needs matrices of one size, got {tuple(mats[0].shape)} and {tuple(G.shape)}")
+    return mats
+
+
+def _batch_work(mats, n: int, overwrite: bool):
+    """What a batched solver works on: every matrix with leading dimension ``n``, cloned unless it may be overwritten."""
+    work = []
+    for G in mats:
+        A = _as2d(G)
+        if _ld(A) != n:
+            A = A.contiguous()   # one leading dimension for the whole batch
+        if A.data_ptr() == G.data_ptr() and not overwrite:
+            A = A.clone()  # the solver destroys its inputs
+        work.append(A)
+    return work
+
+
+def _keep_indices(keep, n: int):
+    """``keep`` (ints or an integer tensor, any order, repeats, negatives) as a list of positions in ``range(n)``."""
+    keep = [int(k) for k in (keep.tolist() if isinstance(keep, torch.Tensor) else keep)]
+    keep = [k + n if k < 0 else k for k in keep]
+    if any(k < 0 or k >= n for k in keep):
+        raise IndexError(f"eigenvector index out of range for n = {n}")
+    return keep
+
+
+def _rows_in_order(Zt, uniq, keep):
+    """Rows of ``Zt`` (one per entry of ``uniq = sorted(set(keep))``) in the caller's order, repeats included."""
+    if uniq == keep:
+        return Zt
+    pos = {k: i for i, k in enumerate(uniq)}
+    return Zt[torch.tensor([pos[k] for k in keep], dtype=torch.long, device=Zt.device)]
+
+
 class SymeigPlan:
     """A symmetric matrix reduced to tridiagonal form with ALL eigenvalues known (``evals``, ascending), waiting for
     the caller to say which eigenvectors it wants: the two launches around the reference's ``criterion`` callback
@@ -572,10 +617,7 @@ class SymeigPlan:
         """``[n, K]`` column eigenvectors of ``evals[keep]`` (``keep``: any order, list of ints or an integer tensor)."""
         n = self.n
         dev = self.evals.device
-        keep = [int(k) for k in (keep.tolist() if isinstance(keep, torch.Tensor) else keep)]
-        keep = [k + n if k < 0 else k for k in keep]
-        if any(k < 0 or k >= n for k in keep):
-            raise IndexError(f"eigenvector index out of range for n = {n}")
+        keep = _keep_indices(keep, n)
         K = len(keep)
         if self._full is not None:  # small problem: all vectors already there
             return self._full[:, keep]
@@ -592,10 +634,7 @@ class SymeigPlan:
             self._state.numel(), ws, wsb, info.data_ptr(), _stream(self.evals))
         _lib.check(st, "vivit_symeig_select_f32")
         check_info(info)
-        if uniq != keep:  # caller's order / repeated indices
-            pos = {k: i for i, k in enumerate(uniq)}
-            Zt = Zt[torch.tensor([pos[k] for k in keep], dtype=torch.long, device=dev)]
-        return Zt.T
+        return _rows_in_order(Zt, uniq, keep).T
 
 
 @_launcher
@@ -683,22 +722,26 @@ def _wants_backup(G: torch.Tensor) -> bool:
     return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
 
 
-def _retry_on_launch_chain(solve, intact: bool, G: Optional[torch.Tensor] = None):
+def _retry_on_launch_chain(solve, intact: bool, G=None, what: str = "symeig"):
     """Run ``solve()``; if it ends with :class:`PersistentKernelTimeout` and the input is still there -- the solve worked
-    on a copy (``intact``), or ``G`` is solved in place and was backed up (:func:`_wants_backup`) -- repeat it ONCE with the
-    persistent kernels switched off: the same stages as launch chains, which need no co-residency.  Otherwise the error
-    propagates (the input is gone)."""
-    backup = G.clone() if (not intact and G is not None and _wants_backup(G)) else None
+    on a copy (``intact``), or ``G`` (one matrix, or the list of a batch) is solved in place and was backed up
+    (:func:`_wants_backup`, all of a batch or none) -- repeat it ONCE with the persistent kernels switched off: the same
+    stages as launch chains, which need no co-residency.  Otherwise the error propagates (the input is gone)."""
+    batch = isinstance(G, (list, tuple))
+    Gs = list(G) if batch else ([] if G is None else [G])
+    backups = [g.clone() for g in Gs] if (not intact and Gs and all(_wants_backup(g) for g in Gs)) else None
     try:
         return solve()
     except PersistentKernelTimeout:
-        if not intact and backup is None:
+        if not intact and backups is None:
             raise
         import warnings
 
-        warnings.warn("symeig: persistent kernel timed out; repeating the solve on the launch chains", RuntimeWarning)
-        if backup is not None:
-            G.copy_(backup)
+        warnings.warn(f"{what}: persistent kernel timed out; repeating the {'batch' if batch else 'solve'} on the launch chains",
+                      RuntimeWarning)
+        if backups is not None:
+            for g, b in zip(Gs, backups):
+                g.copy_(b)
         with persistent_kernels(False):
             return solve()
 
@@ -734,15 +777,7 @@ def symeigvals_batched(mats, overwrite: bool = False, info_out: Optional[list] =
     vector is read once (``RuntimeError`` names the failing problem) unless a list is passed as ``info_out``, which then
     receives it; a :class:`PersistentKernelTimeout` repeats the batch once on the launch chains when the inputs are
     still there (copies, or backed up: :func:`_wants_backup`)."""
-    mats = list(mats.unbind(0)) if isinstance(mats, torch.Tensor) and mats.dim() == 3 else list(mats)
-    if not mats:
-        raise ValueError("symeigvals_batched needs at least one matrix")
-    _require_device(*mats)
-    for G in mats:
-        if G.dim() != 2 or G.shape[0] != G.shape[1]:
-            raise ValueError(f"Input must be a square matrix. Got shape {tuple(G.shape)}.")
-        if G.shape != mats[0].shape:
-            raise ValueError(f"symeigvals_batched needs matrices of one size, got {tuple(mats[0].shape)} and {tuple(G.shape)}")
+    mats = _square_batch(mats, "symeigvals_batched")
     n, B, dev = mats[0].shape[0], len(mats), mats[0].device
     if n > SYMEIGVALS_BATCHED_MAX_N or n == 0:
         infos = [] if info_out is not None else None
@@ -754,14 +789,7 @@ def symeigvals_batched(mats, overwrite: bool = False, info_out: Optional[list] =
     lib = _lib.load()
 
     def solve():
-        work = []
-        for G in mats:
-            A = _as2d(G)
-            if _ld(A) != n:
-                A = A.contiguous()   # one leading dimension for the whole batch
-            if A.data_ptr() == G.data_ptr() and not overwrite:
-                A = A.clone()  # the solver destroys its inputs
-            work.append(A)
+        work = _batch_work(mats, n, overwrite)
         W = torch.empty((B, n), dtype=torch.float32, device=dev)
         info = torch.zeros(B, dtype=torch.int32, device=dev)
         ws, wsb = _workspace(lib.vivit_symeigvals_batched_f32_workspace_bytes(n, B), mats[0])
@@ -774,20 +802,7 @@ def symeigvals_batched(mats, overwrite: bool = False, info_out: Optional[list] =
             check_info_batched(info)
         return W
 
-    backups = [G.clone() for G in mats] if overwrite and all(_wants_backup(G) for G in mats) else None
-    try:
-        return solve()
-    except PersistentKernelTimeout:
-        if overwrite and backups is None:
-            raise
-        import warnings
-
-        warnings.warn("symeigvals_batched: persistent kernel timed out; repeating the batch on the launch chains", RuntimeWarning)
-        if backups is not None:
-            for G, b in zip(mats, backups):
-                G.copy_(b)
-        with persistent_kernels(False):
-            return solve()
+    return _retry_on_launch_chain(solve, intact=not overwrite, G=mats, what="symeigvals_batched")
 
 
 class SymeigBatchPlan:
@@ -804,12 +819,10 @@ class SymeigBatchPlan:
         """``keeps``: ``B`` index lists (rules of :meth:`SymeigPlan.select`: any order, repeats, negatives, ``IndexError``
         out of range; the lists may differ in length and may be empty).  Returns a list of ``[n, K_b]`` tensors."""
         n, B, dev = self.n, len(self.plans), self.evals.device
-        keeps = [[int(k) for k in (keep.tolist() if isinstance(keep, torch.Tensor) else keep)] for keep in keeps]
+        keeps = [keep.tolist() if isinstance(keep, torch.Tensor) else list(keep) for keep in keeps]
         if len(keeps) != B:
             raise ValueError(f"need one index list per problem: got {len(keeps)} for {B} problems")
-        keeps = [[k + n if k < 0 else k for k in keep] for keep in keeps]
-        if any(k < 0 or k >= n for keep in keeps for k in keep):
-            raise IndexError(f"eigenvector index out of range for n = {n}")
+        keeps = [_keep_indices(keep, n) for keep in keeps]
         if self._state is None:  # sizes outside the batched range: problem after problem
             return [plan.select(keep) for plan, keep in zip(self.plans, keeps)]
         uniqs = [sorted(set(keep)) for keep in keeps]
@@ -830,13 +843,7 @@ class SymeigBatchPlan:
                                                  self._state[0].numel(), ws, wsb, info.data_ptr(), _stream(self.evals))
         _lib.check(st, "vivit_symeig_select_batched_f32")
         check_info_batched(info, "symeig_reduce_batched.select")
-        out = []
-        for r, uniq, keep in zip(rows, uniqs, keeps):
-            if uniq != keep:  # caller's order / repeated indices
-                pos = {k: i for i, k in enumerate(uniq)}
-                r = r[torch.tensor([pos[k] for k in keep], dtype=torch.long, device=dev)]
-            out.append(r.T)
-        return out
+        return [_rows_in_order(r, uniq, keep).T for r, uniq, keep in zip(rows, uniqs, keeps)]
 
 
 @_launcher
@@ -853,15 +860,7 @@ def symeig_reduce_batched(mats, overwrite: bool = False, info_out: Optional[list
     one leading dimension per batch, ONE device->host read of the ``[B]`` ``info`` vector (``RuntimeError`` names the
     failing problem; a list passed as ``info_out`` receives the vector instead), and a
     :class:`PersistentKernelTimeout` repeats the batch once on the launch chains when the inputs are still there."""
-    mats = list(mats.unbind(0)) if isinstance(mats, torch.Tensor) and mats.dim() == 3 else list(mats)
-    if not mats:
-        raise ValueError("symeig_reduce_batched needs at least one matrix")
-    _require_device(*mats)
-    for G in mats:
-        if G.dim() != 2 or G.shape[0] != G.shape[1]:
-            raise ValueError(f"Input must be a square matrix. Got shape {tuple(G.shape)}.")
-        if G.shape != mats[0].shape:
-            raise ValueError(f"symeig_reduce_batched needs matrices of one size, got {tuple(mats[0].shape)} and {tuple(G.shape)}")
+    mats = _square_batch(mats, "symeig_reduce_batched")
     n, B, dev = mats[0].shape[0], len(mats), mats[0].device
     if n < SYMEIG_ROWS_MIN_N or n > SYMEIGVALS_BATCHED_MAX_N:
         plans = [symeig_reduce(G, overwrite=overwrite) for G in mats]
@@ -871,14 +870,7 @@ def symeig_reduce_batched(mats, overwrite: bool = False, info_out: Optional[list
     lib = _lib.load()
 
     def solve():
-        work = []
-        for G in mats:
-            A = _as2d(G)
-            if _ld(A) != n:
-                A = A.contiguous()   # one leading dimension for the whole batch
-            if A.data_ptr() == G.data_ptr() and not overwrite:
-                A = A.clone()  # the solver destroys its inputs
-            work.append(A)
+        work = _batch_work(mats, n, overwrite)
         W = torch.empty((B, n), dtype=torch.float32, device=dev)
         info = torch.zeros(B, dtype=torch.int32, device=dev)
         each = (lib.vivit_symeig_reduce_f32_workspace_bytes(n) + 256 + 255) // 256 * 256
@@ -894,20 +886,7 @@ def symeig_reduce_batched(mats, overwrite: bool = False, info_out: Optional[list
         plans = [SymeigPlan(W[b], n, A=work[b], state=state[b]) for b in range(B)]
         return SymeigBatchPlan(W, n, plans, work=work, state=state)
 
-    backups = [G.clone() for G in mats] if overwrite and all(_wants_backup(G) for G in mats) else None
-    try:
-        return solve()
-    except PersistentKernelTimeout:
-        if overwrite and backups is None:
-            raise
-        import warnings
-
-        warnings.warn("symeig_reduce_batched: persistent kernel timed out; repeating the batch on the launch chains", RuntimeWarning)
-        if backups is not None:
-            for G, b in zip(mats, backups):
-                G.copy_(b)
-        with persistent_kernels(False):
-            return solve()
+    return _retry_on_launch_chain(solve, intact=not overwrite, G=mats, what="symeig_reduce_batched")
 
 
 SYMEIG_ROWS_MIN_N = 193  # below: single-workgroup solver, no row-range entry point
