@@ -260,6 +260,24 @@ int vivit_norm_rules_f32(const float *M, const float *X, const float *gamma, con
  * summed serially over a, one thread per d.  pw or pb may be NULL. */
 int vivit_norm_position_sums_f32(const float *M, const float *X, const float *mean, const float *rstd, float *pw, float *pb, int64_t V,
                                  int64_t N, int64_t A, int64_t D, void *stream);
+/* Scaled dot-product self-attention on the packed projection (attention.hip; no counterpart in the reference's module map -- it
+ * replaces the generic rule of the factor provider, a recomputed forward and torch.autograd.grad(..., is_grads_batched=True) at
+ * vivit_amd/backend/extensions.py:_jac_t_mat_prod, for vivit_amd.backend.ScaledDotProductAttention).  The module input is
+ * qkv [N, T, 3 H d] = q | k | v with head h in columns h d .. (h + 1) d of each third, its output out [N, T, H d].  Per factor row
+ * v, sample n and head h, with dO = M[v, n, :, h]:
+ *   S = scale Q K^T (causal != 0: entries j > i masked),  P = softmax_rows(S),  D_i = sum_c dO_ic out_ic,
+ *   dV = P^T dO,  dP = dO V^T,  dS = P o (dP - D),  dQ = scale dS K,  dK = scale dS^T Q,   G[v, n] = dQ | dK | dV (packed as qkv).
+ * No T x T data is written to memory: the workspace holds the row log-sum-exp [N, H, T] and D [V, N, H, T]; the tiles of P are
+ * recomputed from it, once per workgroup for the factor rows it handles.  fp32 throughout (products on the fp32 matrix pipe), exp
+ * only of arguments from which the row maximum or the row log-sum-exp has been subtracted.  No atomics and a fixed summation
+ * order: the bytes of G[v, n] do not depend on V, N or the position of v and n.  Any T, H, V, N >= 1 and 1 <= d <= 128;
+ * VIVIT_E_UNSUPPORTED (nothing launched) for d > 128, for more chunks of factor rows than the launch grid's second dimension takes
+ * (a workgroup handles 2 rows for d > 32 and 4 otherwise, 65535 chunks: V above 131070 or 262140), and for sizes beyond the
+ * kernels' index arithmetic (3 H d, N H ceil(T / 32) or V N H T / 256 above 2^31 - 1, N H T above 2^40). */
+size_t vivit_attention_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t d);
+int vivit_attention_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
+                              int64_t H, int64_t d, float scale, int causal, void *workspace, size_t workspace_bytes,
+                              void *stream);
 /* Cross-entropy loss-Hessian square root from the logits [N, C]: p = softmax.  onehot == NULL (exact, V must equal C):
  * S[v, n, c] = sqrt(p_nv) (delta_vc - p_nc) scale;  onehot [V, N, C] (sampled): S[v, n, c] = (p_nc - onehot[v, n, c]) scale. */
 int vivit_ce_sqrt_hessian_f32(const float *logits, const float *onehot, float *S, int64_t N, int64_t C, int64_t V, float scale,

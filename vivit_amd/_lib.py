@@ -49,6 +49,8 @@ SIGNATURES = {
     "vivit_norm_stats_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _f32, _ptr]),
     "vivit_norm_rules_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr]),
     "vivit_norm_position_sums_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr]),
+    "vivit_attention_jac_t_f32_workspace_bytes": (_sz, [_i64] * 5),
+    "vivit_attention_jac_t_f32": (_int, [_ptr, _ptr, _ptr, _ptr] + [_i64] * 5 + [_f32, _int, _ptr, _sz, _ptr]),
     "vivit_ce_sqrt_hessian_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _f32, _ptr]),
     "vivit_symeig_f32_workspace_bytes": (_sz, [_i64, _int]),
     "vivit_symeig_f32": (_int, [_ptr, _i64, _i64, _ptr, _ptr, _i64, _ptr, _sz, _ptr, _ptr]),

@@ -74,3 +74,65 @@ class ScaleModule(nn.Module):
 
     def forward(self, x: Tensor) -> Tensor:
         return x * self.weight
+
+
+class ScaledDotProductAttention(nn.Module):
+    """Multi-head scaled dot-product self-attention on a packed projection (no counterpart in BackPACK): a parameter-free leaf.
+
+    Input ``qkv [N, T, 3 E]`` with ``q = qkv[..., :E]``, ``k = qkv[..., E:2 E]``, ``v = qkv[..., 2 E:]``; head ``h`` owns the columns
+    ``h d .. (h + 1) d`` of each third (``d = E / num_heads``, the layout of ``nn.MultiheadAttention``'s packed projection).  Output
+    ``[N, T, E]``: per head ``softmax(scale q k^T) v`` with ``scale = 1 / sqrt(d)`` by default; ``causal`` masks the keys ``j > i``.
+    No dropout and no other mask."""
+
+    def __init__(self, num_heads: int, causal: bool = False, scale: float = None):
+        super().__init__()
+        if num_heads < 1:
+            raise ValueError(f"num_heads must be positive, got {num_heads}")
+        self.num_heads, self.causal, self.scale = int(num_heads), bool(causal), scale
+
+    def head_dim(self, qkv: Tensor) -> int:
+        if qkv.dim() != 3:
+            raise ValueError(f"expected a packed projection [N, T, 3 E], got {qkv.dim()} dimensions")
+        if qkv.shape[2] == 0 or qkv.shape[2] % (3 * self.num_heads) != 0:
+            raise ValueError(f"the last dimension ({qkv.shape[2]}) is not 3 * {self.num_heads} heads * head dimension")
+        return qkv.shape[2] // (3 * self.num_heads)
+
+    def scale_for(self, d: int) -> float:
+        return float(self.scale) if self.scale is not None else d ** -0.5
+
+    def forward(self, qkv: Tensor) -> Tensor:
+        d = self.head_dim(qkv)
+        N, T, H = qkv.shape[0], qkv.shape[1], self.num_heads
+        q, k, v = qkv.view(N, T, 3, H, d).permute(2, 0, 3, 1, 4)          # each [N, H, T, d]
+        s = (q @ k.transpose(-1, -2)) * self.scale_for(d)
+        if self.causal:
+            s = s.masked_fill(torch.ones(T, T, dtype=torch.bool, device=qkv.device).triu(1), float("-inf"))
+        return (s.softmax(-1) @ v).transpose(1, 2).reshape(N, T, H * d)    # (a new tensor: the heads are gathered into a copy)
+
+
+class MultiheadSelfAttention(nn.Sequential):
+    """``Linear(E, 3 E)`` -> :class:`ScaledDotProductAttention` -> ``Linear(E, E)``: ``nn.MultiheadAttention(batch_first=True)``
+    applied to ``(x, x, x)`` as a container of single-input leaves, which is what the extensions' rules are written for."""
+
+    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True, causal: bool = False):
+        if embed_dim % num_heads != 0:
+            raise ValueError(f"embed_dim ({embed_dim}) is not divisible by num_heads ({num_heads})")
+        super().__init__(nn.Linear(embed_dim, 3 * embed_dim, bias=bias), ScaledDotProductAttention(num_heads, causal=causal),
+                         nn.Linear(embed_dim, embed_dim, bias=bias))
+
+    @classmethod
+    def from_torch(cls, mha: nn.MultiheadAttention, causal: bool = False) -> "MultiheadSelfAttention":
+        """A copy of ``mha``'s projections (packed rows q | k | v, as ``in_proj_weight`` has them)."""
+        if mha.kdim != mha.embed_dim or mha.vdim != mha.embed_dim or mha.in_proj_weight is None:
+            raise ValueError("nn.MultiheadAttention with equal q / k / v dimensions is required")
+        if not mha.batch_first or mha.bias_k is not None or mha.add_zero_attn or mha.dropout != 0.0:
+            raise ValueError("batch_first=True, no dropout, no bias_k / bias_v and no add_zero_attn are required")
+        w = mha.in_proj_weight
+        new = cls(mha.embed_dim, mha.num_heads, bias=mha.in_proj_bias is not None, causal=causal).to(device=w.device, dtype=w.dtype)
+        with torch.no_grad():
+            new[0].weight.copy_(w)
+            new[2].weight.copy_(mha.out_proj.weight)
+            if mha.in_proj_bias is not None:
+                new[0].bias.copy_(mha.in_proj_bias)
+                new[2].bias.copy_(mha.out_proj.bias)
+        return new

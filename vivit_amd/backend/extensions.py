@@ -17,7 +17,7 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from vivit_amd import _lib, kernels
-from vivit_amd.backend.custom_module import ActiveIdentity, Pad, ScaleModule, Slicing, SumModule
+from vivit_amd.backend.custom_module import ActiveIdentity, Pad, ScaledDotProductAttention, ScaleModule, Slicing, SumModule
 from vivit_amd.utils.ggn import Vmp
 from vivit_amd.utils.gram import mVp, pairwise_dot
 
@@ -477,13 +477,50 @@ def _single(v):
     return v if isinstance(v, int) else tuple(v)[0]
 
 
-def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor) -> Optional[Tensor]:
-    """The layer rules that have a HIP kernel (csrc/jacobians.hip, csrc/norm_rules.hip): activations (ReLU, Sigmoid, Tanh, LeakyReLU,
+def _attention_out(module, x: Tensor, subsampling) -> Tensor:
+    """The forward output of a :class:`ScaledDotProductAttention` for the samples of ``x``: what the forward pass left on the module,
+    sub-sampled as ``x`` was (repeated indices repeat rows).  Only a module that was called outside the engine has none: one forward.
+    An output that does not belong to ``x`` (samples, tokens, device or dtype) is an error, never a second forward."""
+    out = getattr(module, "output", None)
+    if out is None:
+        with torch.no_grad():
+            return module.forward(x)
+    out = subsample(out.detach(), 0, subsampling)
+    want = (*x.shape[:2], x.shape[2] // 3)
+    if tuple(out.shape) != want or out.device != x.device or out.dtype != x.dtype:
+        raise ValueError(f"ScaledDotProductAttention: module.output {tuple(out.shape)} {out.dtype} on {out.device} after sub-sampling "
+                         f"does not belong to the input {tuple(x.shape)} {x.dtype} on {x.device} (expected {want})")
+    return out
+
+
+def _attention_jac_t_torch(module, M: Tensor, x: Tensor, out: Tensor) -> Tensor:
+    """The rule of csrc/attention.hip in plain torch (non-HIP or non-fp32 tensors): ``M [V, N, T, E]``, ``x [N, T, 3 E]``,
+    ``out [N, T, E]`` -> ``[V, N, T, 3 E]``.  No autograd."""
+    d, H = module.head_dim(x), module.num_heads
+    scale = module.scale_for(d)
+    V, (N, T) = M.shape[0], x.shape[:2]
+    q, k, v = x.view(N, T, 3, H, d).permute(2, 0, 3, 1, 4)                       # each [N, H, T, d]
+    S = (q @ k.transpose(-1, -2)) * scale
+    if module.causal:
+        S = S.masked_fill(torch.ones(T, T, dtype=torch.bool, device=x.device).triu(1), float("-inf"))
+    P = S.softmax(-1)                                                             # [N, H, T, T], shared by the V slices
+    dO = M.reshape(V, N, T, H, d).permute(0, 1, 3, 2, 4)                          # [V, N, H, T, d]
+    D = (dO * out.view(N, T, H, d).permute(0, 2, 1, 3)).sum(-1, keepdim=True)
+    dV = P.transpose(-1, -2) @ dO
+    dS = P * (dO @ v.transpose(-1, -2) - D)
+    dQ, dK = (dS @ k) * scale, (dS.transpose(-1, -2) @ q) * scale
+    return torch.stack((dQ, dK, dV), 0).permute(1, 2, 4, 0, 3, 5).reshape(V, N, T, 3 * H * d)
+
+
+def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optional[Tensor]:
+    """The layer rules that have a HIP kernel (csrc/jacobians.hip, csrc/norm_rules.hip, csrc/attention.hip): activations (ReLU, Sigmoid, Tanh, LeakyReLU,
     LogSigmoid, ELU, SELU, GELU in both forms, SiLU), Flatten / Identity / ActiveIdentity / Dropout(eval), ScaleModule,
     Max/AvgPool1d/2d, Conv1d / Conv2d and ConvTranspose1d / 2d (any groups, zero padding), Pad / ZeroPad2d / Slicing,
     BatchNorm (eval), LayerNorm and GroupNorm (with or without affine parameters; the same visit of the factor serves their
-    parameter rules), and -- on the same two-dimensional kernels -- Conv3d, ConvTranspose3d, MaxPool3d, AvgPool3d.  ``None``: no
-    kernel for this module (custom modules, unsupported options such as ceil_mode) -- the generic autograd rule takes over."""
+    parameter rules), ScaledDotProductAttention (head dimensions up to 128; the forward output it needs is ``module.output``,
+    sub-sampled by ``subsampling`` as ``x`` was), and -- on the same two-dimensional kernels -- Conv3d, ConvTranspose3d, MaxPool3d,
+    AvgPool3d.  ``None``: no kernel for this module (custom modules, unsupported options such as ceil_mode) -- the generic autograd
+    rule takes over."""
     kind = _activation_kind(module)
     if kind is not None:
         return kernels.act_jac_t(M, x, *kind)
@@ -569,6 +606,14 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor) -> Optional[Tensor]:
             return g
     if isinstance(module, _NORMS):
         return _norm_rules(module, M, x, True)[0]
+    if isinstance(module, ScaledDotProductAttention):
+        # (a head dimension above the kernel's 128 has no kernel: the generic rule, before any operand is prepared; sizes beyond
+        # the kernel's index arithmetic come back as VIVIT_E_UNSUPPORTED and the caller falls through likewise)
+        d = module.head_dim(x)
+        if d > 128:
+            return None
+        return kernels.attention_jac_t(M.reshape(M.shape[0], *x.shape[:2], -1), x, _attention_out(module, x, subsampling), module.num_heads,
+                                       module.scale_for(d), module.causal)
     if isinstance(module, _BATCHNORM) and x.dim() >= 2:
         if _own_params(module):   # the parameter rules want the two row sums of the same pass
             return _bn_eval_rules(module, M, x)[0]
@@ -621,8 +666,19 @@ def _hip_convtranspose_jac_t(module, M: Tensor, x: Tensor) -> Optional[Tensor]:
     return out.squeeze(3) if one_d else out
 
 
-def _jac_t_mat_prod(module, M: Tensor, x: Tensor) -> Tensor:
-    """Apply the transposed input-Jacobian of ``module`` to ``M`` [V, N, *out] -> [V, N, *in]."""
+def _generic_jac_t_mat_prod(module, M: Tensor, x: Tensor) -> Tensor:
+    """The generic rule of :func:`_jac_t_mat_prod` for a module without a kernel: batched vector-Jacobian product through a recomputed
+    forward (bypasses hooks)."""
+    with torch.enable_grad():
+        xi = x.detach().requires_grad_(True)
+        y = module.forward(xi)
+        (g,) = torch.autograd.grad(y, xi, grad_outputs=M.reshape(M.shape[0], *y.shape), is_grads_batched=True)
+    return g
+
+
+def _jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Tensor:
+    """Apply the transposed input-Jacobian of ``module`` to ``M`` [V, N, *out] -> [V, N, *in].  ``subsampling``: the indices ``x`` was
+    sub-sampled with (rules that read ``module.output`` sub-sample it likewise)."""
     if isinstance(module, nn.Linear):   # (any number of extra dimensions between batch and features: linear.py:38-39)
         if M.is_cuda and M.dtype == torch.float32:
             O = M.shape[-1]
@@ -634,19 +690,16 @@ def _jac_t_mat_prod(module, M: Tensor, x: Tensor) -> Tensor:
         raise NotImplementedError("BatchNorm must be in eval mode")
     if M.is_cuda and M.dtype == torch.float32:
         try:
-            g = _hip_jac_t_mat_prod(module, M, x)
+            g = _hip_jac_t_mat_prod(module, M, x, subsampling)
         except _lib.VivitHipError as exc:  # a shape beyond a kernel's launch limits: the generic rule below
             if exc.status != _lib.VIVIT_E_UNSUPPORTED:
                 raise
             g = None
         if g is not None:
             return g
-    # generic rule: batched vector-Jacobian product through a recomputed forward (bypasses hooks)
-    with torch.enable_grad():
-        xi = x.detach().requires_grad_(True)
-        y = module.forward(xi)
-        (g,) = torch.autograd.grad(y, xi, grad_outputs=M.reshape(M.shape[0], *y.shape), is_grads_batched=True)
-    return g
+    elif isinstance(module, ScaledDotProductAttention):   # non-HIP or non-fp32 tensors: the same formula in torch
+        return _attention_jac_t_torch(module, M, x, _attention_out(module, x, subsampling))
+    return _generic_jac_t_mat_prod(module, M, x)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -755,7 +808,7 @@ class _SqrtGGN(_Extension):
         for name, p in _own_params(module):
             self._store(module, name, p, M, x)
         if module.input0.requires_grad:
-            ctx.put(self, module.input0, _jac_t_mat_prod(module, M, x))
+            ctx.put(self, module.input0, _jac_t_mat_prod(module, M, x, sub))
 
 
 class SqrtGGNExact(_SqrtGGN):

@@ -1,0 +1,444 @@
+// Scaled dot-product self-attention: the transposed input Jacobian applied to the sqrt-GGN factor (f1).  The module input is the
+// packed projection qkv [N, T, 3 E] (q | k | v, head h in columns h d .. (h + 1) d of each third, E = H d), its output O [N, T, E].
+// Per factor row v, sample n and head h, with dO = M[v, n, :, h]:
+//   S = scale Q K^T (+ causal mask),  P = softmax_rows(S),  D_i = sum_c dO_ic O_ic,
+//   dV = P^T dO,  dP = dO V^T,  dS = P o (dP - D),  dQ = scale dS K,  dK = scale dS^T Q,      G[v, n] = dQ | dK | dV (packed).
+// No T x T data leaves the chip.  Four launches:
+//   attn_lse_kernel    lse[n, h, i] = log sum_j exp(S_ij), online over key blocks with the running row maximum subtracted
+//   attn_rowdot_kernel D[v, n, h, i]
+//   attn_dkv_kernel    the KEY-block owner: K and V of its 32 keys stay in LDS, it walks the query blocks in ascending order and
+//                      accumulates dK and dV in registers
+//   attn_dq_kernel     the QUERY-block owner: Q and dO of its 32 queries stay in LDS, it walks the key blocks and accumulates dQ
+// A workgroup (256 threads, four waves) owns one block of one (n, h) for VC factor rows at a time: the tile P = exp(S - lse) of a
+// (query block, key block) pair is recomputed ONCE per workgroup and multiplies the dO of all VC rows; the accumulators of the VC
+// rows live in registers, which is what limits VC.  All products run on v_mfma_f32_16x16x4_f32 from LDS tiles whose
+// edges (rows beyond T, columns beyond d) are zero.  No atomics; every output element is the sum over the blocks in ascending order
+// of per-block sums over k in ascending order (the S and dP tiles: two interleaved chains, even and odd steps of four, added at
+// the end), so the bytes of G[v, n] depend on (T, H, d, scale, causal) and the data of (v, n) only.
+#include <math.h>
+
+#include "common.h"
+
+namespace vivit {
+
+constexpr int ATT_B = 32;          // queries per query block = keys per key block
+constexpr int ATT_LDP = 36;        // row pitch of the 32 x 32 tiles P and dS
+constexpr int ATT_D_MAX = 128;
+typedef float att_f32x4 __attribute__((ext_vector_type(4)));
+
+// NT = column tiles of 16 that hold a head (d <= 16 NT).  VC = factor rows per workgroup.
+template <int NT> struct AttCfg {
+  static constexpr int DP = 16 * NT;
+  static constexpr int LD = DP + 4;                      // row pitch of the [32][d] blocks
+  static constexpr int VC = NT >= 4 ? 2 : 4;
+  static constexpr int TPW = (2 * NT + 3) / 4;           // 16 x 16 tiles of a [32][DP] result per wave
+  static constexpr int BLK = ATT_B * LD;
+  static constexpr int TILE = ATT_B * ATT_LDP;
+  // floats of LDS: the lse launch holds Q, K and the S tile; the owners hold three operand blocks, VC blocks of dO, P, VC tiles
+  // dS, the row statistics lse[32] and D[VC][32]
+  static constexpr int LSE_FLOATS = 2 * BLK + ATT_B * 33;
+  static constexpr int OWN_FLOATS = (3 + VC) * BLK + (1 + VC) * TILE + ATT_B + VC * ATT_B;
+};
+
+// rows r0 .. r0 + 31 of a [T][stride] matrix, columns 0 .. d - 1 from `src` (already offset to the head) -> dst[32][LD]; rows
+// beyond T and columns d .. DP - 1 are zero.  vec: d % 4 == 0 and every row start is 16-byte aligned.
+template <int NT>
+__device__ __forceinline__ void att_load_block(float *__restrict__ dst, const float *__restrict__ src, int64_t stride, int r0, int T,
+                                               int d, bool vec) {
+  constexpr int DP = AttCfg<NT>::DP, LD = AttCfg<NT>::LD;
+  const int tid = threadIdx.x;
+  if (vec) {
+    constexpr int DP4 = DP / 4;
+    for (int idx = tid; idx < ATT_B * DP4; idx += 256) {
+      const int r = idx / DP4, c = 4 * (idx - r * DP4);
+      float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (r0 + r < T && c < d) q = *reinterpret_cast<const float4 *>(src + (int64_t)(r0 + r) * stride + c);
+      *reinterpret_cast<float4 *>(dst + r * LD + c) = q;
+    }
+  } else {
+    for (int idx = tid; idx < ATT_B * DP; idx += 256) {
+      const int r = idx / DP, c = idx - r * DP;
+      dst[r * LD + c] = (r0 + r < T && c < d) ? src[(int64_t)(r0 + r) * stride + c] : 0.f;
+    }
+  }
+}
+
+// C[i][j] = sum_c A[i][c] B[j][c] for one 16 x 16 tile; A, B: first row of the tile's rows in [..][LD] blocks; dk = d rounded up to 4.
+// The lane holds C[4 (lane >> 4) + e][lane & 15], e < 4.
+template <int NT>
+__device__ __forceinline__ att_f32x4 att_tile_nt(const float *__restrict__ A, const float *__restrict__ B, int dk, int lane) {
+  constexpr int LD = AttCfg<NT>::LD;
+  const float *a = A + (lane & 15) * LD + (lane >> 4), *b = B + (lane & 15) * LD + (lane >> 4);
+  att_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+  int c = 0;
+  for (; c + 8 <= dk; c += 8) {
+    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], b[c], acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c + 4], b[c + 4], acc1, 0, 0, 0);
+  }
+  if (c < dk) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], b[c], acc0, 0, 0, 0);
+  return acc0 + acc1;
+}
+
+// acc[r][c] += sum_{k < 32} At[k][r] Bm[k][c]: At a [32][ATT_LDP] tile (k-major), Bm a [32][LD] block; tile (rt, ct) of the result
+template <int NT>
+__device__ __forceinline__ att_f32x4 att_acc_tn(const float *__restrict__ At, const float *__restrict__ Bm, int rt, int ct, int lane,
+                                                att_f32x4 acc) {
+  constexpr int LD = AttCfg<NT>::LD;
+  const float *a = At + (lane >> 4) * ATT_LDP + 16 * rt + (lane & 15), *b = Bm + (lane >> 4) * LD + 16 * ct + (lane & 15);
+#pragma unroll
+  for (int k = 0; k < ATT_B; k += 4) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[k * ATT_LDP], b[k * LD], acc, 0, 0, 0);
+  return acc;
+}
+
+// acc[r][c] += sum_{k < 32} A[r][k] Bm[k][c]: A a [32][ATT_LDP] tile (row-major), Bm a [32][LD] block
+template <int NT>
+__device__ __forceinline__ att_f32x4 att_acc_nn(const float *__restrict__ A, const float *__restrict__ Bm, int rt, int ct, int lane,
+                                                att_f32x4 acc) {
+  constexpr int LD = AttCfg<NT>::LD;
+  const float *a = A + (16 * rt + (lane & 15)) * ATT_LDP + (lane >> 4), *b = Bm + (lane >> 4) * LD + 16 * ct + (lane & 15);
+#pragma unroll
+  for (int k = 0; k < ATT_B; k += 4) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[k], b[k * LD], acc, 0, 0, 0);
+  return acc;
+}
+
+struct AttGeom {
+  int N, T, H, d, KB;        // KB = blocks of 32 along T
+  int causal, vec;
+  float scale;
+};
+
+__device__ __forceinline__ bool att_valid(const AttGeom &g, int gi, int gj) {
+  return gi < g.T && gj < g.T && (!g.causal || gj <= gi);
+}
+
+// ---- row log-sum-exp --------------------------------------------------------------------------------------------------------------
+template <int NT>
+__global__ __launch_bounds__(256) void attn_lse_kernel(const float *__restrict__ qkv, float *__restrict__ lse, AttGeom g) {
+  extern __shared__ __attribute__((aligned(16))) float att_smem[];
+  using C = AttCfg<NT>;
+  float *sQ = att_smem, *sK = sQ + C::BLK, *sS = sK + C::BLK;   // sS [32][33]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t nh = blockIdx.x / g.KB;
+  const int ib = (int)(blockIdx.x - nh * g.KB), i0 = ib * ATT_B;
+  const int64_t n = nh / g.H;
+  const int h = (int)(nh - n * g.H), E = g.H * g.d, dk = (g.d + 3) & ~3;
+  const float *base = qkv + n * g.T * 3 * (int64_t)E + (int64_t)h * g.d;
+  att_load_block<NT>(sQ, base, 3 * (int64_t)E, i0, g.T, g.d, g.vec);
+  const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
+  const int row = tid >> 3, sub = tid & 7;
+  float m = -INFINITY, l = 0.f;
+  const int jb_end = g.causal ? ib : g.KB - 1;
+  for (int jb = 0; jb <= jb_end; ++jb) {
+    const int j0 = jb * ATT_B;
+    __syncthreads();   // the previous block's reads of sK and sS are done
+    att_load_block<NT>(sK, base + E, 3 * (int64_t)E, j0, g.T, g.d, g.vec);
+    __syncthreads();
+    const att_f32x4 s = att_tile_nt<NT>(sQ + 16 * ri * C::LD, sK + 16 * cj * C::LD, dk, lane);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int r = 16 * ri + 4 * kq + e, c = 16 * cj + j;
+      sS[r * 33 + c] = att_valid(g, i0 + r, j0 + c) ? s[e] * g.scale : -INFINITY;
+    }
+    __syncthreads();
+    // eight lanes per row, four columns each; every lane of a row keeps the same (m, l)
+    float x[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) x[q] = sS[row * 33 + 4 * sub + q];
+    float tm = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
+#pragma unroll
+    for (int off = 1; off < 8; off <<= 1) tm = fmaxf(tm, __shfl_xor(tm, off, 64));
+    const float mn = fmaxf(m, tm);
+    const float mref = mn == -INFINITY ? 0.f : mn;   // (a row with nothing unmasked so far: every term below is exp(-inf) = 0)
+    float ts = ((expf(x[0] - mref) + expf(x[1] - mref)) + expf(x[2] - mref)) + expf(x[3] - mref);
+#pragma unroll
+    for (int off = 1; off < 8; off <<= 1) ts += __shfl_xor(ts, off, 64);
+    l = l * expf(m - mref) + ts;
+    m = mn;
+  }
+  if (sub == 0 && i0 + row < g.T) lse[nh * g.T + i0 + row] = m + logf(l);
+}
+
+// ---- D[v, n, h, i] = sum_c M[v, n, i, h d + c] O[n, i, h d + c] --------------------------------------------------------------
+__global__ __launch_bounds__(256) void attn_rowdot_kernel(const float *__restrict__ M, const float *__restrict__ O, float *__restrict__ D,
+                                                          int64_t total, AttGeom g) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const int64_t vnh = e / g.T;
+  const int t = (int)(e - vnh * g.T);
+  const int64_t vn = vnh / g.H;
+  const int h = (int)(vnh - vn * g.H);
+  const int64_t n = vn % g.N, E = (int64_t)g.H * g.d;
+  const float *m = M + (vn * g.T + t) * E + (int64_t)h * g.d, *o = O + (n * g.T + t) * E + (int64_t)h * g.d;
+  float a = 0.f;
+  for (int c = 0; c < g.d; ++c) a = fmaf(m[c], o[c], a);
+  D[e] = a;
+}
+
+// what the two owners share: the dO blocks and D of the workgroup's factor rows for the query block at i0
+template <int NT>
+__device__ __forceinline__ void att_load_factor(float *__restrict__ sdO, float *__restrict__ sD, const float *__restrict__ M,
+                                                const float *__restrict__ Dws, const AttGeom &g, int64_t v0, int nv, int64_t n, int h,
+                                                int i0) {
+  using C = AttCfg<NT>;
+  const int64_t E = (int64_t)g.H * g.d;
+#pragma unroll
+  for (int vi = 0; vi < C::VC; ++vi)
+    if (vi < nv) {
+      const int64_t vn = (v0 + vi) * g.N + n;
+      att_load_block<NT>(sdO + vi * C::BLK, M + vn * g.T * E + (int64_t)h * g.d, E, i0, g.T, g.d, g.vec);
+      if (threadIdx.x < ATT_B)
+        sD[vi * ATT_B + threadIdx.x] = i0 + (int)threadIdx.x < g.T ? Dws[(vn * g.H + h) * g.T + i0 + threadIdx.x] : 0.f;
+    }
+}
+
+// one wave's 16 x 16 part of P = exp(S - lse) for the tile (query block at i0, key block at j0); zero where masked or beyond T
+template <int NT>
+__device__ __forceinline__ att_f32x4 att_p_tile(const float *__restrict__ sQ, const float *__restrict__ sK, const float *__restrict__ sL,
+                                                const AttGeom &g, int i0, int j0, int dk, int lane, int ri, int cj) {
+  using C = AttCfg<NT>;
+  const att_f32x4 s = att_tile_nt<NT>(sQ + 16 * ri * C::LD, sK + 16 * cj * C::LD, dk, lane);
+  att_f32x4 p;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int r = 16 * ri + 4 * (lane >> 4) + e, c = 16 * cj + (lane & 15);
+    p[e] = att_valid(g, i0 + r, j0 + c) ? expf(s[e] * g.scale - sL[r]) : 0.f;
+  }
+  return p;
+}
+
+// ---- key-block owner: dK and dV ---------------------------------------------------------------------------------------------------
+template <int NT>
+__global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__ M, const float *__restrict__ qkv,
+                                                       const float *__restrict__ lse, const float *__restrict__ Dws, float *__restrict__ G,
+                                                       int64_t V, AttGeom g) {
+  extern __shared__ __attribute__((aligned(16))) float att_smem[];
+  using C = AttCfg<NT>;
+  float *sK = att_smem, *sV = sK + C::BLK, *sQ = sV + C::BLK, *sdO = sQ + C::BLK;
+  float *sP = sdO + C::VC * C::BLK, *sdS = sP + C::TILE, *sL = sdS + C::VC * C::TILE, *sD = sL + ATT_B;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t nh = blockIdx.x / g.KB;
+  const int jb = (int)(blockIdx.x - nh * g.KB), j0 = jb * ATT_B;
+  const int64_t n = nh / g.H;
+  const int h = (int)(nh - n * g.H), dk = (g.d + 3) & ~3;
+  const int64_t E = (int64_t)g.H * g.d;
+  const int64_t v0 = (int64_t)blockIdx.y * C::VC;
+  const int nv = V - v0 < C::VC ? (int)(V - v0) : C::VC;
+  const float *base = qkv + n * g.T * 3 * E + (int64_t)h * g.d;
+  att_load_block<NT>(sK, base + E, 3 * E, j0, g.T, g.d, g.vec);
+  att_load_block<NT>(sV, base + 2 * E, 3 * E, j0, g.T, g.d, g.vec);
+  const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
+  att_f32x4 accK[C::VC][C::TPW], accV[C::VC][C::TPW];
+#pragma unroll
+  for (int vi = 0; vi < C::VC; ++vi)
+#pragma unroll
+    for (int u = 0; u < C::TPW; ++u) accK[vi][u] = accV[vi][u] = (att_f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int ib = g.causal ? jb : 0; ib < g.KB; ++ib) {
+    const int i0 = ib * ATT_B;
+    __syncthreads();   // the previous query block's tiles and operands have been read
+    att_load_block<NT>(sQ, base, 3 * E, i0, g.T, g.d, g.vec);
+    if (tid < ATT_B) sL[tid] = i0 + tid < g.T ? lse[nh * g.T + i0 + tid] : 0.f;
+    att_load_factor<NT>(sdO, sD, M, Dws, g, v0, nv, n, h, i0);
+    __syncthreads();
+    const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g, i0, j0, dk, lane, ri, cj);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sP[(16 * ri + 4 * kq + e) * ATT_LDP + 16 * cj + j] = p[e];
+#pragma unroll
+    for (int vi = 0; vi < C::VC; ++vi)
+      if (vi < nv) {
+        const att_f32x4 dp = att_tile_nt<NT>(sdO + vi * C::BLK + 16 * ri * C::LD, sV + 16 * cj * C::LD, dk, lane);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int r = 16 * ri + 4 * kq + e;
+          sdS[vi * C::TILE + r * ATT_LDP + 16 * cj + j] = p[e] * (dp[e] - sD[vi * ATT_B + r]);
+        }
+      }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < C::TPW; ++u) {
+      const int t = wave + 4 * u, rt = t & 1, ct = t >> 1;
+      if (t < 2 * NT && 16 * ct < g.d) {
+#pragma unroll
+        for (int vi = 0; vi < C::VC; ++vi)
+          if (vi < nv) {
+            accV[vi][u] = att_acc_tn<NT>(sP, sdO + vi * C::BLK, rt, ct, lane, accV[vi][u]);
+            accK[vi][u] = att_acc_tn<NT>(sdS + vi * C::TILE, sQ, rt, ct, lane, accK[vi][u]);
+          }
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < C::TPW; ++u) {
+    const int t = wave + 4 * u, rt = t & 1, ct = t >> 1, c = 16 * ct + j;
+    if (t < 2 * NT && c < g.d) {
+#pragma unroll
+      for (int vi = 0; vi < C::VC; ++vi)
+        if (vi < nv) {
+          float *gk = G + ((v0 + vi) * g.N + n) * g.T * 3 * E + E + (int64_t)h * g.d + c;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = j0 + 16 * rt + 4 * kq + e;
+            if (r < g.T) {
+              gk[(int64_t)r * 3 * E] = g.scale * accK[vi][u][e];
+              gk[(int64_t)r * 3 * E + E] = accV[vi][u][e];
+            }
+          }
+        }
+    }
+  }
+}
+
+// ---- query-block owner: dQ --------------------------------------------------------------------------------------------------------
+template <int NT>
+__global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ M, const float *__restrict__ qkv,
+                                                      const float *__restrict__ lse, const float *__restrict__ Dws, float *__restrict__ G,
+                                                      int64_t V, AttGeom g) {
+  extern __shared__ __attribute__((aligned(16))) float att_smem[];
+  using C = AttCfg<NT>;
+  float *sK = att_smem, *sV = sK + C::BLK, *sQ = sV + C::BLK, *sdO = sQ + C::BLK;
+  float *sdS = sdO + C::VC * C::BLK + C::TILE, *sL = sdS + C::VC * C::TILE, *sD = sL + ATT_B;   // (the P tile's room is unused here)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t nh = blockIdx.x / g.KB;
+  const int ib = (int)(blockIdx.x - nh * g.KB), i0 = ib * ATT_B;
+  const int64_t n = nh / g.H;
+  const int h = (int)(nh - n * g.H), dk = (g.d + 3) & ~3;
+  const int64_t E = (int64_t)g.H * g.d;
+  const int64_t v0 = (int64_t)blockIdx.y * C::VC;
+  const int nv = V - v0 < C::VC ? (int)(V - v0) : C::VC;
+  const float *base = qkv + n * g.T * 3 * E + (int64_t)h * g.d;
+  att_load_block<NT>(sQ, base, 3 * E, i0, g.T, g.d, g.vec);
+  if (tid < ATT_B) sL[tid] = i0 + tid < g.T ? lse[nh * g.T + i0 + tid] : 0.f;
+  att_load_factor<NT>(sdO, sD, M, Dws, g, v0, nv, n, h, i0);
+  const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
+  att_f32x4 accQ[C::VC][C::TPW];
+#pragma unroll
+  for (int vi = 0; vi < C::VC; ++vi)
+#pragma unroll
+    for (int u = 0; u < C::TPW; ++u) accQ[vi][u] = (att_f32x4){0.f, 0.f, 0.f, 0.f};
+  const int jb_end = g.causal ? ib : g.KB - 1;
+  for (int jb = 0; jb <= jb_end; ++jb) {
+    const int j0 = jb * ATT_B;
+    __syncthreads();   // the previous key block's tiles and operands have been read
+    att_load_block<NT>(sK, base + E, 3 * E, j0, g.T, g.d, g.vec);
+    att_load_block<NT>(sV, base + 2 * E, 3 * E, j0, g.T, g.d, g.vec);
+    __syncthreads();
+    const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g, i0, j0, dk, lane, ri, cj);
+#pragma unroll
+    for (int vi = 0; vi < C::VC; ++vi)
+      if (vi < nv) {
+        const att_f32x4 dp = att_tile_nt<NT>(sdO + vi * C::BLK + 16 * ri * C::LD, sV + 16 * cj * C::LD, dk, lane);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int r = 16 * ri + 4 * kq + e;
+          sdS[vi * C::TILE + r * ATT_LDP + 16 * cj + j] = p[e] * (dp[e] - sD[vi * ATT_B + r]);
+        }
+      }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < C::TPW; ++u) {
+      const int t = wave + 4 * u, rt = t & 1, ct = t >> 1;
+      if (t < 2 * NT && 16 * ct < g.d) {
+#pragma unroll
+        for (int vi = 0; vi < C::VC; ++vi)
+          if (vi < nv) accQ[vi][u] = att_acc_nn<NT>(sdS + vi * C::TILE, sK, rt, ct, lane, accQ[vi][u]);
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < C::TPW; ++u) {
+    const int t = wave + 4 * u, rt = t & 1, ct = t >> 1, c = 16 * ct + j;
+    if (t < 2 * NT && c < g.d) {
+#pragma unroll
+      for (int vi = 0; vi < C::VC; ++vi)
+        if (vi < nv) {
+          float *gq = G + ((v0 + vi) * g.N + n) * g.T * 3 * E + (int64_t)h * g.d + c;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int r = i0 + 16 * rt + 4 * kq + e;
+            if (r < g.T) gq[(int64_t)r * 3 * E] = g.scale * accQ[vi][u][e];
+          }
+        }
+    }
+  }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+struct AttPlan {
+  int status;            // VIVIT_OK, or why nothing is launched
+  size_t lse_bytes, bytes;
+  int64_t KB;
+};
+
+static AttPlan attention_plan(int64_t V, int64_t N, int64_t T, int64_t H, int64_t d) {
+  AttPlan p{VIVIT_OK, 0, 0, 0};
+  if (V <= 0 || N <= 0 || T <= 0 || H <= 0 || d <= 0) return p.status = VIVIT_E_BADARG, p;
+  if (d > ATT_D_MAX) return p.status = VIVIT_E_UNSUPPORTED, p;
+  // 32-bit quantities of the kernels: T + 32, 3 H d, the block index N H KB, the row-dot grid; 64-bit: every element offset
+  const int64_t lim = 0x7fffffffLL;
+  const int64_t VC = d > 32 ? 2 : 4;
+  p.KB = cdiv(T, ATT_B);
+  if (T > lim - ATT_B || H > lim / (3 * d) || N > lim / H || N * H > lim / p.KB || cdiv(V, VC) > 65535) return p.status = VIVIT_E_UNSUPPORTED, p;
+  const int64_t per_v = N * H * T;   // (< 2^62: three factors below 2^31 ... checked next with d and V)
+  if (per_v > (int64_t)1 << 40 || V > ((int64_t)1 << 58) / (per_v * 3 * d) || cdiv(V * per_v, 256) > lim) return p.status = VIVIT_E_UNSUPPORTED, p;
+  p.lse_bytes = align_up((size_t)per_v * 4, 256);
+  p.bytes = p.lse_bytes + (size_t)(V * per_v) * 4;
+  return p;
+}
+
+template <int NT>
+static int attention_launch(const float *M, const float *qkv, const float *out, float *G, float *lse, float *Dws, int64_t V,
+                            const AttGeom &g, hipStream_t s) {
+  using C = AttCfg<NT>;
+  static unsigned long long attr_done = 0;
+  constexpr int lse_lds = C::LSE_FLOATS * 4, own_lds = C::OWN_FLOATS * 4;
+  if (own_lds > 64 * 1024) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return VIVIT_E_LAUNCH;
+    if (!ensure_dynamic_lds(reinterpret_cast<const void *>(attn_dkv_kernel<NT>), own_lds, attr_done) ||
+        !ensure_dynamic_lds(reinterpret_cast<const void *>(attn_dq_kernel<NT>), own_lds, attr_done))
+      return VIVIT_E_LAUNCH;
+    attr_done |= 1ull << (dev & 63);
+  }
+  const int64_t NH = (int64_t)g.N * g.H, total = V * NH * g.T;
+  const unsigned blocks = (unsigned)(NH * g.KB);
+  attn_lse_kernel<NT><<<blocks, 256, lse_lds, s>>>(qkv, lse, g);
+  attn_rowdot_kernel<<<(unsigned)cdiv(total, 256), 256, 0, s>>>(M, out, Dws, total, g);
+  const dim3 grid(blocks, (unsigned)cdiv(V, C::VC));
+  attn_dkv_kernel<NT><<<grid, 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g);
+  attn_dq_kernel<NT><<<grid, 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g);
+  return launch_status();
+}
+
+static inline bool att_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+} // namespace vivit
+
+using namespace vivit;
+
+extern "C" {
+
+size_t vivit_attention_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t d) {
+  const AttPlan p = attention_plan(V, N, T, H, d);
+  return p.status == VIVIT_OK ? p.bytes : 0;
+}
+
+int vivit_attention_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T, int64_t H,
+                              int64_t d, float scale, int causal, void *workspace, size_t workspace_bytes, void *stream) {
+  if (!M || !qkv || !out || !G) return VIVIT_E_BADARG;
+  const AttPlan p = attention_plan(V, N, T, H, d);
+  if (p.status != VIVIT_OK) return p.status;
+  if (!workspace || workspace_bytes < p.bytes) return VIVIT_E_WORKSPACE;
+  AttGeom g;
+  g.N = (int)N, g.T = (int)T, g.H = (int)H, g.d = (int)d, g.KB = (int)p.KB;
+  g.causal = causal != 0;
+  g.vec = (d & 3) == 0 && att_aligned16(M) && att_aligned16(qkv);
+  g.scale = scale;
+  float *lse = static_cast<float *>(workspace);
+  float *Dws = reinterpret_cast<float *>(static_cast<char *>(workspace) + p.lse_bytes);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (d <= 16) return attention_launch<1>(M, qkv, out, G, lse, Dws, V, g, s);
+  if (d <= 32) return attention_launch<2>(M, qkv, out, G, lse, Dws, V, g, s);
+  if (d <= 64) return attention_launch<4>(M, qkv, out, G, lse, Dws, V, g, s);
+  return attention_launch<8>(M, qkv, out, G, lse, Dws, V, g, s);
+}
+
+} // extern "C"

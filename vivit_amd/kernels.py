@@ -500,6 +500,33 @@ def norm_position_sums(M, x, mean, rstd):
 
 
 @_launcher
+def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool):
+    """Transposed input Jacobian of scaled dot-product self-attention (``vivit_attention_jac_t_f32``): ``M [V, N, T, E]`` (the factor
+    at the module output), ``qkv [N, T, 3 E]`` (the module input, q | k | v), ``out [N, T, E]`` (the module output of the forward
+    pass) -> ``[V, N, T, 3 E]``.  ``E = num_heads * d``; no ``T x T`` tensor is allocated."""
+    _require_device(M, qkv, out)
+    M, qkv, out = M.contiguous(), qkv.contiguous(), out.contiguous()
+    if qkv.dim() != 3 or num_heads < 1 or qkv.shape[2] == 0 or qkv.shape[2] % (3 * num_heads) != 0:
+        raise ValueError(f"qkv must be [N, T, 3 * {num_heads} * d], got {tuple(qkv.shape)}")
+    N, T, E3 = qkv.shape
+    E = E3 // 3
+    if tuple(out.shape) != (N, T, E):
+        raise ValueError(f"out must be {(N, T, E)}, got {tuple(out.shape)}")
+    if M.dim() != 4 or tuple(M.shape[1:]) != (N, T, E):
+        raise ValueError(f"M must be [V, {N}, {T}, {E}], got {tuple(M.shape)}")
+    Vd, d = M.shape[0], E // num_heads
+    if Vd == 0 or N == 0 or T == 0:
+        raise ValueError(f"empty operands: M {tuple(M.shape)}")
+    G = torch.empty((Vd, N, T, E3), dtype=torch.float32, device=M.device)
+    lib = _lib.load()
+    ws, ws_bytes = _workspace(lib.vivit_attention_jac_t_f32_workspace_bytes(Vd, N, T, num_heads, d), M)
+    st = lib.vivit_attention_jac_t_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), G.data_ptr(), Vd, N, T, num_heads, d, float(scale),
+                                       int(bool(causal)), ws, ws_bytes, _stream(M))
+    _lib.check(st, "vivit_attention_jac_t_f32")
+    return G
+
+
+@_launcher
 def row_dot(M, X=None, rows_x: int = 1):
     """``out[r] = sum_l M[r, l] * (X[r % rows_x, l] if X is given else 1)`` for ``M [rows, L]`` (fixed summation order)."""
     _require_device(M, X)
