@@ -278,6 +278,45 @@ size_t vivit_attention_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T
 int vivit_attention_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
                               int64_t H, int64_t d, float scale, int causal, void *workspace, size_t workspace_bytes,
                               void *stream);
+/* nn.Embedding (embedding.hip; the reference has no rule for it): the weight factor Vt[v, n, w, :] = sum_{t: idx[n, t] = w} M[v, n, t, :]
+ * of the factor M [V, N, T, D] at the module output has at most T non-zero rows per (v, n) out of W = num_embeddings and is kept
+ * compact: ids [N, T] int32 holds sample n's distinct tokens in strictly increasing order in its first U_n slots and -1 in the rest,
+ * B [V, N, T, D] the sum of the rows of M[v, n] per slot (rows of -1 slots are zero).  fp32, no atomics, fixed summation orders.
+ * Every entry point: VIVIT_E_BADARG for a null pointer or a non-positive size, VIVIT_E_UNSUPPORTED (nothing launched) for sizes
+ * beyond the kernels' 32-bit index arithmetic (any size, D + 128 or N (T + 1) + 256 above 2^31 - 1, V N T D above 2^39 - 256).
+ *
+ * vivit_embedding_compact_f32 (vivit_amd/kernels.py:embedding_compact, which sorts each sample's tokens with torch): perm [N, T] are
+ * the positions t of sample n ordered by token, stably; slot u owns the seg_count[n, u] sorted positions from seg_start[n, u] on:
+ *   B[v, n, u, :] = sum_{j < seg_count[n, u]} M[v, n, perm[n, seg_start[n, u] + j], :]      (ascending j, i.e. ascending t) */
+int vivit_embedding_compact_f32(const float *M, const int32_t *perm, const int32_t *seg_start, const int32_t *seg_count, float *B,
+                                int64_t V, int64_t N, int64_t T, int64_t D, void *stream);
+/* The Gram matrix of the weight factor from its compact form (vivit_amd/backend/extensions.py:_embedding_closures, gram_mat):
+ *   G[v N + n, v' N + n'] = alpha sum_{u, u'} [ids[n, u] = ids[n', u'] >= 0] <B[v, n, u, :], B[v', n', u', :]> + beta G[..]
+ * G [V N, V N] contiguous; beta == 0: G is not read.  Output-stationary on v_mfma_f32_16x16x4_f32: a workgroup owns a pair of
+ * 16-sample blocks and 4 x 4 classes and walks the tokens the two blocks share in ascending order.  The bytes of a sample pair's
+ * V x V block depend on the two samples only; samples without a common token give exact zeros (for finite B: a sample that lacks a token of
+ * its block enters with a zero row, and 0 x inf is NaN); entries on and below the diagonal
+ * are computed and written to both positions, so alpha-term and result are exactly symmetric (for a symmetric G when beta != 0).
+ * Workspace: the token tables of the sample blocks, 4 (2 N T + N + 17 * 16 ceil(N / 16) T) bytes and alignment -- nothing of size
+ * W, (N T)^2 or per token.  VIVIT_E_UNSUPPORTED also for N above 16 * 65535 (the pairs of sample blocks are the grid's first dimension), V above 1020 or V N
+ * above 2^31 - 1. */
+size_t vivit_embedding_gram_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t D);
+int vivit_embedding_gram_f32(const float *B, const int32_t *ids, float *G, int64_t V, int64_t N, int64_t T, int64_t D, float alpha,
+                             float beta, void *workspace, size_t workspace_bytes, void *stream);
+/* V_mat_prod of the closures: out[f, w, :] = sum_{v, n, u: ids[n, u] = w} mat[f, v, n] B[v, n, u, :], out [F, W, D], mat [F, V, N].
+ * order [N T] int32: the entries n T + u stably sorted by token (vivit_amd/kernels.py:embedding_vmp sorts with torch); token w owns
+ * the positions tok_start[w] .. tok_start[w + 1] (tok_start [W + 1]).  One wave per (w, f) sums its members in that order; rows of
+ * absent tokens are zero.  VIVIT_E_UNSUPPORTED also for F above 65535. */
+int vivit_embedding_vmp_f32(const float *B, const int32_t *order, const int32_t *tok_start, const float *mat, float *out, int64_t F,
+                            int64_t V, int64_t N, int64_t T, int64_t D, int64_t W, void *stream);
+/* V_t_mat_prod of the closures: out[f, v, n] = sum_u <mat[f, ids[n, u], :], B[v, n, u, :]>, mat [F, W, D], out [F, V, N]; ids outside
+ * [0, W) are skipped.  VIVIT_E_UNSUPPORTED also for F V N above 2^31 - 1. */
+int vivit_embedding_vtmp_f32(const float *B, const int32_t *ids, const float *mat, float *out, int64_t F, int64_t V, int64_t N,
+                             int64_t T, int64_t D, int64_t W, void *stream);
+/* The explicit factor (vivit_amd/backend/extensions.py:_param_factor, and factor() of the closures): out [V, N, W, D] = zeros, then
+ * out[v, n, ids[n, u], :] = B[v, n, u, :] for ids[n, u] in [0, W).  VIVIT_E_UNSUPPORTED also for V N W D above 2^60. */
+int vivit_embedding_weight_mjp_f32(const float *B, const int32_t *ids, float *out, int64_t V, int64_t N, int64_t T, int64_t D,
+                                   int64_t W, void *stream);
 /* Cross-entropy loss-Hessian square root from the logits [N, C]: p = softmax.  onehot == NULL (exact, V must equal C):
  * S[v, n, c] = sqrt(p_nv) (delta_vc - p_nc) scale;  onehot [V, N, C] (sampled): S[v, n, c] = (p_nc - onehot[v, n, c]) scale. */
 int vivit_ce_sqrt_hessian_f32(const float *logits, const float *onehot, float *S, int64_t N, int64_t C, int64_t V, float scale,

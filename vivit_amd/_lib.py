@@ -51,6 +51,12 @@ SIGNATURES = {
     "vivit_norm_position_sums_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr]),
     "vivit_attention_jac_t_f32_workspace_bytes": (_sz, [_i64] * 5),
     "vivit_attention_jac_t_f32": (_int, [_ptr, _ptr, _ptr, _ptr] + [_i64] * 5 + [_f32, _int, _ptr, _sz, _ptr]),
+    "vivit_embedding_compact_f32": (_int, [_ptr] * 5 + [_i64] * 4 + [_ptr]),
+    "vivit_embedding_gram_f32_workspace_bytes": (_sz, [_i64] * 4),
+    "vivit_embedding_gram_f32": (_int, [_ptr, _ptr, _ptr] + [_i64] * 4 + [_f32, _f32, _ptr, _sz, _ptr]),
+    "vivit_embedding_vmp_f32": (_int, [_ptr] * 5 + [_i64] * 6 + [_ptr]),
+    "vivit_embedding_vtmp_f32": (_int, [_ptr] * 4 + [_i64] * 6 + [_ptr]),
+    "vivit_embedding_weight_mjp_f32": (_int, [_ptr] * 3 + [_i64] * 5 + [_ptr]),
     "vivit_ce_sqrt_hessian_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _f32, _ptr]),
     "vivit_symeig_f32_workspace_bytes": (_sz, [_i64, _int]),
     "vivit_symeig_f32": (_int, [_ptr, _i64, _i64, _ptr, _ptr, _i64, _ptr, _sz, _ptr, _ptr]),

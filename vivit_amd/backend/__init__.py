@@ -7,7 +7,7 @@ extension's ``savefield``, ``hook(module)`` called per module after its extensio
 provided here for feed-forward and residual nets (Linear, Conv1d/2d/3d, ConvTranspose1d/2d/3d, BatchNorm in
 eval mode, element-wise activations, pooling, Flatten, Dropout in eval mode, and the branching modules
 ``Parallel`` / ``SumModule`` / ``Pad`` / ``Slicing`` / ``ScaleModule`` of ``backpack.custom_module``, LayerNorm / GroupNorm,
-and the self-attention modules ``ScaledDotProductAttention`` / ``MultiheadSelfAttention`` of ``custom_module``;
+the self-attention modules ``ScaledDotProductAttention`` / ``MultiheadSelfAttention`` of ``custom_module``, and ``nn.Embedding``;
 CrossEntropyLoss / MSELoss with ``reduction='mean'``).  When the real BackPACK is importable the Computation classes can be used
 with it directly; this module is never imported in that case.
 

@@ -251,7 +251,42 @@ def _param_factor(module, name: str, M: Tensor, x: Tensor) -> Tensor:
             extra = tuple(range(2, M.dim() - len(module.normalized_shape)))
             return T.sum(extra) if extra else T
         return T.flatten(3).sum(3) if T.dim() > 3 else T
+    if isinstance(module, nn.Embedding):
+        B, ids = _embedding_compact(module, M, x)
+        return _embedding_factor(B, ids, module.num_embeddings)
     raise NotImplementedError(f"no parameter rule for {type(module).__name__}")
+
+
+def _embedding_compact(module, M: Tensor, idx: Tensor):
+    """Compact form ``(B [V, N, T, D], ids [N, T])`` of an Embedding's weight factor ``Vt[v, n, w] = sum_{t: idx[n, t] = w} M[v, n, t]``
+    (csrc/embedding.hip): sample n's distinct tokens in increasing order, then -1, and the rows of ``M [V, N, *, D]`` summed per token;
+    positions with ``idx == padding_idx`` contribute nothing.  Extra input dimensions are flattened into ``T``.  HIP fp32 tensors:
+    ``kernels.embedding_compact``; any other tensor: the same in plain torch (``index_add_``)."""
+    if module.max_norm is not None:        # the forward rewrites the weights
+        raise NotImplementedError("nn.Embedding with max_norm is not supported by the stand-in backend")
+    if module.scale_grad_by_freq:          # the gradient is rescaled per token
+        raise NotImplementedError("nn.Embedding with scale_grad_by_freq is not supported by the stand-in backend")
+    if idx.is_floating_point():
+        raise ValueError(f"nn.Embedding expects integer token ids, got {idx.dtype}")
+    V, N, D = M.shape[0], idx.shape[0], module.embedding_dim
+    M, idx = M.reshape(V, N, -1, D), idx.reshape(N, -1)
+    if M.is_cuda and M.dtype == torch.float32:
+        return kernels.embedding_compact(M, idx, module.padding_idx)
+    T = idx.shape[1]
+    ids, _, _, _, slot_of_t = kernels.embedding_token_slots(idx, module.padding_idx)
+    dest = slot_of_t + (T + 1) * torch.arange(N, device=idx.device).unsqueeze(1)     # padding positions go to a spare slot T
+    B = M.new_zeros((V, N * (T + 1), D)).index_add_(1, dest.reshape(-1), M.reshape(V, N * T, D))
+    return B.view(V, N, T + 1, D)[:, :, :T].contiguous(), ids
+
+
+def _embedding_factor(B: Tensor, ids: Tensor, W: int) -> Tensor:
+    """The explicit factor ``[V, N, W, D]`` from the compact form: zeros plus the rows ``B[v, n, u]`` at ``ids[n, u]``."""
+    if B.is_cuda and B.dtype == torch.float32:
+        return kernels.embedding_weight_mjp(B, ids, W)
+    V, N, T, D = B.shape
+    dest = ids.to(torch.int64).masked_fill(ids < 0, W) + (W + 1) * torch.arange(N, device=ids.device).unsqueeze(1)
+    out = B.new_zeros((V, N * (W + 1), D)).index_add_(1, dest.reshape(-1), B.reshape(V, N * T, D))
+    return out.view(V, N, W + 1, D)[:, :, :W].contiguous()
 
 
 _CONV_FN = {nn.Conv1d: F.conv1d, nn.Conv2d: F.conv2d, nn.Conv3d: F.conv3d, nn.ConvTranspose1d: F.conv_transpose1d,
@@ -890,6 +925,43 @@ def _linear_weight_closures(s: Tensor, z: Tensor):
             "shape_cn": (C, N), "dp_add": lambda acc: acc.add_linear(s, z)}
 
 
+def _embedding_closures(M: Tensor, idx: Tensor, module):
+    """Closures for an Embedding weight on the compact form ``(B, ids)`` of :func:`_embedding_compact`: the factor
+    ``V_t[c, n, w, :] = sum_{t: idx[n, t] = w} M[c, n, t, :]`` ([C, N, num_embeddings, D], at most T non-zero rows per (c, n)) exists
+    only when ``factor()`` or ``dp_add`` ask for it.
+
+    Gram: ``kernels.embedding_gram``, the products of the rows of samples that share a token; products: ``kernels.embedding_vmp`` /
+    ``embedding_vtmp``.  Non-HIP or non-fp32 tensors: the same formulas in plain torch (a masked einsum, ``index_add_``).
+    """
+    B, ids = _embedding_compact(module, M, idx)
+    C, N, T, D = B.shape
+    W = module.num_embeddings
+    hip = B.is_cuda and B.dtype == torch.float32
+
+    def gram_mat(out=None, beta=0.0):
+        if hip:
+            out2d = None if out is None else out.view(C * N, C * N)
+            return kernels.embedding_gram(B, ids, out=out2d, alpha=1.0, beta=beta).view(C, N, C, N)
+        same = (ids.view(N, T, 1, 1) == ids.view(1, 1, N, T)) & (ids.view(N, T, 1, 1) >= 0)
+        G = torch.einsum("cnud,emkd,numk->cnem", B, B, same.to(B.dtype)).contiguous()
+        if out is None:
+            return G
+        out.copy_(G + beta * out if beta != 0.0 else G)
+        return out
+
+    def factor():  # the explicit V_t; only asked for by the parameter side
+        return _embedding_factor(B, ids, W)
+
+    def V_mat_prod(mat):  # [F, C, N] -> [F, W, D]
+        return kernels.embedding_vmp(B, ids, mat, W) if hip else Vmp(factor(), mat, 2)
+
+    def V_t_mat_prod(mat):  # [F, W, D] -> [F, C, N]
+        return kernels.embedding_vtmp(B, ids, mat) if hip else mVp(factor(), mat, 2)
+
+    return {"V_mat_prod": V_mat_prod, "V_t_mat_prod": V_t_mat_prod, "gram_mat": gram_mat, "factor": factor,
+            "shape_cn": (C, N), "dp_add": lambda acc: _materialised_closures(factor())["dp_add"](acc)}
+
+
 class _ViViTGGN(_SqrtGGN):
     """Functional access to ``V``, ``V^T`` and the Gram matrix
     (vivit/extensions/secondorder/vivit/__init__.py:63-133)."""
@@ -897,6 +969,8 @@ class _ViViTGGN(_SqrtGGN):
     def _store(self, module, name, param, M, x):
         if isinstance(module, nn.Linear) and name == "weight" and M.dim() == 3:
             closures = _linear_weight_closures(M, x)
+        elif isinstance(module, nn.Embedding):
+            closures = _embedding_closures(M, x, module)
         else:
             closures = _materialised_closures(_param_factor(module, name, M, x))
         setattr(param, self.savefield, closures)

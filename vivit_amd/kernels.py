@@ -526,6 +526,139 @@ def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool):
     return G
 
 
+_I32_MAX = 2 ** 31 - 1
+
+
+def embedding_token_slots(idx, padding_idx=None):
+    """The slots of the compact form of an Embedding's weight factor, from the token ids ``idx [N, T]`` (any integer dtype) -- torch
+    ops on the device of ``idx``, no host synchronisation (plumbing shared by :func:`embedding_compact` and the torch rule of
+    non-HIP tensors).  Returns ``(ids, perm, seg_start, seg_count, slot_of_t)``, all ``[N, T]``: ``ids`` (int32) holds sample n's
+    distinct tokens in strictly increasing order and -1 in the unused slots; ``perm`` (int32) the positions ``t`` ordered by token,
+    stably; slot ``u`` owns the ``seg_count[n, u]`` sorted positions from ``seg_start[n, u]`` on (int32); ``slot_of_t`` (int64) is the
+    slot of position ``t``, ``T`` for a padding position.  Padding positions are sorted under the key 2^31 - 1, which no token the
+    kernels accept can have (ids are int32 and below ``num_embeddings``)."""
+    N, T = idx.shape
+    key = idx.to(torch.int64)
+    if padding_idx is not None:
+        key = key.masked_fill(key == padding_idx, _I32_MAX)       # padding sorts behind every token
+    sk, perm = torch.sort(key, dim=1, stable=True)
+    valid = sk != _I32_MAX if padding_idx is not None else torch.ones_like(sk, dtype=torch.bool)
+    new = torch.ones_like(valid)
+    new[:, 1:] = sk[:, 1:] != sk[:, :-1]
+    slot = new.cumsum(1) - 1                                      # slot of every sorted position
+    ids = torch.full((N, T), -1, dtype=torch.int64, device=idx.device)
+    ids.scatter_(1, slot, sk.masked_fill(~valid, -1))             # (the writes that meet in a slot carry the same value)
+    cnt = torch.zeros((N, T), dtype=torch.int64, device=idx.device).scatter_add_(1, slot, valid.to(torch.int64))
+    start = cnt.cumsum(1) - cnt
+    slot_of_t = torch.empty_like(slot).scatter_(1, perm, slot.masked_fill(~valid, T))
+    return ids.to(torch.int32), perm.to(torch.int32), start.to(torch.int32), cnt.to(torch.int32), slot_of_t
+
+
+def _embedding_operands(B, ids):
+    _require_device(B)
+    if B.dim() != 4 or B.numel() == 0:
+        raise ValueError(f"B must be a non-empty [V, N, T, D] tensor, got {tuple(B.shape)}")
+    if not ids.is_cuda or ids.device != B.device or ids.dtype != torch.int32 or tuple(ids.shape) != tuple(B.shape[1:3]):
+        raise ValueError(f"ids must be an int32 [{B.shape[1]}, {B.shape[2]}] tensor on {B.device}, got {ids.dtype} {tuple(ids.shape)} on {ids.device}")
+    return B.contiguous(), ids.contiguous()
+
+
+@_launcher
+def embedding_compact(M, idx, padding_idx=None):
+    """Compact form of an Embedding's weight factor (``vivit_embedding_compact_f32``): ``M [V, N, T, D]`` (the factor at the module
+    output), ``idx [N, T]`` (integer token ids) -> ``(B [V, N, T, D], ids [N, T] int32)``.  ``ids[n]``: sample n's distinct tokens,
+    strictly increasing, then -1; ``B[v, n, u]``: the sum of the rows of ``M[v, n]`` whose token is ``ids[n, u]`` in ascending ``t``,
+    zero for a -1 slot.  Positions with ``idx == padding_idx`` contribute nothing.  The per-sample sort is torch's, on the device."""
+    _require_device(M)
+    if M.dim() != 4 or M.numel() == 0:
+        raise ValueError(f"M must be a non-empty [V, N, T, D] tensor, got {tuple(M.shape)}")
+    if idx.is_floating_point() or idx.device != M.device or tuple(idx.shape) != tuple(M.shape[1:3]):
+        raise ValueError(f"idx must be an integer [{M.shape[1]}, {M.shape[2]}] tensor on {M.device}, got {idx.dtype} {tuple(idx.shape)} on {idx.device}")
+    M = M.contiguous()
+    V, N, T, D = M.shape
+    ids, perm, start, cnt, _ = embedding_token_slots(idx, padding_idx)
+    B = torch.empty_like(M)
+    st = _lib.load().vivit_embedding_compact_f32(M.data_ptr(), perm.data_ptr(), start.data_ptr(), cnt.data_ptr(), B.data_ptr(), V, N, T, D,
+                                                 _stream(M))
+    _lib.check(st, "vivit_embedding_compact_f32")
+    return B, ids
+
+
+@_launcher
+def embedding_gram(B, ids, out=None, alpha: float = 1.0, beta: float = 0.0):
+    """``out = alpha * G + beta * out`` with the Gram matrix ``G [V N, V N]`` (rows ``v N + n``) of an Embedding's weight factor from
+    its compact form (``vivit_embedding_gram_f32``): ``G[(v, n), (v', n')] = sum_{u, u'} [ids[n, u] = ids[n', u'] >= 0]
+    <B[v, n, u], B[v', n', u']>``.  Exactly symmetric; exact zeros for samples without a common token; no tensor with an axis of
+    length ``num_embeddings``."""
+    B, ids = _embedding_operands(B, ids)
+    _require_device(out)
+    V, N, T, D = B.shape
+    n = V * N
+    if out is None:
+        out = torch.empty((n, n), dtype=torch.float32, device=B.device)
+        beta = 0.0
+    if not out.is_contiguous() or tuple(out.shape) != (n, n):
+        raise ValueError(f"out must be a contiguous [{n}, {n}] matrix")
+    _check_out(out, n, n, B)
+    lib = _lib.load()
+    ws, ws_bytes = _workspace(lib.vivit_embedding_gram_f32_workspace_bytes(V, N, T, D), B)
+    st = lib.vivit_embedding_gram_f32(B.data_ptr(), ids.data_ptr(), out.data_ptr(), V, N, T, D, alpha, beta, ws, ws_bytes, _stream(B))
+    _lib.check(st, "vivit_embedding_gram_f32")
+    return out
+
+
+@_launcher
+def embedding_vmp(B, ids, mat, W: int):
+    """``out[f, w, :] = sum_{v, n, u: ids[n, u] = w} mat[f, v, n] * B[v, n, u, :]`` (``vivit_embedding_vmp_f32``): ``mat [F, V, N]`` ->
+    ``[F, W, D]``, rows of absent tokens zero.  The token-major member list (a stable sort of the entries by token) is torch's."""
+    B, ids = _embedding_operands(B, ids)
+    _require_device(mat)
+    V, N, T, D = B.shape
+    if mat.dim() != 3 or tuple(mat.shape[1:]) != (V, N) or mat.shape[0] == 0 or W < 1:
+        raise ValueError(f"mat must be [F, {V}, {N}] with F >= 1 and W >= 1, got {tuple(mat.shape)}, W = {W}")
+    mat = mat.contiguous()
+    F_ = mat.shape[0]
+    flat = ids.reshape(-1).to(torch.int64)
+    sk, order = torch.sort(flat.masked_fill(flat < 0, W), stable=True)
+    tok_start = torch.searchsorted(sk, torch.arange(W + 1, device=B.device)).to(torch.int32)
+    order = order.to(torch.int32)
+    out = torch.empty((F_, W, D), dtype=torch.float32, device=B.device)
+    st = _lib.load().vivit_embedding_vmp_f32(B.data_ptr(), order.data_ptr(), tok_start.data_ptr(), mat.data_ptr(), out.data_ptr(), F_, V, N, T,
+                                             D, W, _stream(B))
+    _lib.check(st, "vivit_embedding_vmp_f32")
+    return out
+
+
+@_launcher
+def embedding_vtmp(B, ids, mat):
+    """``out[f, v, n] = sum_u <mat[f, ids[n, u], :], B[v, n, u, :]>`` (``vivit_embedding_vtmp_f32``): ``mat [F, W, D]`` -> ``[F, V, N]``."""
+    B, ids = _embedding_operands(B, ids)
+    _require_device(mat)
+    V, N, T, D = B.shape
+    if mat.dim() != 3 or mat.shape[2] != D or mat.shape[0] == 0 or mat.shape[1] == 0:
+        raise ValueError(f"mat must be a non-empty [F, W, {D}] tensor, got {tuple(mat.shape)}")
+    mat = mat.contiguous()
+    F_, W = mat.shape[:2]
+    out = torch.empty((F_, V, N), dtype=torch.float32, device=B.device)
+    st = _lib.load().vivit_embedding_vtmp_f32(B.data_ptr(), ids.data_ptr(), mat.data_ptr(), out.data_ptr(), F_, V, N, T, D, W, _stream(B))
+    _lib.check(st, "vivit_embedding_vtmp_f32")
+    return out
+
+
+@_launcher
+def embedding_weight_mjp(B, ids, W: int):
+    """The explicit weight factor ``[V, N, W, D]`` of an Embedding from its compact form (``vivit_embedding_weight_mjp_f32``): zeros,
+    then ``out[v, n, ids[n, u]] = B[v, n, u]``."""
+    B, ids = _embedding_operands(B, ids)
+    V, N, T, D = B.shape
+    if W < 1:
+        raise ValueError(f"W must be positive, got {W}")
+    out = torch.empty((V, N, W, D), dtype=torch.float32, device=B.device)
+    st = _lib.load().vivit_embedding_weight_mjp_f32(B.data_ptr(), ids.data_ptr(), out.data_ptr(), V, N, T, D, W, _stream(B))
+    _lib.check(st, "vivit_embedding_weight_mjp_f32")
+    return out
+
+
 @_launcher
 def row_dot(M, X=None, rows_x: int = 1):
     """``out[r] = sum_l M[r, l] * (X[r % rows_x, l] if X is given else 1)`` for ``M [rows, L]`` (fixed summation order)."""
