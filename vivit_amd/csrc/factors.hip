@@ -258,6 +258,7 @@ __global__ __launch_bounds__(CWM_THREADS) void conv2d_weight_mjp_mfma_kernel(con
 }
 
 // LDS bytes of the matrix-pipe kernel for a geometry (0: it does not apply) and the number of position splits
+// (tests/conv_refs.py::weight_plan mirrors this planner: change them together)
 static size_t conv2d_weight_mjp_mfma_lds(const Conv2dGeom &g, int *splits, int *threads) {
   static int on = -1;
   if (on < 0) {

@@ -376,7 +376,9 @@ struct ConvJtPlan {
   size_t lds;
   int CC, S, threads, RT;
 };
-// the matrix-pipe kernel's plan for a geometry (lds = 0: it does not apply)
+// the matrix-pipe kernel's plan for a geometry (lds = 0: it does not apply).  No floor on the problem size: the plan is only
+// asked for slices the scalar kernel cannot hold, so a tiny one (128 x 3 x 3 on a 1 x 1 plane) has nowhere else to go.
+// (tests/conv_refs.py::input_plan mirrors this planner and the dispatch of vivit_conv2d_jac_t_f32: change them together)
 static ConvJtPlan conv2d_jac_t_mfma_plan(const ConvGeom &g) {
   static int on = -1;
   if (on < 0) {
@@ -388,7 +390,6 @@ static ConvJtPlan conv2d_jac_t_mfma_plan(const ConvGeom &g) {
   const int64_t KK = (int64_t)g.KH * g.KW;
   const int64_t Bh = (g.KH - 1) * g.dh > g.ph ? (g.KH - 1) * g.dh - g.ph : 0, Bw = (g.KW - 1) * g.dw > g.pw ? (g.KW - 1) * g.dw - g.pw : 0;
   const int64_t plane = (g.H + g.ph + Bh) * (g.W + g.pw + Bw), HW = (int64_t)g.H * g.W;
-  if (HW * g.Cout * KK < 4096) return p;   // (tiny problems: the scalar kernel's launch is cheaper)
   p.RT = (g.Cin < CJM_IC ? g.Cin : CJM_IC) > 16 ? 2 : 1;
   const int64_t WS = 16 * p.RT + 1;
   auto floats = [&](int64_t cc) { const int64_t qp = (cc * KK + 3) & ~3LL; return ((cc * plane + 3) & ~3LL) + qp * WS + qp; };
