@@ -1,5 +1,5 @@
 """fp64 reference and derived error bounds for the attention rule (csrc/attention.hip, ``vivit_attention_jac_t_f32``).  TEST
-INFRASTRUCTURE shared by tests/test_attention_rule_gpu.py; in the manner of tests/norm_refs.py.
+INFRASTRUCTURE shared by tests/test_attention_rule_gpu.py and tests/test_attention_refs_host.py; in the manner of tests/norm_refs.py.
 
 The reference restates the formula of include/vivit_hip.h in torch fp64 from the fp32 operands the kernel is given (the factor ``M``,
 the packed projection ``qkv`` and the module output ``out``: an fp32 INPUT of the rule, used as it is).
@@ -35,11 +35,41 @@ import math
 
 import torch
 
-from epilogue_refs import EPS, F64, gen, within   # noqa: F401  (re-exported for the test module)
+from epilogue_refs import EPS, F64, gen, misaligned, within   # noqa: F401  (re-exported for the test modules)
 
 FLT_MIN = 2.0 ** -126
 BLOCK = 32        # queries per query block = keys per key block (ATT_B of csrc/attention.hip)
 D_MAX = 128       # largest head dimension the kernel takes
+TB = 2 * BLOCK + 1   # both owners walk three blocks, the last one ragged
+
+
+def chunk(d):
+    """Factor rows a workgroup takes at a time (AttCfg<NT>::VC of csrc/attention.hip)."""
+    return 2 if d > 32 else 4
+
+
+# The cases of tests/test_attention_rule_gpu.py (shared with tests/test_attention_refs_host.py), (T, d, H, V, N, causal, scale).
+# The kernel has four instances (d <= 16, <= 32, <= 64, <= 128) and takes chunk(d) factor rows per workgroup.  The rule of the list:
+# every instance meets a V of zero, one and two full chunks plus a remainder (and full chunks without one), every instance meets
+# its smallest and its largest d, and T is listed both as exact multiples of 32 (32, 64) and as ragged lengths (1, 5, 16, 17, 33,
+# TB = 65); H in {1, 2, 3}, N in {1, 2}, both masks; a negative and a zero scale once each.
+CASES = [(1, 1, 1, 1, 1, False, None), (1, 4, 3, 3, 2, True, None), (1, 128, 1, 3, 1, False, None),
+         (5, 20, 3, 1, 2, True, None), (5, 64, 1, 3, 1, False, None),
+         (16, 4, 1, 3, 2, False, None), (16, 128, 3, 1, 1, True, None),
+         (17, 1, 3, 3, 2, True, None), (17, 64, 1, 1, 2, False, 0.37), (17, 20, 3, 3, 1, False, None),
+         (33, 20, 1, 3, 1, False, None), (33, 128, 3, 3, 2, True, None), (33, 4, 3, 1, 2, True, None),
+         (TB, 4, 3, 1, 2, False, None), (TB, 64, 3, 3, 2, True, None), (TB, 128, 1, 3, 1, False, None), (TB, 20, 1, 3, 2, True, 0.5),
+         (TB, 1, 1, 3, 1, True, None), (TB, 64, 1, 1, 1, False, None),
+         # chunks of four rows (d <= 32): V = 4, 5, 8, 9
+         (5, 1, 1, 4, 1, False, None), (33, 4, 1, 5, 1, True, None), (32, 16, 2, 5, 2, True, None), (17, 16, 2, 8, 1, False, None),
+         (TB, 20, 1, 9, 2, True, None), (32, 32, 3, 8, 1, False, None), (33, 16, 1, 9, 1, True, None), (17, 32, 1, 6, 2, False, None),
+         # chunks of two rows (d > 32): V = 4, 5
+         (33, 64, 1, 4, 1, False, None), (17, 128, 1, 5, 1, True, None), (TB, 33, 2, 4, 1, True, None), (17, 64, 2, 5, 1, True, None),
+         # the edges of the instances, and sequences that are whole blocks
+         (64, 17, 1, 9, 1, False, None), (64, 32, 1, 3, 1, True, None), (33, 65, 1, 5, 2, False, -0.5), (64, 127, 1, 2, 1, True, None),
+         (TB, 128, 1, 5, 1, True, None), (32, 33, 1, 1, 1, False, None),
+         # scale 0: P is uniform over the unmasked keys, dQ and dK are exactly zero
+         (33, 20, 2, 5, 1, True, 0.0)]
 
 
 def forward(qkv, H, scale, causal):

@@ -11,17 +11,7 @@ from vivit_amd.backend.extensions import _jac_t_mat_prod
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-TB = 2 * ar.BLOCK + 1   # both owners walk three blocks, the last one ragged
-
-# (T, d, H, V, N, causal, scale): a pruned product of T in {1, 5, 16, 17, 33, TB}, d in {1, 4, 20, 64, 128}, H in {1, 3}, V in {1, 3},
-# N in {1, 2}, both masks; every T meets a d of each kernel instance (d <= 16, <= 32, <= 64, <= 128) at least once across the list
-CASES = [(1, 1, 1, 1, 1, False, None), (1, 4, 3, 3, 2, True, None), (1, 128, 1, 3, 1, False, None),
-         (5, 20, 3, 1, 2, True, None), (5, 64, 1, 3, 1, False, None),
-         (16, 4, 1, 3, 2, False, None), (16, 128, 3, 1, 1, True, None),
-         (17, 1, 3, 3, 2, True, None), (17, 64, 1, 1, 2, False, 0.37), (17, 20, 3, 3, 1, False, None),
-         (33, 20, 1, 3, 1, False, None), (33, 128, 3, 3, 2, True, None), (33, 4, 3, 1, 2, True, None),
-         (TB, 4, 3, 1, 2, False, None), (TB, 64, 3, 3, 2, True, None), (TB, 128, 1, 3, 1, False, None), (TB, 20, 1, 3, 2, True, 0.5),
-         (TB, 1, 1, 3, 1, True, None), (TB, 64, 1, 1, 1, False, None)]
+TB, CASES = ar.TB, ar.CASES   # the list and its rule: tests/attention_refs.py
 
 
 def run(M, qkv, out, H, scale, causal):
@@ -44,7 +34,11 @@ def check(G, M, qkv, out, H, scale, causal):
 @pytest.mark.parametrize("T,d,H,V,N,causal,scale", CASES)
 def test_edge_shapes(T, d, H, V, N, causal, scale):
     M, qkv, out, scale = ar.make_case(1000 * T + d, V, N, T, H, d, scale, causal)
-    check(run(M, qkv, out, H, scale, causal), M, qkv, out, H, scale, causal)
+    G = run(M, qkv, out, H, scale, causal)
+    check(G, M, qkv, out, H, scale, causal)
+    if scale == 0.0:
+        assert bool((G[..., :2 * H * d] == 0).all())                     # dQ and dK
+        assert bool((G[..., 2 * H * d:].abs().amax((0, 2, 3)) > 0).all())    # dV does not depend on the scale
 
 
 @pytest.mark.parametrize("causal", [False, True])
@@ -65,6 +59,36 @@ def test_bytes_do_not_depend_on_the_call_or_the_batch(d):
     assert torch.equal(G1, G2)
     alone = run(M[1:2, 2:3].contiguous(), qkv[2:3].contiguous(), out[2:3].contiguous(), H, scale, True)
     assert torch.equal(G1[1, 2], alone[0, 0])
+    # rows of a later chunk, of a chunk's last place and of a ragged last chunk: chunks 4, 4, 1 (d = 20) and 2, 2, 1 (d = 64)
+    V, rows = (9, (3, 4, 8)) if d == 20 else (5, (1, 2, 4))
+    assert V == 2 * ar.chunk(d) + 1
+    M, qkv, out, scale = ar.make_case(13 + d, V, N, T, H, d, None, True)
+    G = run(M, qkv, out, H, scale, True)
+    check(G, M, qkv, out, H, scale, True)
+    for v in rows:
+        alone = run(M[v:v + 1].contiguous(), qkv, out, H, scale, True)
+        assert torch.equal(G[v], alone[0]), v
+
+
+@pytest.mark.parametrize("which", ["M", "qkv"])
+@pytest.mark.parametrize("d", [4, 20, 64, 128])
+def test_operand_four_bytes_off_a_16_byte_boundary(d, which):
+    """d % 4 == 0 with an operand that is not 16-byte aligned: the scalar load body of every instance.  The loads change, the
+    arithmetic does not: the bytes are those of the aligned call."""
+    V, N, T, H = 3, 1, 33, 1
+    M, qkv, out, scale = ar.make_case(17 + d, V, N, T, H, d, None, True)
+    Md, qd, od = M.to(DEV), qkv.to(DEV), out.to(DEV)
+    assert Md.data_ptr() % 16 == 0 and qd.data_ptr() % 16 == 0
+    aligned = kernels.attention_jac_t(Md, qd, od, H, scale, True)
+    if which == "M":
+        Md = ar.misaligned(Md)
+        assert Md.data_ptr() % 16 == 4 and Md.is_contiguous()
+    else:
+        qd = ar.misaligned(qd)
+        assert qd.data_ptr() % 16 == 4 and qd.is_contiguous()
+    G = kernels.attention_jac_t(Md, qd, od, H, scale, True)
+    check(G, M, qkv, out, H, scale, True)
+    assert torch.equal(G, aligned)
 
 
 @pytest.mark.parametrize("j0", [19, 32])

@@ -11,14 +11,7 @@ from vivit_amd import kernels
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
-# (T, D, V, N, W, pattern, padding_idx): a pruned product of T in {1, 2, 5, 17}, D in {1, 3, 4, 20, 64, 67}, V in {1, 3},
-# N in {1, 2, 17, 33} (17 and 33 cross one and two sample-block edges), W in {1, 2, 7, 50} and the five token patterns
-CASES = [(1, 1, 1, 1, 1, "equal", None), (1, 3, 3, 2, 2, "random", None), (1, 4, 1, 17, 7, "random", 0), (1, 64, 3, 33, 50, "distinct", None),
-         (2, 1, 3, 17, 50, "distinct", None), (2, 20, 1, 33, 7, "random", None), (2, 67, 3, 2, 2, "equal", None), (2, 4, 3, 2, 7, "onepad", 0),
-         (5, 3, 1, 1, 1, "equal", None), (5, 4, 3, 17, 7, "random", 0), (5, 20, 3, 2, 50, "distinct", None), (5, 64, 1, 33, 50, "onepad", 0),
-         (5, 67, 3, 33, 7, "random", None), (5, 20, 3, 17, 7, "allpad", 0),
-         (17, 1, 3, 2, 7, "random", None), (17, 3, 3, 17, 50, "random", 3), (17, 20, 1, 2, 1, "equal", None), (17, 64, 3, 17, 2, "random", None),
-         (17, 67, 1, 33, 50, "random", 0), (17, 4, 3, 33, 50, "allpad", 0), (17, 20, 3, 33, 50, "onepad", 5), (17, 64, 3, 33, 7, "equal", None)]
+CASES = er.CASES   # the list and what it is a product of: tests/embedding_refs.py
 
 
 def report(name, got, ref, bound):
@@ -55,9 +48,9 @@ def check_gram(case, G, alpha=1.0, beta=0.0, G0=None):
         assert bool((blocks.permute(1, 3, 0, 2)[disjoint] == 0).all())                  # no common token: an exactly zero V x V block
 
 
-@pytest.mark.parametrize("T,D,V,N,W,pattern,pad", CASES)
-def test_edge_shapes(T, D, V, N, W, pattern, pad):
-    case = er.make_case(100000 * T + 1000 * D + 10 * N + V, V, N, T, D, W, pattern, pad)
+def check_all(case, pattern):
+    """Every kernel of the rule on one case: compact, gram (symmetry, exact zero blocks), weight_mjp, vmp, vtmp."""
+    V, N, D, W = case.V, case.N, case.D, case.W
     B, ids = compact(case)
     check_compact(case, B, ids)
     G = kernels.embedding_gram(B, ids)
@@ -86,6 +79,70 @@ def test_edge_shapes(T, D, V, N, W, pattern, pad):
     report("vtmp", out, ref, bound)
     ok, msg = er.within(out.cpu(), torch.einsum("fwd,vnwd->fvn", mat.double(), Vt.cpu().double()), 2 * bound)
     assert ok, f"vtmp against mat @ factor^T: {msg}"
+
+
+@pytest.mark.parametrize("T,D,V,N,W,pattern,pad", CASES)
+def test_edge_shapes(T, D, V, N, W, pattern, pad):
+    check_all(er.case_of(T, D, V, N, W, pattern, pad), pattern)
+
+
+@pytest.mark.parametrize("N,T,S,V,D", er.STAIRCASE_CASES)
+def test_token_tables_at_the_edge_of_a_join_pass(N, T, S, V, D):
+    """Staircase token patterns (tests/embedding_refs.py): token tables of 256, 257 and 275 entries, tokens shared on both sides of
+    the edge between two passes of the join and across sample blocks, under two and three class chunks."""
+    case = er.staircase_of(N, T, S, V, D)
+    er.check_staircase(case, N, T, S)
+    check_all(case, "staircase")
+
+
+@pytest.mark.parametrize("pad", [False, True], ids=["nopad", "pad"])
+def test_token_ids_at_the_top_of_int32(pad):
+    """Tokens up to 2^31 - 2: the padding key 2^31 - 1 of the sort and the unsigned order of the id rows (-1 behind every token).
+    An output with a vocabulary axis cannot exist here: compact and gram only."""
+    case = er.large_id_case(pad)
+    B, ids = compact(case)
+    check_compact(case, B, ids)
+    assert int(ids.max()) == er.I32_MAX - 1 and int((ids >= 0).sum()) == 2 * case.T - (1 if pad else 0)
+    G = kernels.embedding_gram(B, ids)
+    check_gram(case, G)
+    assert bool((G.cpu().view(case.V, 2, case.V, 2)[:, 0, :, 1] != 0).all())      # the samples share two tokens
+
+
+def test_classes_do_not_depend_on_their_chunk():
+    """The Gram matrix of the classes 2 and 7 alone (one class chunk) against their blocks of the matrix of all nine (chunks 0 and
+    1): tokens in ascending order and columns in a fixed order whatever wave and accumulator a class pair lands on, equal bytes."""
+    V, N, T, D, W = 9, 17, 5, 20, 7
+    case = er.make_case(8, V, N, T, D, W, "random")
+    G = kernels.embedding_gram(*compact(case))
+    check_gram(case, G)
+    sel = [2, 7]
+    assert sel[0] // er.CLASS_CHUNK != sel[1] // er.CLASS_CHUNK
+    two = er.Case(case.M[sel].contiguous(), case.idx, W)
+    G2 = kernels.embedding_gram(*compact(two))
+    check_gram(two, G2)
+    assert torch.equal(G.view(V, N, V, N)[sel][:, :, sel], G2.view(2, N, 2, N))
+
+
+@pytest.mark.parametrize("D", [4, 20, 128])
+def test_compact_form_four_bytes_off_a_16_byte_boundary(D):
+    """D % 4 == 0 with a B that is not 16-byte aligned: the scalar load body of the Gram kernel, same arithmetic, same bytes."""
+    V, N, T, W = 5, 17, 5, 7
+    case = er.make_case(9 + D, V, N, T, D, W, "random")
+    B, ids = compact(case)
+    Bs = er.misaligned(B)
+    assert B.data_ptr() % 16 == 0 and Bs.data_ptr() % 16 == 4 and Bs.is_contiguous() and torch.equal(B, Bs)
+    G = kernels.embedding_gram(Bs, ids)
+    check_gram(case, G)
+    assert torch.equal(G, kernels.embedding_gram(B, ids))
+    g = er.gen(7)
+    mat = torch.randn(2, V, N, generator=g).to(DEV)
+    out = kernels.embedding_vmp(Bs, ids, mat, W)
+    report("vmp", out, *case.vmp(mat.cpu()))
+    assert torch.equal(out, kernels.embedding_vmp(B, ids, mat, W))
+    mat = torch.randn(2, W, D, generator=g).to(DEV)
+    out = kernels.embedding_vtmp(Bs, ids, mat)
+    report("vtmp", out, *case.vtmp(mat.cpu()))
+    assert torch.equal(out, kernels.embedding_vtmp(B, ids, mat))
 
 
 def test_disjoint_samples_give_exact_zero_blocks():
@@ -130,14 +187,15 @@ def test_bytes_of_a_pair_across_sample_blocks():
 
 @pytest.mark.parametrize("alpha,beta", [(1.0, 1.0), (0.5, -2.0)])
 def test_out_and_beta_accumulate(alpha, beta):
-    V, N, T, D, W = 3, 17, 5, 20, 7
-    case = er.make_case(4, V, N, T, D, W, "random", 0)
-    B, ids = compact(case)
-    prior = kernels.embedding_gram(*compact(er.make_case(5, V, N, T, D, W, "random")))
-    G0 = prior.clone()
-    out = kernels.embedding_gram(B, ids, out=prior, alpha=alpha, beta=beta)
-    assert out.data_ptr() == prior.data_ptr()
-    check_gram(case, out, alpha, beta, G0.cpu())
+    for V in (3, 5):                                                 # one class chunk; two: mirror writes across chunks
+        N, T, D, W = 17, 5, 20, 7
+        case = er.make_case(4, V, N, T, D, W, "random", 0)
+        B, ids = compact(case)
+        prior = kernels.embedding_gram(*compact(er.make_case(5, V, N, T, D, W, "random")))
+        G0 = prior.clone()
+        out = kernels.embedding_gram(B, ids, out=prior, alpha=alpha, beta=beta)
+        assert out.data_ptr() == prior.data_ptr()
+        check_gram(case, out, alpha, beta, G0.cpu())
 
 
 def test_no_materialisation():
