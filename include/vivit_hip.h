@@ -159,6 +159,30 @@ int vivit_gram_hadamard_f32(const float *Gz, const float *Gs, float *G, int64_t 
 int vivit_gram_hadamard_block_f32(const float *Gz, const float *Gs, float *G, int64_t Cr, int64_t Nr, int64_t Cc,
                                   int64_t Nc, int64_t ldg, float alpha, float beta, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Factorised Gram of a Linear weight on a sequence input [N, T, in] (any extra dimensions between batch and features,
+ * vivit/extensions/secondorder/vivit/linear.py:38-39, flattened into T): with s = [C, N, T, O] the factor at the module output and
+ * z = [N, T, I] the input, V_t[c,n,o,i] = sum_t s[c,n,t,o] z[n,t,i] and
+ *   G[(c,n), (e,m)] = sum_{t,u < T} Gs[(c,n,t), (e,m,u)] * Gz[(n,t), (m,u)],   Gs = s' s'^T (s' = [C N T, O]), Gz = z' z'^T (z' = [N T, I]).
+ * vivit_gram_seq_reduce_f32 is the last step, on a rectangular block (rows (c, n) with c < Cr, n < Nr; columns (e, m), e < Cc, m < Nc):
+ *   G[(c Nr + n) ldg + e Nc + m] = alpha * sum_{t<T} sum_{u<T} Gz[(n T + t) ldz + m T + u] * Gs[((c Nr + n) T + t) lds + (e Nc + m) T + u]
+ *                                  + beta * G[...]                 (G is not read when beta == 0)
+ *   Gz: [Nr T, >= Nc T] ldz, Gs: [Cr Nr T, >= Cc Nc T] lds, G: [Cr Nr, >= Cc Nc] ldg; columns of G beyond Cc Nc are left untouched.
+ * Call site: the row slabs of route A of vivit_amd/backend/extensions.py:_linear_seq_weight_closures (ViViTGGN{Exact,MC}).
+ * No atomics.  The summation order of an entry depends on T alone (per u an fma chain over t, then the T sums added in the order
+ * of u, then alpha, then fma(beta, G, .)): the bytes of an entry are a function of its two T x T operand blocks, alpha, beta and
+ * the prior entry, whatever its position, the block's sizes or the operands' alignment.  T = 1 gives the bytes of
+ * vivit_gram_hadamard_block_f32.  Operands 16-byte aligned with ldz, lds and Nc T multiples of 4 take the float4 body.
+ * Status: negative sizes, ldz < Nc T, lds < Cc Nc T, ldg < Cc Nc, or a null pointer with non-zero sizes: VIVIT_E_BADARG; any zero
+ * size: VIVIT_OK, nothing is launched.  LIMITS (VIVIT_E_UNSUPPORTED beyond them): T <= 1024 (a T x T block is summed by one
+ * workgroup); every size, leading dimension, Cr Nr T and Cc Nc T below 2^31; for T > 1 at most 2^24 - 1 rows Cr Nr (one
+ * workgroup of 256 lanes per row along the grid's first dimension) and at most 65 535 column spans of (1024 / T rounded down to a
+ * multiple of 4 / gcd(T, 4)) outputs.
+ * ------------------------------------------------------------------------------------------- */
+int vivit_gram_seq_reduce_f32(const float *Gz, int64_t ldz, const float *Gs, int64_t lds, float *G, int64_t ldg,
+                              int64_t Cr, int64_t Nr, int64_t Cc, int64_t Nc, int64_t T,
+                              float alpha, float beta, void *stream);
+
 /* Length-C contractions of the factorised Linear products (the MFMA GEMM with z does the rest):
  *   vivit_class_contract_f32:  T[f, o, n] = sum_c mat[f, c, n] * s[c, n, o]      mat: [F,C,N], s: [C,N,O], T: [F,O,N]
  *     first half of einsum("cno,vcn,ni->voi")  vivit/extensions/secondorder/vivit/linear.py:53

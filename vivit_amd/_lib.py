@@ -35,6 +35,7 @@ SIGNATURES = {
     "vivit_gemm_tn_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _ptr, _sz, _ptr]),
     "vivit_gram_hadamard_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _f32, _f32, _ptr]),
     "vivit_gram_hadamard_block_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _ptr]),
+    "vivit_gram_seq_reduce_f32": (_int, [_ptr, _i64, _ptr, _i64, _ptr, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _ptr]),
     "vivit_class_contract_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr]),
     "vivit_class_expand_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr]),
     "vivit_linear_weight_mjp_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr]),
@@ -101,7 +102,7 @@ SIGNATURES = {
 }
 
 # include/vivit_hip.h of this checkout (vivit_hip_abi_version).  The batched entry points (two-phase solve, Gram-space
-# directions) only ADD exports: the
+# directions, the attention, Embedding and sequence-Linear rules) only ADD exports: the
 # number stays; a library without them is refused by the symbol lookup in load() and by the source hash (_check_provenance).
 ABI_VERSION = 1008
 

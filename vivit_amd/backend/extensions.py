@@ -7,7 +7,8 @@ Data contract (identical to BackPACK's):
   ``param.vivit_ggn_exact|mc``  dict with closures ``gram_mat() -> [C,N,C,N]``,
       ``V_mat_prod(mat[F,C,N]) -> [F,*param]``, ``V_t_mat_prod(mat[F,*param]) -> [F,C,N]``
       (vivit/extensions/secondorder/vivit/base.py:126-130); Linear weights keep the factorised
-      form ``s=[C,N,out], z=[N,in]`` (vivit/extensions/secondorder/vivit/linear.py:41-81).
+      form ``s=[C,N,out], z=[N,in]`` (vivit/extensions/secondorder/vivit/linear.py:41-81); on sequence inputs
+      ``[N,*,in]`` with a large explicit factor, ``s=[C,N,*,out], z=[N,*,in]`` (``_linear_seq_weight_closures``).
 """
 import math
 from typing import List, Optional
@@ -23,6 +24,18 @@ from vivit_amd.utils.gram import mVp, pairwise_dot
 
 DP_ROWS_MAX_COLUMNS = 4096  # data parallel: narrower materialised factors are all-gathered (block rows), wider ones
                             # go through the all-to-all to parameter shards (vivit_amd.distributed.BatchShardedGram)
+# A Linear weight on a sequence input [N, T, in] (ViViTGGN*): an explicit factor [C, N, O, I] above SEQ_LINEAR_EXPLICIT_MAX_BYTES is
+# never built (_linear_seq_weight_closures), and the Gram build's own scratch (a row slab of Gs on route A, a chunk of the factor on
+# route B) stays within SEQ_LINEAR_WORKSPACE_BYTES.  Both are policies, not measurements; both are read at call time.
+SEQ_LINEAR_EXPLICIT_MAX_BYTES = 64 << 20
+SEQ_LINEAR_WORKSPACE_BYTES = 256 << 20
+# Route A (expanded) is taken when SEQ_LINEAR_KAPPA * macs_A <= macs_B (_seq_linear_plan).  Measured
+# (profiles/seq_linear_gram_time.log; N = 64, C = 10, (O, I) = (3072, 768) and (768, 3072), T in {4, 16, 64, 197}): route A is the
+# faster of the two at the six shapes with macs_B / macs_A >= 0.224 and the slower at the two with macs_B / macs_A <= 0.123 (T = 197),
+# so the planner never picks the slower one for kappa in (0.123, 0.224]; this is the smallest such value to three digits.  (A
+# multiply-add of route A is the cheaper one: its products are large GEMMs, route B's are ninety small SYRKs and convolution rules.)
+SEQ_LINEAR_KAPPA = 0.124
+GEMM_PIECE_MIN_ROWS = 256   # _gemm_nt_within cuts a product no finer than this (read at call time)
 _LOSSES = (nn.CrossEntropyLoss, nn.MSELoss)
 _BATCHNORM = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d)
 _NORMS = (nn.LayerNorm, nn.GroupNorm)   # normalisations over each sample's own elements: no train / eval distinction
@@ -208,13 +221,7 @@ def _param_factor(module, name: str, M: Tensor, x: Tensor) -> Tensor:
             return M if M.dim() == 3 else M.flatten(2, -2).sum(2)
         if M.dim() == 3:
             return kernels.linear_weight_mjp(M, x)           # "vno,ni->vnoi" (HIP store-stream kernel)
-        Ma, xa = M.flatten(2, -2), x.flatten(1, -2)          # [V, N, A, O], [N, A, I]  (linear.py:52-81: extra dims are summed)
-        if M.is_cuda and M.dtype == torch.float32:
-            # a 1 x 1 convolution over the A positions: the HIP weight rule of the convolution, "vnoa,nia->vnoi"
-            out = kernels.conv2d_weight_mjp(Ma.transpose(2, 3).unsqueeze(3).contiguous(), xa.transpose(1, 2).unsqueeze(2).contiguous(),
-                                            (1, 1), (1, 1), (0, 0), (1, 1))
-            return out.reshape(out.shape[:4])
-        return torch.einsum("vnao,nai->vnoi", Ma, xa)
+        return _linear_seq_weight_factor(M, x)
     if isinstance(module, _CONVS):
         if name == "bias":
             return _spatial_sum(M, 3)
@@ -255,6 +262,17 @@ def _param_factor(module, name: str, M: Tensor, x: Tensor) -> Tensor:
         B, ids = _embedding_compact(module, M, x)
         return _embedding_factor(B, ids, module.num_embeddings)
     raise NotImplementedError(f"no parameter rule for {type(module).__name__}")
+
+
+def _linear_seq_weight_factor(M: Tensor, x: Tensor) -> Tensor:
+    """The explicit weight factor ``[V, N, O, I]`` of a Linear on ``x [N, *A, I]`` from ``M [V, N, *A, O]``."""
+    Ma, xa = M.flatten(2, -2), x.flatten(1, -2)              # [V, N, A, O], [N, A, I]  (linear.py:52-81: extra dims are summed)
+    if M.is_cuda and M.dtype == torch.float32:
+        # a 1 x 1 convolution over the A positions: the HIP weight rule of the convolution, "vnoa,nia->vnoi"
+        out = kernels.conv2d_weight_mjp(Ma.transpose(2, 3).unsqueeze(3).contiguous(), xa.transpose(1, 2).unsqueeze(2).contiguous(),
+                                        (1, 1), (1, 1), (0, 0), (1, 1))
+        return out.reshape(out.shape[:4])
+    return torch.einsum("vnao,nai->vnoi", Ma, xa)
 
 
 def _embedding_compact(module, M: Tensor, idx: Tensor):
@@ -925,6 +943,173 @@ def _linear_weight_closures(s: Tensor, z: Tensor):
             "shape_cn": (C, N), "dp_add": lambda acc: acc.add_linear(s, z)}
 
 
+def _seq_linear_plan(C: int, N: int, T: int, O: int, I: int, workspace_bytes: Optional[int] = None, kappa: Optional[float] = None,
+                     syrk_workspace=None):
+    """How ``_linear_seq_weight_closures`` builds its Gram matrix; pure arithmetic on the sizes (no tensor, no device).
+
+    Multiply-adds, symmetric halves: route A (expanded) ``(C N T)^2 / 2 * O + (N T)^2 / 2 * I``, route B (explicit, chunked)
+    ``(C N)^2 / 2 * O I + C N T O I``.  Route A is taken when ``kappa * macs_A <= macs_B`` and one row of T x T blocks fits the
+    workspace.  Returns ``{"route", "macs_A", "macs_B", "slabs", "chunks"}``:
+
+    * ``slabs`` (route A): ``(r0, r1, cols)``: ranges ``r0 .. r1 - 1`` of the rows ``(c, n) = c N + n`` of G, in order, covering
+      ``0 .. C N``, and the number of columns ``0 .. cols - 1`` the slab computes: ``cols = r1``, its own last row (lower block
+      trapezoid).  A slab is a range of whole classes or a range of samples of one class, so its rows of ``s'`` are contiguous;
+      its block of Gs, ``[(r1 - r0) T, cols T]`` floats, fits HALF the workspace.
+    * ``chunks`` (route B): ``(o0, o1)`` ranges of the output features, a chunk ``[C, N, o1 - o0, I]`` of the factor and the scratch
+      buffer of its SYRK together within the workspace (one feature at least).
+
+    The scratch buffer of the GEMM / SYRK launchers holds the bf16 pieces of large operands, 1.5 times their size.  Route A keeps it
+    in the other half of the workspace by cutting its products into pieces (``_gemm_nt_within``); route B shrinks the chunk until
+    both fit.  ``syrk_workspace(n, p)`` (default ``kernels.gram_syrk_workspace_bytes``, a host-side query) gives those bytes."""
+    W = (SEQ_LINEAR_WORKSPACE_BYTES if workspace_bytes is None else workspace_bytes) // 2
+    kappa = SEQ_LINEAR_KAPPA if kappa is None else kappa
+    syrk_workspace = kernels.gram_syrk_workspace_bytes if syrk_workspace is None else syrk_workspace
+    n = C * N
+    macs_A = (n * T) ** 2 / 2 * O + (N * T) ** 2 / 2 * I
+    macs_B = n ** 2 / 2 * O * I + n * T * O * I
+    plan = {"macs_A": macs_A, "macs_B": macs_B, "slabs": [], "chunks": []}
+    fits = 4 * T * n * T <= W                      # the last row's blocks: the widest a one-row slab gets
+    if fits and kappa * macs_A <= macs_B:
+        plan["route"] = "A"
+        r0 = 0
+        while r0 < n:
+            # the largest r1 with 4 (r1 - r0) T * r1 T <= W
+            r1 = min(n, int((r0 + math.sqrt(r0 * r0 + W / (T * T))) / 2))
+            while r1 < n and 4 * (r1 + 1 - r0) * T * (r1 + 1) * T <= W:
+                r1 += 1
+            while 4 * (r1 - r0) * T * r1 * T > W:
+                r1 -= 1
+            c0, n0 = divmod(r0, N)
+            if n0 == 0 and r1 - r0 >= N:
+                r1 = r0 + (r1 - r0) // N * N       # whole classes
+            else:
+                r1 = min(r1, (c0 + 1) * N)         # samples of class c0
+            plan["slabs"].append((r0, r1, r1))
+            r0 = r1
+    else:
+        plan["route"] = "B"
+        step = max(1, min(O, 2 * W // (4 * n * I)))
+        while step > 1 and 4 * n * step * I + syrk_workspace(n, step * I) > 2 * W:
+            step = step * 7 // 8
+        plan["chunks"] = [(o0, min(O, o0 + step)) for o0 in range(0, O, step)]
+    return plan
+
+
+def _gemm_nt_within(A: Tensor, B: Tensor, cap: int, out: Optional[Tensor] = None) -> Tensor:
+    """``A B^T`` by ``kernels.gemm_nt`` on pieces of the rows of ``A`` and ``B`` small enough for the launcher's scratch buffer to
+    stay within ``cap`` bytes (pieces of ``GEMM_PIECE_MIN_ROWS`` rows at the least); into ``out`` (a row-strided view) if given."""
+    m, k = A.shape
+    nb = B.shape[0]
+    mp, bp = m, nb
+    while kernels.gemm_workspace_bytes(mp, bp, k) > cap and max(mp, bp) > GEMM_PIECE_MIN_ROWS:
+        if mp >= bp:
+            mp = (mp + 1) // 2
+        else:
+            bp = (bp + 1) // 2
+    if out is None:
+        out = torch.empty((m, nb), dtype=A.dtype, device=A.device)
+    for i in range(0, m, mp):
+        for j in range(0, nb, bp):
+            kernels.gemm_nt(A[i:i + mp], B[j:j + bp], out=out[i:i + mp, j:j + bp])
+    return out
+
+
+def _gram_within(A: Tensor, cap: int, out: Optional[Tensor] = None) -> Tensor:
+    """``A A^T``: the SYRK where its scratch buffer stays within ``cap`` bytes, ``_gemm_nt_within`` otherwise; into ``out`` (a
+    row-strided view) if given."""
+    if kernels.gram_syrk_workspace_bytes(A.shape[0], A.shape[1]) <= cap:
+        return kernels.gram_syrk(A, out=out)
+    return _gemm_nt_within(A, A, cap, out=out)
+
+
+def _slab_of_gs(s2: Tensor, r0: int, r1: int, cols: int, T: int, cap: int) -> Tensor:
+    """Rows ``r0 T .. r1 T - 1``, columns ``0 .. cols T - 1`` of ``Gs = s' s'^T``: the columns left of the slab's diagonal block by
+    GEMM, the diagonal block itself (where the slab ends with it, ``cols = r1``) by the SYRK, which computes half of it."""
+    if (r0, cols) == (0, r1):
+        return _gram_within(s2[:r1 * T], cap)
+    rows = s2[r0 * T:r1 * T]
+    Gs = torch.empty(((r1 - r0) * T, cols * T), dtype=s2.dtype, device=s2.device)
+    if r0 > 0:
+        _gemm_nt_within(rows, s2[:r0 * T], cap, out=Gs[:, :r0 * T])
+    if cols == r1:
+        _gram_within(rows, cap, out=Gs[:, r0 * T:])
+    else:
+        _gemm_nt_within(rows, s2[r0 * T:cols * T], cap, out=Gs[:, r0 * T:])
+    return Gs
+
+
+def _linear_seq_weight_closures(s: Tensor, z: Tensor):
+    """Factorised closures for a Linear weight on a sequence input: ``s [C, N, *A, O]`` the factor at the module output, ``z [N, *A, I]``
+    the input, ``T = prod(A)``.  ``V_t[c,n,o,i] = sum_t s[c,n,t,o] z[n,t,i]`` ([C, N, O, I]) exists only when ``factor()`` or ``dp_add``
+    ask for it (HIP fp32 tensors).
+
+    Gram, by :func:`_seq_linear_plan`: route A, ``G[(c,n),(e,m)] = sum_{t,u} Gs[(c,n,t),(e,m,u)] Gz[(n,t),(m,u)]`` with the Gram
+    matrices ``Gs`` of ``s' = [C N T, O]`` (in row slabs within ``SEQ_LINEAR_WORKSPACE_BYTES``) and ``Gz`` of ``z' = [N T, I]``, summed
+    by ``kernels.gram_seq_reduce``, lower block trapezoid, then mirrored; or route B, the explicit factor in chunks of the output
+    features, each added by the SYRK.  Products: the chains of :func:`_linear_weight_closures` on ``s'``, ``z'`` with ``N T`` for ``N``.
+    """
+    C, N, O = s.shape[0], s.shape[1], s.shape[-1]
+    I = z.shape[-1]
+    s3 = s.reshape(C, N, -1, O).contiguous()       # [C, N, T, O]
+    T = s3.shape[2]
+    s2 = s3.view(C * N * T, O)                     # s'
+    z2 = z.reshape(N * T, I).contiguous()          # z'
+    n = C * N
+
+    def gram_A(G, beta, slabs):
+        cap = SEQ_LINEAR_WORKSPACE_BYTES // 2
+        Gz = _gram_within(z2, cap)                                             # [N T, N T]
+        for r0, r1, cols in slabs:                 # rows r0 .. r1 - 1 against the columns 0 .. cols - 1
+            Gs = _slab_of_gs(s2, r0, r1, cols, T, cap)                         # [(r1 - r0) T, cols T]
+            c0, n0 = divmod(r0, N)
+            if n0 == 0 and (r1 - r0) % N == 0:     # whole classes c0 .. c1 - 1 against the classes 0 .. cols / N - 1
+                kernels.gram_seq_reduce(Gz, Gs, (r1 - r0) // N, N, cols // N, N, T, out=G[r0:r1, :cols], alpha=1.0, beta=beta)
+            else:                                  # samples n0 .. n1 - 1 of class c0: the classes below it, then its own samples 0 .. mc - 1
+                n1, mc = r1 - c0 * N, cols - c0 * N
+                if c0 > 0:
+                    kernels.gram_seq_reduce(Gz[n0 * T:n1 * T], Gs[:, :c0 * N * T], 1, n1 - n0, c0, N, T, out=G[r0:r1, :c0 * N],
+                                            alpha=1.0, beta=beta)
+                kernels.gram_seq_reduce(Gz[n0 * T:n1 * T, :mc * T], Gs[:, c0 * N * T:], 1, n1 - n0, 1, mc, T,
+                                        out=G[r0:r1, c0 * N:cols], alpha=1.0, beta=beta)
+            del Gs
+        return kernels.symmetrize_lower(G)         # the T x T sums of (i, j) and (j, i) differ in their order: one is kept
+
+    def gram_B(G, beta, chunks):
+        xa = z2.view(N, T, I).transpose(1, 2).unsqueeze(2).contiguous()        # [N, I, 1, T]: a 1 x 1 convolution over the T positions
+        for o0, o1 in chunks:
+            Mc = s3[..., o0:o1].transpose(2, 3).unsqueeze(3).contiguous()      # [C, N, o1 - o0, 1, T]
+            Vc = kernels.conv2d_weight_mjp(Mc, xa, (1, 1), (1, 1), (0, 0), (1, 1))
+            kernels.gram_syrk(Vc.reshape(n, -1), out=G, alpha=1.0, beta=beta)
+            del Vc
+            beta = 1.0
+        return G
+
+    def gram_mat(out=None, beta=0.0):
+        plan = _seq_linear_plan(C, N, T, O, I)
+        G = torch.empty((n, n), dtype=torch.float32, device=s.device) if out is None else out.view(n, n)
+        if out is None:
+            beta = 0.0
+        G = gram_A(G, beta, plan["slabs"]) if plan["route"] == "A" else gram_B(G, beta, plan["chunks"])
+        return G.view(C, N, C, N)
+
+    def V_mat_prod(mat):  # [F, C, N] -> [F, O, I]     "cnto,vcn,nti->voi"
+        Fdim = mat.shape[0]
+        rep = mat.unsqueeze(-1).expand(Fdim, C, N, T).reshape(Fdim, C, N * T)
+        U = kernels.class_contract(rep, s2.view(C, N * T, O)).view(Fdim * O, N * T)
+        return kernels.gemm_nn(U, z2).view(Fdim, O, I)
+
+    def V_t_mat_prod(mat):  # [F, O, I] -> [F, C, N]   "cnto,voi,nti->vcn"
+        Fdim = mat.shape[0]
+        U = kernels.gemm_nt(mat.reshape(Fdim * O, I), z2).view(Fdim, O, N * T)
+        return kernels.class_expand(s2.view(C, N * T, O), U).view(Fdim, C, N, T).sum(3)
+
+    def factor():  # the explicit V_t; only asked for by the parameter side and by dp_add
+        return _linear_seq_weight_factor(s, z)
+
+    return {"V_mat_prod": V_mat_prod, "V_t_mat_prod": V_t_mat_prod, "gram_mat": gram_mat, "factor": factor,
+            "shape_cn": (C, N), "dp_add": lambda acc: _materialised_closures(factor())["dp_add"](acc)}
+
+
 def _embedding_closures(M: Tensor, idx: Tensor, module):
     """Closures for an Embedding weight on the compact form ``(B, ids)`` of :func:`_embedding_compact`: the factor
     ``V_t[c, n, w, :] = sum_{t: idx[n, t] = w} M[c, n, t, :]`` ([C, N, num_embeddings, D], at most T non-zero rows per (c, n)) exists
@@ -969,6 +1154,9 @@ class _ViViTGGN(_SqrtGGN):
     def _store(self, module, name, param, M, x):
         if isinstance(module, nn.Linear) and name == "weight" and M.dim() == 3:
             closures = _linear_weight_closures(M, x)
+        elif (isinstance(module, nn.Linear) and name == "weight" and M.dim() > 3 and M.is_cuda and M.dtype == torch.float32
+              and 4 * M.shape[0] * M.shape[1] * module.out_features * module.in_features > SEQ_LINEAR_EXPLICIT_MAX_BYTES):
+            closures = _linear_seq_weight_closures(M, x)
         elif isinstance(module, nn.Embedding):
             closures = _embedding_closures(M, x, module)
         else:

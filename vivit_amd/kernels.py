@@ -103,7 +103,12 @@ def _workspace(nbytes: int, like: torch.Tensor):
     key = (like.device, _stream(like))
     buf = _WORKSPACES.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=like.device)
+        buf = None
+        # The old buffer is released BEFORE the larger one is allocated, so the two never coexist (a caller that bounds its peak
+        # memory, _linear_seq_weight_closures, counts one scratch buffer).  Safe: the key is the launch stream, every kernel that
+        # used the old buffer was enqueued on it, and torch's allocator hands a freed block out again in that stream's order only.
+        _WORKSPACES.pop(key, None)
+        buf = torch.empty(_workspace_alloc_bytes(nbytes), dtype=torch.uint8, device=like.device)
         _WORKSPACES[key] = buf
     return buf.data_ptr(), buf.numel()
 
@@ -120,6 +125,21 @@ def _as2d(t: torch.Tensor) -> torch.Tensor:
 
 def _ld(t):
     return max(t.stride(0), t.shape[1], 1) if t.shape[0] > 1 else max(t.shape[1], 1)
+
+
+def _workspace_alloc_bytes(nbytes: int) -> int:
+    """What :func:`_workspace` allocates for a request of ``nbytes``."""
+    return int(nbytes * 1.25) + 256 if nbytes else 0
+
+
+def gram_syrk_workspace_bytes(n: int, p: int) -> int:
+    """Bytes of the scratch buffer ``gram_syrk`` takes for ``A: [n, p]`` (a host-side query: no device is touched)."""
+    return _workspace_alloc_bytes(_lib.load().vivit_gram_syrk_f32_workspace_bytes(n, p))
+
+
+def gemm_workspace_bytes(m: int, n: int, k: int) -> int:
+    """Bytes of the scratch buffer ``gemm_nt`` / ``gemm_nn`` / ``gemm_tn`` take for an ``[m, n]`` output with contraction ``k``."""
+    return _workspace_alloc_bytes(_lib.load().vivit_gemm_f32_workspace_bytes(m, n, k))
 
 
 @_launcher
@@ -217,6 +237,37 @@ def gram_hadamard_block(Gz, Gs, Cr: int, Nr: int, Cc: int, Nc: int, out=None, al
                                                    alpha, beta, _stream(Gz))
     _lib.check(st, "vivit_gram_hadamard_block_f32")
     return out
+
+
+@_launcher
+def gram_seq_reduce(Gz, Gs, Cr: int, Nr: int, Cc: int, Nc: int, T: int, out=None, alpha: float = 1.0, beta: float = 0.0):
+    """``out[(c,n),(e,m)] = alpha * sum_{t,u<T} Gz[(n,t),(m,u)] * Gs[(c,n,t),(e,m,u)] + beta * out`` for a rectangular block (rows
+    ``Cr x Nr``, columns ``Cc x Nc``): the Gram matrix of a Linear weight on a sequence input from the Gram matrices of its two
+    factors.  ``Gz [Nr T, Nc T]``, ``Gs [Cr Nr T, Cc Nc T]`` and ``out [Cr Nr, Cc Nc]`` may be row-strided views."""
+    _require_device(Gz, Gs, out)
+    Gz, Gs = _as2d(Gz), _as2d(Gs)
+    rows, cols = Cr * Nr, Cc * Nc
+    if tuple(Gz.shape) != (Nr * T, Nc * T) or tuple(Gs.shape) != (rows * T, cols * T):
+        raise ValueError(f"Gz must be [{Nr * T}, {Nc * T}] and Gs [{rows * T}, {cols * T}], got {tuple(Gz.shape)} and {tuple(Gs.shape)}")
+    if out is None:
+        out = torch.empty((rows, cols), dtype=torch.float32, device=Gz.device)
+        beta = 0.0
+    _check_out(out, rows, cols, Gz, Gs)
+    st = _lib.load().vivit_gram_seq_reduce_f32(Gz.data_ptr(), _ld(Gz), Gs.data_ptr(), _ld(Gs), out.data_ptr(), _ld(out), Cr, Nr, Cc, Nc,
+                                               T, alpha, beta, _stream(Gz))
+    _lib.check(st, "vivit_gram_seq_reduce_f32")
+    return out
+
+
+@_launcher
+def symmetrize_lower(G):
+    """``G[i, j] = G[j, i]`` for ``j > i``, in place, for a square row-strided ``G``; returns ``G``."""
+    _require_device(G)
+    n = G.shape[0]
+    if G.dim() != 2 or G.shape[1] != n or (G.numel() > 0 and (G.stride(1) != 1 or (n > 1 and G.stride(0) < n))):
+        raise ValueError("G must be a square row-major matrix with unit column stride")
+    _lib.check(_lib.load().vivit_symmetrize_lower_f32(G.data_ptr(), n, _ld(G), _stream(G)), "vivit_symmetrize_lower_f32")
+    return G
 
 
 @_launcher
