@@ -284,6 +284,40 @@ int vivit_norm_rules_f32(const float *M, const float *X, const float *gamma, con
  * summed serially over a, one thread per d.  pw or pb may be NULL. */
 int vivit_norm_position_sums_f32(const float *M, const float *X, const float *mean, const float *rstd, float *pw, float *pb, int64_t V,
                                  int64_t N, int64_t A, int64_t D, void *stream);
+/* nn.RMSNorm, the gated product and rotary position embeddings (llama_rules.hip; no counterpart in the reference's module map): the
+ * modules of a LLaMA-style decoder block.  All contiguous fp32, no atomics, fixed summation order.  Status: negative or inconsistent
+ * sizes and a NULL pointer with non-zero sizes give VIVIT_E_BADARG, any zero size VIVIT_OK without a launch, sizes beyond the 32-bit
+ * index arithmetic or the grid VIVIT_E_UNSUPPORTED.  Every kernel has a 16-byte body (lengths multiples of 4 and every operand
+ * 16-byte aligned) and a scalar one.
+ * RMSNorm: a ROW is the set of L = prod(normalized_shape) contiguous elements that share one statistic, rows = numel / L, A = rows / N
+ * rows per sample.  Rows of L <= 1024 are held in the registers of one wavefront, longer ones by one workgroup, as in norm_rules.hip:
+ * the bytes of a row's results depend on L and on the body only. */
+/* rstd[r] = 1 / sqrt(sum_l X[r, l]^2 / L + eps)  for X [rows, L]. */
+int vivit_rms_norm_stats_f32(const float *X, float *rstd, int64_t rows, int64_t L, float eps, void *stream);
+/* M [V rows, L], X [rows, L], rstd [rows], gamma [L] or NULL (= 1).  xhat = x rstd, h = gamma o M; in one visit of each row:
+ *   out[v, r, l] = rstd[r] (h - xhat mean_l(h o xhat))      the transposed input Jacobian of nn.RMSNorm
+ *   w[v, r, l]   = M[v, r, l] xhat[r, l]                    the weight rule when A == 1
+ * out or w may be NULL; both NULL: VIVIT_E_BADARG. */
+int vivit_rms_norm_rules_f32(const float *M, const float *X, const float *gamma, const float *rstd, float *out, float *w, int64_t V,
+                             int64_t rows, int64_t L, void *stream);
+/* nn.RMSNorm with A > 1 rows per sample, M [V, N, A, D], X [N, A, D], rstd [N A]:
+ *   pw[v, n, d] = sum_a M[v, n, a, d] X[n, a, d] rstd[n A + a]   (weight rule), summed serially over a, one thread per d. */
+int vivit_rms_norm_position_sums_f32(const float *M, const float *X, const float *rstd, float *pw, int64_t V, int64_t N, int64_t A,
+                                     int64_t D, void *stream);
+/* The product a o b of two branches (vivit_amd.backend.ProductModule; SwiGLU): M [V, n], a / b [n],
+ *   Ga[v, i] = M[v, i] b[i]   (the factor handed to a),   Gb[v, i] = M[v, i] a[i]   (the factor handed to b)
+ * from one read of M; each result is a single rounded product.  Ga or Gb may be NULL (not both); the operand of a NULL output (a
+ * for Gb, b for Ga) is not read and may be NULL. */
+int vivit_gate_jac_t_f32(const float *M, const float *a, const float *b, float *Ga, float *Gb, int64_t V, int64_t n, void *stream);
+/* Rotary position embedding on the packed projection of the attention module (vivit_amd.backend.RotaryEmbedding; half-split
+ * pairing): M, G [R, T, 3, H, d] (R = V N), cosT / sinT [T, d / 2]; d odd: VIVIT_E_BADARG.  For the q and k thirds, with j < d / 2,
+ * m1 = M[..., j], m2 = M[..., j + d / 2], c = cosT[t, j], s = sinT[t, j]:
+ *   G[..., j]         = fmaf( m2, s, m1 c)
+ *   G[..., j + d / 2] = fmaf(-m1, s, m2 c)
+ * (the transpose of y1 = x1 c - x2 s, y2 = x2 c + x1 s).  The v third is copied bit for bit.  G may be M itself (in place; no other
+ * overlap).  No sine or cosine is evaluated: the tables are the fp32 values the forward pass used. */
+int vivit_rope_jac_t_f32(const float *M, const float *cosT, const float *sinT, float *G, int64_t R, int64_t T, int64_t H, int64_t d,
+                         void *stream);
 /* Scaled dot-product self-attention on the packed projection (attention.hip; no counterpart in the reference's module map -- it
  * replaces the generic rule of the factor provider, a recomputed forward and torch.autograd.grad(..., is_grads_batched=True) at
  * vivit_amd/backend/extensions.py:_jac_t_mat_prod, for vivit_amd.backend.ScaledDotProductAttention).  The module input is

@@ -50,6 +50,11 @@ SIGNATURES = {
     "vivit_norm_stats_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _f32, _ptr]),
     "vivit_norm_rules_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i64, _ptr]),
     "vivit_norm_position_sums_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr]),
+    "vivit_rms_norm_stats_f32": (_int, [_ptr, _ptr, _i64, _i64, _f32, _ptr]),
+    "vivit_rms_norm_rules_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr]),
+    "vivit_rms_norm_position_sums_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr]),
+    "vivit_gate_jac_t_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr]),
+    "vivit_rope_jac_t_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr]),
     "vivit_attention_jac_t_f32_workspace_bytes": (_sz, [_i64] * 5),
     "vivit_attention_jac_t_f32": (_int, [_ptr, _ptr, _ptr, _ptr] + [_i64] * 5 + [_f32, _int, _ptr, _sz, _ptr]),
     "vivit_embedding_compact_f32": (_int, [_ptr] * 5 + [_i64] * 4 + [_ptr]),

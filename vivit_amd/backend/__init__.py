@@ -7,7 +7,8 @@ extension's ``savefield``, ``hook(module)`` called per module after its extensio
 provided here for feed-forward and residual nets (Linear, Conv1d/2d/3d, ConvTranspose1d/2d/3d, BatchNorm in
 eval mode, element-wise activations, pooling, Flatten, Dropout in eval mode, and the branching modules
 ``Parallel`` / ``SumModule`` / ``Pad`` / ``Slicing`` / ``ScaleModule`` of ``backpack.custom_module``, LayerNorm / GroupNorm,
-the self-attention modules ``ScaledDotProductAttention`` / ``MultiheadSelfAttention`` of ``custom_module``, and ``nn.Embedding``;
+the self-attention modules ``ScaledDotProductAttention`` / ``MultiheadSelfAttention`` of ``custom_module``, ``nn.Embedding``,
+``nn.RMSNorm`` and the modules ``ProductModule`` (gated MLPs) / ``RotaryEmbedding`` of ``custom_module``;
 CrossEntropyLoss / MSELoss with ``reduction='mean'``).  When the real BackPACK is importable the Computation classes can be used
 with it directly; this module is never imported in that case.
 
@@ -20,6 +21,8 @@ from vivit_amd.backend.custom_module import (
     MultiheadSelfAttention,
     Pad,
     Parallel,
+    ProductModule,
+    RotaryEmbedding,
     ScaledDotProductAttention,
     ScaleModule,
     Slicing,
@@ -34,4 +37,4 @@ from vivit_amd.backend.extensions import (
     ViViTGGNMC,
 )
 
-__all__ = ["ActiveIdentity", "MultiheadSelfAttention", "Pad", "Parallel", "ScaledDotProductAttention", "ScaleModule", "Slicing", "SumModule", "backpack", "extend", "BatchGrad", "SqrtGGNExact", "SqrtGGNMC", "ViViTGGNExact", "ViViTGGNMC"]
+__all__ = ["ActiveIdentity", "MultiheadSelfAttention", "Pad", "Parallel", "ProductModule", "RotaryEmbedding", "ScaledDotProductAttention", "ScaleModule", "Slicing", "SumModule", "backpack", "extend", "BatchGrad", "SqrtGGNExact", "SqrtGGNMC", "ViViTGGNExact", "ViViTGGNMC"]

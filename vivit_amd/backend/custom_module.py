@@ -22,6 +22,19 @@ class SumModule(nn.Module):
         return out if len(inputs) > 1 else out * 1.0
 
 
+class ProductModule(nn.Module):
+    """Elementwise product of exactly two inputs of equal shape (no counterpart in BackPACK): the merge of a gated MLP,
+    ``Parallel(Sequential(Linear, SiLU), Linear, merge_module=ProductModule())`` is SwiGLU's ``silu(x W1) * (x W3)``."""
+
+    def forward(self, *inputs: Tensor) -> Tensor:
+        if len(inputs) != 2:
+            raise ValueError(f"ProductModule multiplies exactly two inputs, got {len(inputs)}")
+        a, b = inputs
+        if a.shape != b.shape:
+            raise ValueError(f"ProductModule needs inputs of equal shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+        return a * b
+
+
 class ActiveIdentity(nn.Module):
     """Identity that produces a new tensor (``backpack.custom_module.branching.ActiveIdentity``)."""
 
@@ -108,6 +121,53 @@ class ScaledDotProductAttention(nn.Module):
         if self.causal:
             s = s.masked_fill(torch.ones(T, T, dtype=torch.bool, device=qkv.device).triu(1), float("-inf"))
         return (s.softmax(-1) @ v).transpose(1, 2).reshape(N, T, H * d)    # (a new tensor: the heads are gathered into a copy)
+
+
+class RotaryEmbedding(nn.Module):
+    """Rotary position embedding on a packed projection ``qkv [N, T, 3 E]`` (no counterpart in BackPACK): a parameter-free leaf
+    in front of :class:`ScaledDotProductAttention`, whose layout it shares (head ``h`` owns the columns ``h d .. (h + 1) d`` of each
+    third, ``d = E / num_heads``, which must be even).
+
+    Half-split pairing ("rotate_half", as LLaMA / GPT-NeoX): in every head of the q and k thirds the pair ``(j, j + d / 2)`` at
+    position ``t`` is rotated by the angle ``t * base^(-2 j / d)``, ``y1 = x1 cos - x2 sin``, ``y2 = x2 cos + x1 sin``; the v third
+    passes through.  Positions start at 0."""
+
+    def __init__(self, num_heads: int, base: float = 10000.0):
+        super().__init__()
+        if num_heads < 1:
+            raise ValueError(f"num_heads must be positive, got {num_heads}")
+        self.num_heads, self.base = int(num_heads), float(base)
+        self._tables = None   # (key, cos, sin): what forward() used is what the rule of the extensions uses
+
+    def head_dim(self, qkv: Tensor) -> int:
+        if qkv.dim() != 3:
+            raise ValueError(f"expected a packed projection [N, T, 3 E], got {qkv.dim()} dimensions")
+        if qkv.shape[2] == 0 or qkv.shape[2] % (3 * self.num_heads) != 0:
+            raise ValueError(f"the last dimension ({qkv.shape[2]}) is not 3 * {self.num_heads} heads * head dimension")
+        d = qkv.shape[2] // (3 * self.num_heads)
+        if d % 2 != 0:
+            raise ValueError(f"the head dimension ({d}) must be even: rotary embeddings rotate pairs of columns")
+        return d
+
+    def tables(self, T: int, d: int, device, dtype) -> Tuple[Tensor, Tensor]:
+        """``(cos, sin)``, each ``[T, d / 2]`` in ``dtype``: the angles ``t * base^(-2 j / d)`` are computed in fp32 and the tables
+        cached on the module, so that every caller with the same arguments gets the same tensors."""
+        key = (int(T), int(d), torch.device(device), dtype, self.base)
+        if self._tables is None or self._tables[0] != key:
+            j = torch.arange(d // 2, dtype=torch.float32, device=device)
+            inv_freq = self.base ** (-2.0 * j / d)
+            angle = torch.arange(T, dtype=torch.float32, device=device)[:, None] * inv_freq[None, :]
+            self._tables = (key, angle.cos().to(dtype), angle.sin().to(dtype))
+        return self._tables[1], self._tables[2]
+
+    def forward(self, qkv: Tensor) -> Tensor:
+        d = self.head_dim(qkv)
+        N, T, H, half = qkv.shape[0], qkv.shape[1], self.num_heads, d // 2
+        cos, sin = (t.view(1, T, 1, 1, half) for t in self.tables(T, d, qkv.device, qkv.dtype))
+        x = qkv.view(N, T, 3, H, d)
+        x1, x2 = x[:, :, :2, :, :half], x[:, :, :2, :, half:]
+        rot = torch.cat((x1 * cos - x2 * sin, x2 * cos + x1 * sin), -1)          # q and k
+        return torch.cat((rot, x[:, :, 2:]), 2).reshape(N, T, 3 * H * d)
 
 
 class MultiheadSelfAttention(nn.Sequential):

@@ -18,7 +18,8 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from vivit_amd import _lib, kernels
-from vivit_amd.backend.custom_module import ActiveIdentity, Pad, ScaledDotProductAttention, ScaleModule, Slicing, SumModule
+from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, ProductModule, RotaryEmbedding, ScaledDotProductAttention, ScaleModule, Slicing,
+                                              SumModule)
 from vivit_amd.utils.ggn import Vmp
 from vivit_amd.utils.gram import mVp, pairwise_dot
 
@@ -214,6 +215,59 @@ def _norm_xhat(module, x: Tensor) -> Tensor:
     return F.group_norm(x, module.num_groups, None, None, module.eps)
 
 
+def _rms_geometry(module, x: Tensor):
+    """``(rows, A, eps)`` of an RMSNorm on the input ``x`` in the notation of csrc/llama_rules.hip: ``rows`` sets of ``L =
+    prod(normalized_shape)`` contiguous elements that share one statistic, ``A`` rows per sample; ``eps=None`` is the machine
+    epsilon of the input's dtype, as in ``F.rms_norm``."""
+    rows = x.numel() // math.prod(module.normalized_shape)
+    return rows, rows // x.shape[0], module.eps if module.eps is not None else torch.finfo(x.dtype).eps
+
+
+def _rms_norm_rules(module, M: Tensor, x: Tensor, input_rule: bool):
+    """``(input rule, weight rule)`` of an RMSNorm on the HIP kernels, remembered on the factor tensor as :func:`_norm_rules` does.
+    ``rstd`` is computed once (``vivit_rms_norm_stats_f32``), then ONE launch visits every row of ``M`` for the input rule and --
+    without extra dimensions -- the weight rule ``M xhat`` (``vivit_rms_norm_rules_f32``); with extra dimensions the weight rule sums
+    over them in a launch of its own (``vivit_rms_norm_position_sums_f32``).  Nothing is computed for an absent or frozen weight
+    (``None``), the input rule only when ``input_rule`` says that it will be asked for.  Nothing is remembered on the module."""
+    memo = getattr(M, "_vivit_rms_norm_rules", None)
+    if memo is not None and memo[0] is module and (memo[1] is not None or not input_rule):
+        return memo[1:]
+    own = bool(_own_params(module))
+    rows, A, eps = _rms_geometry(module, x)
+    gamma = module.weight.detach() if module.weight is not None else None
+    out = w = None
+    if input_rule or own:
+        rstd = kernels.rms_norm_stats(x, rows, eps)
+        shape = tuple(M.shape[:2]) + tuple(module.normalized_shape)
+        if A == 1:     # the rows are the samples: the weight rule is elementwise
+            out, w = kernels.rms_norm_rules(M, x, gamma, rstd, want=(input_rule, own))
+            w = w.view(shape) if w is not None else None
+        else:
+            out = kernels.rms_norm_rules(M, x, gamma, rstd, want=(True, False))[0] if input_rule else None
+            if own:
+                D = math.prod(module.normalized_shape)
+                w = kernels.rms_norm_position_sums(M.reshape(M.shape[0], M.shape[1], A, D), x.reshape(-1, A, D), rstd).view(shape)
+    memo = (module, out, w)
+    try:
+        M._vivit_rms_norm_rules = memo
+    except AttributeError:   # (tensor subclasses without a __dict__)
+        pass
+    return memo[1:]
+
+
+def _rms_norm_jac_t_torch(module, M: Tensor, x: Tensor) -> Tensor:
+    """The input rule of csrc/llama_rules.hip in plain torch (non-HIP or non-fp32 tensors): ``rstd (h - xhat mean(h xhat))``.  No
+    autograd."""
+    dims = tuple(range(-len(module.normalized_shape), 0))
+    eps = _rms_geometry(module, x)[2]
+    xhat = F.rms_norm(x, module.normalized_shape, None, eps)
+    rstd = torch.rsqrt(x.pow(2).mean(dims, keepdim=True) + eps)
+    h = M.reshape(M.shape[0], *x.shape)
+    if module.weight is not None:
+        h = h * module.weight.detach()
+    return rstd * (h - xhat * (h * xhat).mean(dims, keepdim=True))
+
+
 def _param_factor(module, name: str, M: Tensor, x: Tensor) -> Tensor:
     """``param_mjp(..., sum_batch=False)``: ``M`` [V, N, *out] -> [V, N, *param.shape]."""
     if isinstance(module, nn.Linear):
@@ -258,6 +312,13 @@ def _param_factor(module, name: str, M: Tensor, x: Tensor) -> Tensor:
             extra = tuple(range(2, M.dim() - len(module.normalized_shape)))
             return T.sum(extra) if extra else T
         return T.flatten(3).sum(3) if T.dim() > 3 else T
+    if isinstance(module, nn.RMSNorm):   # weight [*D] only
+        if M.is_cuda and M.dtype == torch.float32:
+            # (the input rule rides the same visit of M when the back-propagation goes on below this module)
+            return _rms_norm_rules(module, M, x, module.input0.requires_grad)[1]
+        T = M.reshape(M.shape[0], *x.shape) * F.rms_norm(x, module.normalized_shape, None, _rms_geometry(module, x)[2]).unsqueeze(0)
+        extra = tuple(range(2, T.dim() - len(module.normalized_shape)))   # the extra dimensions between batch and D are summed
+        return T.sum(extra) if extra else T
     if isinstance(module, nn.Embedding):
         B, ids = _embedding_compact(module, M, x)
         return _embedding_factor(B, ids, module.num_embeddings)
@@ -565,12 +626,24 @@ def _attention_jac_t_torch(module, M: Tensor, x: Tensor, out: Tensor) -> Tensor:
     return torch.stack((dQ, dK, dV), 0).permute(1, 2, 4, 0, 3, 5).reshape(V, N, T, 3 * H * d)
 
 
+def _rope_jac_t_torch(module, M: Tensor, x: Tensor) -> Tensor:
+    """The rule of ``vivit_rope_jac_t_f32`` in plain torch (non-HIP or non-fp32 tensors): the transposed rotation on the q and k
+    thirds of ``M [V, N, T, 3 E]`` with the tables of the forward pass, the v third as it is.  No autograd."""
+    d, H = module.head_dim(x), module.num_heads
+    V, (N, T), half = M.shape[0], x.shape[:2], d // 2
+    cos, sin = (t.view(1, 1, T, 1, 1, half) for t in module.tables(T, d, x.device, x.dtype))
+    m = M.reshape(V, N, T, 3, H, d)
+    m1, m2 = m[:, :, :, :2, :, :half], m[:, :, :, :2, :, half:]
+    rot = torch.cat((m1 * cos + m2 * sin, m2 * cos - m1 * sin), -1)
+    return torch.cat((rot, m[:, :, :, 2:]), 3).reshape(V, N, T, 3 * H * d)
+
+
 def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optional[Tensor]:
-    """The layer rules that have a HIP kernel (csrc/jacobians.hip, csrc/norm_rules.hip, csrc/attention.hip): activations (ReLU, Sigmoid, Tanh, LeakyReLU,
+    """The layer rules that have a HIP kernel (csrc/jacobians.hip, csrc/norm_rules.hip, csrc/llama_rules.hip, csrc/attention.hip): activations (ReLU, Sigmoid, Tanh, LeakyReLU,
     LogSigmoid, ELU, SELU, GELU in both forms, SiLU), Flatten / Identity / ActiveIdentity / Dropout(eval), ScaleModule,
     Max/AvgPool1d/2d, Conv1d / Conv2d and ConvTranspose1d / 2d (any groups, zero padding), Pad / ZeroPad2d / Slicing,
     BatchNorm (eval), LayerNorm and GroupNorm (with or without affine parameters; the same visit of the factor serves their
-    parameter rules), ScaledDotProductAttention (head dimensions up to 128; the forward output it needs is ``module.output``,
+    parameter rules), RMSNorm (likewise), RotaryEmbedding, ScaledDotProductAttention (head dimensions up to 128; the forward output it needs is ``module.output``,
     sub-sampled by ``subsampling`` as ``x`` was), and -- on the same two-dimensional kernels -- Conv3d, ConvTranspose3d, MaxPool3d,
     AvgPool3d.  ``None``: no kernel for this module (custom modules, unsupported options such as ceil_mode) -- the generic autograd
     rule takes over."""
@@ -659,6 +732,11 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
             return g
     if isinstance(module, _NORMS):
         return _norm_rules(module, M, x, True)[0]
+    if isinstance(module, nn.RMSNorm):
+        return _rms_norm_rules(module, M, x, True)[0]
+    if isinstance(module, RotaryEmbedding):   # the very tables the forward pass used (cached on the module)
+        d = module.head_dim(x)
+        return kernels.rope_jac_t(M.reshape(M.shape[0], *x.shape), *module.tables(x.shape[1], d, x.device, x.dtype), module.num_heads)
     if isinstance(module, ScaledDotProductAttention):
         # (a head dimension above the kernel's 128 has no kernel: the generic rule, before any operand is prepared; sizes beyond
         # the kernel's index arithmetic come back as VIVIT_E_UNSUPPORTED and the caller falls through likewise)
@@ -752,6 +830,11 @@ def _jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Tensor:
             return g
     elif isinstance(module, ScaledDotProductAttention):   # non-HIP or non-fp32 tensors: the same formula in torch
         return _attention_jac_t_torch(module, M, x, _attention_out(module, x, subsampling))
+    # non-HIP or non-fp32 tensors (or a size beyond the kernels' index arithmetic): the same formulas in torch, never autograd
+    if isinstance(module, nn.RMSNorm):
+        return _rms_norm_jac_t_torch(module, M, x)
+    if isinstance(module, RotaryEmbedding):
+        return _rope_jac_t_torch(module, M, x)
     return _generic_jac_t_mat_prod(module, M, x)
 
 
@@ -856,6 +939,18 @@ class _SqrtGGN(_Extension):
             for inp in module.inputs:
                 if inp.requires_grad:
                     ctx.put(self, inp, M)
+            return
+        if isinstance(module, ProductModule):  # y = a * b: M * b goes to a, M * a to b (the same tensor twice: both, added)
+            a, b = (subsample(t.detach(), 0, sub) for t in module.inputs)
+            need = tuple(t.requires_grad for t in module.inputs)
+            if any(need):
+                if M.is_cuda and M.dtype == torch.float32:
+                    parts = kernels.gate_jac_t(M.reshape(M.shape[0], *a.shape), a, b, want=need)
+                else:
+                    parts = (M * b.unsqueeze(0) if need[0] else None, M * a.unsqueeze(0) if need[1] else None)
+                for inp, g in zip(module.inputs, parts):
+                    if g is not None:
+                        ctx.put(self, inp, g)
             return
         x = subsample(module.input0.detach(), 0, sub)
         for name, p in _own_params(module):

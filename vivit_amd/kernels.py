@@ -550,6 +550,127 @@ def norm_position_sums(M, x, mean, rstd):
     return pw, pb
 
 
+def _out_like(out, ref, what: str):
+    """``out`` (a caller's buffer for a result shaped like ``ref``) checked, or a new tensor."""
+    if out is None:
+        return torch.empty(tuple(ref.shape), dtype=torch.float32, device=ref.device)
+    _require_device(out)
+    if tuple(out.shape) != tuple(ref.shape) or not out.is_contiguous() or out.device != ref.device:
+        raise ValueError(f"{what} must be a contiguous tensor of shape {tuple(ref.shape)} on {ref.device}")
+    return out
+
+
+@_launcher
+def rms_norm_stats(x, rows: int, eps: float):
+    """``rstd [rows]`` of the normalisation rows of ``x`` (``rows * L`` elements, ``vivit_rms_norm_stats_f32``):
+    ``1 / sqrt(mean(x^2) + eps)`` -- the statistic of ``nn.RMSNorm``."""
+    _require_device(x)
+    x = x.contiguous()
+    if rows <= 0 or x.numel() == 0 or x.numel() % rows != 0:
+        raise ValueError(f"x must hold {rows} rows of equal length, got {tuple(x.shape)}")
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    st = _lib.load().vivit_rms_norm_stats_f32(x.data_ptr(), rstd.data_ptr(), rows, x.numel() // rows, float(eps), _stream(x))
+    _lib.check(st, "vivit_rms_norm_stats_f32")
+    return rstd
+
+
+@_launcher
+def rms_norm_rules(M, x, gamma, rstd, want=(True, True), out=None, w=None):
+    """The rules of an RMSNorm in one visit of every normalisation row (``vivit_rms_norm_rules_f32``): ``M [V, *x.shape]``, ``x`` of
+    ``rows = rstd.numel()`` rows of ``L`` elements, ``gamma`` (``L`` values; ``None``: 1) -> ``(out, w)``, both like ``M``: the
+    transposed input Jacobian ``rstd (h - xhat mean(h xhat))`` with ``h = gamma M``, ``xhat = x rstd``, and ``M xhat``.  ``want``:
+    which of the two to compute (``None`` for the other); ``out`` / ``w``: buffers to write them to."""
+    _require_device(M, x, gamma, rstd)
+    M, x, rstd = M.contiguous(), x.contiguous(), rstd.contiguous()
+    if M.dim() < 2 or tuple(M.shape[1:]) != tuple(x.shape):
+        raise ValueError(f"M must be [V, *x.shape], got {tuple(M.shape)} for x {tuple(x.shape)}")
+    rows = rstd.numel()
+    if rows == 0 or x.numel() == 0 or x.numel() % rows != 0:
+        raise ValueError(f"rstd must hold one value per normalisation row of x, got {rows} for x {tuple(x.shape)}")
+    L = x.numel() // rows
+    if gamma is not None:
+        gamma = gamma.contiguous()
+        if gamma.numel() != L:
+            raise ValueError(f"gamma must have {L} elements, got {gamma.numel()}")
+    if not any(want):
+        raise ValueError("nothing to compute")
+    out = _out_like(out, M, "out") if want[0] else None
+    w = _out_like(w, M, "w") if want[1] else None
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    st = _lib.load().vivit_rms_norm_rules_f32(M.data_ptr(), x.data_ptr(), ptr(gamma), rstd.data_ptr(), ptr(out), ptr(w), M.shape[0], rows, L,
+                                             _stream(M))
+    _lib.check(st, "vivit_rms_norm_rules_f32")
+    return out, w
+
+
+@_launcher
+def rms_norm_position_sums(M, x, rstd, out=None):
+    """Weight rule of an RMSNorm with extra dimensions (``vivit_rms_norm_position_sums_f32``): ``M [V, N, A, D]``, ``x [N, A, D]``,
+    ``rstd`` of ``N * A`` values -> ``sum_a M x rstd  [V, N, D]``."""
+    _require_device(M, x, rstd)
+    M, x, rstd = M.contiguous(), x.contiguous(), rstd.contiguous()
+    if M.dim() != 4 or tuple(M.shape[1:]) != tuple(x.shape) or M.numel() == 0:
+        raise ValueError(f"M must be [V, N, A, D] and x [N, A, D], got {tuple(M.shape)} for x {tuple(x.shape)}")
+    Vd, N, A, D = M.shape
+    if rstd.numel() != N * A:
+        raise ValueError(f"rstd must have {N * A} elements, got {rstd.numel()}")
+    pw = _out_like(out, M[:, :, 0], "out")
+    st = _lib.load().vivit_rms_norm_position_sums_f32(M.data_ptr(), x.data_ptr(), rstd.data_ptr(), pw.data_ptr(), Vd, N, A, D, _stream(M))
+    _lib.check(st, "vivit_rms_norm_position_sums_f32")
+    return pw
+
+
+@_launcher
+def gate_jac_t(M, a, b, want=(True, True), out_a=None, out_b=None):
+    """Transposed input Jacobians of the product ``a * b`` (``vivit_gate_jac_t_f32``): ``M [V, *a.shape]`` -> ``(M b, M a)``, the
+    factors handed to ``a`` and to ``b``, from one read of ``M``.  ``want``: which of the two to compute (``None`` for the other,
+    whose operand may be ``None`` as well); ``out_a`` / ``out_b``: buffers to write them to."""
+    _require_device(M, a, b)
+    M = M.contiguous()
+    if not any(want):
+        raise ValueError("nothing to compute")
+    for t, needed, name in ((b, want[0], "b"), (a, want[1], "a")):
+        if needed and (t is None or M.dim() < 1 or tuple(M.shape[1:]) != tuple(t.shape)):
+            raise ValueError(f"M must be [V, *{name}.shape], got {tuple(M.shape)} for {name} {None if t is None else tuple(t.shape)}")
+    if M.numel() == 0:
+        raise ValueError(f"empty operands: M {tuple(M.shape)}")
+    a = a.contiguous() if want[1] else None
+    b = b.contiguous() if want[0] else None
+    Ga = _out_like(out_a, M, "out_a") if want[0] else None
+    Gb = _out_like(out_b, M, "out_b") if want[1] else None
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    st = _lib.load().vivit_gate_jac_t_f32(M.data_ptr(), ptr(a), ptr(b), ptr(Ga), ptr(Gb), M.shape[0], M.numel() // M.shape[0], _stream(M))
+    _lib.check(st, "vivit_gate_jac_t_f32")
+    return Ga, Gb
+
+
+@_launcher
+def rope_jac_t(M, cos, sin, num_heads: int, out=None):
+    """Transposed Jacobian of the rotary position embedding on a packed projection (``vivit_rope_jac_t_f32``): ``M [..., T, 3 E]``
+    (``E = num_heads * d``), ``cos`` / ``sin [T, d / 2]`` -> like ``M``: the q and k thirds rotated back, the v third copied.
+    ``out``: a buffer for the result; ``M`` itself for the rule in place."""
+    _require_device(M, cos, sin)
+    if out is M and not M.is_contiguous():
+        raise ValueError("the rule in place needs a contiguous M")
+    M, cos, sin = M.contiguous(), cos.contiguous(), sin.contiguous()
+    if M.dim() < 2 or num_heads < 1 or M.shape[-1] == 0 or M.shape[-1] % (6 * num_heads) != 0:
+        raise ValueError(f"M must be [..., T, 3 * {num_heads} heads * an even head dimension], got {tuple(M.shape)}")
+    T, d = M.shape[-2], M.shape[-1] // (3 * num_heads)
+    if tuple(cos.shape) != (T, d // 2) or tuple(sin.shape) != (T, d // 2):
+        raise ValueError(f"cos and sin must be {(T, d // 2)}, got {tuple(cos.shape)} and {tuple(sin.shape)}")
+    if M.numel() == 0:
+        raise ValueError(f"empty operands: M {tuple(M.shape)}")
+    G = _out_like(out, M, "out")
+    if G is not M and G.untyped_storage().data_ptr() == M.untyped_storage().data_ptr():
+        lo, hi = G.data_ptr(), G.data_ptr() + 4 * G.numel()
+        if M.data_ptr() < hi and lo < M.data_ptr() + 4 * M.numel() and G.data_ptr() != M.data_ptr():
+            raise ValueError("out must be M itself or must not overlap it")
+    st = _lib.load().vivit_rope_jac_t_f32(M.data_ptr(), cos.data_ptr(), sin.data_ptr(), G.data_ptr(), M.numel() // (T * M.shape[-1]), T,
+                                         num_heads, d, _stream(M))
+    _lib.check(st, "vivit_rope_jac_t_f32")
+    return G
+
+
 @_launcher
 def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool):
     """Transposed input Jacobian of scaled dot-product self-attention (``vivit_attention_jac_t_f32``): ``M [V, N, T, E]`` (the factor
