@@ -100,10 +100,11 @@ def _threads(nbytes):
     return 1024 if nbytes > 80 * 1024 else (512 if nbytes > 40 * 1024 else 256)
 
 
-def weight_plan(g, mfma=True):
-    """conv2d_weight_mjp_mfma_lds of csrc/factors.hip (``mfma``: VIVIT_CONV_MFMA) and what the launch derives from it."""
+def weight_plan(g, mfma=True, out=None):
+    """conv2d_weight_mjp_mfma_lds of csrc/factors.hip (``mfma``: VIVIT_CONV_MFMA) and what the launch derives from it.
+    ``out``: the (OH, OW) the entry point is given, where they are not the floor formula's (tests/conv_family_refs.py)."""
     (KH, KW), (ph, pw) = g.k, g.p
-    OH, OW = out_hw(*g[2:])
+    OH, OW = out or out_hw(*g[2:])
     L, K = OH * OW, g.Cin * KH * KW
     plan = {"route": "scalar", "reason": None, "L": L, "Lmod4": L % 4, "OW": OW, "K": K, "Kmod16": K % 16, "RT": None, "S": 1,
             "threads": 256, "lds": 0, "nct": cdiv(K, 16), "trips": None, "idle_waves": None, "groups": cdiv(g.Cout, CWM_OC),
@@ -128,11 +129,11 @@ def weight_plan(g, mfma=True):
     return plan
 
 
-def input_plan(g, mfma=True, rows=V_SLICES * N_BATCH):
+def input_plan(g, mfma=True, rows=V_SLICES * N_BATCH, out=None):
     """The dispatch of vivit_conv2d_jac_t_f32 and conv2d_jac_t_mfma_plan of csrc/jacobians.hip (``mfma``: VIVIT_CONV_MFMA).
-    route: "scalar", "mfma" or "unsupported"."""
+    route: "scalar", "mfma" or "unsupported".  ``out``: as for :func:`weight_plan`."""
     (KH, KW), (sh, sw), (ph, pw), (dh, dw) = g.k, g.s, g.p, g.d
-    OH, OW = out_hw(*g[2:])
+    OH, OW = out or out_hw(*g[2:])
     KK, HW = KH * KW, g.H * g.W
     scalar_lds = g.Cout * KK * CIT * 4
     tiles = cdiv(HW, 256)
