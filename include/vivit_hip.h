@@ -379,6 +379,17 @@ int vivit_embedding_weight_mjp_f32(const float *B, const int32_t *ids, float *ou
  * S[v, n, c] = sqrt(p_nv) (delta_vc - p_nc) scale;  onehot [V, N, C] (sampled): S[v, n, c] = (p_nc - onehot[v, n, c]) scale. */
 int vivit_ce_sqrt_hessian_f32(const float *logits, const float *onehot, float *S, int64_t N, int64_t C, int64_t V, float scale,
                               void *stream);
+/* The same for outputs with positions (csrc/loss_positions.hip): N samples of C classes at L positions, sample stride C L, a softmax
+ * over the classes at every position, p[n, :, l] = softmax_c(logits[n, :, l]).  layout 0 ("NCL"): class stride L, position stride 1
+ * (a contiguous [N, C, *D]); layout 1 ("NLC"): class stride 1, position stride C (a contiguous [N, *D, C] seen as [N, C, *D]).
+ * idx == NULL (exact, V must equal C L, row v = c' L + l'):  S[v, n, c, l] = [l = l'] sqrt(p[n, c', l]) ([c = c'] - p[n, c, l]) scale;
+ * idx [V, N, L] int32 class indices (sampled):               S[m, n, c, l] = (p[n, c, l] - [c = idx[m, n, l]]) scale.
+ * Every (v, n) slice of S has the layout of a sample of the logits; every element is written, the zeros of the exact factor included.
+ * An index outside [0, C) matches no class: that position of the slice is p scale, and no address is formed from an index.  C has no
+ * upper limit other than the index arithmetic.  Any zero size: VIVIT_OK, no pointer is read.  VIVIT_E_BADARG: a negative size, layout
+ * other than 0 or 1, logits or S null, exact with V != C L.  VIVIT_E_UNSUPPORTED: a size or N L above 2^31 - 1, V N C L above 2^60. */
+int vivit_ce_pos_sqrt_hessian_f32(const float *logits, const int32_t *idx, float *S, int64_t N, int64_t C, int64_t L, int64_t V, int layout,
+                                  float scale, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K3/K4  Symmetric eigendecomposition (Householder tridiagonalisation + implicit-shift QL,

@@ -64,6 +64,7 @@ SIGNATURES = {
     "vivit_embedding_vtmp_f32": (_int, [_ptr] * 4 + [_i64] * 6 + [_ptr]),
     "vivit_embedding_weight_mjp_f32": (_int, [_ptr] * 3 + [_i64] * 5 + [_ptr]),
     "vivit_ce_sqrt_hessian_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _f32, _ptr]),
+    "vivit_ce_pos_sqrt_hessian_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _f32, _ptr]),
     "vivit_symeig_f32_workspace_bytes": (_sz, [_i64, _int]),
     "vivit_symeig_f32": (_int, [_ptr, _i64, _i64, _ptr, _ptr, _i64, _ptr, _sz, _ptr, _ptr]),
     "vivit_symeigvals_batched_f32_workspace_bytes": (_sz, [_i64, _i64]),
@@ -107,7 +108,7 @@ SIGNATURES = {
 }
 
 # include/vivit_hip.h of this checkout (vivit_hip_abi_version).  The batched entry points (two-phase solve, Gram-space
-# directions, the attention, Embedding and sequence-Linear rules) only ADD exports: the
+# directions, the attention, Embedding and sequence-Linear rules, the per-position loss factor) only ADD exports: the
 # number stays; a library without them is refused by the symbol lookup in load() and by the source hash (_check_provenance).
 ABI_VERSION = 1008
 

@@ -9,7 +9,9 @@ eval mode, element-wise activations, pooling, Flatten, Dropout in eval mode, and
 ``Parallel`` / ``SumModule`` / ``Pad`` / ``Slicing`` / ``ScaleModule`` of ``backpack.custom_module``, LayerNorm / GroupNorm,
 the self-attention modules ``ScaledDotProductAttention`` / ``MultiheadSelfAttention`` of ``custom_module``, ``nn.Embedding``,
 ``nn.RMSNorm`` and the modules ``ProductModule`` (gated MLPs) / ``RotaryEmbedding`` of ``custom_module``;
-CrossEntropyLoss / MSELoss with ``reduction='mean'``).  When the real BackPACK is importable the Computation classes can be used
+CrossEntropyLoss / MSELoss with ``reduction='mean'`` or ``'sum'``, on outputs ``[N, C]`` and on outputs with positions
+``[N, C, *D]`` -- next-token cross entropy over a whole sequence, segmentation, dense regression -- with ``Permute`` of
+``custom_module`` to bring a head's ``[N, T, C]`` to ``[N, C, T]``).  When the real BackPACK is importable the Computation classes can be used
 with it directly; this module is never imported in that case.
 
 This is the FACTOR PROVIDER, i.e. the producer of the path's inputs
@@ -21,6 +23,7 @@ from vivit_amd.backend.custom_module import (
     MultiheadSelfAttention,
     Pad,
     Parallel,
+    Permute,
     ProductModule,
     RotaryEmbedding,
     ScaledDotProductAttention,
@@ -37,4 +40,4 @@ from vivit_amd.backend.extensions import (
     ViViTGGNMC,
 )
 
-__all__ = ["ActiveIdentity", "MultiheadSelfAttention", "Pad", "Parallel", "ProductModule", "RotaryEmbedding", "ScaledDotProductAttention", "ScaleModule", "Slicing", "SumModule", "backpack", "extend", "BatchGrad", "SqrtGGNExact", "SqrtGGNMC", "ViViTGGNExact", "ViViTGGNMC"]
+__all__ = ["ActiveIdentity", "MultiheadSelfAttention", "Pad", "Parallel", "Permute", "ProductModule", "RotaryEmbedding", "ScaledDotProductAttention", "ScaleModule", "Slicing", "SumModule", "backpack", "extend", "BatchGrad", "SqrtGGNExact", "SqrtGGNMC", "ViViTGGNExact", "ViViTGGNMC"]

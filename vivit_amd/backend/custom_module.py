@@ -78,6 +78,30 @@ class Slicing(nn.Module):
         return x[self.slice_info]
 
 
+class Permute(nn.Module):
+    """``x.permute(dims)`` as a module (``backpack.custom_module.permute.Permute``); the batch axis stays in front
+    (``dims[0] == 0``).  ``Permute(0, 2, 1)`` takes a head's ``[N, T, C]`` to the ``[N, C, T]`` that ``nn.CrossEntropyLoss`` wants."""
+
+    def __init__(self, *dims: int):
+        super().__init__()
+        if len(dims) == 1 and isinstance(dims[0], (tuple, list)):
+            dims = tuple(dims[0])
+        if not all(isinstance(d, int) for d in dims) or sorted(dims) != list(range(len(dims))):
+            raise ValueError(f"dims must be a permutation of 0 .. {len(dims) - 1}, got {dims}")
+        if not dims or dims[0] != 0:
+            raise ValueError(f"the batch axis must stay in front (dims[0] == 0), got {dims}")
+        self.dims = tuple(dims)
+
+    def inverse_dims(self) -> Tuple[int, ...]:
+        inv = [0] * len(self.dims)
+        for i, d in enumerate(self.dims):
+            inv[d] = i
+        return tuple(inv)
+
+    def forward(self, x: Tensor) -> Tensor:
+        return x.permute(self.dims)
+
+
 class ScaleModule(nn.Module):
     """``x * weight`` with a constant scalar (``backpack.custom_module.scale_module.ScaleModule``)."""
 

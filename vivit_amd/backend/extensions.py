@@ -18,7 +18,8 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from vivit_amd import _lib, kernels
-from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, ProductModule, RotaryEmbedding, ScaledDotProductAttention, ScaleModule, Slicing,
+from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, Permute, ProductModule, RotaryEmbedding, ScaledDotProductAttention, ScaleModule,
+                                              Slicing,
                                               SumModule)
 from vivit_amd.utils.ggn import Vmp
 from vivit_amd.utils.gram import mVp, pairwise_dot
@@ -815,6 +816,8 @@ def _jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Tensor:
             O = M.shape[-1]
             return kernels.gemm_nn(M.reshape(-1, O), module.weight.detach()).view(*M.shape[:-1], -1)
         return M @ module.weight.detach()
+    if isinstance(module, Permute):     # a view on every device: the inverse permutation behind the leading V axis (no copy, no kernel)
+        return M.permute((0,) + tuple(d + 1 for d in module.inverse_dims()))
     if isinstance(module, nn.Dropout) and module.training and module.p > 0:
         raise NotImplementedError("Dropout must be in eval mode")
     if isinstance(module, _BATCHNORM) and module.training:
@@ -864,11 +867,70 @@ class BatchGrad(_Extension):
 
 
 # ---------------------------------------------------------------------------------------------
+def _loss_hessian_sqrt_positions(module, out: Tensor, strategy: str, mc_samples: int, samples: Optional[Tensor]) -> Tensor:
+    """Symmetric factor S [V, N, C, *D] of the loss Hessian w.r.t. an output with positions, ``out [N, C, *D]``, ``L = prod(D)``.
+
+    CrossEntropyLoss (a softmax over the classes at every position; 'mean' averages over the ``N L`` positions): exact, ``V = C L``,
+    row ``v = c' L + l'``, ``S[v, n, c, l] = [l = l'] sqrt(p[n, c', l]) ([c = c'] - p[n, c, l]) / sqrt(norm)``; sampled, ``V = M``,
+    ``S[m, n, c, l] = (p[n, c, l] - [c = idx[m, n, l]]) / sqrt(M norm)`` with class indices ``idx [M, N, *D]`` -- ``samples`` of an
+    integer dtype, the argmax of one-hot ``samples [M, N, C, *D]``, or drawn here from ``p``.  HIP fp32 tensors: one kernel
+    (``kernels.ce_sqrt_hessian_positions``, in the memory format of ``out``); otherwise the same formulas in torch, no autograd.
+    MSELoss ('mean' averages over ``N C L`` elements): ``sqrt(2 / norm) I`` as ``[C L, N, C, *D]``, or ``M`` normal samples.
+    ``ignore_index``, ``weight`` and ``label_smoothing`` of CrossEntropyLoss are not looked at (as for ``[N, C]``)."""
+    N, C, D = out.shape[0], out.shape[1], tuple(out.shape[2:])
+    L = math.prod(D)
+    red = module.reduction
+    if red not in ("mean", "sum"):
+        raise NotImplementedError(f"reduction={red}")
+    if isinstance(module, nn.CrossEntropyLoss):
+        norm = N * L if red == "mean" else 1
+        hip = out.is_cuda and out.dtype == torch.float32
+        if strategy == "exact":
+            if hip:
+                return kernels.ce_sqrt_hessian_positions(out, 1.0 / math.sqrt(norm))
+            p = out.softmax(dim=1).reshape(N, C, L)
+            eye_c = torch.eye(C, dtype=out.dtype, device=out.device)
+            eye_l = torch.eye(L, dtype=out.dtype, device=out.device)
+            inner = p.sqrt().permute(1, 0, 2).unsqueeze(2) * (eye_c[:, None, :, None] - p.unsqueeze(0))      # [c', n, c, l]
+            S = inner.unsqueeze(1) * eye_l[None, :, None, None, :]                                           # [c', l', n, c, l]
+            return S.reshape(C * L, N, C, *D) / math.sqrt(norm)
+        if samples is None:
+            p = out.softmax(dim=1)
+            idx = torch.multinomial(p.movedim(1, -1).reshape(N * L, C), mc_samples, replacement=True).t().reshape(mc_samples, N, *D)
+        elif samples.is_floating_point():
+            if tuple(samples.shape[1:]) != tuple(out.shape):
+                raise ValueError(f"one-hot samples must be [M, {', '.join(map(str, out.shape))}], got {tuple(samples.shape)}")
+            idx = samples.argmax(dim=2)
+        else:
+            if tuple(samples.shape[1:]) != (N,) + D:
+                raise ValueError(f"class-index samples must be [M, {', '.join(map(str, (N,) + D))}], got {tuple(samples.shape)}")
+            idx = samples
+        scale = 1.0 / math.sqrt(idx.shape[0] * norm)
+        if hip:
+            return kernels.ce_sqrt_hessian_positions(out, scale, idx=idx.to(out.device, torch.int32))
+        onehot = F.one_hot(idx.to(out.device, torch.long), C).movedim(-1, 2).to(out.dtype)                   # [M, N, C, *D]
+        return (out.softmax(dim=1).unsqueeze(0) - onehot) * scale
+    if isinstance(module, nn.MSELoss):
+        norm = N * C * L if red == "mean" else 1
+        if strategy == "exact":
+            S = torch.eye(C * L, dtype=out.dtype, device=out.device).unsqueeze(1).expand(C * L, N, C * L)
+            return (S * math.sqrt(2.0 / norm)).view(C * L, N, C, *D)
+        if samples is None:
+            samples = torch.randn(mc_samples, N, C, *D, dtype=out.dtype, device=out.device)
+        elif tuple(samples.shape[1:]) != tuple(out.shape):
+            raise ValueError(f"samples must be [M, {', '.join(map(str, out.shape))}], got {tuple(samples.shape)}")
+        return samples.to(out.device, out.dtype) * math.sqrt(2.0 / (samples.shape[0] * norm))
+    raise NotImplementedError(type(module).__name__)
+
+
 def _loss_hessian_sqrt(module, strategy: str, mc_samples: int, samples: Optional[Tensor]) -> Tensor:
-    """Symmetric factor S [V, N, C] of the loss Hessian w.r.t. the model output."""
+    """Symmetric factor S [V, N, C] of the loss Hessian w.r.t. the model output ``[N, C]``; ``[V, N, C, *D]`` for an output with
+    positions ``[N, C, *D]`` (:func:`_loss_hessian_sqrt_positions`)."""
     out = module.input0.detach()
+    if out.dim() > 2:
+        return _loss_hessian_sqrt_positions(module, out, strategy, mc_samples, samples)
     if out.dim() != 2:
-        raise NotImplementedError("loss input must be [N, C]")
+        raise NotImplementedError("loss input must be [N, C] or [N, C, *D]")
     N, C = out.shape
     red = module.reduction
     if red not in ("mean", "sum"):

@@ -867,6 +867,47 @@ def ce_sqrt_hessian(logits, scale: float, onehot=None):
 
 
 @_launcher
+def ce_sqrt_hessian_positions(logits, scale: float, idx=None):
+    """Cross-entropy loss-Hessian square root for ``logits [N, C, *D]`` (a softmax over the classes at each of the ``L = prod(D)``
+    positions): exact, ``S [C L, N, C, *D]`` with row ``v = c' L + l'`` and
+    ``S[v, n, c, l] = [l = l'] sqrt(p[n, c', l]) ([c = c'] - p[n, c, l]) * scale``, or, with ``idx [M, N, *D]`` int32 class indices,
+    the sampled factor ``S[m, n, c, l] = (p[n, c, l] - [c = idx[m, n, l]]) * scale`` (an index outside ``[0, C)`` matches no class).
+
+    ``logits`` may be contiguous (class stride ``L``) or a permuted view of a contiguous ``[N, *D, C]`` (class stride 1); any other
+    strides are copied first.  Every ``(v, n)`` slice of ``S`` has the memory format of a sample of ``logits``: for a permuted view,
+    ``S.movedim(2, -1)`` is contiguous."""
+    _require_device(logits)
+    if logits.dim() < 3:
+        raise ValueError(f"logits must be [N, C, *D] with at least one position dimension, got {tuple(logits.shape)}")
+    N, C, D = logits.shape[0], logits.shape[1], tuple(logits.shape[2:])
+    if C < 1:
+        raise ValueError("logits must have at least one class")
+    L = 1
+    for d in D:
+        L *= d
+    if idx is not None:
+        if idx.dtype != torch.int32:
+            raise ValueError(f"idx must be int32 class indices, got {idx.dtype}")
+        if idx.dim() != logits.dim() or tuple(idx.shape[1:]) != (N,) + D:
+            raise ValueError(f"idx must be [M, {N}, {', '.join(map(str, D))}], got {tuple(idx.shape)}")
+        if idx.device != logits.device:
+            raise RuntimeError(f"all operands must live on one device (got {logits.device} and {idx.device})")
+        idx = idx.contiguous()
+    classes_last = logits.movedim(1, -1).is_contiguous()
+    if not classes_last:
+        logits = logits.contiguous()
+    Vd = C * L if idx is None else idx.shape[0]
+    if classes_last:
+        S = torch.empty((Vd, N) + D + (C,), dtype=torch.float32, device=logits.device).movedim(-1, 2)
+    else:
+        S = torch.empty((Vd, N, C) + D, dtype=torch.float32, device=logits.device)
+    st = _lib.load().vivit_ce_pos_sqrt_hessian_f32(logits.data_ptr(), idx.data_ptr() if idx is not None else None, S.data_ptr(), N, C, L, Vd,
+                                                  1 if classes_last else 0, float(scale), _stream(logits))
+    _lib.check(st, "vivit_ce_pos_sqrt_hessian_f32")
+    return S
+
+
+@_launcher
 def pack_lower(G: torch.Tensor) -> torch.Tensor:
     """Lower triangle (diagonal included) of the square matrix ``G`` as a packed ``n (n + 1) / 2`` vector (row-major)."""
     _require_device(G)
