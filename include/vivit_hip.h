@@ -385,7 +385,9 @@ int vivit_ce_sqrt_hessian_f32(const float *logits, const float *onehot, float *S
  * idx == NULL (exact, V must equal C L, row v = c' L + l'):  S[v, n, c, l] = [l = l'] sqrt(p[n, c', l]) ([c = c'] - p[n, c, l]) scale;
  * idx [V, N, L] int32 class indices (sampled):               S[m, n, c, l] = (p[n, c, l] - [c = idx[m, n, l]]) scale.
  * Every (v, n) slice of S has the layout of a sample of the logits; every element is written, the zeros of the exact factor included.
- * An index outside [0, C) matches no class: that position of the slice is p scale, and no address is formed from an index.  C has no
+ * An index outside [0, C) matches no class: that position of the slice is p scale, and no address is formed from an index.
+ * Non-finite logits follow torch.softmax: -inf beside finite classes is p = 0; a NaN or +inf at any class of a position, or -inf at
+ * all of them, makes every class of that position NaN in every slice that writes it, and changes no other position.  C has no
  * upper limit other than the index arithmetic.  Any zero size: VIVIT_OK, no pointer is read.  VIVIT_E_BADARG: a negative size, layout
  * other than 0 or 1, logits or S null, exact with V != C L.  VIVIT_E_UNSUPPORTED: a size or N L above 2^31 - 1, V N C L above 2^60. */
 int vivit_ce_pos_sqrt_hessian_f32(const float *logits, const int32_t *idx, float *S, int64_t N, int64_t C, int64_t L, int64_t V, int layout,

@@ -2,7 +2,9 @@
 vivit_amd/backend/extensions.py).  TEST INFRASTRUCTURE shared by tests/test_loss_positions_refs_host.py (no GPU),
 tests/test_loss_positions_kernels_gpu.py and tests/test_loss_positions_layers.py; in the manner of tests/llama_refs.py.
 
-Every reference restates the formula of include/vivit_hip.h in torch fp64 with a plain loop over the positions: for an output
+Every reference restates the formula of include/vivit_hip.h in torch fp64 with a plain loop over the positions (``ce_sampled_vec`` and
+``ce_exact_vec`` are the same formulas without the loop, for the tests with 10^5 to 10^7 positions;
+tests/test_loss_positions_refs_host.py holds them to the loops bit for bit): for an output
 ``[N, C, *D]`` with ``L = prod(D)`` positions and ``p[n, :, l] = softmax_c(out[n, :, l])``,
 
 * cross entropy, exact (``V = C L``, row ``v = c' L + l'``):  ``S[v, n, c, l] = [l = l'] sqrt(p[n, c', l]) ([c = c'] - p[n, c, l]) scale``
@@ -59,6 +61,38 @@ def ce_sampled(out, idx, scale):
                     e[int(k[m, n, l])] = 1.0
                 S[m, n, :, l] = (p - e) * scale
     return S.reshape(M, N, C, *D)
+
+
+def _softmax_over_classes(z):
+    """fp64 z [N, C, L] -> softmax over C.  Taken along the last axis of a contiguous [N, L, C], the arrangement in which torch sums
+    the classes of a position in the order it uses for the single vector ``z[n, :, l]`` of the loops: the same bits."""
+    return torch.softmax(z.movedim(1, 2).contiguous(), 2).movedim(2, 1)
+
+
+def ce_sampled_vec(out, idx, scale):
+    """:func:`ce_sampled` without the loop over the positions (for 10^5 to 10^7 of them): one fp64 ``torch.softmax`` over the classes
+    and a comparison of the class numbers with the indices.  Non-finite logits follow torch: a NaN, a ``+inf`` or nothing but ``-inf``
+    among the classes of a position makes every class of that position NaN; a ``-inf`` beside finite classes is a probability of 0."""
+    N, C, D = out.shape[0], out.shape[1], tuple(out.shape[2:])
+    L = math.prod(D)
+    M = idx.shape[0]
+    p = _softmax_over_classes(out.to(F64).reshape(N, C, L))
+    hit = idx.reshape(M, N, 1, L) == torch.arange(C).view(1, 1, C, 1)          # (an index outside [0, C) equals no class number)
+    return ((p.unsqueeze(0) - hit.to(F64)) * scale).reshape(M, N, C, *D)
+
+
+def ce_exact_vec(out, scale):
+    """:func:`ce_exact` without the loop over the positions.  The rows ``v = c' L + l'`` are written at ``l = l'`` only, so a NaN at one
+    position leaves the structural zeros of every other position exactly 0.0 (a product with a mask would not)."""
+    N, C, D = out.shape[0], out.shape[1], tuple(out.shape[2:])
+    L = math.prod(D)
+    p = _softmax_over_classes(out.to(F64).reshape(N, C, L))
+    e = torch.eye(C, dtype=F64).view(C, 1, C, 1)                               # [c', 1, c, 1]
+    block = torch.sqrt(p).movedim(1, 0).unsqueeze(2) * (e - p.unsqueeze(0)) * scale   # [c', n, c, l]
+    S = torch.zeros(C, L, N, C, L, dtype=F64)
+    pos = torch.arange(L)
+    S[:, pos, :, :, pos] = block.movedim(3, 0)                                 # (the indexed axes lead: [l, c', n, c])
+    return S.reshape(C * L, N, C, *D)
 
 
 def mse_exact(shape, scale):

@@ -1,7 +1,8 @@
 """The per-position cross-entropy factor kernels (csrc/loss_positions.hip) against the fp64 references of
 tests/loss_positions_refs.py: both memory layouts, both modes, every body (16-byte and scalar) and route (a wavefront or a workgroup
 per row of classes; lanes along the positions), outputs between guard words and pre-filled with NaN.  Tolerances: those
-tests/test_jacobians_gpu.py uses for the [N, C] kernel, rtol 1e-4 and atol 1e-6 (with scales 1 / sqrt(N), N <= 2, of order one)."""
+tests/test_jacobians_gpu.py uses for the [N, C] kernel, rtol 1e-4 and atol 1e-6 (with scales 1 / sqrt(N), N <= 2, of order one).
+Further down: every route past the first trip of its grid-stride loop, offsets of S past 2^31 elements, and non-finite logits."""
 import functools
 import math
 
@@ -196,6 +197,232 @@ def test_a_second_call_gives_the_same_bytes(mode, C, L, layout):
     first = launch(logits_of(N, C, L), idx, layout, 0.5)[1].clone()
     second = launch(logits_of(N, C, L), idx, layout, 0.5)[1]
     assert torch.equal(first, second)
+
+
+# ---- past the first trip of the grid-stride loops --------------------------------------------------------------------------------------
+# Every launch caps its grid at 32 768 workgroups and loops.  The shapes below are the smallest whose LAST trip holds one row (or one
+# group of positions) beyond a whole number of full trips: 4 * 32768 + 1 rows on the wavefront route (one busy wavefront beside three
+# idle ones), 32768 + 1 rows on the workgroup route, 64 * 32768 + 1 positions or groups of four on the position lanes.  The logits are
+# drawn per test and not cached (up to 135 MB); the fp64 references are the vectorised ones of loss_positions_refs, compared on the
+# device in chunks with the formula of numpy's assert_allclose.
+def fresh_logits(N, C, L):
+    return torch.randn(N, C, L, generator=torch.Generator().manual_seed(11 + 7 * C + L)) * 3.0
+
+
+def fresh_indices(M, N, C, L):
+    return torch.randint(0, C, (M, N, L), generator=torch.Generator().manual_seed(13 + M + C + L), dtype=torch.int32)
+
+
+def close_on_device(view, ref, layout, chunk=1 << 24):
+    """|got - ref| <= ATOL + RTOL |ref| (NaN equal to NaN only) for the flat device ``view`` against the CPU fp64 ``ref`` in logical
+    order [V, N, C, L], brought into the memory order of ``layout`` and uploaded ``chunk`` elements at a time."""
+    flat = (ref if layout == 0 else ref.movedim(2, 3)).reshape(-1)
+    assert flat.numel() == view.numel()
+    for o in range(0, flat.numel(), chunk):
+        r = flat[o:o + chunk].to(DEV)
+        g = view[o:o + chunk].double()
+        bad = ~(((g - r).abs() <= ATOL + RTOL * r.abs()) | (g.isnan() & r.isnan()))
+        if bool(bad.any()):
+            i = int(bad.nonzero()[0])
+            raise AssertionError(f"{int(bad.sum())} of the {r.numel()} elements from flat offset {o} differ from the fp64 reference; the "
+                                 f"first, at {o + i}: got {g[i].item()!r}, reference {r[i].item()!r}")
+
+
+def tail_of(z, idx, S, K):
+    """The last K positions of the last sample (the last K samples where L = 1) -- the end of the last trip -- as a problem of its
+    own: (logits, indices, the elements of the large launch's S that the small launch computes)."""
+    if z.shape[2] >= K:
+        return z[-1:, :, -K:], None if idx is None else idx[:, -1:, -K:], S[:, -1:, :, -K:]
+    assert z.shape[2] == 1
+    return z[-K:], None if idx is None else idx[:, -K:], S[:, -K:]
+
+
+def second_trip_checks(N, C, L, M, layout, K):
+    """M = None: the exact factor.  (1) every element against fp64, none left at the NaN prefill, guards intact; (2) a second call
+    gives the same bytes; (3) the end of the last trip has the bytes it gets when launched alone, within a first trip (as
+    tests/test_norm_rules_kernels_gpu.py::test_norm_rules_batch_independence)."""
+    z = fresh_logits(N, C, L)
+    idx = None if M is None else fresh_indices(M, N, C, L)
+    scale = 0.5
+    buf, view, S = launch(z, idx, layout, scale)
+    assert refs.guards_intact(buf, view)
+    nans = int(torch.isnan(view).sum())
+    assert nans == 0, f"{nans} of {view.numel()} elements are NaN: never written, or computed from stale statistics"
+    ref = refs.ce_exact_vec(z, scale).reshape(C * L, N, C, L) if M is None else refs.ce_sampled_vec(z, idx, scale)
+    close_on_device(view, ref, layout)
+    del ref
+    buf2, view2, _ = launch(z, idx, layout, scale)
+    assert refs.guards_intact(buf2, view2) and torch.equal(view, view2)
+    del buf2, view2
+    z_tail, idx_tail, S_tail = tail_of(z, idx, S, K)
+    buf3, view3, S_alone = launch(z_tail, idx_tail, layout, scale)
+    assert refs.guards_intact(buf3, view3) and torch.equal(S_alone, S_tail)
+
+
+ROWS_LAYOUTS = [pytest.param(1, 3, id="nlc-3-samples"), pytest.param(0, None, id="ncl-one-position")]
+
+
+def rows_shape(rows, layout, N):
+    """(N, L) with N L = rows that reach the kernel with a row of classes per position: any split under NLC; L = 1 under NCL."""
+    if N is None:
+        return rows, 1
+    assert rows % N == 0
+    return N, rows // N
+
+
+@pytest.mark.parametrize("layout,N", ROWS_LAYOUTS)
+@pytest.mark.parametrize("C", [pytest.param(3, id="scalar-body"), pytest.param(4, id="16-byte-body")])
+def test_second_trip_wavefront_route_sampled(C, layout, N):
+    """131 073 = 4 * 32768 + 1 rows: trips of 131 072 rows, the last with one row in a workgroup whose other wavefronts have none."""
+    N, L = rows_shape(131073, layout, N)
+    second_trip_checks(N, C, L, 2, layout, K=8)
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_second_trip_wavefront_route_exact(layout):
+    """The exact factor has (C L)^2 N elements: affordable at L = 1 only, where both layouts are the same memory."""
+    second_trip_checks(131073, 3, 1, None, layout, K=8)
+
+
+@pytest.mark.parametrize("layout,N", ROWS_LAYOUTS)
+@pytest.mark.parametrize("C", [pytest.param(1025, id="scalar-body"), pytest.param(1028, id="16-byte-body")])
+def test_second_trip_workgroup_route_sampled(C, layout, N):
+    """32 769 rows of more than 1024 classes: the one workgroup of the second trip writes ``red[8]`` again.  135 MB each way."""
+    N, L = rows_shape(32769, layout, N)
+    second_trip_checks(N, C, L, 1, layout, K=3)
+
+
+@pytest.mark.parametrize("C", [2, 5])
+def test_second_trip_position_lanes_scalar_body(C):
+    """2 097 153 = 64 * 32768 + 1 positions in three samples of an odd length (one position per lane; samples straddle wavefronts);
+    C = 2 leaves two of the four wavefronts of a workgroup without a class, C = 5 gives them 2, 1, 1, 1."""
+    second_trip_checks(3, C, 699051, 2, 0, K=5)
+
+
+def test_second_trip_position_lanes_16_byte_body():
+    """2 097 153 groups of four positions."""
+    second_trip_checks(1, 2, 8388612, 1, 0, K=8)
+
+
+# ---- offsets of S past 2^31 elements ------------------------------------------------------------------------------------------------------
+def offsets_past_2_31(N, C, L, M, layout):
+    """Sampled, S of 2^31 + 65 536 elements (8 GiB) from 65 536 logits: every slice m on the device against
+    (p - onehot(idx[m])) scale with p from CPU fp64, none left at the NaN prefill, guards intact."""
+    assert M * N * C * L == 2 ** 31 + 65536 and N * C * L == 65536
+    free, _ = torch.cuda.mem_get_info()
+    if free < 12 << 30:
+        pytest.skip(f"{free / 2 ** 30:.1f} GiB of HBM free: the 8 GiB factor, its 2 GiB of indices and the compare need 12")
+    try:
+        z = logits_of(N, C, L)
+        scale = 0.5
+        p = z.double().softmax(1)
+        p = (p if layout == 0 else p.movedim(1, 2)).contiguous().to(DEV)               # a sample in memory order, fp64
+        classes = torch.arange(C, device=DEV, dtype=torch.int32).view((1, 1, C, 1) if layout == 0 else (1, 1, 1, C))
+        idx = torch.randint(0, C, (M, N, L), device=DEV, dtype=torch.int32, generator=torch.Generator(device=DEV).manual_seed(M))
+        mem = to_memory(z, layout)
+        buf, view = refs.guarded(M * N * C * L, DEV)
+        st = getattr(_lib.load(), NAME)(mem.data_ptr(), idx.data_ptr(), view.data_ptr(), N, C, L, M, layout, scale,
+                                        torch.cuda.current_stream(DEV).cuda_stream)
+        _lib.check(st, NAME)
+        torch.cuda.synchronize()
+        assert refs.guards_intact(buf, view)
+        Sm = view.view(M, N, C, L) if layout == 0 else view.view(M, N, L, C)
+        step = (1 << 24) // (N * C * L)
+        for m0 in range(0, M, step):
+            got = Sm[m0:m0 + step].double()
+            assert not bool(got.isnan().any()), f"NaN left in the slices from m = {m0}"
+            hit = idx[m0:m0 + step].unsqueeze(2 if layout == 0 else 3) == classes
+            want = (p.unsqueeze(0) - hit.double()) * scale
+            ok = (got - want).abs() <= ATOL + RTOL * want.abs()
+            assert bool(ok.all()), f"{int((~ok).sum())} elements of the slices from m = {m0} (flat offset {m0 * N * C * L}) differ"
+    finally:
+        buf = view = Sm = idx = got = hit = want = ok = None
+        torch.cuda.empty_cache()
+
+
+def test_offsets_past_2_31_wavefront_route():
+    """(m rows + row) C passes 2^31 from m = 32 768 on."""
+    offsets_past_2_31(64, 1024, 1, 32769, 1)
+
+
+def test_offsets_past_2_31_position_lanes():
+    """((m N + n) C + c) L + l passes 2^31 in the last slice; the indices alone are 2 GiB, (m N + n) L + l up to 2^29."""
+    offsets_past_2_31(1, 4, 16384, 32769, 0)
+
+
+# ---- non-finite logits ------------------------------------------------------------------------------------------------------------------------
+# As torch.softmax (and the references): a NaN or +inf at any class, or -inf at all of them, makes every class of THAT position NaN in
+# every slice that writes it, and no other position.  A NaN never becomes a lane's running maximum, so where it stands matters to the
+# kernel: the first class a lane folds (below 64 / 256 on the scalar rows bodies, below 256 / 1024 on the 16-byte ones, below 4 on
+# the position lanes) or a later visit of the lane.
+def nonfinite_cases():
+    shapes = [   # (layout, C, L, classes of a lane's second visit, id)
+        (1, 5, 3, (), "nlc-wavefront-scalar-5x3"), (1, 8, 4, (), "nlc-wavefront-16-byte-8x4"),
+        (1, 70, 3, (64,), "nlc-wavefront-scalar-70x3"), (1, 260, 2, (64, 256), "nlc-wavefront-16-byte-260x2"),
+        (1, 1027, 2, (256,), "nlc-workgroup-scalar-1027x2"), (1, 1028, 2, (256, 1024), "nlc-workgroup-16-byte-1028x2"),
+        (0, 5, 3, (4,), "ncl-lanes-scalar-5x3"), (0, 8, 4, (4,), "ncl-lanes-16-byte-8x4"), (0, 9, 8, (4,), "ncl-lanes-16-byte-9x8"),
+        (0, 6, 65, (4,), "ncl-lanes-scalar-6x65"),
+        (0, 5, 1, (), "ncl-wavefront-scalar-5x1"), (0, 8, 1, (), "ncl-wavefront-16-byte-8x1"),
+        (0, 70, 1, (64,), "ncl-wavefront-scalar-70x1"), (0, 260, 1, (64, 256), "ncl-wavefront-16-byte-260x1"),
+        (0, 1027, 1, (256,), "ncl-workgroup-scalar-1027x1"), (0, 1028, 1, (256, 1024), "ncl-workgroup-16-byte-1028x1"),
+    ]
+    cases = []
+    for layout, C, L, second, name in shapes:
+        for c in sorted({0, 3, C - 1, *second}):
+            cases.append(pytest.param(layout, C, L, "nan", c, id=f"{name}-nan-at-{c}"))
+        cases.append(pytest.param(layout, C, L, "plus_inf", 1, id=f"{name}-plus-inf"))
+        cases.append(pytest.param(layout, C, L, "all_minus_inf", None, id=f"{name}-all-minus-inf"))
+    return cases
+
+
+def assert_poisons_its_position_only(buf, view, S, ref, rows, n, l):
+    """``rows``: the slices that write position l (every other slice holds a structural zero there)."""
+    assert refs.guards_intact(buf, view)
+    got = S.cpu()
+    assert bool(got[rows, n, :, l].isnan().all()), "a class of the poisoned position came out finite"
+    assert torch.equal(got.isnan(), ref.isnan()), f"{int(got.isnan().sum())} NaN for {int(ref.isnan().sum())} in the reference"
+    assert int(ref.isnan().sum()) == len(rows) * S.shape[2] and bool(torch.isfinite(got[~ref.isnan()]).all())
+    close(S, ref)                                                    # (assert_allclose: NaN equal to NaN, the rest within tolerance)
+
+
+@pytest.mark.parametrize("layout,C,L,kind,c", nonfinite_cases())
+def test_a_non_finite_logit_poisons_its_position_only(layout, C, L, kind, c):
+    N, M = 2, 2
+    n, l = N - 1, min(1, L - 1)                                      # (L = 4, 8: inside a lane's group of four positions)
+    z = logits_of(N, C, L, seed=5).clone()
+    if kind == "all_minus_inf":
+        z[n, :, l] = float("-inf")
+    else:
+        z[n, c, l] = float("nan") if kind == "nan" else float("inf")
+    idx = indices_of(M, N, C, L)
+    buf, view, S = launch(z, idx, layout, 0.5)
+    assert_poisons_its_position_only(buf, view, S, refs.ce_sampled_vec(z, idx, 0.5), list(range(M)), n, l)
+    if C * L <= 64:
+        buf, view, S = launch(z, None, layout, 0.5)
+        ref = refs.ce_exact_vec(z, 0.5).reshape(C * L, N, C, L)
+        assert_poisons_its_position_only(buf, view, S, ref, [cp * L + l for cp in range(C)], n, l)
+        assert off_block_is_zero(S, C, L)
+
+
+@pytest.mark.parametrize("C,c", [(5, 0), (5, 3), (5, 4), (70, 0), (70, 64), (70, 69), (260, 3), (260, 256), (1027, 0), (1027, 256),
+                                 (1028, 1024)])
+def test_one_position_has_the_nan_mask_of_the_flat_kernel(C, c):
+    """L = 1, a NaN at class c of the middle sample: the mask of ``kernels.ce_sqrt_hessian`` on the same logits, which is that whole
+    sample and nothing else."""
+    N, M = 3, 2
+    z = logits_of(N, C, 1).clone()
+    z[1, c, 0] = float("nan")
+    z = z.to(DEV)
+    flat = kernels.ce_sqrt_hessian(z[:, :, 0].contiguous(), 0.5)
+    S = kernels.ce_sqrt_hessian_positions(z, 0.5)
+    assert bool(flat[:, 1].isnan().all()) and not bool(flat[:, [0, 2]].isnan().any())
+    assert torch.equal(S[..., 0].isnan(), flat.isnan())
+    idx = indices_of(M, N, C, 1).to(DEV)
+    onehot = torch.nn.functional.one_hot(idx[:, :, 0].long(), C).float()
+    flat = kernels.ce_sqrt_hessian(z[:, :, 0].contiguous(), 0.5, onehot=onehot)
+    S = kernels.ce_sqrt_hessian_positions(z, 0.5, idx=idx)
+    assert bool(flat[:, 1].isnan().all()) and not bool(flat[:, [0, 2]].isnan().any())
+    assert torch.equal(S[..., 0].isnan(), flat.isnan())
 
 
 # ---- the wrapper ----------------------------------------------------------------------------------------------------------------------

@@ -63,6 +63,51 @@ def test_sampled_ce_factor_averages_to_the_exact_hessian(N, C, D, reduction):
             np.testing.assert_allclose(est.numpy(), H[:, l, :, l].numpy(), rtol=1e-9)
 
 
+def same(a, b):
+    """Equal values and equal NaN masks, exactly."""
+    return a.shape == b.shape and a.dtype == b.dtype and bool((a.isnan() == b.isnan()).all()) and torch.equal(a.nan_to_num(nan=-7.0),
+                                                                                                               b.nan_to_num(nan=-7.0))
+
+
+def edge_outputs(out, kind):
+    out = out.clone()
+    z = out.view(out.shape[0], out.shape[1], -1)                  # [N, C, L], the same memory
+    if kind == "minus_inf_class":
+        z[:, 1, :] = float("-inf")
+    elif kind == "nan":
+        z[1, 2, 0] = float("nan")
+    elif kind == "plus_inf":
+        z[0, 0, -1] = float("inf")
+    elif kind == "all_minus_inf":
+        z[1, :, 1] = float("-inf")
+    return out
+
+
+@pytest.mark.parametrize("kind", ["finite", "minus_inf_class", "nan", "plus_inf", "all_minus_inf"])
+@pytest.mark.parametrize("dtype", [torch.float32, F64])
+@pytest.mark.parametrize("N,C,D", SHAPES)
+def test_vectorised_references_equal_the_loops(N, C, D, dtype, kind):
+    """``ce_sampled_vec`` / ``ce_exact_vec`` (what the tests at 10^5 to 10^7 positions compare with) give the values of the loops
+    bit for bit, out-of-range indices included; on non-finite logits both follow torch: a NaN, a +inf or nothing but -inf poisons its
+    position and no other, and the structural zeros of the exact factor stay 0.0."""
+    out = edge_outputs(problem(N, C, D, "ce", seed=3)[0].to(dtype), kind)
+    idx = torch.randint(0, C, (3, N, *D), generator=torch.Generator().manual_seed(5), dtype=torch.int32)
+    idx.view(-1)[[0, 5, 7, 11]] = torch.tensor([-1, C, 2 ** 31 - 1, -2 ** 31], dtype=torch.int32)
+    assert same(refs.ce_sampled_vec(out, idx, 0.5), refs.ce_sampled(out, idx, 0.5))
+    assert same(refs.ce_sampled_vec(out, idx.long(), 0.5), refs.ce_sampled(out, idx, 0.5))
+    E = refs.ce_exact_vec(out, 0.25)
+    assert same(E, refs.ce_exact(out, 0.25))
+    L = math.prod(D)
+    poisoned = out.reshape(N, C, L).softmax(1).isnan().any(1)                                   # [N, L], torch's own verdict
+    assert bool(poisoned.any()) == (kind in ("nan", "plus_inf", "all_minus_inf")) and int(poisoned.sum()) <= 1
+    assert torch.equal(refs.ce_sampled_vec(out, idx, 0.5).reshape(3, N, C, L).isnan(), poisoned.view(1, N, 1, L).expand(3, N, C, L))
+    Ex = E.reshape(C, L, N, C, L)
+    off = ~torch.eye(L, dtype=torch.bool)
+    assert bool((Ex.permute(1, 4, 0, 2, 3)[off] == 0.0).all())
+    diag = Ex.permute(1, 4, 0, 2, 3)[~off]                                                      # [l, c', n, c]
+    assert torch.equal(diag.isnan(), poisoned.t().reshape(L, 1, N, 1).expand(L, C, N, C))
+
+
 def test_sampled_references_follow_their_formulas():
     out, _ = problem(2, 4, (3,), "ce", seed=2)
     idx = torch.tensor([[[0, 3, 1], [2, 2, 0]]])

@@ -5,6 +5,10 @@
 //   exact   (idx == null, V = C L, row v = c' L + l'):  S[v, n, c, l] = [l = l'] sqrt(p[n, c', l]) ([c = c'] - p[n, c, l]) scale
 //   sampled (idx [V, N, L] int32 class indices):        S[m, n, c, l] = (p[n, c, l] - [c = idx[m, n, l]]) scale
 // An index outside [0, C) matches no class; no address is ever formed from an index.
+// Non-finite logits, as torch.softmax and the [N, C] kernel of jacobians.hip: a class at -inf beside finite ones has p = 0 (exact zero
+// rows and columns); a NaN or a +inf at any class, or nothing but -inf, makes every class of THAT position NaN in every slice that
+// writes it (all M sampled slices; the C slices v = c' L + l of the exact factor) and touches no other position -- the structural zeros
+// of the exact factor stay 0.0.
 //
 // Two memory layouts of a sample (of the logits and of every (v, n) slice of S alike), two kernels, lanes along the unit-stride axis:
 //   NLC (class stride 1, position stride C), ce_pos_rows_kernel: a ROW is the C contiguous classes of one position.  Rows of up to
@@ -48,10 +52,12 @@ __device__ __forceinline__ void fold_max(float &mx, float &sum, float bm) {
   }
 }
 
-__device__ __forceinline__ float exp_term(float z, float mx) { return mx > -INFINITY ? expf(z - mx) : 0.f; }
+// A NaN never becomes the maximum (NaN > mx is false), so it has to reach the sum through its own term: while the maximum is still
+// -inf the term is exp(z) -- 0 for z = -inf as before, NaN for a NaN (exp(z - mx) would be exp(NaN) there too, but also for -inf).
+__device__ __forceinline__ float exp_term(float z, float mx) { return expf(z - (mx > -INFINITY ? mx : 0.f)); }
 
-// a lane's part rescaled to the common maximum
-__device__ __forceinline__ float rescaled(float mx, float sum, float common) { return mx > -INFINITY ? sum * expf(mx - common) : 0.f; }
+// a lane's part rescaled to the common maximum; a lane whose maximum is still -inf holds a sum of 0, or NaN if it met one
+__device__ __forceinline__ float rescaled(float mx, float sum, float common) { return mx > -INFINITY ? sum * expf(mx - common) : sum; }
 
 // ---- NLC: one row of C contiguous classes per position -------------------------------------------------------------------------------
 // rows = N L (row = n L + l); S[(v rows + row) C + c]; idx[m rows + row].  TPR threads per row: 64 or 256.
