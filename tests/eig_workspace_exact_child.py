@@ -3,8 +3,8 @@ workspace query asks for, in the environment it was started with (the route swit
 
     python eig_workspace_exact_child.py out.json
 
-A workspace is a slice of a uint8 buffer filled with 0xA5: it starts 16 bytes after a 256-byte boundary (so the alignment
-slack of the query is used), is exactly as long as the query says and has at least 64 KiB of pattern before and after it.
+A workspace (helpers.Guarded) is a slice of a uint8 buffer filled with 0xA5: it starts 16 bytes after a 256-byte boundary (so the
+alignment slack of the query is used), is exactly as long as the query says and has at least 64 KiB of pattern before and after it.
 Every case checks: status OK, info 0, the pattern around every workspace intact, and outputs byte-equal to those of the
 ``vivit_amd.kernels`` wrapper for the same input (which over-allocates its workspace by a quarter).  out.json: {case: "ok" | text}.
 """
@@ -14,35 +14,10 @@ import sys
 
 import torch
 
-from helpers import ROOT  # noqa: F401  (puts the repository root on sys.path)
+from helpers import Guarded  # (importing helpers puts the repository root on sys.path)
 from vivit_amd import _lib, kernels
 
 DEV = "cuda:0"
-PAD = 64 << 10
-FILL = 0xA5
-
-
-class Guarded:
-    """Regions of exactly ``sizes`` bytes inside one pattern-filled buffer; ``ptrs[i]`` is 16 bytes past a 256-byte boundary."""
-
-    def __init__(self, *sizes):
-        self.sizes = [int(s) for s in sizes]
-        self.buf = torch.full((sum(self.sizes) + (PAD + 512) * (len(sizes) + 1),), FILL, dtype=torch.uint8, device=DEV)
-        self.offs, at = [], 0
-        for s in self.sizes:
-            at += PAD
-            at += (-(self.buf.data_ptr() + at)) % 256 + 16
-            self.offs.append(at)
-            at += s
-        assert at + PAD <= self.buf.numel()
-        self.ptrs = [self.buf.data_ptr() + o if s else None for o, s in zip(self.offs, self.sizes)]
-
-    def assert_intact(self):
-        at = 0
-        for o, s in zip(self.offs, self.sizes):
-            assert o - at >= PAD and bool((self.buf[at:o] == FILL).all()), "pattern in front of a workspace overwritten"
-            at = o + s
-        assert self.buf.numel() - at >= PAD and bool((self.buf[at:] == FILL).all()), "pattern behind a workspace overwritten"
 
 
 def same(got, want, what):

@@ -246,6 +246,35 @@ class OracleBackend:
         return tensors
 
 
+GUARD_PAD = 64 << 10
+GUARD_FILL = 0xA5
+
+
+class Guarded:
+    """Device regions of exactly ``sizes`` bytes inside one pattern-filled buffer; ``ptrs[i]`` is 16 bytes past a 256-byte
+    boundary (``None`` for an empty region), with at least 64 KiB of pattern before and after every region.  For the tests
+    that run an entry point of the C ABI on exactly the bytes its workspace query asks for (the wrappers over-allocate)."""
+
+    def __init__(self, *sizes, device="cuda:0"):
+        self.sizes = [int(s) for s in sizes]
+        self.buf = torch.full((sum(self.sizes) + (GUARD_PAD + 512) * (len(sizes) + 1),), GUARD_FILL, dtype=torch.uint8, device=device)
+        self.offs, at = [], 0
+        for s in self.sizes:
+            at += GUARD_PAD
+            at += (-(self.buf.data_ptr() + at)) % 256 + 16
+            self.offs.append(at)
+            at += s
+        assert at + GUARD_PAD <= self.buf.numel()
+        self.ptrs = [self.buf.data_ptr() + o if s else None for o, s in zip(self.offs, self.sizes)]
+
+    def assert_intact(self):
+        at = 0
+        for o, s in zip(self.offs, self.sizes):
+            assert o - at >= GUARD_PAD and bool((self.buf[at:o] == GUARD_FILL).all()), "pattern in front of a workspace overwritten"
+            at = o + s
+        assert self.buf.numel() - at >= GUARD_PAD and bool((self.buf[at:] == GUARD_FILL).all()), "pattern behind a workspace overwritten"
+
+
 _PATCHED = {}
 
 

@@ -65,13 +65,18 @@ size_t gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, bool syrk) {
   return b;
 }
 
-int gemm_launch(int alay, int blay, const float *A, const float *B, float *C, int64_t M, int64_t N,
-                int64_t K, int64_t lda, int64_t ldb, int64_t ldc, float alpha, float beta, bool syrk,
-                void *workspace, size_t workspace_bytes, hipStream_t stream) {
+// `probe`: launch nothing and return what the argument and workspace checks of the launch would return (vivit_gram_syrk_f32
+// asks before it puts its diagonal kernel in front of a product on a short workspace).  SYRK only: of the routes a SYRK
+// can take, Tile128 with a slab is the one that refuses a workspace.
+static int gemm_dispatch(int alay, int blay, const float *A, const float *B, float *C, int64_t M, int64_t N,
+                         int64_t K, int64_t lda, int64_t ldb, int64_t ldc, float alpha, float beta, bool syrk,
+                         void *workspace, size_t workspace_bytes, hipStream_t stream, bool probe) {
+  if (probe && !syrk) return VIVIT_E_UNSUPPORTED;
   if (M < 0 || N < 0 || K < 0) return VIVIT_E_BADARG;
   if (M == 0 || N == 0) return VIVIT_OK;
   if (!C || ldc < N) return VIVIT_E_BADARG;
   if (K == 0) {  // empty contraction: C = beta * C
+    if (probe) return VIVIT_OK;
     launch_scale_c(C, M, N, ldc, beta, stream);
     return launch_status();
   }
@@ -94,7 +99,7 @@ int gemm_launch(int alay, int blay, const float *A, const float *B, float *C, in
     bool on256 = true;
     int st = VIVIT_OK;
     if (plan_tile256_bx(whole, pl) && holds(pl)) {
-      st = launch_tile256_bx(pl, whole, alay, blay, p, workspace, stream);
+      if (!probe) st = launch_tile256_bx(pl, whole, alay, blay, p, workspace, stream);
     } else if (plan_tile256(whole, pl)) {
       // never more splits than the caller's workspace holds (callers size it for their largest problem; the plan
       // of a smaller one may differ)
@@ -102,9 +107,9 @@ int gemm_launch(int alay, int blay, const float *A, const float *B, float *C, in
         const size_t fit = workspace ? workspace_bytes / ((size_t)M * (size_t)N * sizeof(float)) : 1;
         plan_tile256(whole, pl, fit < 1 ? 1 : (int)(fit < 4 ? fit : 4));
       }
-      st = launch_tile256(pl, whole, alay, blay, p, workspace, stream);
+      if (!probe) st = launch_tile256(pl, whole, alay, blay, p, workspace, stream);
     } else if (plan_bx_splitk(whole, pl) && holds(pl)) {
-      st = launch_bx_splitk(pl, whole, alay, blay, p, workspace, stream);
+      if (!probe) st = launch_bx_splitk(pl, whole, alay, blay, p, workspace, stream);
     } else {
       on256 = false;
       p.K = K;
@@ -113,7 +118,8 @@ int gemm_launch(int alay, int blay, const float *A, const float *B, float *C, in
       if (st != VIVIT_OK || whole.K == K) return st;
       // ragged K tail (< 16) through the small-tile kernel, accumulating
       const float *At = A + (alay == LAY_K ? whole.K : whole.K * lda), *Bt = B + (blay == LAY_K ? whole.K : whole.K * ldb);
-      return gemm_launch(alay, blay, At, Bt, C, M, N, K - whole.K, lda, ldb, ldc, alpha, 1.f, syrk, workspace, workspace_bytes, stream);
+      return gemm_dispatch(alay, blay, At, Bt, C, M, N, K - whole.K, lda, ldb, ldc, alpha, 1.f, syrk, workspace, workspace_bytes, stream,
+                           probe);
     }
   }
   if (gemm64_enabled() && ptr_vec && (alay == LAY_K || ((M & 3) == 0 && M >= 4)) && (blay == LAY_K || ((N & 3) == 0 && N >= 4)) &&
@@ -122,7 +128,14 @@ int gemm_launch(int alay, int blay, const float *A, const float *B, float *C, in
   if (tsk_enabled() && ptr_vec && alay == LAY_K && blay == LAY_K && plan_tsk(sh, pl))
     return launch_tsk(pl, p, workspace, workspace_bytes, stream);
   plan_tile128(sh, pl);
+  if (probe) return (pl.ksplit > 1 && !holds(pl)) ? VIVIT_E_WORKSPACE : VIVIT_OK;   // (the check of launch_tile128)
   return launch_tile128(pl, sh, alay, blay, p, workspace, workspace_bytes, stream);
+}
+
+int gemm_launch(int alay, int blay, const float *A, const float *B, float *C, int64_t M, int64_t N,
+                int64_t K, int64_t lda, int64_t ldb, int64_t ldc, float alpha, float beta, bool syrk,
+                void *workspace, size_t workspace_bytes, hipStream_t stream) {
+  return gemm_dispatch(alay, blay, A, B, C, M, N, K, lda, ldb, ldc, alpha, beta, syrk, workspace, workspace_bytes, stream, false);
 }
 
 // dout[i] = beta G[i][i] + alpha sum_k A[i][k]^2, fp64 accumulation, one workgroup per row (16 float4 loads in flight per thread)
@@ -203,8 +216,13 @@ int vivit_gram_syrk_f32(const float *A, int64_t n, int64_t p, int64_t lda, float
   BxStrictScope strict;  // public product: both range bits reroute a chunk to the fp32 MFMA kernel
   hipStream_t s = static_cast<hipStream_t>(stream);
   // (the leading dimensions are checked here too: gemm_launch refuses lda < p / ldg < n, and nothing may be launched before it does)
-  const bool fix_diag = A && G && workspace && n > 0 && p >= SYRK_DIAG_MIN_K && lda >= p && ldg >= n &&
-                        workspace_bytes >= syrk_diag_bytes(n) + gemm_workspace_bytes(n, n, p, true);
+  bool fix_diag = A && G && workspace && n > 0 && p >= SYRK_DIAG_MIN_K && lda >= p && ldg >= n && workspace_bytes >= syrk_diag_bytes(n);
+  // A workspace shorter than the query still gives the diagonal its n floats when the product accepts what is left behind them
+  // (its routes cope with a short workspace: gemm_plan.h); asked first, since nothing may be launched in front of a refusal.
+  // Where the rest is refused the product gets all of it, as it does when not even the diagonal fits, and the diagonal is its own.
+  if (fix_diag && workspace_bytes < syrk_diag_bytes(n) + gemm_workspace_bytes(n, n, p, true))
+    fix_diag = gemm_dispatch(LAY_K, LAY_K, A, A, G, n, n, p, lda, lda, ldg, alpha, beta, true, static_cast<char *>(workspace) + syrk_diag_bytes(n),
+                             workspace_bytes - syrk_diag_bytes(n), s, true) == VIVIT_OK;
   float *diag = nullptr;
   if (fix_diag) {
     diag = reinterpret_cast<float *>(align_up(reinterpret_cast<uintptr_t>(workspace), 256));

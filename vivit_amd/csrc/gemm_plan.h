@@ -30,6 +30,13 @@ namespace vivit {
 // routes of the 256 tile have an fp32 route of the same tile behind them that needs less; the last three routes have
 // nothing behind them whose result (summation order) would be the same.  Every launch_<route> finishes its argument and
 // workspace checks before its first HIP call.
+// What the column does not say (tests/test_gemm_output_gpu.py runs every row of it):
+//   - BxSplitK skipped means Tile128 with its own slab, i.e. VIVIT_E_WORKSPACE once that slab does not fit either.
+//   - vivit_gram_syrk_f32 keeps the n floats of its fp64 diagonal (p >= 1024) in FRONT of this workspace.  A workspace shorter
+//     than its query still gives them their room whenever the rows above accept what is left behind them (asked with a probe
+//     of the dispatcher, before anything is launched); the diagonal is then the fp64 value rounded once, as on the whole
+//     query.  Only where not even the n floats fit (a NULL workspace) or the rest would be refused does the product get all
+//     of it, and the diagonal is the product's own: a k-ordered fp32 sum within the bound of every other entry.
 enum class GemmRoute { Tile256Bx, Tile256, BxSplitK, Gemm64, Tsk, Tile128 };
 
 struct GemmShape {

@@ -727,6 +727,8 @@ bool plan_tile256_bx(const GemmShape &sh, GemmPlan &pl) {
   const size_t pieces = bx_carve_pieces(sh, pl.kchunk, &pl.b_off);
   pl.flags_off = align_up(pieces, 256);
   const size_t nch = (size_t)cdiv(sh.K, bx_chunk_cols(sh.K, true));   // (the larger of the two counts)
+  // (both + 256 are slack: ws_at does not align the base, and every piece size is a multiple of 6 x 16 x 32 bytes, so the flags
+  // sit at align_up(pieces, 256) = pieces and the launch ends 512 bytes before pl.bytes)
   pl.bytes = pieces + 256 + 4 * nch + 256;
   return true;
 }
