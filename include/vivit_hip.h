@@ -392,6 +392,35 @@ int vivit_ce_sqrt_hessian_f32(const float *logits, const float *onehot, float *S
  * other than 0 or 1, logits or S null, exact with V != C L.  VIVIT_E_UNSUPPORTED: a size or N L above 2^31 - 1, V N C L above 2^60. */
 int vivit_ce_pos_sqrt_hessian_f32(const float *logits, const int32_t *idx, float *S, int64_t N, int64_t C, int64_t L, int64_t V, int layout,
                                   float scale, void *stream);
+/* The two factors above with one scale per position instead of one float, for cross entropy with ignore_index, class weights and
+ * label smoothing: the loss Hessian at position i = (n, l) is omega_i (diag p_i - p_i p_i^T), and the factors are those above times
+ * s_i = sqrt(omega_i) (exact) or sqrt(omega_i / M) (sampled) at position i.  pos_scale [N L] (row n L + l; row_scale [N] for the
+ * [N, C] kernel) holds s_i; it enters where `scale` enters above, (p - e) * s and sqrtf(p) * s with the same operations in the same
+ * order, so an array whose elements all hold one float s gives the bytes of the entry point above called with scale = s.
+ * A position with s == 0 is written as exact zeros in every slice that covers it, whatever its logits hold (NaN and +-inf included:
+ * padded positions carry garbage); in layout 1 and in the [N, C] kernel its logits are not read.  A position with s != 0 follows the
+ * non-finite rules above.  Status codes, zero sizes and limits as above; pos_scale / row_scale null is VIVIT_E_BADARG. */
+int vivit_ce_pos_sqrt_hessian_w_f32(const float *logits, const int32_t *idx, const float *pos_scale, float *S, int64_t N, int64_t C,
+                                    int64_t L, int64_t V, int layout, void *stream);
+int vivit_ce_sqrt_hessian_w_f32(const float *logits, const float *onehot, const float *row_scale, float *S, int64_t N, int64_t C,
+                                int64_t V, void *stream);
+/* pos_scale [R] of the two entry points above from class-index targets, on the device (nothing returns to the host; no atomics, two
+ * calls give the same bytes).  target [R] int64 (R = N L, row r = n L + l); class_weight [C] or NULL (all ones); wbar = mean_c w_c;
+ * eps = label_smoothing; mean = 1 for reduction 'mean', 0 for 'sum'; mult = M for the sampled factor, 1 for the exact one.
+ *   counted_r = target[r] != ignore_index and 0 <= target[r] < C
+ *   a_r       = counted_r ? (1 - eps) w[target[r]] + eps wbar : 0          (exactly 1 without weights)
+ *   norm      = mean ? sum over the counted rows of w[target[r]] : 1       (over all R rows: before any sub-sampling)
+ *   pos_scale[r] = (float)(sqrt(a_r) / sqrt(mult norm)),  evaluated in fp64 in exactly this form: with no weights and nothing
+ *   ignored it is the float 1 / sqrt(mult R) that the unweighted entry points are handed as `scale`.
+ * norm and wbar are fp64 sums in a fixed order (per-workgroup partials in the workspace, added in index order).
+ * Decisions: a_r == 0 gives 0, also when norm == 0 (every target ignored: the factor is zero where torch's loss is NaN); a_r < 0
+ * (negative class weights) gives NaN at that row; a target outside [0, C) other than ignore_index has weight 0, and no address is
+ * formed from it.  R == 0: VIVIT_OK, no pointer is read.  VIVIT_E_BADARG: R or C negative, mult < 1, mean outside {0, 1}, target or
+ * pos_scale null.  VIVIT_E_UNSUPPORTED: R, C or mult above 2^31 - 1.  VIVIT_E_WORKSPACE: workspace null, not 8-byte aligned or
+ * smaller than vivit_ce_target_scales_f32_workspace_bytes(R, C). */
+size_t vivit_ce_target_scales_f32_workspace_bytes(int64_t R, int64_t C);
+int vivit_ce_target_scales_f32(const int64_t *target, const float *class_weight, float *pos_scale, int64_t R, int64_t C, int64_t ignore_index,
+                               double label_smoothing, int mean, int64_t mult, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K3/K4  Symmetric eigendecomposition (Householder tridiagonalisation + implicit-shift QL,

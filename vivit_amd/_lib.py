@@ -65,6 +65,10 @@ SIGNATURES = {
     "vivit_embedding_weight_mjp_f32": (_int, [_ptr] * 3 + [_i64] * 5 + [_ptr]),
     "vivit_ce_sqrt_hessian_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _f32, _ptr]),
     "vivit_ce_pos_sqrt_hessian_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _f32, _ptr]),
+    "vivit_ce_pos_sqrt_hessian_w_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _int, _ptr]),
+    "vivit_ce_sqrt_hessian_w_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr]),
+    "vivit_ce_target_scales_f32_workspace_bytes": (_sz, [_i64, _i64]),
+    "vivit_ce_target_scales_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, ctypes.c_double, _int, _i64, _ptr, _sz, _ptr]),
     "vivit_symeig_f32_workspace_bytes": (_sz, [_i64, _int]),
     "vivit_symeig_f32": (_int, [_ptr, _i64, _i64, _ptr, _ptr, _i64, _ptr, _sz, _ptr, _ptr]),
     "vivit_symeigvals_batched_f32_workspace_bytes": (_sz, [_i64, _i64]),

@@ -867,16 +867,78 @@ class BatchGrad(_Extension):
 
 
 # ---------------------------------------------------------------------------------------------
+def _ce_position_weights(module, target: Tensor, C: int) -> Tensor:
+    """``omega [N, *D]`` (fp64): the loss Hessian of ``nn.CrossEntropyLoss`` w.r.t. the logits of position ``i = (n, l)`` is
+    ``omega_i (diag p_i - p_i p_i^T)``.  With ``w`` the class weights (ones if absent), ``wbar = mean_c w_c``, ``eps`` the label smoothing:
+
+    * class-index targets ``y [N, *D]``: position ``i`` counts iff ``y_i != ignore_index`` and ``0 <= y_i < C``; then
+      ``a_i = (1 - eps) w[y_i] + eps wbar``, else ``a_i = 0``; ``omega_i = a_i / norm`` with ``norm`` the sum of ``w[y_i]`` over the
+      counted positions of the whole batch ('mean') or 1 ('sum');
+    * probability targets ``t [N, C, *D]`` (floating point): ``omega_i = sum_c w_c ((1 - eps) t_ic + eps / C) / norm``, ``norm`` the
+      number of positions ``N L`` ('mean') or 1; there is no ``ignore_index``.
+
+    ``a_i == 0`` gives ``omega_i = 0`` even when ``norm == 0`` (every target ignored: torch's loss is NaN, the factor is zero); a
+    negative ``omega_i`` (negative class weights) becomes NaN under the square root; a target outside ``[0, C)`` that is not
+    ``ignore_index`` has weight 0 and indexes nothing.  Torch ops only, nothing comes back to the host."""
+    eps = float(module.label_smoothing)
+    w = None if module.weight is None else module.weight.detach().to(target.device, torch.float64)
+    mean = module.reduction == "mean"
+    if target.is_floating_point():
+        mix = (1.0 - eps) * target.detach().to(torch.float64) + eps / C
+        if w is not None:
+            mix = mix * w.view(1, C, *([1] * (mix.dim() - 2)))
+        a = mix.sum(dim=1)
+        return a / a.numel() if mean else a
+    y = target.detach()
+    counted = (y != module.ignore_index) & (y >= 0) & (y < C)
+    if w is None:
+        wy = counted.to(torch.float64)
+        a = wy                                                             # (1 - eps) + eps, exactly
+    else:
+        wy = torch.where(counted, w[torch.where(counted, y, torch.zeros_like(y))], torch.zeros((), dtype=torch.float64, device=y.device))
+        a = wy if eps == 0.0 else torch.where(counted, (1.0 - eps) * wy + eps * w.mean(), torch.zeros_like(wy))
+    if not mean:
+        return a
+    return torch.where(a == 0, torch.zeros_like(a), a / wy.sum())
+
+
+def _ce_position_scale(module, out: Tensor, mult: int) -> Optional[Tensor]:
+    """``s [N, *D] = sqrt(omega / mult)`` in the dtype of ``out`` (:func:`_ce_position_weights`; ``mult = M`` for the sampled factor),
+    or None for a loss that recorded no target (nothing to look at: the unweighted factor).  Class-index targets of HIP fp32 logits:
+    one kernel pair on the device (``kernels.ce_target_scales``), which for a default loss with nothing ignored gives the very float
+    ``1 / sqrt(mult norm)`` of the unweighted path; otherwise torch ops.  Never a host synchronisation: the factor pass runs on its
+    own stream beside the backward pass (engine.py)."""
+    target = getattr(module, "input1", None)
+    if not isinstance(target, Tensor):
+        return None
+    C = out.shape[1]
+    if not target.is_floating_point() and out.is_cuda and out.dtype == torch.float32 and target.device == out.device:
+        w = None if module.weight is None else module.weight.detach().to(out.device, torch.float32)
+        return kernels.ce_target_scales(target.detach().long(), C, weight=w, ignore_index=module.ignore_index,
+                                        label_smoothing=module.label_smoothing, mean=module.reduction == "mean", mult=mult)
+    return (_ce_position_weights(module, target.to(out.device), C) / mult).sqrt().to(out.dtype)
+
+
+def _scaled_positions(S: Tensor, s: Tensor) -> Tensor:
+    """``S [V, N, C, *D]`` times the scale ``s [N, *D]`` of its positions; zeros where ``s == 0`` whatever ``S`` holds there (a padded
+    position's logits may be NaN, and ``0 * NaN`` must not reach the factor)."""
+    s = s.unsqueeze(0).unsqueeze(2)
+    return torch.where(s == 0, torch.zeros((), dtype=S.dtype, device=S.device), S * s)
+
+
 def _loss_hessian_sqrt_positions(module, out: Tensor, strategy: str, mc_samples: int, samples: Optional[Tensor]) -> Tensor:
     """Symmetric factor S [V, N, C, *D] of the loss Hessian w.r.t. an output with positions, ``out [N, C, *D]``, ``L = prod(D)``.
 
-    CrossEntropyLoss (a softmax over the classes at every position; 'mean' averages over the ``N L`` positions): exact, ``V = C L``,
-    row ``v = c' L + l'``, ``S[v, n, c, l] = [l = l'] sqrt(p[n, c', l]) ([c = c'] - p[n, c, l]) / sqrt(norm)``; sampled, ``V = M``,
-    ``S[m, n, c, l] = (p[n, c, l] - [c = idx[m, n, l]]) / sqrt(M norm)`` with class indices ``idx [M, N, *D]`` -- ``samples`` of an
-    integer dtype, the argmax of one-hot ``samples [M, N, C, *D]``, or drawn here from ``p``.  HIP fp32 tensors: one kernel
-    (``kernels.ce_sqrt_hessian_positions``, in the memory format of ``out``); otherwise the same formulas in torch, no autograd.
-    MSELoss ('mean' averages over ``N C L`` elements): ``sqrt(2 / norm) I`` as ``[C L, N, C, *D]``, or ``M`` normal samples.
-    ``ignore_index``, ``weight`` and ``label_smoothing`` of CrossEntropyLoss are not looked at (as for ``[N, C]``)."""
+    CrossEntropyLoss (a softmax over the classes at every position; the Hessian at position ``i`` is ``omega_i (diag p_i - p_i p_i^T)``
+    with ``omega`` of :func:`_ce_position_weights` -- ``ignore_index``, class ``weight``, ``label_smoothing`` and probability targets
+    included; ``1 / (N L)`` for a default 'mean' loss with nothing ignored): exact, ``V = C L``, row ``v = c' L + l'``,
+    ``S[v, n, c, l] = [l = l'] sqrt(p[n, c', l]) ([c = c'] - p[n, c, l]) sqrt(omega[n, l])``; sampled, ``V = M``,
+    ``S[m, n, c, l] = (p[n, c, l] - [c = idx[m, n, l]]) sqrt(omega[n, l] / M)`` with class indices ``idx [M, N, *D]`` -- ``samples`` of an
+    integer dtype, the argmax of one-hot ``samples [M, N, C, *D]``, or drawn here from ``p``.  A position with ``omega = 0`` is exact
+    zeros.  HIP fp32 tensors: one kernel (``kernels.ce_sqrt_hessian_positions_w``, in the memory format of ``out``); otherwise the same
+    formulas in torch, no autograd.  A loss that recorded no target: ``omega = 1 / norm``, ``norm = N L`` for 'mean'
+    (``kernels.ce_sqrt_hessian_positions``).
+    MSELoss ('mean' averages over ``N C L`` elements): ``sqrt(2 / norm) I`` as ``[C L, N, C, *D]``, or ``M`` normal samples."""
     N, C, D = out.shape[0], out.shape[1], tuple(out.shape[2:])
     L = math.prod(D)
     red = module.reduction
@@ -886,14 +948,18 @@ def _loss_hessian_sqrt_positions(module, out: Tensor, strategy: str, mc_samples:
         norm = N * L if red == "mean" else 1
         hip = out.is_cuda and out.dtype == torch.float32
         if strategy == "exact":
+            s = _ce_position_scale(module, out, 1)
             if hip:
+                if s is not None:
+                    return kernels.ce_sqrt_hessian_positions_w(out, s)
                 return kernels.ce_sqrt_hessian_positions(out, 1.0 / math.sqrt(norm))
             p = out.softmax(dim=1).reshape(N, C, L)
             eye_c = torch.eye(C, dtype=out.dtype, device=out.device)
             eye_l = torch.eye(L, dtype=out.dtype, device=out.device)
             inner = p.sqrt().permute(1, 0, 2).unsqueeze(2) * (eye_c[:, None, :, None] - p.unsqueeze(0))      # [c', n, c, l]
             S = inner.unsqueeze(1) * eye_l[None, :, None, None, :]                                           # [c', l', n, c, l]
-            return S.reshape(C * L, N, C, *D) / math.sqrt(norm)
+            S = S.reshape(C * L, N, C, *D)
+            return _scaled_positions(S, s) if s is not None else S / math.sqrt(norm)
         if samples is None:
             p = out.softmax(dim=1)
             idx = torch.multinomial(p.movedim(1, -1).reshape(N * L, C), mc_samples, replacement=True).t().reshape(mc_samples, N, *D)
@@ -905,11 +971,15 @@ def _loss_hessian_sqrt_positions(module, out: Tensor, strategy: str, mc_samples:
             if tuple(samples.shape[1:]) != (N,) + D:
                 raise ValueError(f"class-index samples must be [M, {', '.join(map(str, (N,) + D))}], got {tuple(samples.shape)}")
             idx = samples
+        s = _ce_position_scale(module, out, idx.shape[0])
         scale = 1.0 / math.sqrt(idx.shape[0] * norm)
         if hip:
+            if s is not None:
+                return kernels.ce_sqrt_hessian_positions_w(out, s, idx=idx.to(out.device, torch.int32))
             return kernels.ce_sqrt_hessian_positions(out, scale, idx=idx.to(out.device, torch.int32))
         onehot = F.one_hot(idx.to(out.device, torch.long), C).movedim(-1, 2).to(out.dtype)                   # [M, N, C, *D]
-        return (out.softmax(dim=1).unsqueeze(0) - onehot) * scale
+        S = out.softmax(dim=1).unsqueeze(0) - onehot
+        return _scaled_positions(S, s) if s is not None else S * scale
     if isinstance(module, nn.MSELoss):
         norm = N * C * L if red == "mean" else 1
         if strategy == "exact":
@@ -925,7 +995,9 @@ def _loss_hessian_sqrt_positions(module, out: Tensor, strategy: str, mc_samples:
 
 def _loss_hessian_sqrt(module, strategy: str, mc_samples: int, samples: Optional[Tensor]) -> Tensor:
     """Symmetric factor S [V, N, C] of the loss Hessian w.r.t. the model output ``[N, C]``; ``[V, N, C, *D]`` for an output with
-    positions ``[N, C, *D]`` (:func:`_loss_hessian_sqrt_positions`)."""
+    positions ``[N, C, *D]`` (:func:`_loss_hessian_sqrt_positions`).  CrossEntropyLoss on ``[N, C]`` is the case of one position per
+    sample: the factor of sample ``n`` times ``sqrt(omega_n)`` (``sqrt(omega_n / M)`` sampled) with ``omega`` of
+    :func:`_ce_position_weights`, exact zeros where ``omega_n = 0``."""
     out = module.input0.detach()
     if out.dim() > 2:
         return _loss_hessian_sqrt_positions(module, out, strategy, mc_samples, samples)
@@ -938,11 +1010,17 @@ def _loss_hessian_sqrt(module, strategy: str, mc_samples: int, samples: Optional
     if isinstance(module, nn.CrossEntropyLoss) and out.is_cuda and out.dtype == torch.float32 and C * 4 <= 60 * 1024:
         norm = N if red == "mean" else 1
         if strategy == "exact":
+            s = _ce_position_scale(module, out, 1)
+            if s is not None:
+                return kernels.ce_sqrt_hessian_w(out, s)
             return kernels.ce_sqrt_hessian(out, 1.0 / math.sqrt(norm))     # softmax + sqrt(p_v)(delta_vc - p_c) in one kernel
         if samples is None:
             idx = torch.multinomial(out.softmax(dim=1), mc_samples, replacement=True)  # [N, M]
             samples = F.one_hot(idx.t(), C).to(out.dtype)  # [M, N, C]
         samples = samples.to(out.device, out.dtype)
+        s = _ce_position_scale(module, out, samples.shape[0])
+        if s is not None:
+            return kernels.ce_sqrt_hessian_w(out, s, onehot=samples)
         return kernels.ce_sqrt_hessian(out, 1.0 / math.sqrt(samples.shape[0] * norm), onehot=samples)
     if isinstance(module, nn.CrossEntropyLoss):
         p = out.softmax(dim=1)
@@ -953,11 +1031,14 @@ def _loss_hessian_sqrt(module, strategy: str, mc_samples: int, samples: Optional
             S = torch.einsum("nv,vc->vnc", sq, torch.eye(C, dtype=out.dtype, device=out.device)) - torch.einsum(
                 "nv,nc->vnc", sq, p
             )
-            return S / math.sqrt(norm)
+            s = _ce_position_scale(module, out, 1)
+            return _scaled_positions(S, s) if s is not None else S / math.sqrt(norm)
         if samples is None:
             idx = torch.multinomial(p, mc_samples, replacement=True)  # [N, M]
             samples = F.one_hot(idx.t(), C).to(out.dtype)  # [M, N, C]
-        return (p.unsqueeze(0) - samples.to(out.device, out.dtype)) / math.sqrt(samples.shape[0] * norm)
+        S = p.unsqueeze(0) - samples.to(out.device, out.dtype)
+        s = _ce_position_scale(module, out, samples.shape[0])
+        return _scaled_positions(S, s) if s is not None else S / math.sqrt(samples.shape[0] * norm)
     if isinstance(module, nn.MSELoss):
         norm = N * C if red == "mean" else 1
         if strategy == "exact":

@@ -525,11 +525,22 @@ __global__ __launch_bounds__(256) void bn_eval_rules_kernel(const float *__restr
 // ---- loss-Hessian square roots ------------------------------------------------------------------------------------------
 // Cross entropy: p = softmax(logits[n, :]).  exact: S[v, n, c] = sqrt(p_v) (delta_vc - p_c) * scale  (V = C slices);
 // sampled:  S[m, n, c] = (p_c - onehot[m, n, c]) * scale.   One workgroup per sample.
+// PS (vivit_ce_sqrt_hessian_w_f32): the scale of sample n is row_scale[n]; a sample whose scale is zero is written as zeros in every
+// slice and its logits are not read.
+template <bool PS>
 __global__ __launch_bounds__(256) void ce_sqrt_hessian_kernel(const float *__restrict__ logits, const float *__restrict__ onehot,
-                                                              float *__restrict__ S, int64_t N, int64_t C, int64_t Vd, float scale) {
+                                                              const float *__restrict__ row_scale, float *__restrict__ S, int64_t N,
+                                                              int64_t C, int64_t Vd, float scale) {
   extern __shared__ float p[];  // [C]
   __shared__ float red[256];
   const int64_t n = blockIdx.x;
+  if constexpr (PS) {
+    scale = row_scale[n];
+    if (scale == 0.f) {         // (the whole workgroup: no barrier is left out)
+      for (int64_t i = threadIdx.x; i < Vd * C; i += 256) S[(i / C * N + n) * C + i % C] = 0.f;
+      return;
+    }
+  }
   const float *z = logits + n * C;
   float mx = -INFINITY;
   for (int64_t c = threadIdx.x; c < C; c += 256) mx = fmaxf(mx, z[c]);
@@ -690,15 +701,30 @@ int vivit_bn_eval_rules_f32(const float *M, const float *X, const float *scale, 
   return launch_status();
 }
 
-int vivit_ce_sqrt_hessian_f32(const float *logits, const float *onehot, float *S, int64_t N, int64_t C, int64_t Vd, float scale,
-                              void *stream) {
+} // extern "C"
+
+template <bool PS>
+static int ce_sqrt_hessian(const float *logits, const float *onehot, const float *row_scale, float *S, int64_t N, int64_t C, int64_t Vd,
+                           float scale, void *stream) {
   if (N < 0 || C <= 0 || Vd <= 0) return VIVIT_E_BADARG;
   if (N == 0) return VIVIT_OK;
-  if (!logits || !S || (!onehot && Vd != C)) return VIVIT_E_BADARG;
+  if (!logits || !S || (PS && !row_scale) || (!onehot && Vd != C)) return VIVIT_E_BADARG;
   if ((size_t)C * sizeof(float) > 60 * 1024 || N > 0x7fffffffLL) return VIVIT_E_UNSUPPORTED;
-  ce_sqrt_hessian_kernel<<<(unsigned)N, 256, (size_t)C * sizeof(float), static_cast<hipStream_t>(stream)>>>(logits, onehot, S, N, C, Vd,
-                                                                                                              scale);
+  ce_sqrt_hessian_kernel<PS><<<(unsigned)N, 256, (size_t)C * sizeof(float), static_cast<hipStream_t>(stream)>>>(logits, onehot, row_scale, S,
+                                                                                                                  N, C, Vd, scale);
   return launch_status();
+}
+
+extern "C" {
+
+int vivit_ce_sqrt_hessian_f32(const float *logits, const float *onehot, float *S, int64_t N, int64_t C, int64_t Vd, float scale,
+                              void *stream) {
+  return ce_sqrt_hessian<false>(logits, onehot, nullptr, S, N, C, Vd, scale, stream);
+}
+
+int vivit_ce_sqrt_hessian_w_f32(const float *logits, const float *onehot, const float *row_scale, float *S, int64_t N, int64_t C,
+                                int64_t Vd, void *stream) {
+  return ce_sqrt_hessian<true>(logits, onehot, row_scale, S, N, C, Vd, 0.f, stream);
 }
 
 } // extern "C"

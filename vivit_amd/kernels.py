@@ -908,6 +908,97 @@ def ce_sqrt_hessian_positions(logits, scale: float, idx=None):
 
 
 @_launcher
+def ce_target_scales(target, num_classes: int, weight=None, ignore_index: int = -100, label_smoothing: float = 0.0, mean: bool = True,
+                     mult: int = 1):
+    """The scale of every position of a cross entropy with class-index targets, ``pos_scale`` (float32, the shape of ``target``), for
+    :func:`ce_sqrt_hessian_positions_w` and :func:`ce_sqrt_hessian_w` (``vivit_ce_target_scales_f32``): with ``w`` the class weights
+    (ones if absent) and ``a = (1 - eps) w[y] + eps mean(w)`` at a counted position (``y != ignore_index`` and ``0 <= y < C``), else 0,
+    ``pos_scale = sqrt(a) / sqrt(mult norm)``, ``norm`` the sum of ``w[y]`` over the counted positions (``mean``) or 1.  ``target``
+    int64 ``[N, *D]`` on the device; nothing comes back to the host."""
+    if not target.is_cuda or target.dtype != torch.int64:
+        raise RuntimeError(f"target must be an int64 tensor on a HIP device (got {target.dtype} on {target.device})")
+    _require_device(weight)
+    if weight is not None:
+        if weight.device != target.device:
+            raise RuntimeError(f"all operands must live on one device (got {target.device} and {weight.device})")
+        if tuple(weight.shape) != (num_classes,):
+            raise ValueError(f"weight must be [{num_classes}], got {tuple(weight.shape)}")
+        weight = weight.contiguous()
+    if mult < 1:
+        raise ValueError(f"mult must be positive, got {mult}")
+    target = target.contiguous()
+    lib = _lib.load()
+    R = target.numel()
+    out = torch.empty(target.shape, dtype=torch.float32, device=target.device)
+    ws, wsb = _workspace(lib.vivit_ce_target_scales_f32_workspace_bytes(R, num_classes), out)
+    st = lib.vivit_ce_target_scales_f32(target.data_ptr(), weight.data_ptr() if weight is not None else None, out.data_ptr(), R, num_classes,
+                                        int(ignore_index), float(label_smoothing), 1 if mean else 0, int(mult), ws, wsb, _stream(out))
+    _lib.check(st, "vivit_ce_target_scales_f32")
+    return out
+
+
+@_launcher
+def ce_sqrt_hessian_w(logits, row_scale, onehot=None):
+    """:func:`ce_sqrt_hessian` with one scale per sample, ``row_scale [N]`` (``vivit_ce_sqrt_hessian_w_f32``): a sample whose scale is
+    zero is exact zeros in every slice, whatever its logits hold."""
+    _require_device(logits, onehot, row_scale)
+    logits = logits.contiguous()
+    N, C = logits.shape
+    Vd = C if onehot is None else onehot.shape[0]
+    if onehot is not None:
+        onehot = onehot.contiguous()
+        if tuple(onehot.shape[1:]) != (N, C):
+            raise ValueError(f"onehot must be [M, {N}, {C}], got {tuple(onehot.shape)}")
+    if row_scale.numel() != N:
+        raise ValueError(f"row_scale must hold {N} floats, got {tuple(row_scale.shape)}")
+    row_scale = row_scale.contiguous()
+    S = torch.empty((Vd, N, C), dtype=torch.float32, device=logits.device)
+    st = _lib.load().vivit_ce_sqrt_hessian_w_f32(logits.data_ptr(), onehot.data_ptr() if onehot is not None else None, row_scale.data_ptr(),
+                                                S.data_ptr(), N, C, Vd, _stream(logits))
+    _lib.check(st, "vivit_ce_sqrt_hessian_w_f32")
+    return S
+
+
+@_launcher
+def ce_sqrt_hessian_positions_w(logits, pos_scale, idx=None):
+    """:func:`ce_sqrt_hessian_positions` with one scale per position, ``pos_scale [N, *D]`` (``vivit_ce_pos_sqrt_hessian_w_f32``;
+    ``sqrt(omega)`` for the exact factor, ``sqrt(omega / M)`` for the sampled one): a position whose scale is zero is exact zeros in
+    every slice that covers it, whatever its logits hold.  Shapes, strides and the memory format of ``S`` as there."""
+    _require_device(logits, pos_scale)
+    if logits.dim() < 3:
+        raise ValueError(f"logits must be [N, C, *D] with at least one position dimension, got {tuple(logits.shape)}")
+    N, C, D = logits.shape[0], logits.shape[1], tuple(logits.shape[2:])
+    if C < 1:
+        raise ValueError("logits must have at least one class")
+    L = 1
+    for d in D:
+        L *= d
+    if tuple(pos_scale.shape) != (N,) + D:
+        raise ValueError(f"pos_scale must be [{N}, {', '.join(map(str, D))}], got {tuple(pos_scale.shape)}")
+    pos_scale = pos_scale.contiguous()
+    if idx is not None:
+        if idx.dtype != torch.int32:
+            raise ValueError(f"idx must be int32 class indices, got {idx.dtype}")
+        if idx.dim() != logits.dim() or tuple(idx.shape[1:]) != (N,) + D:
+            raise ValueError(f"idx must be [M, {N}, {', '.join(map(str, D))}], got {tuple(idx.shape)}")
+        if idx.device != logits.device:
+            raise RuntimeError(f"all operands must live on one device (got {logits.device} and {idx.device})")
+        idx = idx.contiguous()
+    classes_last = logits.movedim(1, -1).is_contiguous()
+    if not classes_last:
+        logits = logits.contiguous()
+    Vd = C * L if idx is None else idx.shape[0]
+    if classes_last:
+        S = torch.empty((Vd, N) + D + (C,), dtype=torch.float32, device=logits.device).movedim(-1, 2)
+    else:
+        S = torch.empty((Vd, N, C) + D, dtype=torch.float32, device=logits.device)
+    st = _lib.load().vivit_ce_pos_sqrt_hessian_w_f32(logits.data_ptr(), idx.data_ptr() if idx is not None else None, pos_scale.data_ptr(),
+                                                    S.data_ptr(), N, C, L, Vd, 1 if classes_last else 0, _stream(logits))
+    _lib.check(st, "vivit_ce_pos_sqrt_hessian_w_f32")
+    return S
+
+
+@_launcher
 def pack_lower(G: torch.Tensor) -> torch.Tensor:
     """Lower triangle (diagonal included) of the square matrix ``G`` as a packed ``n (n + 1) / 2`` vector (row-major)."""
     _require_device(G)
