@@ -1,6 +1,5 @@
 """GGN eigenpairs during backpropagation (API of ``vivit.linalg.eigh``)."""
-import contextlib
-from typing import Any, Callable, Dict, List, Tuple
+from typing import Any, Callable, Dict, Iterable, List, Tuple
 from warnings import warn
 
 import torch
@@ -10,7 +9,7 @@ from torch.nn import Module, Parameter
 from vivit_amd import kernels
 from vivit_amd.linalg.utils import (
     get_closures,
-    get_hook_store_batch_size,
+    get_hook_for_groups,
     get_vivit_extension,
     normalize,
     parameter_side_symeig,
@@ -20,6 +19,7 @@ from vivit_amd.utils import delete_savefield
 from vivit_amd.utils.checks import check_key_exists, check_subsampling_unique, check_unique_params
 from vivit_amd.utils.gram import reshape_as_square
 from vivit_amd.utils.hooks import ParameterGroupsHook
+from vivit_amd.utils.solve_queue import SolveQueue
 
 
 class EighComputation:
@@ -57,10 +57,8 @@ class EighComputation:
         eigenvectors agree to rounding (another back-transformation kernel).  The save-fields are deleted in the hook
         either way.  The price: the factors of up to eight queued groups (kept alive by the closures) and their Gram
         matrices stay in memory until their flush, where the immediate path frees each group's factors in its hook.
-        Parameter-side groups and ``data_parallel=True`` keep the immediate solve.  Streams as in
-        :class:`vivit_amd.linalg.EigvalshComputation`: every flush runs on the stream its matrices were queued on;
-        when ``get_result`` finds another stream current, that stream waits for the flush and the results are
-        recorded on it."""
+        Parameter-side groups and ``data_parallel=True`` keep the immediate solve.  Which stream a flush runs on and how
+        ``get_result`` is ordered behind it: :class:`vivit_amd.utils.solve_queue.SolveQueue`."""
         check_subsampling_unique(subsampling)
         use_parameter_side([], 1, side)  # validates ``side``
         if data_parallel and side != "gram":
@@ -77,9 +75,9 @@ class EighComputation:
         self._evecs: Dict[int, List[Tensor]] = {}
         self._batched_solve = bool(batched_solve) and not data_parallel
         # (device, n, stream) -> [(gram, group_id, scale, criterion, V_mat_prod closures, (C, N))]
-        self._pending: Dict[Any, List] = {}
+        self._queue = SolveQueue(self._solve_queued)
+        self._pending = self._queue.pending
 
-    _FLUSH_AT = 8  # matrices of one size that make a full launch (one per XCD)
     _SMALL_WARNING = (
         "Some eigenvectors have small eigenvalues."
         + " Their parameter space transformation is numerically unstable."
@@ -87,44 +85,42 @@ class EighComputation:
         + " Maybe use a more restrictive eigenvalue filter criterion."
     )
 
-    def _flush(self, key):
-        """Solve the queue ``key`` in one batched two-phase call on the stream it was filled on, store the eigenpairs."""
-        items = self._pending.pop(key, [])
-        if not items:
-            return
-        grams = [it[0] for it in items]
-        stream = key[2]
-        current = None if stream is None else torch.cuda.current_stream(grams[0].device)
-        foreign = stream is not None and current != stream
+    def _solve_queued(self, items) -> List[Tensor]:
+        """Solve the queued Gram matrices in one batched two-phase call, store the eigenpairs and return their tensors."""
+        plan = kernels.symeig_reduce_batched([it[0] for it in items], overwrite=True)
+        rows, keeps = list(plan.evals.unbind(0)), []
+        for row, (_, _, scale, criterion, _, _) in zip(rows, items):
+            if scale is not None:  # eigh.py:245-246; eigenvectors are scale invariant
+                row *= scale
+            keeps.append(criterion(row))
+        all_evecs = plan.select(keeps)
+        del plan
         results = []
-        with torch.cuda.stream(stream) if foreign else contextlib.nullcontext():
-            plan = kernels.symeig_reduce_batched(grams, overwrite=True)
-            rows, keeps = list(plan.evals.unbind(0)), []
-            for row, (_, _, scale, criterion, _, _) in zip(rows, items):
-                if scale is not None:  # eigh.py:245-246; eigenvectors are scale invariant
-                    row *= scale
-                keeps.append(criterion(row))
-            all_evecs = plan.select(keeps)
-            del plan
-            for row, keep, gram_evecs, (_, group_id, _, _, v_mat_prods, (C, N)) in zip(rows, keeps, all_evecs, items):
-                gram_evals = row[keep]
-                if (gram_evals.abs() < self._warn_small_eigvals).any():
-                    warn(self._SMALL_WARNING)
-                gram_evecs = gram_evecs.transpose(0, 1).reshape(-1, C, N)  # [K, C, N] (eigh.py:265)
-                group_evecs = [v_mat_prod(gram_evecs) for v_mat_prod in v_mat_prods]
-                normalize(group_evecs)
-                self._evals[group_id] = gram_evals
-                self._evecs[group_id] = group_evecs
-                results += [gram_evals] + group_evecs
-        if foreign:
-            current.wait_stream(stream)
-            for t in results:
-                t.record_stream(current)
+        for row, keep, gram_evecs, (_, group_id, _, _, v_mat_prods, (C, N)) in zip(rows, keeps, all_evecs, items):
+            results += self._finish(group_id, row[keep], gram_evecs, C, N, v_mat_prods)
+        return results
+
+    def _finish(self, group_id: int, gram_evals: Tensor, gram_evecs: Tensor, C: int, N: int,
+                v_mat_prods: Iterable[Callable[[Tensor], Tensor]], acc=None) -> List[Tensor]:
+        """From the kept eigenpairs ``(gram_evals [K], gram_evecs [n, K])`` of a group's Gram matrix to its result:
+        warn, back-project through one ``V_mat_prod`` per parameter, normalise, store; returns the stored tensors.
+
+        ``v_mat_prods`` is consumed one product at a time, so a generator can free a factor right after its product.
+        ``acc``: the :class:`BatchShardedGram` of a data-parallel group -- this rank applies the rows of V it owns."""
+        if (gram_evals.abs() < self._warn_small_eigvals).any():
+            warn(self._SMALL_WARNING)
+        gram_evecs = gram_evecs.transpose(0, 1).reshape(-1, C, N)  # selectable via the first axis: [K, C, N] (eigh.py:265)
+        if acc is not None:
+            gram_evecs = acc.local_samples(gram_evecs, 2).contiguous()
+        group_evecs = [v_mat_prod(gram_evecs) for v_mat_prod in v_mat_prods]
+        normalize(group_evecs)
+        self._evals[group_id] = gram_evals
+        self._evecs[group_id] = group_evecs
+        return [gram_evals] + group_evecs
 
     def get_result(self, group: Dict) -> Tuple[Tensor, List[Tensor]]:
         """``(evals, evecs)`` of the group's GGN block; KeyError if unavailable."""
-        for key in list(self._pending):
-            self._flush(key)
+        self._queue.flush_all()
         try:
             return self._evals[id(group)], self._evecs[id(group)]
         except KeyError as e:
@@ -135,22 +131,10 @@ class EighComputation:
 
     def get_extension_hook(self, param_groups: List[Dict]) -> Callable[[Module], None]:
         self._check_param_groups(param_groups)
-        store_batch_size = get_hook_store_batch_size(param_groups, self._batch_size, verbose=self._verbose)
         hook = ParameterGroupsHook.from_functions(
             param_groups, self.get_param_computation(), self.get_group_hook(), self.get_accumulate()
         )
-
-        def extension_hook(module: Module):
-            if self._verbose:
-                print(f"Extension hook on module {id(module)} {module}")
-            store_batch_size(module)
-            hook(module)
-
-        if self._verbose:
-            print("ID map groups → params")
-            for group in param_groups:
-                print(f"{id(group)} → {[id(p) for p in group['params']]}")
-        return extension_hook
+        return get_hook_for_groups(param_groups, self._batch_size, hook, verbose=self._verbose)
 
     def get_param_computation(self) -> Callable[[ParameterGroupsHook, Parameter], None]:
         def param_computation(self: ParameterGroupsHook, param: Parameter):
@@ -170,7 +154,7 @@ class EighComputation:
         evals, evecs, verbose = self._evals, self._evecs, self._verbose
         warn_small_eigvals, side, dp = self._warn_small_eigvals, self._side, self._dp
         small_warning = self._SMALL_WARNING
-        batched, pending, flush, flush_at = self._batched_solve, self._pending, self._flush, self._FLUSH_AT
+        batched, queue, finish = self._batched_solve, self._queue, self._finish
 
         def group_hook(self: ParameterGroupsHook, accumulation: None, group: Dict[str, Any]) -> None:
             group_id = id(group)
@@ -228,11 +212,8 @@ class EighComputation:
                 for param in group["params"]:
                     v_mat_prods.append(get_closures(param, savefield)["V_mat_prod"])
                     delete_savefield(param, savefield, verbose=verbose)
-                stream = torch.cuda.current_stream(square.device) if square.is_cuda else None
-                key = (square.device, square.shape[0], stream)
-                pending.setdefault(key, []).append((square, group_id, scale, group["criterion"], v_mat_prods, (C, N)))
-                if len(pending[key]) >= flush_at:
-                    flush(key)
+                item = (square, group_id, scale, group["criterion"], v_mat_prods, (C, N))
+                queue.add(square, (square.shape[0],), item)
                 return
 
             # two launches around the criterion callback: reduction + all eigenvalues, then only the kept eigenvectors
@@ -248,25 +229,16 @@ class EighComputation:
             gram_evals, gram_evecs = gram_evals[keep], plan.select(keep)
             del plan
 
-            if (gram_evals.abs() < warn_small_eigvals).any():
-                warn(small_warning)
+            def v_mat_prods():  # one at a time: each parameter's factor is freed right after its product
+                for param in group["params"]:
+                    v_mat_prod = get_closures(param, savefield)["V_mat_prod"]
+                    if acc is None:
+                        yield v_mat_prod
+                    else:  # every rank applied the rows of V it owns; one all-reduce per parameter sums them
+                        yield lambda mat: all_reduce_sum_(v_mat_prod(mat).contiguous(), acc.group)
+                    delete_savefield(param, savefield, verbose=verbose)
 
-            # eigenvectors selectable via the first axis: [K, C, N] (eigh.py:265)
-            gram_evecs = gram_evecs.transpose(0, 1).reshape(-1, C, N)
-
-            group_evecs = []
-            if acc is not None:  # every rank applies the rows of V it owns; one all-reduce per parameter sums them
-                gram_evecs = acc.local_samples(gram_evecs, 2).contiguous()
-            for param in group["params"]:
-                vecs = get_closures(param, savefield)["V_mat_prod"](gram_evecs)
-                if acc is not None:
-                    vecs = all_reduce_sum_(vecs.contiguous(), acc.group)
-                group_evecs.append(vecs)
-                delete_savefield(param, savefield, verbose=verbose)
-            normalize(group_evecs)
-
-            evals[group_id] = gram_evals
-            evecs[group_id] = group_evecs
+            finish(group_id, gram_evals, gram_evecs, C, N, v_mat_prods(), acc)
 
         return group_hook
 

@@ -1,15 +1,13 @@
 """GGN eigenvalues during backpropagation (API of ``vivit.linalg.eigvalsh``)."""
-import contextlib
 from typing import Any, Callable, Dict, List
 
-import torch
 from torch import Tensor
 from torch.nn import Module, Parameter
 
 from vivit_amd import kernels
 from vivit_amd.linalg.utils import (
     get_closures,
-    get_hook_store_batch_size,
+    get_hook_for_groups,
     get_vivit_extension,
     parameter_side_symeig,
     use_parameter_side,
@@ -18,6 +16,7 @@ from vivit_amd.utils import delete_savefield
 from vivit_amd.utils.checks import check_key_exists, check_subsampling_unique, check_unique_params
 from vivit_amd.utils.gram import reshape_as_square
 from vivit_amd.utils.hooks import ParameterGroupsHook
+from vivit_amd.utils.solve_queue import SolveQueue
 
 
 class EigvalshComputation:
@@ -41,13 +40,8 @@ class EigvalshComputation:
         the queue goes through ``kernels.symeigvals_batched`` -- eight matrices of 193 <= n <= 1280 share one launch,
         one per XCD, where a single solve idles seven of the eight -- as soon as eight matrices of one size wait, and
         for the remainder on the first ``get_result``.  The eigenvalues are those of ``batched_solve=False`` bit for
-        bit.  Parameter-side groups and ``data_parallel=True`` keep the immediate solve.
-        Streams: the hooks run on the backend's side stream (vivit_amd/backend/engine.py), so that is where a Gram
-        matrix is allocated and accumulated.  Each queue remembers the stream its matrices were queued on and EVERY
-        flush runs on that stream -- behind all accumulations by stream order, on memory that belongs to that stream
-        as far as the caching allocator is concerned (no ``record_stream`` is needed for the inputs).  When the flush
-        of ``get_result`` finds another stream current, that stream then waits for the flush and the result tensor is
-        recorded on it."""
+        bit.  Parameter-side groups and ``data_parallel=True`` keep the immediate solve.  Which stream a flush runs on
+        and how ``get_result`` is ordered behind it: :class:`vivit_amd.utils.solve_queue.SolveQueue`."""
         check_subsampling_unique(subsampling)
         use_parameter_side([], 1, side)  # validates ``side``
         if data_parallel and side != "gram":
@@ -63,36 +57,24 @@ class EigvalshComputation:
         self._evals: Dict[int, Tensor] = {}
         self._batched_solve = bool(batched_solve) and not data_parallel
         # (device, n, stream) -> [(gram, group_id, scale)]: Gram matrices waiting for a batched solve
-        self._pending: Dict[Any, List] = {}
+        self._queue = SolveQueue(self._solve_queued)
+        self._pending = self._queue.pending
 
-    _FLUSH_AT = 8  # matrices of one size that make a full launch (one per XCD)
-
-    def _flush(self, key):
-        """Solve the queue ``key`` in one batched call on the stream it was filled on, store the spectra."""
-        items = self._pending.pop(key, [])
-        if not items:
-            return
-        grams = [g for g, _, _ in items]
-        stream = key[2]
-        current = None if stream is None else torch.cuda.current_stream(grams[0].device)
-        foreign = stream is not None and current != stream
-        with torch.cuda.stream(stream) if foreign else contextlib.nullcontext():
-            W = kernels.symeigvals_batched(grams, overwrite=True)
-            for row, (_, group_id, scale) in zip(W.unbind(0), items):
-                # eigenvalues are homogeneous of degree one: the O(n) vector is scaled instead of the n x n Gram
-                if scale is not None:
-                    row *= scale
-                if self._verbose:
-                    print(f"Group {group_id}: Store 'gram_evals'")
-                self._evals[group_id] = row
-        if foreign:
-            current.wait_stream(stream)
-            W.record_stream(current)
+    def _solve_queued(self, items) -> List[Tensor]:
+        """Solve the queued Gram matrices in one batched call, store the spectra (rows of the one tensor returned)."""
+        W = kernels.symeigvals_batched([g for g, _, _ in items], overwrite=True)
+        for row, (_, group_id, scale) in zip(W.unbind(0), items):
+            # eigenvalues are homogeneous of degree one: the O(n) vector is scaled instead of the n x n Gram
+            if scale is not None:
+                row *= scale
+            if self._verbose:
+                print(f"Group {group_id}: Store 'gram_evals'")
+            self._evals[group_id] = row
+        return [W]
 
     def get_result(self, group: Dict) -> Tensor:
         """Eigenvalues (ascending) of the group's GGN block; KeyError if unavailable."""
-        for key in list(self._pending):
-            self._flush(key)
+        self._queue.flush_all()
         try:
             return self._evals[id(group)]
         except KeyError as e:
@@ -105,22 +87,10 @@ class EigvalshComputation:
     def get_extension_hook(self, param_groups: List[Dict]) -> Callable[[Module], None]:
         """Hook to pass as ``extension_hook``; groups need the ``'params'`` key."""
         self._check_param_groups(param_groups)
-        store_batch_size = get_hook_store_batch_size(param_groups, self._batch_size, verbose=self._verbose)
         hook = ParameterGroupsHook.from_functions(
             param_groups, self.get_param_computation(), self.get_group_hook(), self.get_accumulate()
         )
-
-        def extension_hook(module: Module):
-            if self._verbose:
-                print(f"Extension hook on module {id(module)} {module}")
-            store_batch_size(module)
-            hook(module)
-
-        if self._verbose:
-            print("ID map groups → params")
-            for group in param_groups:
-                print(f"{id(group)} → {[id(p) for p in group['params']]}")
-        return extension_hook
+        return get_hook_for_groups(param_groups, self._batch_size, hook, verbose=self._verbose)
 
     def get_param_computation(self) -> Callable[[ParameterGroupsHook, Parameter], Tensor]:
         verbose, savefield, side, dp = self._verbose, self._savefield, self._side, self._dp
@@ -168,7 +138,7 @@ class EigvalshComputation:
     def get_group_hook(self) -> Callable[[ParameterGroupsHook, Tensor, Dict[str, Any]], None]:
         batch_sizes, subsampling = self._batch_size, self._subsampling
         evals, verbose, savefield = self._evals, self._verbose, self._savefield
-        batched, pending, flush, flush_at = self._batched_solve, self._pending, self._flush, self._FLUSH_AT
+        batched, queue = self._batched_solve, self._queue
 
         def group_hook(self: ParameterGroupsHook, accumulation: Tensor, group: Dict):
             group_id = id(group)
@@ -188,11 +158,7 @@ class EigvalshComputation:
                     accumulation = accumulation.finalize()
                 gram_mat = reshape_as_square(accumulation)
                 if batched:
-                    stream = torch.cuda.current_stream(gram_mat.device) if gram_mat.is_cuda else None
-                    key = (gram_mat.device, gram_mat.shape[0], stream)
-                    pending.setdefault(key, []).append((gram_mat, group_id, scale))
-                    if len(pending[key]) >= flush_at:
-                        flush(key)
+                    queue.add(gram_mat, (gram_mat.shape[0],), (gram_mat, group_id, scale))
                     return
                 gram_evals, _ = kernels.symeig(gram_mat, eigenvectors=False, overwrite=True)
             # eigenvalues are homogeneous of degree one: the O(n) vector is scaled instead of the n x n Gram

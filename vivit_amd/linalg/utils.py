@@ -121,6 +121,26 @@ def get_hook_store_batch_size(
     return hook_store_batch_size
 
 
+def get_hook_for_groups(
+    param_groups: List[Dict], batch_size: Dict[int, int], hook: Callable[[Module], None], verbose: bool = False
+) -> Callable[[Module], None]:
+    """The ``extension_hook`` of a computation: record the batch size into ``batch_size``, then run ``hook``
+    (a :class:`vivit_amd.utils.hooks.ParameterGroupsHook`) on the module (vivit/linalg/eigvalsh.py:101-131)."""
+    store_batch_size = get_hook_store_batch_size(param_groups, batch_size, verbose=verbose)
+
+    def extension_hook(module: Module):
+        if verbose:
+            print(f"Extension hook on module {id(module)} {module}")
+        store_batch_size(module)
+        hook(module)
+
+    if verbose:
+        print("ID map groups → params")
+        for group in param_groups:
+            print(f"{id(group)} → {[id(p) for p in group['params']]}")
+    return extension_hook
+
+
 def normalize(tensors: List[Tensor]):
     """Unit-normalise stacked vectors in parameter-list format, in place (K10;
     vivit/linalg/utils.py:67-76): one fused sum-of-squares pass + one scaling pass per tensor."""

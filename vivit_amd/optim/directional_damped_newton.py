@@ -6,7 +6,7 @@ from torch import Tensor
 from torch.nn import Module
 
 from vivit_amd import kernels
-from vivit_amd.linalg.utils import get_hook_store_batch_size
+from vivit_amd.linalg.utils import get_hook_for_groups
 from vivit_amd.optim.directional_derivatives import (
     GramDirectionsQueue,
     accumulate_dot_products,
@@ -72,9 +72,7 @@ class DirectionalDampedNewtonComputation:
           size stay in memory until their flush, where the immediate mode frees each group's factors in its hook.  The
           steps agree with the immediate mode to rounding (the eigenvalues bit for bit; the eigenvectors come from
           another back-transformation kernel, their sign cancels in the step).  ``data_parallel=True`` keeps the
-          immediate path.  Streams as in :class:`vivit_amd.linalg.EighComputation`: a flush runs on the stream its groups
-          were queued on; when ``get_result`` finds another stream current, that stream waits for the flush and the
-          results are recorded on it.
+          immediate path.  Streams: :class:`vivit_amd.utils.solve_queue.SolveQueue`.
         """
         check_subsampling_unique(subsampling_grad)
         check_subsampling_unique(subsampling_ggn)
@@ -92,7 +90,7 @@ class DirectionalDampedNewtonComputation:
         self._batch_size: Dict[int, int] = {}
         self._newton_steps: Dict[int, Tuple[Tensor]] = {}
         self._batched_solve = bool(batched_solve) and not data_parallel
-        self._queue = GramDirectionsQueue(self._finish_queued, warn_small_eigvals, _SMALL_EVALS_NEWTON, verbose)
+        self._queue = GramDirectionsQueue(self._step, warn_small_eigvals, _SMALL_EVALS_NEWTON, verbose)
 
     def get_result(self, group: Dict) -> Tuple[Tensor]:
         self._queue.flush_all()
@@ -110,31 +108,17 @@ class DirectionalDampedNewtonComputation:
 
     def get_extension_hook(self, param_groups: List[Dict]) -> Callable[[Module], None]:
         self._check_param_groups(param_groups)
-        store_batch_size = get_hook_store_batch_size(param_groups, self._batch_size, verbose=self._verbose)
         hook = ParameterGroupsHook.from_functions(
             param_groups,
             lambda hook, param: self._param_computation(
                 hook, param, self._savefield_ggn, self._savefield_grad, self._verbose, self._dp
             ),
-            lambda hook, accumulation, group: self._queue_group(accumulation, group)
-            if self._batched_solve else self._group_hook(
-                hook, accumulation, group, self._batch_size, self._savefield_ggn, self._newton_steps,
-                self._verbose, self._warn_small_eigvals,
+            lambda hook, accumulation, group: (self._queue_group if self._batched_solve else self._group_hook)(
+                accumulation, group
             ),
             lambda hook, existing, update: accumulate_dot_products(existing, update, self._verbose),
         )
-
-        def extension_hook(module: Module):
-            if self._verbose:
-                print(f"Extension hook on module {id(module)} {module}")
-            store_batch_size(module)
-            hook(module)
-
-        if self._verbose:
-            print("ID map groups → params")
-            for group in param_groups:
-                print(f"{id(group)} → {[id(p) for p in group['params']]}")
-        return extension_hook
+        return get_hook_for_groups(param_groups, self._batch_size, hook, verbose=self._verbose)
 
     @staticmethod
     def _param_computation(hook, param, savefield_ggn, savefield_grad, verbose, data_parallel=None):
@@ -151,47 +135,40 @@ class DirectionalDampedNewtonComputation:
             delete_savefield(param, self._savefield_ggn, verbose=self._verbose)
         self._queue.add(accumulation, group, self._batch_size.pop(id(group)), payload=factors)
 
-    def _finish_queued(self, group, factors, evals, evecs, gammas, lambdas, V_correction, C, N_ggn):
-        """The tail of :meth:`_group_hook` for a group that went through the queue."""
+    def _group_hook(self, accumulation, group):
+        """The immediate mode: directions, step and the end of the factors' save-fields in the group's hook."""
+        N = self._batch_size.pop(id(group))
+        *directions, dp_acc = gram_space_directions(
+            accumulation, group, N, self._verbose, self._warn_small_eigvals, _SMALL_EVALS_NEWTON
+        )
+        params = group["params"]
+        self._step(group, [getattr(param, self._savefield_ggn) for param in params], *directions, dp_acc=dp_acc)
+        for param in params:
+            delete_savefield(param, self._savefield_ggn, verbose=self._verbose)
+
+    def _step(self, group, factors, evals, evecs, gammas, lambdas, V_correction, C, N_ggn, dp_acc=None) -> List[Tensor]:
+        """From a group's directions (:func:`gram_space_directions` or the queue's flush) and the factors of its
+        parameters to its Newton step: stored, and returned as the list of its tensors."""
+        # coefficients along the directions (directional_damped_newton.py:353-359): O(K) glue
         coefficients = (
             -gammas.mean(0) / (lambdas.mean(0) + group["damping"](evals, evecs, gammas, lambdas)) / evals.sqrt()
-        )
-        v = kernels.gemm_nn(evecs, coefficients.reshape(-1, 1).contiguous(), alpha=V_correction)  # [n, 1]
-        coef = v.reshape(1, C, N_ggn)
-        steps = [apply_factor(V, coef)[0].view(param.shape) for V, param in zip(factors, group["params"])]
-        self._newton_steps[id(group)] = steps
-        return steps
-
-    @staticmethod
-    def _group_hook(hook, accumulation, group, batch_size, savefield_ggn, newton_steps, verbose,
-                    warn_small_eigvals):
-        N = batch_size.pop(id(group))
-        evals, evecs, gammas, lambdas, V_correction, C, N_ggn, dp_acc = gram_space_directions(
-            accumulation, group, N, verbose, warn_small_eigvals, _SMALL_EVALS_NEWTON
-        )
-        # coefficients along the directions (directional_damped_newton.py:353-359): O(K) glue
-        damping = group["damping"]
-        coefficients = (
-            -gammas.mean(0) / (lambdas.mean(0) + damping(evals, evecs, gammas, lambdas)) / evals.sqrt()
         )
         # weight in Gram space (:362-366), then apply V (K7, :370-373): step_p = v^T V_p
         v = kernels.gemm_nn(evecs, coefficients.reshape(-1, 1).contiguous(), alpha=V_correction)  # [n, 1]
         coef = v.reshape(1, C, N_ggn)
-        params = group["params"]
-        steps = []
         if dp_acc is not None:
             # data parallel: this rank applies the rows of V it owns, one all-reduce of P floats sums the shards
             from vivit_amd.distributed import all_reduce_sum_
 
             coef = dp_acc.local_samples(coef, 2).contiguous()
-        for param in params:
-            step = apply_factor(getattr(param, savefield_ggn), coef)[0]
+        steps = []
+        for V, param in zip(factors, group["params"]):
+            step = apply_factor(V, coef)[0]
             if dp_acc is not None:
                 all_reduce_sum_(step, dp_acc.group)
             steps.append(step.view(param.shape))
-        for param in params:
-            delete_savefield(param, savefield_ggn, verbose=verbose)
-        newton_steps[id(group)] = steps
+        self._newton_steps[id(group)] = steps
+        return steps
 
     @staticmethod
     def _check_param_groups(param_groups: List[Dict]):

@@ -4,22 +4,21 @@ API of ``vivit.optim.directional_derivatives`` (vivit/optim/directional_derivati
 computed on the MI355X kernels.  The Gram-space part shared with the damped Newton step lives
 in :func:`gram_space_directions`.
 """
-import contextlib
 import math
 from typing import Callable, Dict, List, Optional, Tuple
 from warnings import warn
 
-import torch
 from torch import Tensor
 from torch.nn import Module
 
 from vivit_amd import kernels
-from vivit_amd.linalg.utils import get_hook_store_batch_size
+from vivit_amd.linalg.utils import get_hook_for_groups
 from vivit_amd.optim.utils import get_batch_grad_extension, get_sqrt_ggn_extension
 from vivit_amd.utils import delete_savefield
 from vivit_amd.utils.checks import check_key_exists, check_subsampling_unique, check_unique_params
 from vivit_amd.utils.gram import partial_contract, reshape_as_square
 from vivit_amd.utils.hooks import ParameterGroupsHook
+from vivit_amd.utils.solve_queue import SolveQueue
 
 _SMALL_EVALS_GAMMA = (
     "Some eigenvalues are small. This can lead to numerical instabilities"
@@ -190,52 +189,28 @@ def gram_space_directions(accumulation: Dict[str, Tensor], group: Dict, N: int, 
 
 class GramDirectionsQueue:
     """The ``batched_solve=True`` mode of the two optim computations: groups whose dot products are complete wait here
-    instead of going through :func:`gram_space_directions` one by one (modelled on ``EighComputation._pending``).
+    instead of going through :func:`gram_space_directions` one by one.
 
-    Key ``(device, n, C, M, stream)``; a key is flushed when :attr:`FLUSH_AT` groups wait under it, everything else by
-    :meth:`flush_all` (the computations call it first thing in ``get_result``).  A flush runs, on the stream the groups
-    were queued on: ``kernels.symeig_reduce_batched`` on copies (the Gram matrices are needed again), per group the
-    eigenvalue scaling and ``criterion``, ONE batched ``select``, ONE ``kernels.gram_directions_batched``, then per group
-    the small-eigenvalue warning and ``finish(group, payload, evals, evecs, gammas, lambdas, V_correction, C, N_ggn)``, which
-    stores the group's result and returns its tensors (recorded on the current stream when that is another one).
-    Until its flush a queued group keeps its Gram matrix, ``V_t_g_n`` and whatever ``payload`` references alive."""
-
-    FLUSH_AT = 8  # matrices of one size that make a full launch of the batched eigensolver (one per XCD)
+    A :class:`vivit_amd.utils.solve_queue.SolveQueue` (when a key is flushed, on which stream) with the key
+    ``(device, n, C, M, stream)``.  A flush runs: ``kernels.symeig_reduce_batched`` on copies (the Gram matrices are needed
+    again), per group the eigenvalue scaling and ``criterion``, ONE batched ``select``, ONE
+    ``kernels.gram_directions_batched``, then per group the small-eigenvalue warning and
+    ``finish(group, payload, evals, evecs, gammas, lambdas, V_correction, C, N_ggn)``, which stores the group's result and
+    returns its tensors.  Until its flush a queued group keeps its Gram matrix, ``V_t_g_n`` and whatever ``payload``
+    references alive."""
 
     def __init__(self, finish: Callable, warn_small_eigvals: float, warning: str, verbose: bool):
         self._finish, self._warn_small_eigvals, self._warning, self._verbose = finish, warn_small_eigvals, warning, verbose
         # key -> [(gram [n, n], V_t_g_n [n, M], group, N, C, N_ggn, payload)]
-        self.pending: Dict[Tuple, List] = {}
+        self._queue = SolveQueue(self._solve)
+        self.pending, self.flush_all = self._queue.pending, self._queue.flush_all
 
     def add(self, accumulation: Dict[str, Tensor], group: Dict, N: int, payload=None):
         V_t_V = accumulation.pop("V_t_V")
         C, N_ggn = V_t_V.shape[0], V_t_V.shape[1]
         gram = reshape_as_square(V_t_V)
         vtg = accumulation.pop("V_t_g_n").flatten(start_dim=0, end_dim=1)  # [n, N_grad]
-        stream = torch.cuda.current_stream(gram.device) if gram.is_cuda else None
-        key = (gram.device, gram.shape[0], C, vtg.shape[1], stream)
-        self.pending.setdefault(key, []).append((gram, vtg, group, N, C, N_ggn, payload))
-        if len(self.pending[key]) >= self.FLUSH_AT:
-            self.flush(key)
-
-    def flush_all(self):
-        for key in list(self.pending):
-            self.flush(key)
-
-    def flush(self, key):
-        items = self.pending.pop(key, [])
-        if not items:
-            return
-        stream = key[4]
-        current = None if stream is None else torch.cuda.current_stream(key[0])
-        foreign = stream is not None and current != stream
-        results = []
-        with torch.cuda.stream(stream) if foreign else contextlib.nullcontext():
-            results = self._solve(items)
-        if foreign:
-            current.wait_stream(stream)
-            for t in results:
-                t.record_stream(current)
+        self._queue.add(gram, (gram.shape[0], C, vtg.shape[1]), (gram, vtg, group, N, C, N_ggn, payload))
 
     def _solve(self, items) -> List[Tensor]:
         verbose = self._verbose
@@ -340,7 +315,6 @@ class DirectionalDerivativesComputation:
 
     def get_extension_hook(self, param_groups: List[Dict]) -> Callable[[Module], None]:
         self._check_param_groups(param_groups)
-        store_batch_size = get_hook_store_batch_size(param_groups, self._batch_size, verbose=self._verbose)
         hook = ParameterGroupsHook.from_functions(
             param_groups,
             lambda hook, param: self._param_computation(
@@ -353,18 +327,7 @@ class DirectionalDerivativesComputation:
             ),
             lambda hook, existing, update: accumulate_dot_products(existing, update, self._verbose),
         )
-
-        def extension_hook(module: Module):
-            if self._verbose:
-                print(f"Extension hook on module {id(module)} {module}")
-            store_batch_size(module)
-            hook(module)
-
-        if self._verbose:
-            print("ID map groups → params")
-            for group in param_groups:
-                print(f"{id(group)} → {[id(p) for p in group['params']]}")
-        return extension_hook
+        return get_hook_for_groups(param_groups, self._batch_size, hook, verbose=self._verbose)
 
     @staticmethod
     def _param_computation(hook, param, savefield_ggn, savefield_grad, verbose, data_parallel=None):
