@@ -318,6 +318,13 @@ int vivit_gate_jac_t_f32(const float *M, const float *a, const float *b, float *
  * overlap).  No sine or cosine is evaluated: the tables are the fp32 values the forward pass used. */
 int vivit_rope_jac_t_f32(const float *M, const float *cosT, const float *sinT, float *G, int64_t R, int64_t T, int64_t H, int64_t d,
                          void *stream);
+/* The same rule on the packed projection of grouped-query attention (vivit_amd.backend.RotaryEmbedding with num_kv_heads; call
+ * site vivit_amd/kernels.py:rope_jac_t): M, G [R, T, (H + 2 Hkv) d] = H query heads | Hkv key heads | Hkv value heads of d columns
+ * each.  The H + Hkv heads of the q and k parts are rotated back by the formula above, the Hkv d columns of the v part are copied
+ * bit for bit; G may be M itself.  Hkv <= 0 or H % Hkv != 0: VIVIT_E_BADARG.  vivit_rope_jac_t_f32 is this entry point with
+ * Hkv = H.  VIVIT_E_UNSUPPORTED (nothing launched) for (H + 2 Hkv) d, R T or T d above 2^31 - 1. */
+int vivit_rope_gqa_jac_t_f32(const float *M, const float *cosT, const float *sinT, float *G, int64_t R, int64_t T, int64_t H,
+                             int64_t Hkv, int64_t d, void *stream);
 /* Scaled dot-product self-attention on the packed projection (attention.hip; no counterpart in the reference's module map -- it
  * replaces the generic rule of the factor provider, a recomputed forward and torch.autograd.grad(..., is_grads_batched=True) at
  * vivit_amd/backend/extensions.py:_jac_t_mat_prod, for vivit_amd.backend.ScaledDotProductAttention).  The module input is
@@ -336,6 +343,26 @@ size_t vivit_attention_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T
 int vivit_attention_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
                               int64_t H, int64_t d, float scale, int causal, void *workspace, size_t workspace_bytes,
                               void *stream);
+/* Grouped-query attention: the same rule when H query heads share Hkv key / value heads (attention.hip; call site
+ * vivit_amd/kernels.py:attention_jac_t with num_kv_heads, for vivit_amd.backend.ScaledDotProductAttention(num_kv_heads=...)).
+ * qkv [N, T, (H + 2 Hkv) d] = q | k | v: q is the first H d columns, k the next Hkv d, v the last Hkv d; query head h attends to
+ * key / value head g = h / R, R = H / Hkv consecutive query heads per group (Hkv == H: the layout above, Hkv == 1: multi-query
+ * attention).  out and M [V, N, T, H d] as above, G [V, N, T, (H + 2 Hkv) d] = dQ | dK | dV packed as qkv.  Per query head h of
+ * group g, S, P, D, dP, dS and dQ_h are the formulas above with K_g and V_g as operands, and
+ *   dV_g = sum_{h in g} P_h^T dO_h,     dK_g = scale sum_{h in g} dS_h^T Q_h.
+ * One workgroup owns a block of 32 keys of one (n, g): it walks the query heads g R .. g R + R - 1 in ascending order and inside
+ * each head the query blocks in ascending order, and accumulates into one set of registers.  The summation order of every element
+ * of dK and dV is therefore head, then query block, then k within the block: no atomics, no second pass, and the bytes of G[v, n]
+ * depend on (T, H, Hkv, d, scale, causal) and the data of (v, n) only.  The workspace is counted in QUERY heads, lse [N, H, T] and
+ * D [V, N, H, T], the same number of bytes as vivit_attention_jac_t_f32_workspace_bytes(V, N, T, H, d); the query returns 0 for
+ * arguments the entry point refuses.  Hkv <= 0 or H % Hkv != 0: VIVIT_E_BADARG.  VIVIT_E_UNSUPPORTED (nothing launched, and
+ * before the workspace is looked at) for d > 128, for the chunk limit above, and for sizes beyond the kernels' index arithmetic
+ * ((H + 2 Hkv) d, N H ceil(T / 32), N Hkv ceil(T / 32) or V N H T / 256 above 2^31 - 1, N H T above 2^40).
+ * vivit_attention_jac_t_f32 and its workspace query are these two entry points with Hkv = H. */
+size_t vivit_attention_gqa_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d);
+int vivit_attention_gqa_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
+                                  int64_t H, int64_t Hkv, int64_t d, float scale, int causal, void *workspace,
+                                  size_t workspace_bytes, void *stream);
 /* nn.Embedding (embedding.hip; the reference has no rule for it): the weight factor Vt[v, n, w, :] = sum_{t: idx[n, t] = w} M[v, n, t, :]
  * of the factor M [V, N, T, D] at the module output has at most T non-zero rows per (v, n) out of W = num_embeddings and is kept
  * compact: ids [N, T] int32 holds sample n's distinct tokens in strictly increasing order in its first U_n slots and -1 in the rest,

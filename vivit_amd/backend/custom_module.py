@@ -113,21 +113,59 @@ class ScaleModule(nn.Module):
         return x * self.weight
 
 
+def _kv_heads(num_heads: int, num_kv_heads):
+    """The ``num_kv_heads`` argument of the attention modules, validated (``None`` stays ``None``: multi-head attention)."""
+    if num_kv_heads is None:
+        return None
+    if num_kv_heads < 1:
+        raise ValueError(f"num_kv_heads (Hkv) must be positive, got {num_kv_heads}")
+    if num_heads % num_kv_heads != 0:
+        raise ValueError(f"num_heads (H = {num_heads}) is not a multiple of num_kv_heads (Hkv = {num_kv_heads})")
+    return int(num_kv_heads)
+
+
+def _gqa_head_dim(qkv: Tensor, H: int, Hkv: int) -> int:
+    if qkv.dim() != 3:
+        raise ValueError(f"expected a packed projection [N, T, (H + 2 Hkv) d], got {qkv.dim()} dimensions")
+    if qkv.shape[2] == 0 or qkv.shape[2] % (H + 2 * Hkv) != 0:
+        raise ValueError(f"the last dimension ({qkv.shape[2]}) is not (H + 2 Hkv) = ({H} + 2 * {Hkv}) heads * head dimension")
+    return qkv.shape[2] // (H + 2 * Hkv)
+
+
+def _gqa_split(x: Tensor, H: int, Hkv: int, d: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """Views of a packed projection ``x [*B, T, (H + 2 Hkv) d]``: ``q [*B, Hkv, R, T, d]`` and ``k``, ``v [*B, Hkv, 1, T, d]``."""
+    B, T = x.shape[:-2], x.shape[-2]
+    nb = len(B)
+    q = x[..., :H * d].unflatten(-1, (Hkv, H // Hkv, d)).permute(*range(nb), nb + 1, nb + 2, nb, nb + 3)
+    k = x[..., H * d:(H + Hkv) * d].unflatten(-1, (Hkv, 1, d)).permute(*range(nb), nb + 1, nb + 2, nb, nb + 3)
+    v = x[..., (H + Hkv) * d:].unflatten(-1, (Hkv, 1, d)).permute(*range(nb), nb + 1, nb + 2, nb, nb + 3)
+    return q, k, v
+
+
 class ScaledDotProductAttention(nn.Module):
     """Multi-head scaled dot-product self-attention on a packed projection (no counterpart in BackPACK): a parameter-free leaf.
 
     Input ``qkv [N, T, 3 E]`` with ``q = qkv[..., :E]``, ``k = qkv[..., E:2 E]``, ``v = qkv[..., 2 E:]``; head ``h`` owns the columns
     ``h d .. (h + 1) d`` of each third (``d = E / num_heads``, the layout of ``nn.MultiheadAttention``'s packed projection).  Output
     ``[N, T, E]``: per head ``softmax(scale q k^T) v`` with ``scale = 1 / sqrt(d)`` by default; ``causal`` masks the keys ``j > i``.
-    No dropout and no other mask."""
+    No dropout and no other mask.
 
-    def __init__(self, num_heads: int, causal: bool = False, scale: float = None):
+    ``num_kv_heads`` (grouped-query attention; ``None``: every query head has its own key and value head): the ``H = num_heads``
+    query heads share ``Hkv = num_kv_heads`` key / value heads, ``H % Hkv == 0``.  Input ``qkv [N, T, (H + 2 Hkv) d]``: ``q`` is the
+    first ``H d`` columns, ``k`` the next ``Hkv d``, ``v`` the last ``Hkv d``; query head ``h`` attends to key / value head
+    ``h // (H / Hkv)`` (groups of consecutive heads, as LLaMA's ``repeat_kv``).  Output ``[N, T, H d]``.  ``Hkv == 1`` is multi-query
+    attention."""
+
+    def __init__(self, num_heads: int, causal: bool = False, scale: float = None, num_kv_heads: int = None):
         super().__init__()
         if num_heads < 1:
             raise ValueError(f"num_heads must be positive, got {num_heads}")
         self.num_heads, self.causal, self.scale = int(num_heads), bool(causal), scale
+        self.num_kv_heads = _kv_heads(num_heads, num_kv_heads)
 
     def head_dim(self, qkv: Tensor) -> int:
+        if self.num_kv_heads is not None:
+            return _gqa_head_dim(qkv, self.num_heads, self.num_kv_heads)
         if qkv.dim() != 3:
             raise ValueError(f"expected a packed projection [N, T, 3 E], got {qkv.dim()} dimensions")
         if qkv.shape[2] == 0 or qkv.shape[2] % (3 * self.num_heads) != 0:
@@ -140,6 +178,13 @@ class ScaledDotProductAttention(nn.Module):
     def forward(self, qkv: Tensor) -> Tensor:
         d = self.head_dim(qkv)
         N, T, H = qkv.shape[0], qkv.shape[1], self.num_heads
+        if self.num_kv_heads is not None:
+            Hkv = self.num_kv_heads
+            q, k, v = _gqa_split(qkv, H, Hkv, d)                          # q [N, Hkv, R, T, d]; k, v [N, Hkv, 1, T, d]: views
+            s = (q @ k.transpose(-1, -2)) * self.scale_for(d)             # (the matmul broadcasts k and v over the group)
+            if self.causal:
+                s = s.masked_fill(torch.ones(T, T, dtype=torch.bool, device=qkv.device).triu(1), float("-inf"))
+            return (s.softmax(-1) @ v).reshape(N, H, T, d).transpose(1, 2).reshape(N, T, H * d)
         q, k, v = qkv.view(N, T, 3, H, d).permute(2, 0, 3, 1, 4)          # each [N, H, T, d]
         s = (q @ k.transpose(-1, -2)) * self.scale_for(d)
         if self.causal:
@@ -154,16 +199,25 @@ class RotaryEmbedding(nn.Module):
 
     Half-split pairing ("rotate_half", as LLaMA / GPT-NeoX): in every head of the q and k thirds the pair ``(j, j + d / 2)`` at
     position ``t`` is rotated by the angle ``t * base^(-2 j / d)``, ``y1 = x1 cos - x2 sin``, ``y2 = x2 cos + x1 sin``; the v third
-    passes through.  Positions start at 0."""
+    passes through.  Positions start at 0.
 
-    def __init__(self, num_heads: int, base: float = 10000.0):
+    ``num_kv_heads`` (grouped-query attention, as :class:`ScaledDotProductAttention`): ``qkv [N, T, (H + 2 Hkv) d]``; the ``H`` query
+    heads and the ``Hkv`` key heads are rotated, the ``Hkv d`` columns of v pass through."""
+
+    def __init__(self, num_heads: int, base: float = 10000.0, num_kv_heads: int = None):
         super().__init__()
         if num_heads < 1:
             raise ValueError(f"num_heads must be positive, got {num_heads}")
         self.num_heads, self.base = int(num_heads), float(base)
+        self.num_kv_heads = _kv_heads(num_heads, num_kv_heads)
         self._tables = None   # (key, cos, sin): what forward() used is what the rule of the extensions uses
 
     def head_dim(self, qkv: Tensor) -> int:
+        if self.num_kv_heads is not None:
+            d = _gqa_head_dim(qkv, self.num_heads, self.num_kv_heads)
+            if d % 2 != 0:
+                raise ValueError(f"the head dimension ({d}) must be even: rotary embeddings rotate pairs of columns")
+            return d
         if qkv.dim() != 3:
             raise ValueError(f"expected a packed projection [N, T, 3 E], got {qkv.dim()} dimensions")
         if qkv.shape[2] == 0 or qkv.shape[2] % (3 * self.num_heads) != 0:
@@ -187,6 +241,13 @@ class RotaryEmbedding(nn.Module):
     def forward(self, qkv: Tensor) -> Tensor:
         d = self.head_dim(qkv)
         N, T, H, half = qkv.shape[0], qkv.shape[1], self.num_heads, d // 2
+        if self.num_kv_heads is not None:   # q | k is H + Hkv heads of d columns
+            rotated = H + self.num_kv_heads
+            cos, sin = (t.view(1, T, 1, half) for t in self.tables(T, d, qkv.device, qkv.dtype))
+            x = qkv[..., :rotated * d].view(N, T, rotated, d)
+            x1, x2 = x[..., :half], x[..., half:]
+            rot = torch.cat((x1 * cos - x2 * sin, x2 * cos + x1 * sin), -1).reshape(N, T, rotated * d)
+            return torch.cat((rot, qkv[..., rotated * d:]), -1)
         cos, sin = (t.view(1, T, 1, 1, half) for t in self.tables(T, d, qkv.device, qkv.dtype))
         x = qkv.view(N, T, 3, H, d)
         x1, x2 = x[:, :, :2, :, :half], x[:, :, :2, :, half:]
@@ -196,12 +257,15 @@ class RotaryEmbedding(nn.Module):
 
 class MultiheadSelfAttention(nn.Sequential):
     """``Linear(E, 3 E)`` -> :class:`ScaledDotProductAttention` -> ``Linear(E, E)``: ``nn.MultiheadAttention(batch_first=True)``
-    applied to ``(x, x, x)`` as a container of single-input leaves, which is what the extensions' rules are written for."""
+    applied to ``(x, x, x)`` as a container of single-input leaves, which is what the extensions' rules are written for.  With
+    ``num_kv_heads`` (grouped-query attention) the first projection is ``Linear(E, (H + 2 Hkv) d)``, ``d = E / H``."""
 
-    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True, causal: bool = False):
+    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True, causal: bool = False, num_kv_heads: int = None):
         if embed_dim % num_heads != 0:
             raise ValueError(f"embed_dim ({embed_dim}) is not divisible by num_heads ({num_heads})")
-        super().__init__(nn.Linear(embed_dim, 3 * embed_dim, bias=bias), ScaledDotProductAttention(num_heads, causal=causal),
+        Hkv = _kv_heads(num_heads, num_kv_heads)
+        packed = 3 * embed_dim if Hkv is None else (num_heads + 2 * Hkv) * (embed_dim // num_heads)
+        super().__init__(nn.Linear(embed_dim, packed, bias=bias), ScaledDotProductAttention(num_heads, causal=causal, num_kv_heads=Hkv),
                          nn.Linear(embed_dim, embed_dim, bias=bias))
 
     @classmethod

@@ -20,7 +20,7 @@ from torch import Tensor, nn
 from vivit_amd import _lib, kernels
 from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, Permute, ProductModule, RotaryEmbedding, ScaledDotProductAttention, ScaleModule,
                                               Slicing,
-                                              SumModule)
+                                              SumModule, _gqa_split)
 from vivit_amd.utils.ggn import Vmp
 from vivit_amd.utils.gram import mVp, pairwise_dot
 
@@ -601,7 +601,8 @@ def _attention_out(module, x: Tensor, subsampling) -> Tensor:
         with torch.no_grad():
             return module.forward(x)
     out = subsample(out.detach(), 0, subsampling)
-    want = (*x.shape[:2], x.shape[2] // 3)
+    Hkv = getattr(module, "num_kv_heads", None)   # the output has H d columns
+    want = (*x.shape[:2], x.shape[2] // 3 if Hkv is None else module.head_dim(x) * module.num_heads)
     if tuple(out.shape) != want or out.device != x.device or out.dtype != x.dtype:
         raise ValueError(f"ScaledDotProductAttention: module.output {tuple(out.shape)} {out.dtype} on {out.device} after sub-sampling "
                          f"does not belong to the input {tuple(x.shape)} {x.dtype} on {x.device} (expected {want})")
@@ -614,6 +615,8 @@ def _attention_jac_t_torch(module, M: Tensor, x: Tensor, out: Tensor) -> Tensor:
     d, H = module.head_dim(x), module.num_heads
     scale = module.scale_for(d)
     V, (N, T) = M.shape[0], x.shape[:2]
+    if getattr(module, "num_kv_heads", None) is not None:
+        return _attention_gqa_jac_t_torch(M, x, out, H, module.num_kv_heads, d, scale, module.causal)
     q, k, v = x.view(N, T, 3, H, d).permute(2, 0, 3, 1, 4)                       # each [N, H, T, d]
     S = (q @ k.transpose(-1, -2)) * scale
     if module.causal:
@@ -627,11 +630,40 @@ def _attention_jac_t_torch(module, M: Tensor, x: Tensor, out: Tensor) -> Tensor:
     return torch.stack((dQ, dK, dV), 0).permute(1, 2, 4, 0, 3, 5).reshape(V, N, T, 3 * H * d)
 
 
+def _attention_gqa_jac_t_torch(M: Tensor, x: Tensor, out: Tensor, H: int, Hkv: int, d: int, scale: float, causal: bool) -> Tensor:
+    """Grouped-query attention, the same rule: ``x [N, T, (H + 2 Hkv) d]``, ``M [V, N, T, H d]`` -> ``[V, N, T, (H + 2 Hkv) d]``.
+    Query head ``h`` uses key / value head ``h // R``; dK and dV of a group are the sums over its ``R = H / Hkv`` query heads.  K and
+    V are broadcast views over the group axis, never expanded copies.  No autograd."""
+    V, (N, T), R = M.shape[0], x.shape[:2], H // Hkv
+    q, k, v = _gqa_split(x, H, Hkv, d)                                             # q [N, Hkv, R, T, d]; k, v [N, Hkv, 1, T, d]
+    S = (q @ k.transpose(-1, -2)) * scale
+    if causal:
+        S = S.masked_fill(torch.ones(T, T, dtype=torch.bool, device=x.device).triu(1), float("-inf"))
+    P = S.softmax(-1)                                                             # [N, Hkv, R, T, T], shared by the V slices
+    dO = M.reshape(V, N, T, Hkv, R, d).permute(0, 1, 3, 4, 2, 5)                  # [V, N, Hkv, R, T, d]
+    D = (dO * out.view(N, T, Hkv, R, d).permute(0, 2, 3, 1, 4)).sum(-1, keepdim=True)
+    dS = P * (dO @ v.transpose(-1, -2) - D)
+    dQ = (dS @ k) * scale                                                         # [V, N, Hkv, R, T, d]
+    # the sum over the group's heads and over the queries is one contraction of length R T
+    dV = P.reshape(N, Hkv, R * T, T).transpose(-1, -2) @ dO.reshape(V, N, Hkv, R * T, d)
+    dK = (dS.reshape(V, N, Hkv, R * T, T).transpose(-1, -2) @ q.reshape(N, Hkv, R * T, d)) * scale
+    return torch.cat((dQ.permute(0, 1, 4, 2, 3, 5).reshape(V, N, T, H * d), dK.permute(0, 1, 3, 2, 4).reshape(V, N, T, Hkv * d),
+                      dV.permute(0, 1, 3, 2, 4).reshape(V, N, T, Hkv * d)), -1)
+
+
 def _rope_jac_t_torch(module, M: Tensor, x: Tensor) -> Tensor:
     """The rule of ``vivit_rope_jac_t_f32`` in plain torch (non-HIP or non-fp32 tensors): the transposed rotation on the q and k
     thirds of ``M [V, N, T, 3 E]`` with the tables of the forward pass, the v third as it is.  No autograd."""
     d, H = module.head_dim(x), module.num_heads
     V, (N, T), half = M.shape[0], x.shape[:2], d // 2
+    if getattr(module, "num_kv_heads", None) is not None:   # q | k is H + Hkv heads of d columns, then Hkv d columns of v
+        rotated = H + module.num_kv_heads
+        cos, sin = (t.view(1, 1, T, 1, half) for t in module.tables(T, d, x.device, x.dtype))
+        m = M.reshape(V, N, T, -1)
+        mr = m[..., :rotated * d].reshape(V, N, T, rotated, d)
+        m1, m2 = mr[..., :half], mr[..., half:]
+        rot = torch.cat((m1 * cos + m2 * sin, m2 * cos - m1 * sin), -1).reshape(V, N, T, rotated * d)
+        return torch.cat((rot, m[..., rotated * d:]), -1)
     cos, sin = (t.view(1, 1, T, 1, 1, half) for t in module.tables(T, d, x.device, x.dtype))
     m = M.reshape(V, N, T, 3, H, d)
     m1, m2 = m[:, :, :, :2, :, :half], m[:, :, :, :2, :, half:]
@@ -737,7 +769,8 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
         return _rms_norm_rules(module, M, x, True)[0]
     if isinstance(module, RotaryEmbedding):   # the very tables the forward pass used (cached on the module)
         d = module.head_dim(x)
-        return kernels.rope_jac_t(M.reshape(M.shape[0], *x.shape), *module.tables(x.shape[1], d, x.device, x.dtype), module.num_heads)
+        return kernels.rope_jac_t(M.reshape(M.shape[0], *x.shape), *module.tables(x.shape[1], d, x.device, x.dtype), module.num_heads,
+                                  num_kv_heads=module.num_kv_heads)
     if isinstance(module, ScaledDotProductAttention):
         # (a head dimension above the kernel's 128 has no kernel: the generic rule, before any operand is prepared; sizes beyond
         # the kernel's index arithmetic come back as VIVIT_E_UNSUPPORTED and the caller falls through likewise)
@@ -745,7 +778,7 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
         if d > 128:
             return None
         return kernels.attention_jac_t(M.reshape(M.shape[0], *x.shape[:2], -1), x, _attention_out(module, x, subsampling), module.num_heads,
-                                       module.scale_for(d), module.causal)
+                                       module.scale_for(d), module.causal, num_kv_heads=module.num_kv_heads)
     if isinstance(module, _BATCHNORM) and x.dim() >= 2:
         if _own_params(module):   # the parameter rules want the two row sums of the same pass
             return _bn_eval_rules(module, M, x)[0]

@@ -1,20 +1,28 @@
 // Scaled dot-product self-attention: the transposed input Jacobian applied to the sqrt-GGN factor (f1).  The module input is the
-// packed projection qkv [N, T, 3 E] (q | k | v, head h in columns h d .. (h + 1) d of each third, E = H d), its output O [N, T, E].
-// Per factor row v, sample n and head h, with dO = M[v, n, :, h]:
-//   S = scale Q K^T (+ causal mask),  P = softmax_rows(S),  D_i = sum_c dO_ic O_ic,
-//   dV = P^T dO,  dP = dO V^T,  dS = P o (dP - D),  dQ = scale dS K,  dK = scale dS^T Q,      G[v, n] = dQ | dK | dV (packed).
+// packed projection qkv [N, T, (H + 2 Hkv) d] (q | k | v: H query heads of d columns, then Hkv key heads, then Hkv value heads),
+// its output O [N, T, E], E = H d.  Query head h attends to key / value head g = h / R, R = H / Hkv consecutive query heads per
+// group (grouped-query attention; Hkv == H is multi-head attention with three equal thirds, Hkv == 1 multi-query attention).
+// Per factor row v, sample n and query head h of group g, with dO = M[v, n, :, h]:
+//   S = scale Q_h K_g^T (+ causal mask),  P = softmax_rows(S),  D_i = sum_c dO_ic O_ic,
+//   dP = dO V_g^T,  dS = P o (dP - D),  dQ_h = scale dS K_g,
+//   dV_g = sum_{h in g} P_h^T dO_h,  dK_g = scale sum_{h in g} dS_h^T Q_h,                     G[v, n] = dQ | dK | dV (packed).
 // No T x T data leaves the chip.  Four launches:
 //   attn_lse_kernel    lse[n, h, i] = log sum_j exp(S_ij), online over key blocks with the running row maximum subtracted
 //   attn_rowdot_kernel D[v, n, h, i]
-//   attn_dkv_kernel    the KEY-block owner: K and V of its 32 keys stay in LDS, it walks the query blocks in ascending order and
-//                      accumulates dK and dV in registers
-//   attn_dq_kernel     the QUERY-block owner: Q and dO of its 32 queries stay in LDS, it walks the key blocks and accumulates dQ
-// A workgroup (256 threads, four waves) owns one block of one (n, h) for VC factor rows at a time: the tile P = exp(S - lse) of a
-// (query block, key block) pair is recomputed ONCE per workgroup and multiplies the dO of all VC rows; the accumulators of the VC
-// rows live in registers, which is what limits VC.  All products run on v_mfma_f32_16x16x4_f32 from LDS tiles whose
-// edges (rows beyond T, columns beyond d) are zero.  No atomics; every output element is the sum over the blocks in ascending order
-// of per-block sums over k in ascending order (the S and dP tiles: two interleaved chains, even and odd steps of four, added at
-// the end), so the bytes of G[v, n] depend on (T, H, d, scale, causal) and the data of (v, n) only.
+//   attn_dkv_kernel    the KEY-block owner of one (n, kv head g): K and V of its 32 keys stay in LDS, it walks the query heads
+//                      h = g R .. g R + R - 1 in ascending order and, inside each head, the query blocks in ascending order (Q, lse,
+//                      dO and D of that head are reloaded), and accumulates dK and dV of the group in the same registers
+//   attn_dq_kernel     the QUERY-block owner of one (n, h): Q and dO of its 32 queries stay in LDS, it walks the key blocks of
+//                      head h / R and accumulates dQ
+// A workgroup (256 threads, four waves) owns one block of one (n, h) -- of one (n, g) for dK and dV -- for VC factor rows at a
+// time: the tile P = exp(S - lse) of a (query block, key block) pair is recomputed ONCE per workgroup and multiplies the dO of all
+// VC rows; the accumulators of the VC rows live in registers, which is what limits VC.  All products run on
+// v_mfma_f32_16x16x4_f32 from LDS tiles whose edges (rows beyond T, columns beyond d) are zero.  No atomics and no second pass.
+// SUMMATION ORDER of an output element: head, then block, then k within the block -- for dK and dV the query heads of the group in
+// ascending order, inside a head the query blocks in ascending order, inside a block k in ascending order; for dQ (one head) the
+// key blocks in ascending order (the S and dP tiles: two interleaved chains, even and odd steps of four, added at the end).  So
+// the bytes of G[v, n] depend on (T, H, Hkv, d, scale, causal) and the data of (v, n) only.  With Hkv == H the walk over heads has
+// one step: the order, and the bytes, of multi-head attention.
 #include <math.h>
 
 #include "common.h"
@@ -103,6 +111,8 @@ __device__ __forceinline__ att_f32x4 att_acc_nn(const float *__restrict__ A, con
 
 struct AttGeom {
   int N, T, H, d, KB;        // KB = blocks of 32 along T
+  int Hkv, R;                // key / value heads, query heads per group (H = R Hkv)
+  int pitch, koff, voff;     // of a row of qkv and G: (H + 2 Hkv) d columns, k from column H d, v from column (H + Hkv) d
   int causal, vec;
   float scale;
 };
@@ -121,9 +131,10 @@ __global__ __launch_bounds__(256) void attn_lse_kernel(const float *__restrict__
   const int64_t nh = blockIdx.x / g.KB;
   const int ib = (int)(blockIdx.x - nh * g.KB), i0 = ib * ATT_B;
   const int64_t n = nh / g.H;
-  const int h = (int)(nh - n * g.H), E = g.H * g.d, dk = (g.d + 3) & ~3;
-  const float *base = qkv + n * g.T * 3 * (int64_t)E + (int64_t)h * g.d;
-  att_load_block<NT>(sQ, base, 3 * (int64_t)E, i0, g.T, g.d, g.vec);
+  const int h = (int)(nh - n * g.H), dk = (g.d + 3) & ~3;
+  const int64_t pitch = g.pitch;
+  const float *base = qkv + n * g.T * pitch, *kbase = base + g.koff + (int64_t)(h / g.R) * g.d;
+  att_load_block<NT>(sQ, base + (int64_t)h * g.d, pitch, i0, g.T, g.d, g.vec);
   const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
   const int row = tid >> 3, sub = tid & 7;
   float m = -INFINITY, l = 0.f;
@@ -131,7 +142,7 @@ __global__ __launch_bounds__(256) void attn_lse_kernel(const float *__restrict__
   for (int jb = 0; jb <= jb_end; ++jb) {
     const int j0 = jb * ATT_B;
     __syncthreads();   // the previous block's reads of sK and sS are done
-    att_load_block<NT>(sK, base + E, 3 * (int64_t)E, j0, g.T, g.d, g.vec);
+    att_load_block<NT>(sK, kbase, pitch, j0, g.T, g.d, g.vec);
     __syncthreads();
     const att_f32x4 s = att_tile_nt<NT>(sQ + 16 * ri * C::LD, sK + 16 * cj * C::LD, dk, lane);
 #pragma unroll
@@ -216,26 +227,30 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__
   float *sK = att_smem, *sV = sK + C::BLK, *sQ = sV + C::BLK, *sdO = sQ + C::BLK;
   float *sP = sdO + C::VC * C::BLK, *sdS = sP + C::TILE, *sL = sdS + C::VC * C::TILE, *sD = sL + ATT_B;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t nh = blockIdx.x / g.KB;
-  const int jb = (int)(blockIdx.x - nh * g.KB), j0 = jb * ATT_B;
-  const int64_t n = nh / g.H;
-  const int h = (int)(nh - n * g.H), dk = (g.d + 3) & ~3;
-  const int64_t E = (int64_t)g.H * g.d;
+  const int64_t ng = blockIdx.x / g.KB;
+  const int jb = (int)(blockIdx.x - ng * g.KB), j0 = jb * ATT_B;
+  const int64_t n = ng / g.Hkv;
+  const int kv = (int)(ng - n * g.Hkv), dk = (g.d + 3) & ~3;
+  const int64_t pitch = g.pitch;
   const int64_t v0 = (int64_t)blockIdx.y * C::VC;
   const int nv = V - v0 < C::VC ? (int)(V - v0) : C::VC;
-  const float *base = qkv + n * g.T * 3 * E + (int64_t)h * g.d;
-  att_load_block<NT>(sK, base + E, 3 * E, j0, g.T, g.d, g.vec);
-  att_load_block<NT>(sV, base + 2 * E, 3 * E, j0, g.T, g.d, g.vec);
+  const float *base = qkv + n * g.T * pitch;
+  att_load_block<NT>(sK, base + g.koff + (int64_t)kv * g.d, pitch, j0, g.T, g.d, g.vec);
+  att_load_block<NT>(sV, base + g.voff + (int64_t)kv * g.d, pitch, j0, g.T, g.d, g.vec);
   const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
   att_f32x4 accK[C::VC][C::TPW], accV[C::VC][C::TPW];
 #pragma unroll
   for (int vi = 0; vi < C::VC; ++vi)
 #pragma unroll
     for (int u = 0; u < C::TPW; ++u) accK[vi][u] = accV[vi][u] = (att_f32x4){0.f, 0.f, 0.f, 0.f};
-  for (int ib = g.causal ? jb : 0; ib < g.KB; ++ib) {
-    const int i0 = ib * ATT_B;
+  // the group's query heads in ascending order, the query blocks of each in ascending order: one chain of sums per output element
+  const int ib0 = g.causal ? jb : 0, per_head = g.KB - ib0;   // (causal: the queries before the key block see none of its keys)
+  for (int step = 0; step < g.R * per_head; ++step) {
+    const int hr = step / per_head, ib = ib0 + step - hr * per_head;
+    const int h = kv * g.R + hr, i0 = ib * ATT_B;
+    const int64_t nh = n * g.H + h;
     __syncthreads();   // the previous query block's tiles and operands have been read
-    att_load_block<NT>(sQ, base, 3 * E, i0, g.T, g.d, g.vec);
+    att_load_block<NT>(sQ, base + (int64_t)h * g.d, pitch, i0, g.T, g.d, g.vec);
     if (tid < ATT_B) sL[tid] = i0 + tid < g.T ? lse[nh * g.T + i0 + tid] : 0.f;
     att_load_factor<NT>(sdO, sD, M, Dws, g, v0, nv, n, h, i0);
     __syncthreads();
@@ -273,13 +288,14 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__
 #pragma unroll
       for (int vi = 0; vi < C::VC; ++vi)
         if (vi < nv) {
-          float *gk = G + ((v0 + vi) * g.N + n) * g.T * 3 * E + E + (int64_t)h * g.d + c;
+          float *gk = G + ((v0 + vi) * g.N + n) * g.T * pitch + g.koff + (int64_t)kv * g.d + c;
+          const int kv_to_v = g.voff - g.koff;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int r = j0 + 16 * rt + 4 * kq + e;
             if (r < g.T) {
-              gk[(int64_t)r * 3 * E] = g.scale * accK[vi][u][e];
-              gk[(int64_t)r * 3 * E + E] = accV[vi][u][e];
+              gk[(int64_t)r * pitch] = g.scale * accK[vi][u][e];
+              gk[(int64_t)r * pitch + kv_to_v] = accV[vi][u][e];
             }
           }
         }
@@ -301,11 +317,11 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ 
   const int ib = (int)(blockIdx.x - nh * g.KB), i0 = ib * ATT_B;
   const int64_t n = nh / g.H;
   const int h = (int)(nh - n * g.H), dk = (g.d + 3) & ~3;
-  const int64_t E = (int64_t)g.H * g.d;
+  const int64_t pitch = g.pitch;
   const int64_t v0 = (int64_t)blockIdx.y * C::VC;
   const int nv = V - v0 < C::VC ? (int)(V - v0) : C::VC;
-  const float *base = qkv + n * g.T * 3 * E + (int64_t)h * g.d;
-  att_load_block<NT>(sQ, base, 3 * E, i0, g.T, g.d, g.vec);
+  const float *base = qkv + n * g.T * pitch, *kbase = base + g.koff + (int64_t)(h / g.R) * g.d;
+  att_load_block<NT>(sQ, base + (int64_t)h * g.d, pitch, i0, g.T, g.d, g.vec);
   if (tid < ATT_B) sL[tid] = i0 + tid < g.T ? lse[nh * g.T + i0 + tid] : 0.f;
   att_load_factor<NT>(sdO, sD, M, Dws, g, v0, nv, n, h, i0);
   const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
@@ -318,8 +334,8 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ 
   for (int jb = 0; jb <= jb_end; ++jb) {
     const int j0 = jb * ATT_B;
     __syncthreads();   // the previous key block's tiles and operands have been read
-    att_load_block<NT>(sK, base + E, 3 * E, j0, g.T, g.d, g.vec);
-    att_load_block<NT>(sV, base + 2 * E, 3 * E, j0, g.T, g.d, g.vec);
+    att_load_block<NT>(sK, kbase, pitch, j0, g.T, g.d, g.vec);
+    att_load_block<NT>(sV, kbase + (g.voff - g.koff), pitch, j0, g.T, g.d, g.vec);
     __syncthreads();
     const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g, i0, j0, dk, lane, ri, cj);
 #pragma unroll
@@ -350,11 +366,11 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ 
 #pragma unroll
       for (int vi = 0; vi < C::VC; ++vi)
         if (vi < nv) {
-          float *gq = G + ((v0 + vi) * g.N + n) * g.T * 3 * E + (int64_t)h * g.d + c;
+          float *gq = G + ((v0 + vi) * g.N + n) * g.T * pitch + (int64_t)h * g.d + c;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int r = i0 + 16 * rt + 4 * kq + e;
-            if (r < g.T) gq[(int64_t)r * 3 * E] = g.scale * accQ[vi][u][e];
+            if (r < g.T) gq[(int64_t)r * pitch] = g.scale * accQ[vi][u][e];
           }
         }
     }
@@ -368,15 +384,18 @@ struct AttPlan {
   int64_t KB;
 };
 
-static AttPlan attention_plan(int64_t V, int64_t N, int64_t T, int64_t H, int64_t d) {
+static AttPlan attention_plan(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d) {
   AttPlan p{VIVIT_OK, 0, 0, 0};
-  if (V <= 0 || N <= 0 || T <= 0 || H <= 0 || d <= 0) return p.status = VIVIT_E_BADARG, p;
+  if (V <= 0 || N <= 0 || T <= 0 || H <= 0 || Hkv <= 0 || d <= 0 || H % Hkv != 0) return p.status = VIVIT_E_BADARG, p;
   if (d > ATT_D_MAX) return p.status = VIVIT_E_UNSUPPORTED, p;
-  // 32-bit quantities of the kernels: T + 32, 3 H d, the block index N H KB, the row-dot grid; 64-bit: every element offset
+  // 32-bit quantities of the kernels: T + 32, the row pitch (H + 2 Hkv) d, the block indices N H KB (lse, dQ) and N Hkv KB (dK and
+  // dV; Hkv <= H), the owner's R KB steps (R <= H), the row-dot grid; 64-bit: every element offset
   const int64_t lim = 0x7fffffffLL;
   const int64_t VC = d > 32 ? 2 : 4;
   p.KB = cdiv(T, ATT_B);
-  if (T > lim - ATT_B || H > lim / (3 * d) || N > lim / H || N * H > lim / p.KB || cdiv(V, VC) > 65535) return p.status = VIVIT_E_UNSUPPORTED, p;
+  if (T > lim - ATT_B || H + 2 * Hkv > lim / d || N > lim / H || N * H > lim / p.KB || N * Hkv > lim / p.KB || H > lim / p.KB ||
+      cdiv(V, VC) > 65535)
+    return p.status = VIVIT_E_UNSUPPORTED, p;
   const int64_t per_v = N * H * T;   // (< 2^62: three factors below 2^31 ... checked next with d and V)
   if (per_v > (int64_t)1 << 40 || V > ((int64_t)1 << 58) / (per_v * 3 * d) || cdiv(V * per_v, 256) > lim) return p.status = VIVIT_E_UNSUPPORTED, p;
   p.lse_bytes = align_up((size_t)per_v * 4, 256);
@@ -399,12 +418,12 @@ static int attention_launch(const float *M, const float *qkv, const float *out, 
     attr_done |= 1ull << (dev & 63);
   }
   const int64_t NH = (int64_t)g.N * g.H, total = V * NH * g.T;
-  const unsigned blocks = (unsigned)(NH * g.KB);
+  const unsigned blocks = (unsigned)(NH * g.KB), kv_blocks = (unsigned)((int64_t)g.N * g.Hkv * g.KB);
   attn_lse_kernel<NT><<<blocks, 256, lse_lds, s>>>(qkv, lse, g);
   attn_rowdot_kernel<<<(unsigned)cdiv(total, 256), 256, 0, s>>>(M, out, Dws, total, g);
-  const dim3 grid(blocks, (unsigned)cdiv(V, C::VC));
-  attn_dkv_kernel<NT><<<grid, 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g);
-  attn_dq_kernel<NT><<<grid, 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g);
+  const unsigned chunks = (unsigned)cdiv(V, C::VC);
+  attn_dkv_kernel<NT><<<dim3(kv_blocks, chunks), 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g);
+  attn_dq_kernel<NT><<<dim3(blocks, chunks), 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g);
   return launch_status();
 }
 
@@ -416,19 +435,22 @@ using namespace vivit;
 
 extern "C" {
 
-size_t vivit_attention_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t d) {
-  const AttPlan p = attention_plan(V, N, T, H, d);
+size_t vivit_attention_gqa_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d) {
+  const AttPlan p = attention_plan(V, N, T, H, Hkv, d);
   return p.status == VIVIT_OK ? p.bytes : 0;
 }
 
-int vivit_attention_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T, int64_t H,
-                              int64_t d, float scale, int causal, void *workspace, size_t workspace_bytes, void *stream) {
+int vivit_attention_gqa_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
+                                  int64_t H, int64_t Hkv, int64_t d, float scale, int causal, void *workspace, size_t workspace_bytes,
+                                  void *stream) {
   if (!M || !qkv || !out || !G) return VIVIT_E_BADARG;
-  const AttPlan p = attention_plan(V, N, T, H, d);
+  const AttPlan p = attention_plan(V, N, T, H, Hkv, d);
   if (p.status != VIVIT_OK) return p.status;
   if (!workspace || workspace_bytes < p.bytes) return VIVIT_E_WORKSPACE;
   AttGeom g;
   g.N = (int)N, g.T = (int)T, g.H = (int)H, g.d = (int)d, g.KB = (int)p.KB;
+  g.Hkv = (int)Hkv, g.R = (int)(H / Hkv);
+  g.pitch = (int)((H + 2 * Hkv) * d), g.koff = (int)(H * d), g.voff = (int)((H + Hkv) * d);
   g.causal = causal != 0;
   g.vec = (d & 3) == 0 && att_aligned16(M) && att_aligned16(qkv);
   g.scale = scale;
@@ -439,6 +461,16 @@ int vivit_attention_jac_t_f32(const float *M, const float *qkv, const float *out
   if (d <= 32) return attention_launch<2>(M, qkv, out, G, lse, Dws, V, g, s);
   if (d <= 64) return attention_launch<4>(M, qkv, out, G, lse, Dws, V, g, s);
   return attention_launch<8>(M, qkv, out, G, lse, Dws, V, g, s);
+}
+
+// multi-head attention: every query head has its own key and value head
+size_t vivit_attention_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t d) {
+  return vivit_attention_gqa_jac_t_f32_workspace_bytes(V, N, T, H, H, d);
+}
+
+int vivit_attention_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T, int64_t H,
+                              int64_t d, float scale, int causal, void *workspace, size_t workspace_bytes, void *stream) {
+  return vivit_attention_gqa_jac_t_f32(M, qkv, out, G, V, N, T, H, H, d, scale, causal, workspace, workspace_bytes, stream);
 }
 
 } // extern "C"

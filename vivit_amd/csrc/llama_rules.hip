@@ -244,16 +244,17 @@ __global__ __launch_bounds__(256) void gate_jac_t_kernel(const float *__restrict
 }
 
 // ---- rotary -----------------------------------------------------------------------------------------------------------------------
-// A ROW here is one (r, t): 3 H d floats.  Its work items: 2 H hp pair items (q and k thirds; hp = d / 2 pairs per head, a quarter
-// of that in the 16-byte body) and then the copy items of the v third.  A workgroup takes rpb = max(1, 256 / items) rows per trip.
+// A ROW here is one (r, t): (H + 2 Hkv) d floats, H query heads | Hkv key heads | Hkv value heads (Hkv == H: three equal thirds).
+// Its work items: (H + Hkv) hp pair items (the q and k parts; hp = d / 2 pairs per head, a quarter of that in the 16-byte body) and
+// then the copy items of the v part, Hkv d columns.  A workgroup takes rpb = max(1, 256 / items) rows per trip.
 // Every item reads its operands before it writes, and no two items touch the same element: G may alias M (not __restrict__).
 template <bool VEC>
 __global__ __launch_bounds__(256) void rope_jac_t_kernel(const float *M, const float *__restrict__ cosT, const float *__restrict__ sinT,
-                                                         float *G, int64_t rows, int T, int H, int d, int rpb) {
+                                                         float *G, int64_t rows, int T, int H, int Hkv, int d, int rpb) {
   constexpr int W = VEC ? 4 : 1;
-  const int half = d >> 1, hp = half / W, pair_items = 2 * H * hp, copy_items = M == G ? 0 : H * d / W;
+  const int half = d >> 1, hp = half / W, pair_items = (H + Hkv) * hp, copy_items = M == G ? 0 : Hkv * d / W;
   const int items = pair_items + copy_items;
-  const int64_t row_len = 3 * (int64_t)H * d;
+  const int64_t row_len = ((int64_t)H + 2 * Hkv) * d;
   for (int64_t row0 = (int64_t)blockIdx.x * rpb; row0 < rows; row0 += (int64_t)gridDim.x * rpb) {
     for (int it = threadIdx.x; it < rpb * items; it += 256) {
       const int lr = it / items, wi = it - lr * items;
@@ -262,7 +263,7 @@ __global__ __launch_bounds__(256) void rope_jac_t_kernel(const float *M, const f
       const float *m = M + row * row_len;
       float *g = G + row * row_len;
       if (wi < pair_items) {
-        const int hh = wi / hp, j = (wi - hh * hp) * W;   // hh: (third, head) of the q | k part, which is 2 H heads of d columns
+        const int hh = wi / hp, j = (wi - hh * hp) * W;   // hh: head of the q | k part, which is H + Hkv heads of d columns
         const int t = (int)(row % T);
         const int64_t at = (int64_t)hh * d + j, tab = (int64_t)t * half + j;
         if (VEC) {
@@ -278,7 +279,7 @@ __global__ __launch_bounds__(256) void rope_jac_t_kernel(const float *M, const f
           g[at + half] = fmaf(-m1, s, m2 * c);
         }
       } else {
-        const int64_t at = 2 * (int64_t)H * d + (int64_t)(wi - pair_items) * W;
+        const int64_t at = ((int64_t)H + Hkv) * d + (int64_t)(wi - pair_items) * W;
         if (VEC) *reinterpret_cast<float4 *>(g + at) = *reinterpret_cast<const float4 *>(m + at);
         else g[at] = m[at];
       }
@@ -364,23 +365,35 @@ int vivit_gate_jac_t_f32(const float *M, const float *a, const float *b, float *
   return launch_status();
 }
 
-int vivit_rope_jac_t_f32(const float *M, const float *cosT, const float *sinT, float *G, int64_t R, int64_t T, int64_t H, int64_t d,
-                         void *stream) {
+// the rotary rule on H + Hkv rotated heads and Hkv d copied columns (H = 0 = Hkv: nothing to do)
+static int rope_jac_t(const float *M, const float *cosT, const float *sinT, float *G, int64_t R, int64_t T, int64_t H, int64_t Hkv,
+                      int64_t d, void *stream) {
   if (R < 0 || T < 0 || H < 0 || d < 0 || (d & 1)) return VIVIT_E_BADARG;
   if (R == 0 || T == 0 || H == 0 || d == 0) return VIVIT_OK;
   if (!M || !cosT || !sinT || !G) return VIVIT_E_BADARG;
-  if (R > I32_MAX || T > I32_MAX || H > I32_MAX || d > I32_MAX || R * T > I32_MAX || H * d > I32_MAX / 3 || T * d > I32_MAX)
+  if (R > I32_MAX || T > I32_MAX || H > I32_MAX || d > I32_MAX || R * T > I32_MAX || H + 2 * Hkv > I32_MAX / d || T * d > I32_MAX)
     return VIVIT_E_UNSUPPORTED;
   const int64_t rows = R * T, half = d >> 1;
   const bool vec = (half & 3) == 0 && aligned16(M) && aligned16(G) && aligned16(cosT) && aligned16(sinT);
-  const int64_t items = (2 * H * half + (M == G ? 0 : H * d)) / (vec ? 4 : 1);
+  const int64_t items = ((H + Hkv) * half + (M == G ? 0 : Hkv * d)) / (vec ? 4 : 1);
   const int rpb = items >= 256 ? 1 : (int)(256 / items);
   const int64_t blocks = cdiv(rows, rpb);
   const unsigned grid = (unsigned)(blocks > MAX_STRIDE_BLOCKS ? MAX_STRIDE_BLOCKS : blocks);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (vec) rope_jac_t_kernel<true><<<grid, 256, 0, s>>>(M, cosT, sinT, G, rows, (int)T, (int)H, (int)d, rpb);
-  else rope_jac_t_kernel<false><<<grid, 256, 0, s>>>(M, cosT, sinT, G, rows, (int)T, (int)H, (int)d, rpb);
+  if (vec) rope_jac_t_kernel<true><<<grid, 256, 0, s>>>(M, cosT, sinT, G, rows, (int)T, (int)H, (int)Hkv, (int)d, rpb);
+  else rope_jac_t_kernel<false><<<grid, 256, 0, s>>>(M, cosT, sinT, G, rows, (int)T, (int)H, (int)Hkv, (int)d, rpb);
   return launch_status();
+}
+
+int vivit_rope_jac_t_f32(const float *M, const float *cosT, const float *sinT, float *G, int64_t R, int64_t T, int64_t H, int64_t d,
+                         void *stream) {
+  return rope_jac_t(M, cosT, sinT, G, R, T, H, H, d, stream);
+}
+
+int vivit_rope_gqa_jac_t_f32(const float *M, const float *cosT, const float *sinT, float *G, int64_t R, int64_t T, int64_t H, int64_t Hkv,
+                             int64_t d, void *stream) {
+  if (Hkv <= 0 || H < 0 || H % Hkv != 0) return VIVIT_E_BADARG;
+  return rope_jac_t(M, cosT, sinT, G, R, T, H, Hkv, d, stream);
 }
 
 } // extern "C"

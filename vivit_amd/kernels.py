@@ -645,17 +645,26 @@ def gate_jac_t(M, a, b, want=(True, True), out_a=None, out_b=None):
 
 
 @_launcher
-def rope_jac_t(M, cos, sin, num_heads: int, out=None):
+def rope_jac_t(M, cos, sin, num_heads: int, out=None, num_kv_heads: int = None):
     """Transposed Jacobian of the rotary position embedding on a packed projection (``vivit_rope_jac_t_f32``): ``M [..., T, 3 E]``
     (``E = num_heads * d``), ``cos`` / ``sin [T, d / 2]`` -> like ``M``: the q and k thirds rotated back, the v third copied.
-    ``out``: a buffer for the result; ``M`` itself for the rule in place."""
+    ``out``: a buffer for the result; ``M`` itself for the rule in place.  ``num_kv_heads`` (grouped-query attention,
+    ``vivit_rope_gqa_jac_t_f32``): ``M [..., T, (num_heads + 2 * num_kv_heads) * d]``, the ``num_heads + num_kv_heads`` heads of
+    the q and k parts rotated back, the v part copied."""
     _require_device(M, cos, sin)
     if out is M and not M.is_contiguous():
         raise ValueError("the rule in place needs a contiguous M")
     M, cos, sin = M.contiguous(), cos.contiguous(), sin.contiguous()
-    if M.dim() < 2 or num_heads < 1 or M.shape[-1] == 0 or M.shape[-1] % (6 * num_heads) != 0:
-        raise ValueError(f"M must be [..., T, 3 * {num_heads} heads * an even head dimension], got {tuple(M.shape)}")
-    T, d = M.shape[-2], M.shape[-1] // (3 * num_heads)
+    if num_kv_heads is None:
+        if M.dim() < 2 or num_heads < 1 or M.shape[-1] == 0 or M.shape[-1] % (6 * num_heads) != 0:
+            raise ValueError(f"M must be [..., T, 3 * {num_heads} heads * an even head dimension], got {tuple(M.shape)}")
+        heads = 3 * num_heads
+    else:
+        _check_kv_heads(num_heads, num_kv_heads)
+        heads = num_heads + 2 * num_kv_heads
+        if M.dim() < 2 or M.shape[-1] == 0 or M.shape[-1] % (2 * heads) != 0:
+            raise ValueError(f"M must be [..., T, ({num_heads} + 2 * {num_kv_heads}) heads * an even head dimension], got {tuple(M.shape)}")
+    T, d = M.shape[-2], M.shape[-1] // heads
     if tuple(cos.shape) != (T, d // 2) or tuple(sin.shape) != (T, d // 2):
         raise ValueError(f"cos and sin must be {(T, d // 2)}, got {tuple(cos.shape)} and {tuple(sin.shape)}")
     if M.numel() == 0:
@@ -665,23 +674,44 @@ def rope_jac_t(M, cos, sin, num_heads: int, out=None):
         lo, hi = G.data_ptr(), G.data_ptr() + 4 * G.numel()
         if M.data_ptr() < hi and lo < M.data_ptr() + 4 * M.numel() and G.data_ptr() != M.data_ptr():
             raise ValueError("out must be M itself or must not overlap it")
-    st = _lib.load().vivit_rope_jac_t_f32(M.data_ptr(), cos.data_ptr(), sin.data_ptr(), G.data_ptr(), M.numel() // (T * M.shape[-1]), T,
-                                         num_heads, d, _stream(M))
-    _lib.check(st, "vivit_rope_jac_t_f32")
+    rows = M.numel() // (T * M.shape[-1])
+    if num_kv_heads is None:
+        st = _lib.load().vivit_rope_jac_t_f32(M.data_ptr(), cos.data_ptr(), sin.data_ptr(), G.data_ptr(), rows, T, num_heads, d, _stream(M))
+        _lib.check(st, "vivit_rope_jac_t_f32")
+    else:
+        st = _lib.load().vivit_rope_gqa_jac_t_f32(M.data_ptr(), cos.data_ptr(), sin.data_ptr(), G.data_ptr(), rows, T, num_heads,
+                                                 num_kv_heads, d, _stream(M))
+        _lib.check(st, "vivit_rope_gqa_jac_t_f32")
     return G
 
 
+def _check_kv_heads(num_heads, num_kv_heads):
+    """Grouped-query attention: ``num_heads`` query heads in ``num_kv_heads`` groups of consecutive heads."""
+    if num_heads < 1 or num_kv_heads < 1 or num_heads % num_kv_heads != 0:
+        raise ValueError(f"num_heads H = {num_heads} must be a positive multiple of num_kv_heads Hkv = {num_kv_heads} >= 1")
+
+
 @_launcher
-def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool):
+def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None):
     """Transposed input Jacobian of scaled dot-product self-attention (``vivit_attention_jac_t_f32``): ``M [V, N, T, E]`` (the factor
     at the module output), ``qkv [N, T, 3 E]`` (the module input, q | k | v), ``out [N, T, E]`` (the module output of the forward
-    pass) -> ``[V, N, T, 3 E]``.  ``E = num_heads * d``; no ``T x T`` tensor is allocated."""
+    pass) -> ``[V, N, T, 3 E]``.  ``E = num_heads * d``; no ``T x T`` tensor is allocated.  ``num_kv_heads`` (grouped-query
+    attention, ``vivit_attention_gqa_jac_t_f32``): ``qkv [N, T, (num_heads + 2 * num_kv_heads) * d]``, query head ``h`` attends
+    to key / value head ``h // (num_heads // num_kv_heads)``; the result is packed ``dQ | dK | dV`` like ``qkv``."""
     _require_device(M, qkv, out)
     M, qkv, out = M.contiguous(), qkv.contiguous(), out.contiguous()
-    if qkv.dim() != 3 or num_heads < 1 or qkv.shape[2] == 0 or qkv.shape[2] % (3 * num_heads) != 0:
-        raise ValueError(f"qkv must be [N, T, 3 * {num_heads} * d], got {tuple(qkv.shape)}")
-    N, T, E3 = qkv.shape
-    E = E3 // 3
+    if num_kv_heads is None:
+        if qkv.dim() != 3 or num_heads < 1 or qkv.shape[2] == 0 or qkv.shape[2] % (3 * num_heads) != 0:
+            raise ValueError(f"qkv must be [N, T, 3 * {num_heads} * d], got {tuple(qkv.shape)}")
+        N, T, E3 = qkv.shape
+        E = E3 // 3
+    else:
+        _check_kv_heads(num_heads, num_kv_heads)
+        heads = num_heads + 2 * num_kv_heads
+        if qkv.dim() != 3 or qkv.shape[2] == 0 or qkv.shape[2] % heads != 0:
+            raise ValueError(f"qkv must be [N, T, ({num_heads} + 2 * {num_kv_heads}) * d], got {tuple(qkv.shape)}")
+        N, T, E3 = qkv.shape
+        E = E3 // heads * num_heads
     if tuple(out.shape) != (N, T, E):
         raise ValueError(f"out must be {(N, T, E)}, got {tuple(out.shape)}")
     if M.dim() != 4 or tuple(M.shape[1:]) != (N, T, E):
@@ -691,10 +721,16 @@ def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool):
         raise ValueError(f"empty operands: M {tuple(M.shape)}")
     G = torch.empty((Vd, N, T, E3), dtype=torch.float32, device=M.device)
     lib = _lib.load()
-    ws, ws_bytes = _workspace(lib.vivit_attention_jac_t_f32_workspace_bytes(Vd, N, T, num_heads, d), M)
-    st = lib.vivit_attention_jac_t_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), G.data_ptr(), Vd, N, T, num_heads, d, float(scale),
-                                       int(bool(causal)), ws, ws_bytes, _stream(M))
-    _lib.check(st, "vivit_attention_jac_t_f32")
+    if num_kv_heads is None:
+        ws, ws_bytes = _workspace(lib.vivit_attention_jac_t_f32_workspace_bytes(Vd, N, T, num_heads, d), M)
+        st = lib.vivit_attention_jac_t_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), G.data_ptr(), Vd, N, T, num_heads, d, float(scale),
+                                           int(bool(causal)), ws, ws_bytes, _stream(M))
+        _lib.check(st, "vivit_attention_jac_t_f32")
+    else:
+        ws, ws_bytes = _workspace(lib.vivit_attention_gqa_jac_t_f32_workspace_bytes(Vd, N, T, num_heads, num_kv_heads, d), M)
+        st = lib.vivit_attention_gqa_jac_t_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), G.data_ptr(), Vd, N, T, num_heads,
+                                               num_kv_heads, d, float(scale), int(bool(causal)), ws, ws_bytes, _stream(M))
+        _lib.check(st, "vivit_attention_gqa_jac_t_f32")
     return G
 
 
