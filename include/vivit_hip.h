@@ -363,6 +363,19 @@ size_t vivit_attention_gqa_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64
 int vivit_attention_gqa_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
                                   int64_t H, int64_t Hkv, int64_t d, float scale, int causal, void *workspace,
                                   size_t workspace_bytes, void *stream);
+/* The same rule with per-sample sequence lengths and a sliding window; the two entry points above are this one with lengths = NULL
+ * and window = 0, byte for byte.  lengths [N] int32 on the device (NULL: every sample has T positions): sample n has
+ * Tn = min(max(lengths[n], 0), T) live positions 0 .. Tn - 1 (right padding; the kernels clamp, so no value can carry an access out
+ * of bounds).  window W >= 1 (0: none; W >= T is the same function as none, values above 2^31 - 1 included; W < 0: VIVIT_E_BADARG).
+ * Query i sees key j iff i < Tn and j < Tn, j <= i when causal, and i - j < W and j - i < W when W > 0: with causal the W keys
+ * i - W + 1 .. i, the query's own position included.  Positions t >= Tn are dead: as keys invisible, as queries without output, rows
+ * t >= Tn of G[v, n] are written as +0, and the data of M, qkv and out there is never loaded (NaN there reaches nothing).  Only the
+ * 32 x 32 tiles with a visible pair are visited, in the order above, so G[v, n, :Tn] has the bytes of the call on sample n cut to Tn
+ * positions with T = Tn, whatever the other samples' lengths.  The workspace is that of the grouped-query entry point. */
+size_t vivit_attention_masked_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d);
+int vivit_attention_masked_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
+                                     int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths,
+                                     int64_t window, void *workspace, size_t workspace_bytes, void *stream);
 /* nn.Embedding (embedding.hip; the reference has no rule for it): the weight factor Vt[v, n, w, :] = sum_{t: idx[n, t] = w} M[v, n, t, :]
  * of the factor M [V, N, T, D] at the module output has at most T non-zero rows per (v, n) out of W = num_embeddings and is kept
  * compact: ids [N, T] int32 holds sample n's distinct tokens in strictly increasing order in its first U_n slots and -1 in the rest,

@@ -7,7 +7,8 @@ extension's ``savefield``, ``hook(module)`` called per module after its extensio
 provided here for feed-forward and residual nets (Linear, Conv1d/2d/3d, ConvTranspose1d/2d/3d, BatchNorm in
 eval mode, element-wise activations, pooling, Flatten, Dropout in eval mode, and the branching modules
 ``Parallel`` / ``SumModule`` / ``Pad`` / ``Slicing`` / ``ScaleModule`` of ``backpack.custom_module``, LayerNorm / GroupNorm,
-the self-attention modules ``ScaledDotProductAttention`` / ``MultiheadSelfAttention`` of ``custom_module``, ``nn.Embedding``,
+the self-attention modules ``ScaledDotProductAttention`` / ``MultiheadSelfAttention`` of ``custom_module`` (causal,
+grouped queries, sliding windows, right-padded batches through ``set_lengths``), ``nn.Embedding``,
 ``nn.RMSNorm`` and the modules ``ProductModule`` (gated MLPs) / ``RotaryEmbedding`` of ``custom_module``;
 CrossEntropyLoss / MSELoss with ``reduction='mean'`` or ``'sum'``, on outputs ``[N, C]`` and on outputs with positions
 ``[N, C, *D]`` -- next-token cross entropy over a whole sequence, segmentation, dense regression -- with ``Permute`` of

@@ -142,13 +142,51 @@ def _gqa_split(x: Tensor, H: int, Hkv: int, d: int) -> Tuple[Tensor, Tensor, Ten
     return q, k, v
 
 
+def _window(window):
+    """The ``window`` argument of the attention modules, validated (``None`` stays ``None``: no window)."""
+    if window is None:
+        return None
+    if isinstance(window, bool) or int(window) != window or window < 1:
+        raise ValueError(f"window must be an integer >= 1 (or None), got {window!r}")
+    return int(window)
+
+
+def attention_visible(T: int, lengths, causal: bool, window, device) -> Tensor:
+    """The boolean mask ``[N, T, T]`` (``[1, T, T]`` without lengths) of the attention modules' forward pass: query ``i`` of sample
+    ``n`` sees key ``j`` iff ``i, j < lengths[n]``, ``j <= i`` when ``causal`` and ``|i - j| < window`` when a window is given.  A dead
+    query (``i >= lengths[n]``) is given its own position to look at, so that no row of the softmax is empty: its value row is zero
+    (the forward pass zeroes the dead rows of its input), and so is its output."""
+    t = torch.arange(T, device=device)
+    dist = t[:, None] - t[None, :]                                          # i - j
+    vis = torch.ones(1, T, T, dtype=torch.bool, device=device)
+    if causal:
+        vis = vis & (dist >= 0)
+    if window is not None:
+        vis = vis & (dist.abs() < window)
+    if lengths is not None:
+        live = t[None, :] < lengths.to(device)[:, None]                     # [N, T]
+        vis = (vis & live[:, :, None] & live[:, None, :]) | (dist == 0)
+    return vis
+
+
 class ScaledDotProductAttention(nn.Module):
     """Multi-head scaled dot-product self-attention on a packed projection (no counterpart in BackPACK): a parameter-free leaf.
 
     Input ``qkv [N, T, 3 E]`` with ``q = qkv[..., :E]``, ``k = qkv[..., E:2 E]``, ``v = qkv[..., 2 E:]``; head ``h`` owns the columns
     ``h d .. (h + 1) d`` of each third (``d = E / num_heads``, the layout of ``nn.MultiheadAttention``'s packed projection).  Output
     ``[N, T, E]``: per head ``softmax(scale q k^T) v`` with ``scale = 1 / sqrt(d)`` by default; ``causal`` masks the keys ``j > i``.
-    No dropout and no other mask.
+    No dropout.  ``window`` (an integer ``>= 1``; sliding-window attention): query ``i`` sees the keys with ``|i - j| < window`` --
+    with ``causal`` the ``window`` keys ``i - window + 1 .. i``, its own position included (Mistral's convention); ``window >= T`` is
+    no window.  No arbitrary or additive mask.
+
+    Padded batches: ``set_lengths(lengths)`` gives sample ``n`` the positions ``0 .. lengths[n] - 1`` (RIGHT padding only; a
+    left-padded batch is not supported) for every forward pass until it is reset with ``set_lengths(None)``.  The positions beyond are
+    dead, the convention of variable-length attention kernels and not that of ``key_padding_mask``: as keys they are invisible, as
+    queries their output row is exact zeros, nothing flows back to them, and whatever the input holds there (NaN included) reaches
+    no live position.  A live query always sees itself, so no row of the softmax is empty.  ``lengths`` is a sequence or an integer
+    tensor ``[N]``: one on the host is checked to lie in ``[0, T]`` at the next forward pass; one on a device is never read on the
+    host and is clamped to ``[0, T]``, as the kernel of the extensions' rule clamps it.  The forward pass keeps the int32 tensor it
+    used on the module (``forward_lengths``), and the rule reads that one: the very lengths of the forward pass.
 
     ``num_kv_heads`` (grouped-query attention; ``None``: every query head has its own key and value head): the ``H = num_heads``
     query heads share ``Hkv = num_kv_heads`` key / value heads, ``H % Hkv == 0``.  Input ``qkv [N, T, (H + 2 Hkv) d]``: ``q`` is the
@@ -156,12 +194,34 @@ class ScaledDotProductAttention(nn.Module):
     ``h // (H / Hkv)`` (groups of consecutive heads, as LLaMA's ``repeat_kv``).  Output ``[N, T, H d]``.  ``Hkv == 1`` is multi-query
     attention."""
 
-    def __init__(self, num_heads: int, causal: bool = False, scale: float = None, num_kv_heads: int = None):
+    def __init__(self, num_heads: int, causal: bool = False, scale: float = None, num_kv_heads: int = None, window: int = None):
         super().__init__()
         if num_heads < 1:
             raise ValueError(f"num_heads must be positive, got {num_heads}")
         self.num_heads, self.causal, self.scale = int(num_heads), bool(causal), scale
         self.num_kv_heads = _kv_heads(num_heads, num_kv_heads)
+        self.window = _window(window)
+        self._lengths = None          # what set_lengths() was given
+        self.forward_lengths = None   # int32 [N] on the input's device: what the last forward() used (None: no lengths)
+
+    def set_lengths(self, lengths) -> None:
+        """Per-sample sequence lengths of the batches to come (``None``: none); see the class docstring."""
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths)
+            if lengths.dim() != 1 or lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
+                raise ValueError(f"lengths must be integers [N], got {lengths.dtype} {tuple(lengths.shape)}")
+        self._lengths = lengths
+
+    def lengths_for(self, qkv: Tensor):
+        """The lengths of set_lengths() for the batch ``qkv`` as int32 on its device, checked (on the host only) against it."""
+        if self._lengths is None:
+            return None
+        N, T = qkv.shape[:2]
+        if self._lengths.shape[0] != N:
+            raise ValueError(f"set_lengths() was given {self._lengths.shape[0]} lengths, the batch has {N} samples")
+        if self._lengths.device.type == "cpu" and N > 0 and (int(self._lengths.min()) < 0 or int(self._lengths.max()) > T):
+            raise ValueError(f"lengths must lie in [0, T = {T}], got {self._lengths.tolist()}")
+        return self._lengths.to(device=qkv.device, dtype=torch.int32)
 
     def head_dim(self, qkv: Tensor) -> int:
         if self.num_kv_heads is not None:
@@ -176,19 +236,32 @@ class ScaledDotProductAttention(nn.Module):
         return float(self.scale) if self.scale is not None else d ** -0.5
 
     def forward(self, qkv: Tensor) -> Tensor:
+        self.head_dim(qkv)
+        self.forward_lengths = self.lengths_for(qkv)
+        return self.attend(qkv, self.forward_lengths)
+
+    def attend(self, qkv: Tensor, lengths) -> Tensor:
+        """The forward pass with explicit ``lengths`` (int32 ``[N]`` on the device of ``qkv``, or ``None``)."""
         d = self.head_dim(qkv)
         N, T, H = qkv.shape[0], qkv.shape[1], self.num_heads
+        hidden = None   # [N | 1, T, T]: the pairs that do not see each other (None: the causal mask alone, or none)
+        if lengths is not None or self.window is not None:
+            hidden = ~attention_visible(T, lengths, self.causal, self.window, qkv.device)
+            if lengths is not None:   # the dead rows of q, k and v are zeros, whatever the input holds there
+                qkv = qkv.masked_fill((torch.arange(T, device=qkv.device)[None, :] >= lengths[:, None])[:, :, None], 0.0)
+        elif self.causal:
+            hidden = torch.ones(T, T, dtype=torch.bool, device=qkv.device).triu(1)
         if self.num_kv_heads is not None:
             Hkv = self.num_kv_heads
             q, k, v = _gqa_split(qkv, H, Hkv, d)                          # q [N, Hkv, R, T, d]; k, v [N, Hkv, 1, T, d]: views
             s = (q @ k.transpose(-1, -2)) * self.scale_for(d)             # (the matmul broadcasts k and v over the group)
-            if self.causal:
-                s = s.masked_fill(torch.ones(T, T, dtype=torch.bool, device=qkv.device).triu(1), float("-inf"))
+            if hidden is not None:
+                s = s.masked_fill(hidden if hidden.dim() == 2 else hidden[:, None, None], float("-inf"))
             return (s.softmax(-1) @ v).reshape(N, H, T, d).transpose(1, 2).reshape(N, T, H * d)
         q, k, v = qkv.view(N, T, 3, H, d).permute(2, 0, 3, 1, 4)          # each [N, H, T, d]
         s = (q @ k.transpose(-1, -2)) * self.scale_for(d)
-        if self.causal:
-            s = s.masked_fill(torch.ones(T, T, dtype=torch.bool, device=qkv.device).triu(1), float("-inf"))
+        if hidden is not None:
+            s = s.masked_fill(hidden if hidden.dim() == 2 else hidden[:, None], float("-inf"))
         return (s.softmax(-1) @ v).transpose(1, 2).reshape(N, T, H * d)    # (a new tensor: the heads are gathered into a copy)
 
 
@@ -258,25 +331,31 @@ class RotaryEmbedding(nn.Module):
 class MultiheadSelfAttention(nn.Sequential):
     """``Linear(E, 3 E)`` -> :class:`ScaledDotProductAttention` -> ``Linear(E, E)``: ``nn.MultiheadAttention(batch_first=True)``
     applied to ``(x, x, x)`` as a container of single-input leaves, which is what the extensions' rules are written for.  With
-    ``num_kv_heads`` (grouped-query attention) the first projection is ``Linear(E, (H + 2 Hkv) d)``, ``d = E / H``."""
+    ``num_kv_heads`` (grouped-query attention) the first projection is ``Linear(E, (H + 2 Hkv) d)``, ``d = E / H``.  ``window`` and
+    ``set_lengths`` are those of :class:`ScaledDotProductAttention` (sliding-window attention; right-padded batches)."""
 
-    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True, causal: bool = False, num_kv_heads: int = None):
+    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True, causal: bool = False, num_kv_heads: int = None,
+                 window: int = None):
         if embed_dim % num_heads != 0:
             raise ValueError(f"embed_dim ({embed_dim}) is not divisible by num_heads ({num_heads})")
         Hkv = _kv_heads(num_heads, num_kv_heads)
         packed = 3 * embed_dim if Hkv is None else (num_heads + 2 * Hkv) * (embed_dim // num_heads)
-        super().__init__(nn.Linear(embed_dim, packed, bias=bias), ScaledDotProductAttention(num_heads, causal=causal, num_kv_heads=Hkv),
+        super().__init__(nn.Linear(embed_dim, packed, bias=bias), ScaledDotProductAttention(num_heads, causal=causal, num_kv_heads=Hkv, window=window),
                          nn.Linear(embed_dim, embed_dim, bias=bias))
 
+    def set_lengths(self, lengths) -> None:
+        """Per-sample sequence lengths of the padded batches to come (``None``: none), handed to the attention leaf."""
+        self[1].set_lengths(lengths)
+
     @classmethod
-    def from_torch(cls, mha: nn.MultiheadAttention, causal: bool = False) -> "MultiheadSelfAttention":
+    def from_torch(cls, mha: nn.MultiheadAttention, causal: bool = False, window: int = None) -> "MultiheadSelfAttention":
         """A copy of ``mha``'s projections (packed rows q | k | v, as ``in_proj_weight`` has them)."""
         if mha.kdim != mha.embed_dim or mha.vdim != mha.embed_dim or mha.in_proj_weight is None:
             raise ValueError("nn.MultiheadAttention with equal q / k / v dimensions is required")
         if not mha.batch_first or mha.bias_k is not None or mha.add_zero_attn or mha.dropout != 0.0:
             raise ValueError("batch_first=True, no dropout, no bias_k / bias_v and no add_zero_attn are required")
         w = mha.in_proj_weight
-        new = cls(mha.embed_dim, mha.num_heads, bias=mha.in_proj_bias is not None, causal=causal).to(device=w.device, dtype=w.dtype)
+        new = cls(mha.embed_dim, mha.num_heads, bias=mha.in_proj_bias is not None, causal=causal, window=window).to(device=w.device, dtype=w.dtype)
         with torch.no_grad():
             new[0].weight.copy_(w)
             new[2].weight.copy_(mha.out_proj.weight)

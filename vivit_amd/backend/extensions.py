@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from vivit_amd import _lib, kernels
-from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, Permute, ProductModule, RotaryEmbedding, ScaledDotProductAttention, ScaleModule,
+from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, Permute, ProductModule, RotaryEmbedding, ScaledDotProductAttention, ScaleModule, attention_visible,
                                               Slicing,
                                               SumModule, _gqa_split)
 from vivit_amd.utils.ggn import Vmp
@@ -599,7 +599,7 @@ def _attention_out(module, x: Tensor, subsampling) -> Tensor:
     out = getattr(module, "output", None)
     if out is None:
         with torch.no_grad():
-            return module.forward(x)
+            return module.attend(x, _attention_lengths(module, x, subsampling))
     out = subsample(out.detach(), 0, subsampling)
     Hkv = getattr(module, "num_kv_heads", None)   # the output has H d columns
     want = (*x.shape[:2], x.shape[2] // 3 if Hkv is None else module.head_dim(x) * module.num_heads)
@@ -609,36 +609,68 @@ def _attention_out(module, x: Tensor, subsampling) -> Tensor:
     return out
 
 
-def _attention_jac_t_torch(module, M: Tensor, x: Tensor, out: Tensor) -> Tensor:
+def _attention_lengths(module, x: Tensor, subsampling) -> Optional[Tensor]:
+    """The lengths the forward pass of a :class:`ScaledDotProductAttention` used (int32 ``[N]``, kept on the module), sub-sampled as
+    ``x`` was; ``None``: that pass had none."""
+    lengths = getattr(module, "forward_lengths", None)
+    if lengths is None:
+        return None
+    lengths = subsample(lengths, 0, subsampling).to(x.device)
+    if lengths.shape[0] != x.shape[0]:
+        raise ValueError(f"ScaledDotProductAttention: the forward pass used {lengths.shape[0]} lengths after sub-sampling, the input "
+                         f"has {x.shape[0]} samples")
+    return lengths
+
+
+def _attention_dead(M: Tensor, x: Tensor, out: Tensor, lengths: Tensor):
+    """``M``, ``x`` and ``out`` with zeros at the dead positions ``t >= lengths[n]`` (whatever they hold there is not used), and the
+    mask ``[N, T, 1]`` of those positions."""
+    dead = (torch.arange(x.shape[1], device=x.device)[None, :] >= lengths[:, None])[:, :, None]
+    return M.masked_fill(dead, 0.0), x.masked_fill(dead, 0.0), out.masked_fill(dead, 0.0), dead
+
+
+def _attention_jac_t_torch(module, M: Tensor, x: Tensor, out: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
     """The rule of csrc/attention.hip in plain torch (non-HIP or non-fp32 tensors): ``M [V, N, T, E]``, ``x [N, T, 3 E]``,
-    ``out [N, T, E]`` -> ``[V, N, T, 3 E]``.  No autograd."""
+    ``out [N, T, E]`` -> ``[V, N, T, 3 E]``.  ``lengths`` (int32 ``[N]`` or ``None``) and ``module.window``: the mask of the forward
+    pass; the rows of the dead positions are exact zeros.  No autograd."""
     d, H = module.head_dim(x), module.num_heads
     scale = module.scale_for(d)
     V, (N, T) = M.shape[0], x.shape[:2]
+    window = getattr(module, "window", None)
+    hidden = None
+    if lengths is not None or window is not None:
+        hidden = ~attention_visible(T, lengths, module.causal, window, x.device)
+        if lengths is not None:
+            M, x, out, dead = _attention_dead(M.reshape(V, N, T, -1), x, out, lengths)
+    elif module.causal:
+        hidden = torch.ones(T, T, dtype=torch.bool, device=x.device).triu(1)
     if getattr(module, "num_kv_heads", None) is not None:
-        return _attention_gqa_jac_t_torch(M, x, out, H, module.num_kv_heads, d, scale, module.causal)
+        G = _attention_gqa_jac_t_torch(M, x, out, H, module.num_kv_heads, d, scale, hidden)
+        return G if lengths is None else G.masked_fill(dead, 0.0)
     q, k, v = x.view(N, T, 3, H, d).permute(2, 0, 3, 1, 4)                       # each [N, H, T, d]
     S = (q @ k.transpose(-1, -2)) * scale
-    if module.causal:
-        S = S.masked_fill(torch.ones(T, T, dtype=torch.bool, device=x.device).triu(1), float("-inf"))
+    if hidden is not None:
+        S = S.masked_fill(hidden if hidden.dim() == 2 else hidden[:, None], float("-inf"))
     P = S.softmax(-1)                                                             # [N, H, T, T], shared by the V slices
     dO = M.reshape(V, N, T, H, d).permute(0, 1, 3, 2, 4)                          # [V, N, H, T, d]
     D = (dO * out.view(N, T, H, d).permute(0, 2, 1, 3)).sum(-1, keepdim=True)
     dV = P.transpose(-1, -2) @ dO
     dS = P * (dO @ v.transpose(-1, -2) - D)
     dQ, dK = (dS @ k) * scale, (dS.transpose(-1, -2) @ q) * scale
-    return torch.stack((dQ, dK, dV), 0).permute(1, 2, 4, 0, 3, 5).reshape(V, N, T, 3 * H * d)
+    G = torch.stack((dQ, dK, dV), 0).permute(1, 2, 4, 0, 3, 5).reshape(V, N, T, 3 * H * d)
+    return G if lengths is None else G.masked_fill(dead, 0.0)   # (a dead query saw itself: P = 1 on zeros; the sign of a zero)
 
 
-def _attention_gqa_jac_t_torch(M: Tensor, x: Tensor, out: Tensor, H: int, Hkv: int, d: int, scale: float, causal: bool) -> Tensor:
+def _attention_gqa_jac_t_torch(M: Tensor, x: Tensor, out: Tensor, H: int, Hkv: int, d: int, scale: float, hidden) -> Tensor:
     """Grouped-query attention, the same rule: ``x [N, T, (H + 2 Hkv) d]``, ``M [V, N, T, H d]`` -> ``[V, N, T, (H + 2 Hkv) d]``.
     Query head ``h`` uses key / value head ``h // R``; dK and dV of a group are the sums over its ``R = H / Hkv`` query heads.  K and
-    V are broadcast views over the group axis, never expanded copies.  No autograd."""
+    V are broadcast views over the group axis, never expanded copies.  ``hidden``: the pairs that do not see each other, ``[T, T]``
+    or ``[N, T, T]`` (``None``: none).  No autograd."""
     V, (N, T), R = M.shape[0], x.shape[:2], H // Hkv
     q, k, v = _gqa_split(x, H, Hkv, d)                                             # q [N, Hkv, R, T, d]; k, v [N, Hkv, 1, T, d]
     S = (q @ k.transpose(-1, -2)) * scale
-    if causal:
-        S = S.masked_fill(torch.ones(T, T, dtype=torch.bool, device=x.device).triu(1), float("-inf"))
+    if hidden is not None:
+        S = S.masked_fill(hidden if hidden.dim() == 2 else hidden[:, None, None], float("-inf"))
     P = S.softmax(-1)                                                             # [N, Hkv, R, T, T], shared by the V slices
     dO = M.reshape(V, N, T, Hkv, R, d).permute(0, 1, 3, 4, 2, 5)                  # [V, N, Hkv, R, T, d]
     D = (dO * out.view(N, T, Hkv, R, d).permute(0, 2, 3, 1, 4)).sum(-1, keepdim=True)
@@ -775,10 +807,12 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
         # (a head dimension above the kernel's 128 has no kernel: the generic rule, before any operand is prepared; sizes beyond
         # the kernel's index arithmetic come back as VIVIT_E_UNSUPPORTED and the caller falls through likewise)
         d = module.head_dim(x)
-        if d > 128:
-            return None
+        lengths = _attention_lengths(module, x, subsampling)
+        if d > 128:   # (with lengths the formula in torch: the generic rule's forward pass would not know the sub-sampled ones)
+            return None if lengths is None else _attention_jac_t_torch(module, M, x, _attention_out(module, x, subsampling), lengths)
         return kernels.attention_jac_t(M.reshape(M.shape[0], *x.shape[:2], -1), x, _attention_out(module, x, subsampling), module.num_heads,
-                                       module.scale_for(d), module.causal, num_kv_heads=module.num_kv_heads)
+                                       module.scale_for(d), module.causal, num_kv_heads=module.num_kv_heads, lengths=lengths,
+                                       window=getattr(module, "window", None))
     if isinstance(module, _BATCHNORM) and x.dim() >= 2:
         if _own_params(module):   # the parameter rules want the two row sums of the same pass
             return _bn_eval_rules(module, M, x)[0]
@@ -865,7 +899,7 @@ def _jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Tensor:
         if g is not None:
             return g
     elif isinstance(module, ScaledDotProductAttention):   # non-HIP or non-fp32 tensors: the same formula in torch
-        return _attention_jac_t_torch(module, M, x, _attention_out(module, x, subsampling))
+        return _attention_jac_t_torch(module, M, x, _attention_out(module, x, subsampling), _attention_lengths(module, x, subsampling))
     # non-HIP or non-fp32 tensors (or a size beyond the kernels' index arithmetic): the same formulas in torch, never autograd
     if isinstance(module, nn.RMSNorm):
         return _rms_norm_jac_t_torch(module, M, x)

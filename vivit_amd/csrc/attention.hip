@@ -3,7 +3,7 @@
 // its output O [N, T, E], E = H d.  Query head h attends to key / value head g = h / R, R = H / Hkv consecutive query heads per
 // group (grouped-query attention; Hkv == H is multi-head attention with three equal thirds, Hkv == 1 multi-query attention).
 // Per factor row v, sample n and query head h of group g, with dO = M[v, n, :, h]:
-//   S = scale Q_h K_g^T (+ causal mask),  P = softmax_rows(S),  D_i = sum_c dO_ic O_ic,
+//   S = scale Q_h K_g^T (+ mask),  P = softmax_rows(S),  D_i = sum_c dO_ic O_ic,
 //   dP = dO V_g^T,  dS = P o (dP - D),  dQ_h = scale dS K_g,
 //   dV_g = sum_{h in g} P_h^T dO_h,  dK_g = scale sum_{h in g} dS_h^T Q_h,                     G[v, n] = dQ | dK | dV (packed).
 // No T x T data leaves the chip.  Four launches:
@@ -21,8 +21,27 @@
 // SUMMATION ORDER of an output element: head, then block, then k within the block -- for dK and dV the query heads of the group in
 // ascending order, inside a head the query blocks in ascending order, inside a block k in ascending order; for dQ (one head) the
 // key blocks in ascending order (the S and dP tiles: two interleaved chains, even and odd steps of four, added at the end).  So
-// the bytes of G[v, n] depend on (T, H, Hkv, d, scale, causal) and the data of (v, n) only.  With Hkv == H the walk over heads has
-// one step: the order, and the bytes, of multi-head attention.
+// the bytes of G[v, n] depend on (T, H, Hkv, d, scale, causal; the length of n and the window, below) and the data of (v, n) only.
+// With Hkv == H the walk over heads has one step: the order, and the bytes, of multi-head attention.
+//
+// THE MASK.  Sample n has the length Tn = min(max(lengths[n], 0), T) (no lengths: Tn = T; right padding), and a window W >= 1 may
+// be given (W = 0: none).  Query i and key j of sample n see each other iff
+//   i < Tn and j < Tn,   j <= i when causal,   i - j < W and j - i < W when W > 0                                   (att_valid).
+// Positions >= Tn are DEAD: no operand row >= Tn is ever loaded (att_load_block, the lse and D loads zero-fill by Tn; T is the
+// stride only), so whatever stands there -- NaN included -- reaches nothing, and rows Tn .. T - 1 of G[v, n] are written as +0.
+// BLOCK RANGES.  KBn = ceil(Tn / 32) live blocks, WB = floor((W + 30) / 32).  A tile (query block ib, key block jb), both < KBn, has
+// a visible pair iff
+//   causal:  jb <= ib  (the pair (32 ib, 32 jb) of block starts; both are live);
+//   window:  the smallest i - j of the tile is 32 ib - (32 jb + 31), reached at a live pair when jb < ib (block jb is then full
+//            and 32 ib < Tn); it is < W iff 32 (ib - jb) <= W + 30 iff ib - jb <= floor((W + 30) / 32) = WB.  By symmetry the smallest
+//            j - i is < W iff jb - ib <= WB.  (W = 1: WB = 0, the diagonal alone.  W = 2 .. 33: WB = 1, since query 32 ib sees key
+//            32 ib - 1 from W = 2 on and key 32 ib - 33 of block ib - 2 from W = 34 on, where WB = 2.)
+// So the query-block owners (lse, dQ) walk   jb_lo = max(0, ib - WB) .. jb_hi = causal ? ib : min(KBn - 1, ib + WB),
+// and the key-block owner walks, per head,    ib_lo = causal ? jb : max(0, jb - WB) .. ib_hi = min(KBn - 1, jb + WB),
+// with WB = KBn where W = 0 (no tile is cut).  Every tile outside these ranges is all zero and every tile inside has a visible
+// pair, so the sums have the terms and the order they had: with no lengths and no window the bytes of the unmasked kernels, and
+// G[v, n, :Tn] has the bytes of the sample cut to Tn and run alone with T = Tn.  A workgroup whose own block starts at or beyond Tn
+// has an empty walk: it loads nothing and writes its zero rows of G (G is uninitialised memory: every row < T has one writer).
 #include <math.h>
 
 #include "common.h"
@@ -49,7 +68,7 @@ template <int NT> struct AttCfg {
 };
 
 // rows r0 .. r0 + 31 of a [T][stride] matrix, columns 0 .. d - 1 from `src` (already offset to the head) -> dst[32][LD]; rows
-// beyond T and columns d .. DP - 1 are zero.  vec: d % 4 == 0 and every row start is 16-byte aligned.
+// beyond T (the sample's live length) and columns d .. DP - 1 are zero and never read.  vec: d % 4 == 0 and every row start is 16-byte aligned.
 template <int NT>
 __device__ __forceinline__ void att_load_block(float *__restrict__ dst, const float *__restrict__ src, int64_t stride, int r0, int T,
                                                int d, bool vec) {
@@ -115,10 +134,21 @@ struct AttGeom {
   int pitch, koff, voff;     // of a row of qkv and G: (H + 2 Hkv) d columns, k from column H d, v from column (H + Hkv) d
   int causal, vec;
   float scale;
+  const int32_t *lengths;    // [N] on the device, or null: every sample has T positions
+  int window;                // W >= 1, or 0: none (the host passes 0 for W >= T, so W + 30 stays an int)
 };
 
-__device__ __forceinline__ bool att_valid(const AttGeom &g, int gi, int gj) {
-  return gi < g.T && gj < g.T && (!g.causal || gj <= gi);
+// the live positions of sample n: an out-of-range length is clamped, so that it can never carry an access out of bounds
+__device__ __forceinline__ int att_len(const AttGeom &g, int64_t n) {
+  return g.lengths ? min(max(g.lengths[n], 0), g.T) : g.T;
+}
+
+// blocks a window reaches to either side of the diagonal (the head of the file); KBn where there is no window
+__device__ __forceinline__ int att_reach(const AttGeom &g, int KBn) { return g.window > 0 ? (g.window + 30) >> 5 : KBn; }
+
+__device__ __forceinline__ bool att_valid(const AttGeom &g, int Tn, int gi, int gj) {
+  const int dist = gi - gj;
+  return gi < Tn && gj < Tn && (!g.causal || dist >= 0) && (g.window <= 0 || (dist < g.window && -dist < g.window));
 }
 
 // ---- row log-sum-exp --------------------------------------------------------------------------------------------------------------
@@ -133,22 +163,25 @@ __global__ __launch_bounds__(256) void attn_lse_kernel(const float *__restrict__
   const int64_t n = nh / g.H;
   const int h = (int)(nh - n * g.H), dk = (g.d + 3) & ~3;
   const int64_t pitch = g.pitch;
+  const int Tn = att_len(g, n);
+  if (i0 >= Tn) return;   // a dead query block: its lse is never read
+  const int KBn = (Tn + ATT_B - 1) / ATT_B, wb = att_reach(g, KBn);
   const float *base = qkv + n * g.T * pitch, *kbase = base + g.koff + (int64_t)(h / g.R) * g.d;
-  att_load_block<NT>(sQ, base + (int64_t)h * g.d, pitch, i0, g.T, g.d, g.vec);
+  att_load_block<NT>(sQ, base + (int64_t)h * g.d, pitch, i0, Tn, g.d, g.vec);
   const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
   const int row = tid >> 3, sub = tid & 7;
   float m = -INFINITY, l = 0.f;
-  const int jb_end = g.causal ? ib : g.KB - 1;
-  for (int jb = 0; jb <= jb_end; ++jb) {
+  const int jb_lo = max(ib - wb, 0), jb_hi = g.causal ? ib : min(ib + wb, KBn - 1);
+  for (int jb = jb_lo; jb <= jb_hi; ++jb) {
     const int j0 = jb * ATT_B;
     __syncthreads();   // the previous block's reads of sK and sS are done
-    att_load_block<NT>(sK, kbase, pitch, j0, g.T, g.d, g.vec);
+    att_load_block<NT>(sK, kbase, pitch, j0, Tn, g.d, g.vec);
     __syncthreads();
     const att_f32x4 s = att_tile_nt<NT>(sQ + 16 * ri * C::LD, sK + 16 * cj * C::LD, dk, lane);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int r = 16 * ri + 4 * kq + e, c = 16 * cj + j;
-      sS[r * 33 + c] = att_valid(g, i0 + r, j0 + c) ? s[e] * g.scale : -INFINITY;
+      sS[r * 33 + c] = att_valid(g, Tn, i0 + r, j0 + c) ? s[e] * g.scale : -INFINITY;
     }
     __syncthreads();
     // eight lanes per row, four columns each; every lane of a row keeps the same (m, l)
@@ -166,10 +199,10 @@ __global__ __launch_bounds__(256) void attn_lse_kernel(const float *__restrict__
     l = l * expf(m - mref) + ts;
     m = mn;
   }
-  if (sub == 0 && i0 + row < g.T) lse[nh * g.T + i0 + row] = m + logf(l);
+  if (sub == 0 && i0 + row < Tn) lse[nh * g.T + i0 + row] = m + logf(l);
 }
 
-// ---- D[v, n, h, i] = sum_c M[v, n, i, h d + c] O[n, i, h d + c] --------------------------------------------------------------
+// ---- D[v, n, h, i] = sum_c M[v, n, i, h d + c] O[n, i, h d + c], i < Tn --------------------------------------------------------------
 __global__ __launch_bounds__(256) void attn_rowdot_kernel(const float *__restrict__ M, const float *__restrict__ O, float *__restrict__ D,
                                                           int64_t total, AttGeom g) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -179,40 +212,42 @@ __global__ __launch_bounds__(256) void attn_rowdot_kernel(const float *__restric
   const int64_t vn = vnh / g.H;
   const int h = (int)(vnh - vn * g.H);
   const int64_t n = vn % g.N, E = (int64_t)g.H * g.d;
+  if (t >= att_len(g, n)) return;   // a dead row: D is never read there
   const float *m = M + (vn * g.T + t) * E + (int64_t)h * g.d, *o = O + (n * g.T + t) * E + (int64_t)h * g.d;
   float a = 0.f;
   for (int c = 0; c < g.d; ++c) a = fmaf(m[c], o[c], a);
   D[e] = a;
 }
 
-// what the two owners share: the dO blocks and D of the workgroup's factor rows for the query block at i0
+// what the two owners share: the dO blocks and D of the workgroup's factor rows for the query block at i0 (rows >= Tn: zero)
 template <int NT>
 __device__ __forceinline__ void att_load_factor(float *__restrict__ sdO, float *__restrict__ sD, const float *__restrict__ M,
-                                                const float *__restrict__ Dws, const AttGeom &g, int64_t v0, int nv, int64_t n, int h,
-                                                int i0) {
+                                                const float *__restrict__ Dws, const AttGeom &g, int Tn, int64_t v0, int nv, int64_t n,
+                                                int h, int i0) {
   using C = AttCfg<NT>;
   const int64_t E = (int64_t)g.H * g.d;
 #pragma unroll
   for (int vi = 0; vi < C::VC; ++vi)
     if (vi < nv) {
       const int64_t vn = (v0 + vi) * g.N + n;
-      att_load_block<NT>(sdO + vi * C::BLK, M + vn * g.T * E + (int64_t)h * g.d, E, i0, g.T, g.d, g.vec);
+      att_load_block<NT>(sdO + vi * C::BLK, M + vn * g.T * E + (int64_t)h * g.d, E, i0, Tn, g.d, g.vec);
       if (threadIdx.x < ATT_B)
-        sD[vi * ATT_B + threadIdx.x] = i0 + (int)threadIdx.x < g.T ? Dws[(vn * g.H + h) * g.T + i0 + threadIdx.x] : 0.f;
+        sD[vi * ATT_B + threadIdx.x] = i0 + (int)threadIdx.x < Tn ? Dws[(vn * g.H + h) * g.T + i0 + threadIdx.x] : 0.f;
     }
 }
 
-// one wave's 16 x 16 part of P = exp(S - lse) for the tile (query block at i0, key block at j0); zero where masked or beyond T
-template <int NT>
+// one wave's 16 x 16 part of P = exp(S - lse) for the tile (query block at i0, key block at j0); zero where masked or beyond Tn
+// (`visible(r, c)`: att_valid of the pair at row r and column c of the tile, in whatever form the owner keeps it)
+template <int NT, class Visible>
 __device__ __forceinline__ att_f32x4 att_p_tile(const float *__restrict__ sQ, const float *__restrict__ sK, const float *__restrict__ sL,
-                                                const AttGeom &g, int i0, int j0, int dk, int lane, int ri, int cj) {
+                                                float scale, int dk, int lane, int ri, int cj, Visible visible) {
   using C = AttCfg<NT>;
   const att_f32x4 s = att_tile_nt<NT>(sQ + 16 * ri * C::LD, sK + 16 * cj * C::LD, dk, lane);
   att_f32x4 p;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int r = 16 * ri + 4 * (lane >> 4) + e, c = 16 * cj + (lane & 15);
-    p[e] = att_valid(g, i0 + r, j0 + c) ? expf(s[e] * g.scale - sL[r]) : 0.f;
+    p[e] = visible(r, c) ? expf(s[e] * scale - sL[r]) : 0.f;
   }
   return p;
 }
@@ -235,26 +270,38 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__
   const int64_t v0 = (int64_t)blockIdx.y * C::VC;
   const int nv = V - v0 < C::VC ? (int)(V - v0) : C::VC;
   const float *base = qkv + n * g.T * pitch;
-  att_load_block<NT>(sK, base + g.koff + (int64_t)kv * g.d, pitch, j0, g.T, g.d, g.vec);
-  att_load_block<NT>(sV, base + g.voff + (int64_t)kv * g.d, pitch, j0, g.T, g.d, g.vec);
+  const int Tn = att_len(g, n), KBn = (Tn + ATT_B - 1) / ATT_B, wb = att_reach(g, KBn);
+  // the query blocks that see this key block (the head of the file); a dead key block (j0 >= Tn) has none, loads nothing and
+  // stores its zeros
+  const int ib_lo = g.causal ? jb : max(jb - wb, 0), ib_hi = min(jb + wb, KBn - 1);
+  const int per_head = j0 < Tn ? ib_hi - ib_lo + 1 : 0;
+  if (per_head > 0) {
+    att_load_block<NT>(sK, base + g.koff + (int64_t)kv * g.d, pitch, j0, Tn, g.d, g.vec);
+    att_load_block<NT>(sV, base + g.voff + (int64_t)kv * g.d, pitch, j0, Tn, g.d, g.vec);
+  }
   const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
+  // att_valid for the lane's key gj, which is the same in every tile of the walk, as the range q_lo .. q_hi of the queries that see
+  // it (empty for a dead key): two registers of the lane instead of Tn, the window and the causal flag in the scalar file, which this
+  // kernel fills
+  const int gj = j0 + 16 * cj + j, reach = g.window > 0 ? g.window - 1 : Tn;
+  const int q_lo = gj < Tn ? (g.causal ? gj : gj - reach) : 0x7fffffff;
+  const int q_hi = (int)min((int64_t)gj + reach, (int64_t)Tn - 1);
   att_f32x4 accK[C::VC][C::TPW], accV[C::VC][C::TPW];
 #pragma unroll
   for (int vi = 0; vi < C::VC; ++vi)
 #pragma unroll
     for (int u = 0; u < C::TPW; ++u) accK[vi][u] = accV[vi][u] = (att_f32x4){0.f, 0.f, 0.f, 0.f};
   // the group's query heads in ascending order, the query blocks of each in ascending order: one chain of sums per output element
-  const int ib0 = g.causal ? jb : 0, per_head = g.KB - ib0;   // (causal: the queries before the key block see none of its keys)
   for (int step = 0; step < g.R * per_head; ++step) {
-    const int hr = step / per_head, ib = ib0 + step - hr * per_head;
+    const int hr = step / per_head, ib = ib_lo + step - hr * per_head;
     const int h = kv * g.R + hr, i0 = ib * ATT_B;
     const int64_t nh = n * g.H + h;
     __syncthreads();   // the previous query block's tiles and operands have been read
-    att_load_block<NT>(sQ, base + (int64_t)h * g.d, pitch, i0, g.T, g.d, g.vec);
-    if (tid < ATT_B) sL[tid] = i0 + tid < g.T ? lse[nh * g.T + i0 + tid] : 0.f;
-    att_load_factor<NT>(sdO, sD, M, Dws, g, v0, nv, n, h, i0);
+    att_load_block<NT>(sQ, base + (int64_t)h * g.d, pitch, i0, Tn, g.d, g.vec);
+    if (tid < ATT_B) sL[tid] = i0 + tid < Tn ? lse[nh * g.T + i0 + tid] : 0.f;
+    att_load_factor<NT>(sdO, sD, M, Dws, g, Tn, v0, nv, n, h, i0);
     __syncthreads();
-    const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g, i0, j0, dk, lane, ri, cj);
+    const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g.scale, dk, lane, ri, cj, [&](int r, int) { return i0 + r >= q_lo && i0 + r <= q_hi; });
 #pragma unroll
     for (int e = 0; e < 4; ++e) sP[(16 * ri + 4 * kq + e) * ATT_LDP + 16 * cj + j] = p[e];
 #pragma unroll
@@ -293,9 +340,9 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int r = j0 + 16 * rt + 4 * kq + e;
-            if (r < g.T) {
-              gk[(int64_t)r * pitch] = g.scale * accK[vi][u][e];
-              gk[(int64_t)r * pitch + kv_to_v] = accV[vi][u][e];
+            if (r < g.T) {   // (a dead key's row: +0 whatever the sign of the scale)
+              gk[(int64_t)r * pitch] = r < Tn ? g.scale * accK[vi][u][e] : 0.f;
+              gk[(int64_t)r * pitch + kv_to_v] = r < Tn ? accV[vi][u][e] : 0.f;
             }
           }
         }
@@ -321,23 +368,28 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ 
   const int64_t v0 = (int64_t)blockIdx.y * C::VC;
   const int nv = V - v0 < C::VC ? (int)(V - v0) : C::VC;
   const float *base = qkv + n * g.T * pitch, *kbase = base + g.koff + (int64_t)(h / g.R) * g.d;
-  att_load_block<NT>(sQ, base + (int64_t)h * g.d, pitch, i0, g.T, g.d, g.vec);
-  if (tid < ATT_B) sL[tid] = i0 + tid < g.T ? lse[nh * g.T + i0 + tid] : 0.f;
-  att_load_factor<NT>(sdO, sD, M, Dws, g, v0, nv, n, h, i0);
+  const int Tn = att_len(g, n), KBn = (Tn + ATT_B - 1) / ATT_B, wb = att_reach(g, KBn);
+  // the key blocks this query block sees (the head of the file); a dead query block (i0 >= Tn) has none, loads nothing and stores
+  // its zeros
+  const int jb_lo = max(ib - wb, 0), jb_hi = i0 < Tn ? (g.causal ? ib : min(ib + wb, KBn - 1)) : -1;
+  if (jb_lo <= jb_hi) {
+    att_load_block<NT>(sQ, base + (int64_t)h * g.d, pitch, i0, Tn, g.d, g.vec);
+    if (tid < ATT_B) sL[tid] = i0 + tid < Tn ? lse[nh * g.T + i0 + tid] : 0.f;
+    att_load_factor<NT>(sdO, sD, M, Dws, g, Tn, v0, nv, n, h, i0);
+  }
   const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
   att_f32x4 accQ[C::VC][C::TPW];
 #pragma unroll
   for (int vi = 0; vi < C::VC; ++vi)
 #pragma unroll
     for (int u = 0; u < C::TPW; ++u) accQ[vi][u] = (att_f32x4){0.f, 0.f, 0.f, 0.f};
-  const int jb_end = g.causal ? ib : g.KB - 1;
-  for (int jb = 0; jb <= jb_end; ++jb) {
+  for (int jb = jb_lo; jb <= jb_hi; ++jb) {
     const int j0 = jb * ATT_B;
     __syncthreads();   // the previous key block's tiles and operands have been read
-    att_load_block<NT>(sK, kbase, pitch, j0, g.T, g.d, g.vec);
-    att_load_block<NT>(sV, kbase + (g.voff - g.koff), pitch, j0, g.T, g.d, g.vec);
+    att_load_block<NT>(sK, kbase, pitch, j0, Tn, g.d, g.vec);
+    att_load_block<NT>(sV, kbase + (g.voff - g.koff), pitch, j0, Tn, g.d, g.vec);
     __syncthreads();
-    const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g, i0, j0, dk, lane, ri, cj);
+    const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g.scale, dk, lane, ri, cj, [&](int r, int c) { return att_valid(g, Tn, i0 + r, j0 + c); });
 #pragma unroll
     for (int vi = 0; vi < C::VC; ++vi)
       if (vi < nv) {
@@ -370,7 +422,7 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ 
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int r = i0 + 16 * rt + 4 * kq + e;
-            if (r < g.T) gq[(int64_t)r * pitch] = g.scale * accQ[vi][u][e];
+            if (r < g.T) gq[(int64_t)r * pitch] = r < Tn ? g.scale * accQ[vi][u][e] : 0.f;   // (a dead query's row: +0)
           }
         }
     }
@@ -435,15 +487,16 @@ using namespace vivit;
 
 extern "C" {
 
-size_t vivit_attention_gqa_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d) {
+size_t vivit_attention_masked_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d) {
   const AttPlan p = attention_plan(V, N, T, H, Hkv, d);
   return p.status == VIVIT_OK ? p.bytes : 0;
 }
 
-int vivit_attention_gqa_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
-                                  int64_t H, int64_t Hkv, int64_t d, float scale, int causal, void *workspace, size_t workspace_bytes,
-                                  void *stream) {
-  if (!M || !qkv || !out || !G) return VIVIT_E_BADARG;
+// lengths [N] int32 on the device or null; window >= 1 or 0 (none): the one entry that launches, the others below call it
+int vivit_attention_masked_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
+                                     int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths,
+                                     int64_t window, void *workspace, size_t workspace_bytes, void *stream) {
+  if (!M || !qkv || !out || !G || window < 0) return VIVIT_E_BADARG;
   const AttPlan p = attention_plan(V, N, T, H, Hkv, d);
   if (p.status != VIVIT_OK) return p.status;
   if (!workspace || workspace_bytes < p.bytes) return VIVIT_E_WORKSPACE;
@@ -454,6 +507,8 @@ int vivit_attention_gqa_jac_t_f32(const float *M, const float *qkv, const float 
   g.causal = causal != 0;
   g.vec = (d & 3) == 0 && att_aligned16(M) && att_aligned16(qkv);
   g.scale = scale;
+  g.lengths = lengths;
+  g.window = window >= T ? 0 : (int)window;   // (a window of T or more cuts nothing; this also covers every value beyond an int)
   float *lse = static_cast<float *>(workspace);
   float *Dws = reinterpret_cast<float *>(static_cast<char *>(workspace) + p.lse_bytes);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -463,14 +518,27 @@ int vivit_attention_gqa_jac_t_f32(const float *M, const float *qkv, const float 
   return attention_launch<8>(M, qkv, out, G, lse, Dws, V, g, s);
 }
 
+// grouped-query attention without lengths or a window
+size_t vivit_attention_gqa_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d) {
+  return vivit_attention_masked_jac_t_f32_workspace_bytes(V, N, T, H, Hkv, d);
+}
+
+int vivit_attention_gqa_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
+                                  int64_t H, int64_t Hkv, int64_t d, float scale, int causal, void *workspace, size_t workspace_bytes,
+                                  void *stream) {
+  return vivit_attention_masked_jac_t_f32(M, qkv, out, G, V, N, T, H, Hkv, d, scale, causal, nullptr, 0, workspace, workspace_bytes,
+                                          stream);
+}
+
 // multi-head attention: every query head has its own key and value head
 size_t vivit_attention_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t d) {
-  return vivit_attention_gqa_jac_t_f32_workspace_bytes(V, N, T, H, H, d);
+  return vivit_attention_masked_jac_t_f32_workspace_bytes(V, N, T, H, H, d);
 }
 
 int vivit_attention_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T, int64_t H,
                               int64_t d, float scale, int causal, void *workspace, size_t workspace_bytes, void *stream) {
-  return vivit_attention_gqa_jac_t_f32(M, qkv, out, G, V, N, T, H, H, d, scale, causal, workspace, workspace_bytes, stream);
+  return vivit_attention_masked_jac_t_f32(M, qkv, out, G, V, N, T, H, H, d, scale, causal, nullptr, 0, workspace, workspace_bytes,
+                                          stream);
 }
 
 } // extern "C"

@@ -692,13 +692,29 @@ def _check_kv_heads(num_heads, num_kv_heads):
 
 
 @_launcher
-def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None):
+def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None, window: int = None):
     """Transposed input Jacobian of scaled dot-product self-attention (``vivit_attention_jac_t_f32``): ``M [V, N, T, E]`` (the factor
     at the module output), ``qkv [N, T, 3 E]`` (the module input, q | k | v), ``out [N, T, E]`` (the module output of the forward
     pass) -> ``[V, N, T, 3 E]``.  ``E = num_heads * d``; no ``T x T`` tensor is allocated.  ``num_kv_heads`` (grouped-query
     attention, ``vivit_attention_gqa_jac_t_f32``): ``qkv [N, T, (num_heads + 2 * num_kv_heads) * d]``, query head ``h`` attends
-    to key / value head ``h // (num_heads // num_kv_heads)``; the result is packed ``dQ | dK | dV`` like ``qkv``."""
+    to key / value head ``h // (num_heads // num_kv_heads)``; the result is packed ``dQ | dK | dV`` like ``qkv``.
+
+    ``lengths`` (anything ``torch.as_tensor`` turns into ``N`` integers; ``vivit_attention_masked_jac_t_f32``): sample ``n`` has
+    the positions ``0 .. lengths[n] - 1`` (right padding; the kernel clamps to ``[0, T]``).  The positions beyond are dead: invisible
+    as keys, rows of exact zeros in the result, and whatever ``M``, ``qkv`` and ``out`` hold there is never read.  The values go to
+    ``M``'s device as int32 and are not looked at on the host.  ``window`` (an integer ``>= 1``): query ``i`` sees the keys with
+    ``|i - j| < window`` (with ``causal`` the ``window`` keys up to and including its own).  With both ``None`` the call is the one
+    it was."""
     _require_device(M, qkv, out)
+    if window is not None and (isinstance(window, bool) or int(window) != window or window < 1):
+        raise ValueError(f"window must be an integer >= 1 (or None), got {window!r}")
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths)
+        if lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
+            raise ValueError(f"lengths must be integers, got {lengths.dtype}")
+        if lengths.dim() != 1 or qkv.dim() != 3 or lengths.shape[0] != qkv.shape[0]:
+            raise ValueError(f"lengths must be [N] = [{qkv.shape[0] if qkv.dim() == 3 else '?'}], got {tuple(lengths.shape)}")
+        lengths = lengths.to(device=M.device, dtype=torch.int32).contiguous()
     M, qkv, out = M.contiguous(), qkv.contiguous(), out.contiguous()
     if num_kv_heads is None:
         if qkv.dim() != 3 or num_heads < 1 or qkv.shape[2] == 0 or qkv.shape[2] % (3 * num_heads) != 0:
@@ -721,7 +737,14 @@ def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num
         raise ValueError(f"empty operands: M {tuple(M.shape)}")
     G = torch.empty((Vd, N, T, E3), dtype=torch.float32, device=M.device)
     lib = _lib.load()
-    if num_kv_heads is None:
+    if lengths is not None or window is not None:
+        Hkv = num_heads if num_kv_heads is None else num_kv_heads
+        ws, ws_bytes = _workspace(lib.vivit_attention_masked_jac_t_f32_workspace_bytes(Vd, N, T, num_heads, Hkv, d), M)
+        st = lib.vivit_attention_masked_jac_t_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), G.data_ptr(), Vd, N, T, num_heads, Hkv, d,
+                                                  float(scale), int(bool(causal)), None if lengths is None else lengths.data_ptr(),
+                                                  0 if window is None else int(window), ws, ws_bytes, _stream(M))
+        _lib.check(st, "vivit_attention_masked_jac_t_f32")
+    elif num_kv_heads is None:
         ws, ws_bytes = _workspace(lib.vivit_attention_jac_t_f32_workspace_bytes(Vd, N, T, num_heads, d), M)
         st = lib.vivit_attention_jac_t_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), G.data_ptr(), Vd, N, T, num_heads, d, float(scale),
                                            int(bool(causal)), ws, ws_bytes, _stream(M))
