@@ -124,22 +124,31 @@ def _kv_heads(num_heads: int, num_kv_heads):
     return int(num_kv_heads)
 
 
-def _gqa_head_dim(qkv: Tensor, H: int, Hkv: int) -> int:
+def _head_dim(qkv: Tensor, H: int, num_kv_heads, even: bool = False) -> int:
+    """The head dimension ``d`` of a packed projection ``qkv [N, T, (H + 2 Hkv) d]``, checked (``even``: and even).  Without
+    ``num_kv_heads`` (``Hkv = H``) the messages speak of the three thirds ``[N, T, 3 E]``."""
+    if num_kv_heads is None:
+        heads, layout, count = 3 * H, "3 E", f"3 * {H}"
+    else:
+        heads, layout, count = H + 2 * num_kv_heads, "(H + 2 Hkv) d", f"(H + 2 Hkv) = ({H} + 2 * {num_kv_heads})"
     if qkv.dim() != 3:
-        raise ValueError(f"expected a packed projection [N, T, (H + 2 Hkv) d], got {qkv.dim()} dimensions")
-    if qkv.shape[2] == 0 or qkv.shape[2] % (H + 2 * Hkv) != 0:
-        raise ValueError(f"the last dimension ({qkv.shape[2]}) is not (H + 2 Hkv) = ({H} + 2 * {Hkv}) heads * head dimension")
-    return qkv.shape[2] // (H + 2 * Hkv)
+        raise ValueError(f"expected a packed projection [N, T, {layout}], got {qkv.dim()} dimensions")
+    if qkv.shape[2] == 0 or qkv.shape[2] % heads != 0:
+        raise ValueError(f"the last dimension ({qkv.shape[2]}) is not {count} heads * head dimension")
+    d = qkv.shape[2] // heads
+    if even and d % 2 != 0:
+        raise ValueError(f"the head dimension ({d}) must be even: rotary embeddings rotate pairs of columns")
+    return d
 
 
 def _gqa_split(x: Tensor, H: int, Hkv: int, d: int) -> Tuple[Tensor, Tensor, Tensor]:
     """Views of a packed projection ``x [*B, T, (H + 2 Hkv) d]``: ``q [*B, Hkv, R, T, d]`` and ``k``, ``v [*B, Hkv, 1, T, d]``."""
-    B, T = x.shape[:-2], x.shape[-2]
-    nb = len(B)
-    q = x[..., :H * d].unflatten(-1, (Hkv, H // Hkv, d)).permute(*range(nb), nb + 1, nb + 2, nb, nb + 3)
-    k = x[..., H * d:(H + Hkv) * d].unflatten(-1, (Hkv, 1, d)).permute(*range(nb), nb + 1, nb + 2, nb, nb + 3)
-    v = x[..., (H + Hkv) * d:].unflatten(-1, (Hkv, 1, d)).permute(*range(nb), nb + 1, nb + 2, nb, nb + 3)
-    return q, k, v
+    nb = x.dim() - 2
+    heads = lambda t, R: t.unflatten(-2, (Hkv, R)).permute(*range(nb), nb + 1, nb + 2, nb, nb + 3)   # noqa: E731
+    # (one split of the head axis, not three slices of the columns: its gradient is one concatenation of the three gradients as they
+    # come, where each slice's is a zero-filled copy to be added up)
+    q, k, v = x.unflatten(-1, (H + 2 * Hkv, d)).split((H, Hkv, Hkv), -2)
+    return heads(q, H // Hkv), heads(k, 1), heads(v, 1)
 
 
 def _window(window):
@@ -223,14 +232,13 @@ class ScaledDotProductAttention(nn.Module):
             raise ValueError(f"lengths must lie in [0, T = {T}], got {self._lengths.tolist()}")
         return self._lengths.to(device=qkv.device, dtype=torch.int32)
 
+    @property
+    def kv_heads(self) -> int:
+        """``Hkv``: ``num_kv_heads``, or ``num_heads`` where none was given (multi-head attention is ``Hkv = H``)."""
+        return self.num_heads if self.num_kv_heads is None else self.num_kv_heads
+
     def head_dim(self, qkv: Tensor) -> int:
-        if self.num_kv_heads is not None:
-            return _gqa_head_dim(qkv, self.num_heads, self.num_kv_heads)
-        if qkv.dim() != 3:
-            raise ValueError(f"expected a packed projection [N, T, 3 E], got {qkv.dim()} dimensions")
-        if qkv.shape[2] == 0 or qkv.shape[2] % (3 * self.num_heads) != 0:
-            raise ValueError(f"the last dimension ({qkv.shape[2]}) is not 3 * {self.num_heads} heads * head dimension")
-        return qkv.shape[2] // (3 * self.num_heads)
+        return _head_dim(qkv, self.num_heads, self.num_kv_heads)
 
     def scale_for(self, d: int) -> float:
         return float(self.scale) if self.scale is not None else d ** -0.5
@@ -240,29 +248,32 @@ class ScaledDotProductAttention(nn.Module):
         self.forward_lengths = self.lengths_for(qkv)
         return self.attend(qkv, self.forward_lengths)
 
+    def masks(self, T: int, lengths, device):
+        """``(hidden, dead)`` for ``T`` positions and ``lengths`` (int32 ``[N]`` on ``device``, or ``None``).  ``hidden``: the pairs
+        (query, key) that do not see each other, ``[T, T]`` (the causal mask alone) or ``[N | 1, 1, 1, T, T]``, either of which
+        broadcasts over the scores ``[N, Hkv, R, T, T]``; ``None``: every pair sees each other.  ``dead``: the positions
+        ``t >= lengths[n]``, ``[N, T, 1]``; ``None`` without lengths."""
+        hidden = dead = None
+        if lengths is not None or self.window is not None:
+            hidden = ~attention_visible(T, lengths, self.causal, self.window, device)[:, None, None]
+            if lengths is not None:
+                dead = (torch.arange(T, device=device)[None, :] >= lengths[:, None])[:, :, None]
+        elif self.causal:
+            hidden = torch.ones(T, T, dtype=torch.bool, device=device).triu(1)
+        return hidden, dead
+
     def attend(self, qkv: Tensor, lengths) -> Tensor:
         """The forward pass with explicit ``lengths`` (int32 ``[N]`` on the device of ``qkv``, or ``None``)."""
         d = self.head_dim(qkv)
         N, T, H = qkv.shape[0], qkv.shape[1], self.num_heads
-        hidden = None   # [N | 1, T, T]: the pairs that do not see each other (None: the causal mask alone, or none)
-        if lengths is not None or self.window is not None:
-            hidden = ~attention_visible(T, lengths, self.causal, self.window, qkv.device)
-            if lengths is not None:   # the dead rows of q, k and v are zeros, whatever the input holds there
-                qkv = qkv.masked_fill((torch.arange(T, device=qkv.device)[None, :] >= lengths[:, None])[:, :, None], 0.0)
-        elif self.causal:
-            hidden = torch.ones(T, T, dtype=torch.bool, device=qkv.device).triu(1)
-        if self.num_kv_heads is not None:
-            Hkv = self.num_kv_heads
-            q, k, v = _gqa_split(qkv, H, Hkv, d)                          # q [N, Hkv, R, T, d]; k, v [N, Hkv, 1, T, d]: views
-            s = (q @ k.transpose(-1, -2)) * self.scale_for(d)             # (the matmul broadcasts k and v over the group)
-            if hidden is not None:
-                s = s.masked_fill(hidden if hidden.dim() == 2 else hidden[:, None, None], float("-inf"))
-            return (s.softmax(-1) @ v).reshape(N, H, T, d).transpose(1, 2).reshape(N, T, H * d)
-        q, k, v = qkv.view(N, T, 3, H, d).permute(2, 0, 3, 1, 4)          # each [N, H, T, d]
-        s = (q @ k.transpose(-1, -2)) * self.scale_for(d)
+        hidden, dead = self.masks(T, lengths, qkv.device)
+        if dead is not None:   # the dead rows of q, k and v are zeros, whatever the input holds there
+            qkv = qkv.masked_fill(dead, 0.0)
+        q, k, v = _gqa_split(qkv, H, self.kv_heads, d)                    # q [N, Hkv, R, T, d]; k, v [N, Hkv, 1, T, d]: views
+        s = (q @ k.transpose(-1, -2)) * self.scale_for(d)                 # (the matmul broadcasts k and v over the group)
         if hidden is not None:
-            s = s.masked_fill(hidden if hidden.dim() == 2 else hidden[:, None], float("-inf"))
-        return (s.softmax(-1) @ v).transpose(1, 2).reshape(N, T, H * d)    # (a new tensor: the heads are gathered into a copy)
+            s = s.masked_fill(hidden, float("-inf"))
+        return (s.softmax(-1) @ v).reshape(N, H, T, d).transpose(1, 2).reshape(N, T, H * d)   # (a new tensor: the heads are gathered)
 
 
 class RotaryEmbedding(nn.Module):
@@ -285,20 +296,13 @@ class RotaryEmbedding(nn.Module):
         self.num_kv_heads = _kv_heads(num_heads, num_kv_heads)
         self._tables = None   # (key, cos, sin): what forward() used is what the rule of the extensions uses
 
+    @property
+    def kv_heads(self) -> int:
+        """``Hkv``: ``num_kv_heads``, or ``num_heads`` where none was given (three equal thirds are ``Hkv = H``)."""
+        return self.num_heads if self.num_kv_heads is None else self.num_kv_heads
+
     def head_dim(self, qkv: Tensor) -> int:
-        if self.num_kv_heads is not None:
-            d = _gqa_head_dim(qkv, self.num_heads, self.num_kv_heads)
-            if d % 2 != 0:
-                raise ValueError(f"the head dimension ({d}) must be even: rotary embeddings rotate pairs of columns")
-            return d
-        if qkv.dim() != 3:
-            raise ValueError(f"expected a packed projection [N, T, 3 E], got {qkv.dim()} dimensions")
-        if qkv.shape[2] == 0 or qkv.shape[2] % (3 * self.num_heads) != 0:
-            raise ValueError(f"the last dimension ({qkv.shape[2]}) is not 3 * {self.num_heads} heads * head dimension")
-        d = qkv.shape[2] // (3 * self.num_heads)
-        if d % 2 != 0:
-            raise ValueError(f"the head dimension ({d}) must be even: rotary embeddings rotate pairs of columns")
-        return d
+        return _head_dim(qkv, self.num_heads, self.num_kv_heads, even=True)
 
     def tables(self, T: int, d: int, device, dtype) -> Tuple[Tensor, Tensor]:
         """``(cos, sin)``, each ``[T, d / 2]`` in ``dtype``: the angles ``t * base^(-2 j / d)`` are computed in fp32 and the tables
@@ -313,19 +317,13 @@ class RotaryEmbedding(nn.Module):
 
     def forward(self, qkv: Tensor) -> Tensor:
         d = self.head_dim(qkv)
-        N, T, H, half = qkv.shape[0], qkv.shape[1], self.num_heads, d // 2
-        if self.num_kv_heads is not None:   # q | k is H + Hkv heads of d columns
-            rotated = H + self.num_kv_heads
-            cos, sin = (t.view(1, T, 1, half) for t in self.tables(T, d, qkv.device, qkv.dtype))
-            x = qkv[..., :rotated * d].view(N, T, rotated, d)
-            x1, x2 = x[..., :half], x[..., half:]
-            rot = torch.cat((x1 * cos - x2 * sin, x2 * cos + x1 * sin), -1).reshape(N, T, rotated * d)
-            return torch.cat((rot, qkv[..., rotated * d:]), -1)
-        cos, sin = (t.view(1, T, 1, 1, half) for t in self.tables(T, d, qkv.device, qkv.dtype))
-        x = qkv.view(N, T, 3, H, d)
-        x1, x2 = x[:, :, :2, :, :half], x[:, :, :2, :, half:]
-        rot = torch.cat((x1 * cos - x2 * sin, x2 * cos + x1 * sin), -1)          # q and k
-        return torch.cat((rot, x[:, :, 2:]), 2).reshape(N, T, 3 * H * d)
+        N, T, half = qkv.shape[0], qkv.shape[1], d // 2
+        rotated = self.num_heads + self.kv_heads   # q | k is H + Hkv heads of d columns; the Hkv d columns of v pass through
+        cos, sin = (t.view(1, T, 1, half) for t in self.tables(T, d, qkv.device, qkv.dtype))
+        x = qkv[..., :rotated * d].view(N, T, rotated, d)
+        x1, x2 = x[..., :half], x[..., half:]
+        rot = torch.cat((x1 * cos - x2 * sin, x2 * cos + x1 * sin), -1).reshape(N, T, rotated * d)
+        return torch.cat((rot, qkv[..., rotated * d:]), -1)
 
 
 class MultiheadSelfAttention(nn.Sequential):
@@ -338,10 +336,9 @@ class MultiheadSelfAttention(nn.Sequential):
                  window: int = None):
         if embed_dim % num_heads != 0:
             raise ValueError(f"embed_dim ({embed_dim}) is not divisible by num_heads ({num_heads})")
-        Hkv = _kv_heads(num_heads, num_kv_heads)
-        packed = 3 * embed_dim if Hkv is None else (num_heads + 2 * Hkv) * (embed_dim // num_heads)
-        super().__init__(nn.Linear(embed_dim, packed, bias=bias), ScaledDotProductAttention(num_heads, causal=causal, num_kv_heads=Hkv, window=window),
-                         nn.Linear(embed_dim, embed_dim, bias=bias))
+        attention = ScaledDotProductAttention(num_heads, causal=causal, num_kv_heads=num_kv_heads, window=window)
+        packed = (num_heads + 2 * attention.kv_heads) * (embed_dim // num_heads)
+        super().__init__(nn.Linear(embed_dim, packed, bias=bias), attention, nn.Linear(embed_dim, embed_dim, bias=bias))
 
     def set_lengths(self, lengths) -> None:
         """Per-sample sequence lengths of the padded batches to come (``None``: none), handed to the attention leaf."""

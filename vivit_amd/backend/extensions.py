@@ -18,9 +18,8 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from vivit_amd import _lib, kernels
-from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, Permute, ProductModule, RotaryEmbedding, ScaledDotProductAttention, ScaleModule, attention_visible,
-                                              Slicing,
-                                              SumModule, _gqa_split)
+from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, Permute, ProductModule, RotaryEmbedding, ScaledDotProductAttention, ScaleModule,
+                                              Slicing, SumModule, _gqa_split)
 from vivit_amd.utils.ggn import Vmp
 from vivit_amd.utils.gram import mVp, pairwise_dot
 
@@ -601,8 +600,7 @@ def _attention_out(module, x: Tensor, subsampling) -> Tensor:
         with torch.no_grad():
             return module.attend(x, _attention_lengths(module, x, subsampling))
     out = subsample(out.detach(), 0, subsampling)
-    Hkv = getattr(module, "num_kv_heads", None)   # the output has H d columns
-    want = (*x.shape[:2], x.shape[2] // 3 if Hkv is None else module.head_dim(x) * module.num_heads)
+    want = (*x.shape[:2], module.head_dim(x) * module.num_heads)   # the output has H d columns
     if tuple(out.shape) != want or out.device != x.device or out.dtype != x.dtype:
         raise ValueError(f"ScaledDotProductAttention: module.output {tuple(out.shape)} {out.dtype} on {out.device} after sub-sampling "
                          f"does not belong to the input {tuple(x.shape)} {x.dtype} on {x.device} (expected {want})")
@@ -622,55 +620,23 @@ def _attention_lengths(module, x: Tensor, subsampling) -> Optional[Tensor]:
     return lengths
 
 
-def _attention_dead(M: Tensor, x: Tensor, out: Tensor, lengths: Tensor):
-    """``M``, ``x`` and ``out`` with zeros at the dead positions ``t >= lengths[n]`` (whatever they hold there is not used), and the
-    mask ``[N, T, 1]`` of those positions."""
-    dead = (torch.arange(x.shape[1], device=x.device)[None, :] >= lengths[:, None])[:, :, None]
-    return M.masked_fill(dead, 0.0), x.masked_fill(dead, 0.0), out.masked_fill(dead, 0.0), dead
-
-
 def _attention_jac_t_torch(module, M: Tensor, x: Tensor, out: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
-    """The rule of csrc/attention.hip in plain torch (non-HIP or non-fp32 tensors): ``M [V, N, T, E]``, ``x [N, T, 3 E]``,
-    ``out [N, T, E]`` -> ``[V, N, T, 3 E]``.  ``lengths`` (int32 ``[N]`` or ``None``) and ``module.window``: the mask of the forward
-    pass; the rows of the dead positions are exact zeros.  No autograd."""
-    d, H = module.head_dim(x), module.num_heads
-    scale = module.scale_for(d)
+    """The rule of csrc/attention.hip in plain torch (non-HIP or non-fp32 tensors): ``M [V, N, T, H d]``, ``x [N, T, (H + 2 Hkv) d]``,
+    ``out [N, T, H d]`` -> ``[V, N, T, (H + 2 Hkv) d]``.  Query head ``h`` uses key / value head ``h // R``; dK and dV of a group are
+    the sums over its ``R = H / Hkv`` query heads (multi-head attention: ``R = 1``).  K and V are broadcast views over the group axis,
+    never expanded copies.  ``lengths`` (int32 ``[N]`` or ``None``) and ``module.window``: the mask of the forward pass; the rows of
+    the dead positions are exact zeros.  No autograd."""
+    d, H, Hkv = module.head_dim(x), module.num_heads, module.kv_heads
+    scale, R = module.scale_for(d), H // Hkv
     V, (N, T) = M.shape[0], x.shape[:2]
-    window = getattr(module, "window", None)
-    hidden = None
-    if lengths is not None or window is not None:
-        hidden = ~attention_visible(T, lengths, module.causal, window, x.device)
-        if lengths is not None:
-            M, x, out, dead = _attention_dead(M.reshape(V, N, T, -1), x, out, lengths)
-    elif module.causal:
-        hidden = torch.ones(T, T, dtype=torch.bool, device=x.device).triu(1)
-    if getattr(module, "num_kv_heads", None) is not None:
-        G = _attention_gqa_jac_t_torch(M, x, out, H, module.num_kv_heads, d, scale, hidden)
-        return G if lengths is None else G.masked_fill(dead, 0.0)
-    q, k, v = x.view(N, T, 3, H, d).permute(2, 0, 3, 1, 4)                       # each [N, H, T, d]
-    S = (q @ k.transpose(-1, -2)) * scale
-    if hidden is not None:
-        S = S.masked_fill(hidden if hidden.dim() == 2 else hidden[:, None], float("-inf"))
-    P = S.softmax(-1)                                                             # [N, H, T, T], shared by the V slices
-    dO = M.reshape(V, N, T, H, d).permute(0, 1, 3, 2, 4)                          # [V, N, H, T, d]
-    D = (dO * out.view(N, T, H, d).permute(0, 2, 1, 3)).sum(-1, keepdim=True)
-    dV = P.transpose(-1, -2) @ dO
-    dS = P * (dO @ v.transpose(-1, -2) - D)
-    dQ, dK = (dS @ k) * scale, (dS.transpose(-1, -2) @ q) * scale
-    G = torch.stack((dQ, dK, dV), 0).permute(1, 2, 4, 0, 3, 5).reshape(V, N, T, 3 * H * d)
-    return G if lengths is None else G.masked_fill(dead, 0.0)   # (a dead query saw itself: P = 1 on zeros; the sign of a zero)
-
-
-def _attention_gqa_jac_t_torch(M: Tensor, x: Tensor, out: Tensor, H: int, Hkv: int, d: int, scale: float, hidden) -> Tensor:
-    """Grouped-query attention, the same rule: ``x [N, T, (H + 2 Hkv) d]``, ``M [V, N, T, H d]`` -> ``[V, N, T, (H + 2 Hkv) d]``.
-    Query head ``h`` uses key / value head ``h // R``; dK and dV of a group are the sums over its ``R = H / Hkv`` query heads.  K and
-    V are broadcast views over the group axis, never expanded copies.  ``hidden``: the pairs that do not see each other, ``[T, T]``
-    or ``[N, T, T]`` (``None``: none).  No autograd."""
-    V, (N, T), R = M.shape[0], x.shape[:2], H // Hkv
+    M = M.reshape(V, N, T, H * d)
+    hidden, dead = module.masks(T, lengths, x.device)
+    if dead is not None:   # whatever the dead positions hold is not used
+        M, x, out = M.masked_fill(dead, 0.0), x.masked_fill(dead, 0.0), out.masked_fill(dead, 0.0)
     q, k, v = _gqa_split(x, H, Hkv, d)                                             # q [N, Hkv, R, T, d]; k, v [N, Hkv, 1, T, d]
     S = (q @ k.transpose(-1, -2)) * scale
     if hidden is not None:
-        S = S.masked_fill(hidden if hidden.dim() == 2 else hidden[:, None, None], float("-inf"))
+        S = S.masked_fill(hidden, float("-inf"))
     P = S.softmax(-1)                                                             # [N, Hkv, R, T, T], shared by the V slices
     dO = M.reshape(V, N, T, Hkv, R, d).permute(0, 1, 3, 4, 2, 5)                  # [V, N, Hkv, R, T, d]
     D = (dO * out.view(N, T, Hkv, R, d).permute(0, 2, 3, 1, 4)).sum(-1, keepdim=True)
@@ -679,28 +645,23 @@ def _attention_gqa_jac_t_torch(M: Tensor, x: Tensor, out: Tensor, H: int, Hkv: i
     # the sum over the group's heads and over the queries is one contraction of length R T
     dV = P.reshape(N, Hkv, R * T, T).transpose(-1, -2) @ dO.reshape(V, N, Hkv, R * T, d)
     dK = (dS.reshape(V, N, Hkv, R * T, T).transpose(-1, -2) @ q.reshape(N, Hkv, R * T, d)) * scale
-    return torch.cat((dQ.permute(0, 1, 4, 2, 3, 5).reshape(V, N, T, H * d), dK.permute(0, 1, 3, 2, 4).reshape(V, N, T, Hkv * d),
-                      dV.permute(0, 1, 3, 2, 4).reshape(V, N, T, Hkv * d)), -1)
+    G = torch.cat((dQ.permute(0, 1, 4, 2, 3, 5).reshape(V, N, T, H * d), dK.permute(0, 1, 3, 2, 4).reshape(V, N, T, Hkv * d),
+                   dV.permute(0, 1, 3, 2, 4).reshape(V, N, T, Hkv * d)), -1)
+    return G if dead is None else G.masked_fill(dead, 0.0)   # (a dead query saw itself: P = 1 on zeros; the sign of a zero)
 
 
 def _rope_jac_t_torch(module, M: Tensor, x: Tensor) -> Tensor:
-    """The rule of ``vivit_rope_jac_t_f32`` in plain torch (non-HIP or non-fp32 tensors): the transposed rotation on the q and k
-    thirds of ``M [V, N, T, 3 E]`` with the tables of the forward pass, the v third as it is.  No autograd."""
-    d, H = module.head_dim(x), module.num_heads
+    """The rule of ``vivit_rope_gqa_jac_t_f32`` in plain torch (non-HIP or non-fp32 tensors): the transposed rotation on the
+    ``H + Hkv`` heads of the q and k parts of ``M [V, N, T, (H + 2 Hkv) d]`` with the tables of the forward pass, the ``Hkv d`` columns
+    of v as they are.  No autograd."""
+    d, rotated = module.head_dim(x), module.num_heads + module.kv_heads
     V, (N, T), half = M.shape[0], x.shape[:2], d // 2
-    if getattr(module, "num_kv_heads", None) is not None:   # q | k is H + Hkv heads of d columns, then Hkv d columns of v
-        rotated = H + module.num_kv_heads
-        cos, sin = (t.view(1, 1, T, 1, half) for t in module.tables(T, d, x.device, x.dtype))
-        m = M.reshape(V, N, T, -1)
-        mr = m[..., :rotated * d].reshape(V, N, T, rotated, d)
-        m1, m2 = mr[..., :half], mr[..., half:]
-        rot = torch.cat((m1 * cos + m2 * sin, m2 * cos - m1 * sin), -1).reshape(V, N, T, rotated * d)
-        return torch.cat((rot, m[..., rotated * d:]), -1)
-    cos, sin = (t.view(1, 1, T, 1, 1, half) for t in module.tables(T, d, x.device, x.dtype))
-    m = M.reshape(V, N, T, 3, H, d)
-    m1, m2 = m[:, :, :, :2, :, :half], m[:, :, :, :2, :, half:]
-    rot = torch.cat((m1 * cos + m2 * sin, m2 * cos - m1 * sin), -1)
-    return torch.cat((rot, m[:, :, :, 2:]), 3).reshape(V, N, T, 3 * H * d)
+    cos, sin = (t.view(1, 1, T, 1, half) for t in module.tables(T, d, x.device, x.dtype))
+    m = M.reshape(V, N, T, -1)
+    mr = m[..., :rotated * d].reshape(V, N, T, rotated, d)
+    m1, m2 = mr[..., :half], mr[..., half:]
+    rot = torch.cat((m1 * cos + m2 * sin, m2 * cos - m1 * sin), -1).reshape(V, N, T, rotated * d)
+    return torch.cat((rot, m[..., rotated * d:]), -1)
 
 
 def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optional[Tensor]:
@@ -802,7 +763,7 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
     if isinstance(module, RotaryEmbedding):   # the very tables the forward pass used (cached on the module)
         d = module.head_dim(x)
         return kernels.rope_jac_t(M.reshape(M.shape[0], *x.shape), *module.tables(x.shape[1], d, x.device, x.dtype), module.num_heads,
-                                  num_kv_heads=module.num_kv_heads)
+                                  num_kv_heads=module.kv_heads)
     if isinstance(module, ScaledDotProductAttention):
         # (a head dimension above the kernel's 128 has no kernel: the generic rule, before any operand is prepared; sizes beyond
         # the kernel's index arithmetic come back as VIVIT_E_UNSUPPORTED and the caller falls through likewise)
@@ -811,8 +772,8 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
         if d > 128:   # (with lengths the formula in torch: the generic rule's forward pass would not know the sub-sampled ones)
             return None if lengths is None else _attention_jac_t_torch(module, M, x, _attention_out(module, x, subsampling), lengths)
         return kernels.attention_jac_t(M.reshape(M.shape[0], *x.shape[:2], -1), x, _attention_out(module, x, subsampling), module.num_heads,
-                                       module.scale_for(d), module.causal, num_kv_heads=module.num_kv_heads, lengths=lengths,
-                                       window=getattr(module, "window", None))
+                                       module.scale_for(d), module.causal, num_kv_heads=module.kv_heads, lengths=lengths,
+                                       window=module.window)
     if isinstance(module, _BATCHNORM) and x.dim() >= 2:
         if _own_params(module):   # the parameter rules want the two row sums of the same pass
             return _bn_eval_rules(module, M, x)[0]

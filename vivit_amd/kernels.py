@@ -644,26 +644,32 @@ def gate_jac_t(M, a, b, want=(True, True), out_a=None, out_b=None):
     return Ga, Gb
 
 
+def _packed_heads(num_heads, num_kv_heads):
+    """``(Hkv, text)`` of a packed projection ``[..., (num_heads + 2 Hkv) * d]``: the key / value heads, checked -- ``num_heads`` query
+    heads in ``num_kv_heads`` groups of consecutive heads; ``None`` is multi-head attention, ``Hkv = num_heads`` -- and how the
+    messages write the number of heads."""
+    if num_kv_heads is None:
+        return num_heads, f"3 * {num_heads}"
+    if num_heads < 1 or num_kv_heads < 1 or num_heads % num_kv_heads != 0:
+        raise ValueError(f"num_heads H = {num_heads} must be a positive multiple of num_kv_heads Hkv = {num_kv_heads} >= 1")
+    return num_kv_heads, f"({num_heads} + 2 * {num_kv_heads})"
+
+
 @_launcher
 def rope_jac_t(M, cos, sin, num_heads: int, out=None, num_kv_heads: int = None):
-    """Transposed Jacobian of the rotary position embedding on a packed projection (``vivit_rope_jac_t_f32``): ``M [..., T, 3 E]``
+    """Transposed Jacobian of the rotary position embedding on a packed projection (``vivit_rope_gqa_jac_t_f32``): ``M [..., T, 3 E]``
     (``E = num_heads * d``), ``cos`` / ``sin [T, d / 2]`` -> like ``M``: the q and k thirds rotated back, the v third copied.
-    ``out``: a buffer for the result; ``M`` itself for the rule in place.  ``num_kv_heads`` (grouped-query attention,
-    ``vivit_rope_gqa_jac_t_f32``): ``M [..., T, (num_heads + 2 * num_kv_heads) * d]``, the ``num_heads + num_kv_heads`` heads of
+    ``out``: a buffer for the result; ``M`` itself for the rule in place.  ``num_kv_heads`` (grouped-query attention; ``None`` is
+    ``num_heads``, the three thirds): ``M [..., T, (num_heads + 2 * num_kv_heads) * d]``, the ``num_heads + num_kv_heads`` heads of
     the q and k parts rotated back, the v part copied."""
     _require_device(M, cos, sin)
     if out is M and not M.is_contiguous():
         raise ValueError("the rule in place needs a contiguous M")
     M, cos, sin = M.contiguous(), cos.contiguous(), sin.contiguous()
-    if num_kv_heads is None:
-        if M.dim() < 2 or num_heads < 1 or M.shape[-1] == 0 or M.shape[-1] % (6 * num_heads) != 0:
-            raise ValueError(f"M must be [..., T, 3 * {num_heads} heads * an even head dimension], got {tuple(M.shape)}")
-        heads = 3 * num_heads
-    else:
-        _check_kv_heads(num_heads, num_kv_heads)
-        heads = num_heads + 2 * num_kv_heads
-        if M.dim() < 2 or M.shape[-1] == 0 or M.shape[-1] % (2 * heads) != 0:
-            raise ValueError(f"M must be [..., T, ({num_heads} + 2 * {num_kv_heads}) heads * an even head dimension], got {tuple(M.shape)}")
+    Hkv, heads_text = _packed_heads(num_heads, num_kv_heads)
+    heads = num_heads + 2 * Hkv
+    if M.dim() < 2 or num_heads < 1 or M.shape[-1] == 0 or M.shape[-1] % (2 * heads) != 0:
+        raise ValueError(f"M must be [..., T, {heads_text} heads * an even head dimension], got {tuple(M.shape)}")
     T, d = M.shape[-2], M.shape[-1] // heads
     if tuple(cos.shape) != (T, d // 2) or tuple(sin.shape) != (T, d // 2):
         raise ValueError(f"cos and sin must be {(T, d // 2)}, got {tuple(cos.shape)} and {tuple(sin.shape)}")
@@ -675,36 +681,27 @@ def rope_jac_t(M, cos, sin, num_heads: int, out=None, num_kv_heads: int = None):
         if M.data_ptr() < hi and lo < M.data_ptr() + 4 * M.numel() and G.data_ptr() != M.data_ptr():
             raise ValueError("out must be M itself or must not overlap it")
     rows = M.numel() // (T * M.shape[-1])
-    if num_kv_heads is None:
-        st = _lib.load().vivit_rope_jac_t_f32(M.data_ptr(), cos.data_ptr(), sin.data_ptr(), G.data_ptr(), rows, T, num_heads, d, _stream(M))
-        _lib.check(st, "vivit_rope_jac_t_f32")
-    else:
-        st = _lib.load().vivit_rope_gqa_jac_t_f32(M.data_ptr(), cos.data_ptr(), sin.data_ptr(), G.data_ptr(), rows, T, num_heads,
-                                                 num_kv_heads, d, _stream(M))
-        _lib.check(st, "vivit_rope_gqa_jac_t_f32")
+    st = _lib.load().vivit_rope_gqa_jac_t_f32(M.data_ptr(), cos.data_ptr(), sin.data_ptr(), G.data_ptr(), rows, T, num_heads, Hkv, d, _stream(M))
+    _lib.check(st, "vivit_rope_gqa_jac_t_f32")
     return G
-
-
-def _check_kv_heads(num_heads, num_kv_heads):
-    """Grouped-query attention: ``num_heads`` query heads in ``num_kv_heads`` groups of consecutive heads."""
-    if num_heads < 1 or num_kv_heads < 1 or num_heads % num_kv_heads != 0:
-        raise ValueError(f"num_heads H = {num_heads} must be a positive multiple of num_kv_heads Hkv = {num_kv_heads} >= 1")
 
 
 @_launcher
 def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None, window: int = None):
-    """Transposed input Jacobian of scaled dot-product self-attention (``vivit_attention_jac_t_f32``): ``M [V, N, T, E]`` (the factor
-    at the module output), ``qkv [N, T, 3 E]`` (the module input, q | k | v), ``out [N, T, E]`` (the module output of the forward
-    pass) -> ``[V, N, T, 3 E]``.  ``E = num_heads * d``; no ``T x T`` tensor is allocated.  ``num_kv_heads`` (grouped-query
-    attention, ``vivit_attention_gqa_jac_t_f32``): ``qkv [N, T, (num_heads + 2 * num_kv_heads) * d]``, query head ``h`` attends
-    to key / value head ``h // (num_heads // num_kv_heads)``; the result is packed ``dQ | dK | dV`` like ``qkv``.
+    """Transposed input Jacobian of scaled dot-product self-attention (``vivit_attention_masked_jac_t_f32``, the one entry that
+    launches): ``M [V, N, T, E]`` (the factor at the module output), ``qkv [N, T, 3 E]`` (the module input, q | k | v), ``out [N, T, E]``
+    (the module output of the forward pass) -> ``[V, N, T, 3 E]``.  ``E = num_heads * d``; no ``T x T`` tensor is allocated.
+    ``num_kv_heads`` (grouped-query attention; ``None`` is ``num_heads``, the three thirds): ``qkv [N, T, (num_heads + 2 *
+    num_kv_heads) * d]``, query head ``h`` attends to key / value head ``h // (num_heads // num_kv_heads)``; the result is packed
+    ``dQ | dK | dV`` like ``qkv``.
 
-    ``lengths`` (anything ``torch.as_tensor`` turns into ``N`` integers; ``vivit_attention_masked_jac_t_f32``): sample ``n`` has
-    the positions ``0 .. lengths[n] - 1`` (right padding; the kernel clamps to ``[0, T]``).  The positions beyond are dead: invisible
-    as keys, rows of exact zeros in the result, and whatever ``M``, ``qkv`` and ``out`` hold there is never read.  The values go to
-    ``M``'s device as int32 and are not looked at on the host.  ``window`` (an integer ``>= 1``): query ``i`` sees the keys with
-    ``|i - j| < window`` (with ``causal`` the ``window`` keys up to and including its own).  With both ``None`` the call is the one
-    it was."""
+    ``lengths`` (anything ``torch.as_tensor`` turns into ``N`` integers): sample ``n`` has the positions ``0 .. lengths[n] - 1``
+    (right padding; the kernel clamps to ``[0, T]``).  The positions beyond are dead: invisible as keys, rows of exact zeros in the
+    result, and whatever ``M``, ``qkv`` and ``out`` hold there is never read.  The values go to ``M``'s device as int32 and are not
+    looked at on the host.  ``window`` (an integer ``>= 1``): query ``i`` sees the keys with ``|i - j| < window`` (with ``causal`` the
+    ``window`` keys up to and including its own).  With both ``None`` (a null pointer and ``window = 0`` for the entry) the kernels
+    walk every key block unmasked: what the entries without them, ``vivit_attention_jac_t_f32`` and
+    ``vivit_attention_gqa_jac_t_f32``, hand to the same entry."""
     _require_device(M, qkv, out)
     if window is not None and (isinstance(window, bool) or int(window) != window or window < 1):
         raise ValueError(f"window must be an integer >= 1 (or None), got {window!r}")
@@ -716,44 +713,27 @@ def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num
             raise ValueError(f"lengths must be [N] = [{qkv.shape[0] if qkv.dim() == 3 else '?'}], got {tuple(lengths.shape)}")
         lengths = lengths.to(device=M.device, dtype=torch.int32).contiguous()
     M, qkv, out = M.contiguous(), qkv.contiguous(), out.contiguous()
-    if num_kv_heads is None:
-        if qkv.dim() != 3 or num_heads < 1 or qkv.shape[2] == 0 or qkv.shape[2] % (3 * num_heads) != 0:
-            raise ValueError(f"qkv must be [N, T, 3 * {num_heads} * d], got {tuple(qkv.shape)}")
-        N, T, E3 = qkv.shape
-        E = E3 // 3
-    else:
-        _check_kv_heads(num_heads, num_kv_heads)
-        heads = num_heads + 2 * num_kv_heads
-        if qkv.dim() != 3 or qkv.shape[2] == 0 or qkv.shape[2] % heads != 0:
-            raise ValueError(f"qkv must be [N, T, ({num_heads} + 2 * {num_kv_heads}) * d], got {tuple(qkv.shape)}")
-        N, T, E3 = qkv.shape
-        E = E3 // heads * num_heads
+    Hkv, heads_text = _packed_heads(num_heads, num_kv_heads)
+    heads = num_heads + 2 * Hkv
+    if qkv.dim() != 3 or num_heads < 1 or qkv.shape[2] == 0 or qkv.shape[2] % heads != 0:
+        raise ValueError(f"qkv must be [N, T, {heads_text} * d], got {tuple(qkv.shape)}")
+    N, T, E3 = qkv.shape
+    d = E3 // heads
+    E = num_heads * d
     if tuple(out.shape) != (N, T, E):
         raise ValueError(f"out must be {(N, T, E)}, got {tuple(out.shape)}")
     if M.dim() != 4 or tuple(M.shape[1:]) != (N, T, E):
         raise ValueError(f"M must be [V, {N}, {T}, {E}], got {tuple(M.shape)}")
-    Vd, d = M.shape[0], E // num_heads
+    Vd = M.shape[0]
     if Vd == 0 or N == 0 or T == 0:
         raise ValueError(f"empty operands: M {tuple(M.shape)}")
     G = torch.empty((Vd, N, T, E3), dtype=torch.float32, device=M.device)
     lib = _lib.load()
-    if lengths is not None or window is not None:
-        Hkv = num_heads if num_kv_heads is None else num_kv_heads
-        ws, ws_bytes = _workspace(lib.vivit_attention_masked_jac_t_f32_workspace_bytes(Vd, N, T, num_heads, Hkv, d), M)
-        st = lib.vivit_attention_masked_jac_t_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), G.data_ptr(), Vd, N, T, num_heads, Hkv, d,
-                                                  float(scale), int(bool(causal)), None if lengths is None else lengths.data_ptr(),
-                                                  0 if window is None else int(window), ws, ws_bytes, _stream(M))
-        _lib.check(st, "vivit_attention_masked_jac_t_f32")
-    elif num_kv_heads is None:
-        ws, ws_bytes = _workspace(lib.vivit_attention_jac_t_f32_workspace_bytes(Vd, N, T, num_heads, d), M)
-        st = lib.vivit_attention_jac_t_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), G.data_ptr(), Vd, N, T, num_heads, d, float(scale),
-                                           int(bool(causal)), ws, ws_bytes, _stream(M))
-        _lib.check(st, "vivit_attention_jac_t_f32")
-    else:
-        ws, ws_bytes = _workspace(lib.vivit_attention_gqa_jac_t_f32_workspace_bytes(Vd, N, T, num_heads, num_kv_heads, d), M)
-        st = lib.vivit_attention_gqa_jac_t_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), G.data_ptr(), Vd, N, T, num_heads,
-                                               num_kv_heads, d, float(scale), int(bool(causal)), ws, ws_bytes, _stream(M))
-        _lib.check(st, "vivit_attention_gqa_jac_t_f32")
+    ws, ws_bytes = _workspace(lib.vivit_attention_masked_jac_t_f32_workspace_bytes(Vd, N, T, num_heads, Hkv, d), M)
+    st = lib.vivit_attention_masked_jac_t_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), G.data_ptr(), Vd, N, T, num_heads, Hkv, d,
+                                              float(scale), int(bool(causal)), None if lengths is None else lengths.data_ptr(),
+                                              0 if window is None else int(window), ws, ws_bytes, _stream(M))
+    _lib.check(st, "vivit_attention_masked_jac_t_f32")
     return G
 
 
