@@ -376,6 +376,34 @@ size_t vivit_attention_masked_jac_t_f32_workspace_bytes(int64_t V, int64_t N, in
 int vivit_attention_masked_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
                                      int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths,
                                      int64_t window, void *workspace, size_t workspace_bytes, void *stream);
+/* Cross-attention: the same rule when the queries and the keys come from two sequences (attention.hip; call site
+ * vivit_amd/kernels.py:cross_attention_jac_t, for vivit_amd.backend.ScaledDotProductCrossAttention).  All tensors dense:
+ * q [N, Tq, H d], kv [N, Tk, 2 Hkv d] = k | v (Hkv key heads of d columns, then Hkv value heads: the packed layout above without
+ * its query part), out and M [V, N, Tq, H d]; Gq [V, N, Tq, H d] = dQ and Gkv [V, N, Tk, 2 Hkv d] = dK | dV.  Query head h uses key /
+ * value head h / (H / Hkv).  There is NO causal flag and NO window: with Tq != Tk there is no agreed alignment of the diagonal.
+ * q_lengths, k_lengths [N] int32 on the device, either may be NULL (every sample has Tq / Tk positions): right padding, clamped in
+ * the kernels to Lq in [0, Tq] and Lk in [0, Tk].  Key j of sample n is live iff j < Lk[n]; query i is live iff i < Lq[n] AND
+ * Lk[n] > 0 (a query with no key to look at is dead, it is not a NaN); a live query sees every live key.  The rows of the dead
+ * positions of Gq and Gkv are written as +0, no operand row of a dead position is ever loaded (NaN there reaches nothing), and only
+ * the 32 x 32 tiles with a live pair are visited.  Gq or Gkv may be NULL, not both (VIVIT_E_BADARG): the owner of a NULL result is
+ * not launched -- Gkv == NULL (a frozen memory) skips the key-block owner, Gq == NULL the query-block owner; the lse and row-dot
+ * launches serve either.  The summation orders are those above (dK, dV: query heads of the group ascending, query blocks
+ * ascending, k within the block ascending; dQ: key blocks ascending), no atomics, no second pass, no Tq x Tk data in memory: the
+ * bytes of G[v, n] depend on (Tq, Tk, H, Hkv, d, scale), the two lengths of n and the data of (v, n) only; with Tq = Tk, equal
+ * lengths and q | kv one packed projection they are those of vivit_attention_masked_jac_t_f32 with causal = 0 and window = 0, and
+ * sample n has the bytes of the call on that sample cut to (Lq, Lk) without lengths.  The workspace, lse [N, H, Tq] and
+ * D [V, N, H, Tq], is vivit_attention_gqa_jac_t_f32_workspace_bytes(V, N, Tq, H, Hkv, d) bytes, whatever Tk; the query returns 0 for
+ * arguments the entry point refuses.  VIVIT_E_BADARG: non-positive sizes, H % Hkv != 0, a null operand, both results null.
+ * VIVIT_E_UNSUPPORTED (nothing launched, and before the workspace is looked at): d > 128, the chunk limit above, and sizes beyond
+ * the kernels' index arithmetic (the pitches H d and 2 Hkv d -- (H + 2 Hkv) d is what is checked --, the block counts
+ * N H ceil(Tq / 32) and N Hkv ceil(Tk / 32), or V N H Tq / 256 above 2^31 - 1; N H Tq or N Hkv Tk above 2^40).  VIVIT_E_WORKSPACE: a
+ * missing or short workspace. */
+size_t vivit_attention_cross_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t Tq, int64_t Tk, int64_t H, int64_t Hkv,
+                                                       int64_t d);
+int vivit_attention_cross_jac_t_f32(const float *M, const float *q, const float *kv, const float *out, float *Gq, float *Gkv,
+                                    int64_t V, int64_t N, int64_t Tq, int64_t Tk, int64_t H, int64_t Hkv, int64_t d, float scale,
+                                    const int32_t *q_lengths, const int32_t *k_lengths, void *workspace, size_t workspace_bytes,
+                                    void *stream);
 /* nn.Embedding (embedding.hip; the reference has no rule for it): the weight factor Vt[v, n, w, :] = sum_{t: idx[n, t] = w} M[v, n, t, :]
  * of the factor M [V, N, T, D] at the module output has at most T non-zero rows per (v, n) out of W = num_embeddings and is kept
  * compact: ids [N, T] int32 holds sample n's distinct tokens in strictly increasing order in its first U_n slots and -1 in the rest,

@@ -62,7 +62,9 @@ SIGNATURES = {
     "vivit_attention_gqa_jac_t_f32": (_int, [_ptr, _ptr, _ptr, _ptr] + [_i64] * 6 + [_f32, _int, _ptr, _sz, _ptr]),
     "vivit_attention_masked_jac_t_f32_workspace_bytes": (_sz, [_i64] * 6),
     "vivit_attention_masked_jac_t_f32": (_int, [_ptr, _ptr, _ptr, _ptr] + [_i64] * 6 + [_f32, _int, _ptr, _i64, _ptr, _sz, _ptr]),
-    "vivit_embedding_compact_f32": (_int, [_ptr] * 5 + [_i64] * 4 + [_ptr]),
+    "vivit_attention_cross_jac_t_f32_workspace_bytes": (_sz, [_i64] * 7),
+    "vivit_attention_cross_jac_t_f32": (_int, [_ptr] * 6 + [_i64] * 7 + [_f32, _ptr, _ptr, _ptr, _sz, _ptr]),
+    "vivit_embedding_compact_f32":(_int, [_ptr] * 5 + [_i64] * 4 + [_ptr]),
     "vivit_embedding_gram_f32_workspace_bytes": (_sz, [_i64] * 4),
     "vivit_embedding_gram_f32": (_int, [_ptr, _ptr, _ptr] + [_i64] * 4 + [_f32, _f32, _ptr, _sz, _ptr]),
     "vivit_embedding_vmp_f32": (_int, [_ptr] * 5 + [_i64] * 6 + [_ptr]),
@@ -117,7 +119,7 @@ SIGNATURES = {
 }
 
 # include/vivit_hip.h of this checkout (vivit_hip_abi_version).  The batched entry points (two-phase solve, Gram-space
-# directions, the attention, Embedding and sequence-Linear rules, the per-position loss factor, grouped-query and masked attention) only ADD exports: the
+# directions, the attention, Embedding and sequence-Linear rules, the per-position loss factor, grouped-query, masked and cross attention) only ADD exports: the
 # number stays; a library without them is refused by the symbol lookup in load() and by the source hash (_check_provenance).
 ABI_VERSION = 1008
 

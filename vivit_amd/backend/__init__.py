@@ -8,7 +8,8 @@ provided here for feed-forward and residual nets (Linear, Conv1d/2d/3d, ConvTran
 eval mode, element-wise activations, pooling, Flatten, Dropout in eval mode, and the branching modules
 ``Parallel`` / ``SumModule`` / ``Pad`` / ``Slicing`` / ``ScaleModule`` of ``backpack.custom_module``, LayerNorm / GroupNorm,
 the self-attention modules ``ScaledDotProductAttention`` / ``MultiheadSelfAttention`` of ``custom_module`` (causal,
-grouped queries, sliding windows, right-padded batches through ``set_lengths``), ``nn.Embedding``,
+grouped queries, sliding windows, right-padded batches through ``set_lengths``), the cross-attention modules
+``ScaledDotProductCrossAttention`` / ``MultiheadCrossAttention`` (queries over a second sequence), ``nn.Embedding``,
 ``nn.RMSNorm`` and the modules ``ProductModule`` (gated MLPs) / ``RotaryEmbedding`` of ``custom_module``;
 CrossEntropyLoss / MSELoss with ``reduction='mean'`` or ``'sum'``, on outputs ``[N, C]`` and on outputs with positions
 ``[N, C, *D]`` -- next-token cross entropy over a whole sequence, segmentation, dense regression -- with ``Permute`` of
@@ -21,6 +22,7 @@ Jacobian rules and the HIP kernels only where a rule is GEMM-shaped.
 """
 from vivit_amd.backend.custom_module import (
     ActiveIdentity,
+    MultiheadCrossAttention,
     MultiheadSelfAttention,
     Pad,
     Parallel,
@@ -28,6 +30,7 @@ from vivit_amd.backend.custom_module import (
     ProductModule,
     RotaryEmbedding,
     ScaledDotProductAttention,
+    ScaledDotProductCrossAttention,
     ScaleModule,
     Slicing,
     SumModule,
@@ -41,4 +44,4 @@ from vivit_amd.backend.extensions import (
     ViViTGGNMC,
 )
 
-__all__ = ["ActiveIdentity", "MultiheadSelfAttention", "Pad", "Parallel", "Permute", "ProductModule", "RotaryEmbedding", "ScaledDotProductAttention", "ScaleModule", "Slicing", "SumModule", "backpack", "extend", "BatchGrad", "SqrtGGNExact", "SqrtGGNMC", "ViViTGGNExact", "ViViTGGNMC"]
+__all__ = ["ActiveIdentity", "MultiheadCrossAttention", "MultiheadSelfAttention", "Pad", "Parallel", "Permute", "ProductModule", "RotaryEmbedding", "ScaledDotProductAttention", "ScaledDotProductCrossAttention", "ScaleModule", "Slicing", "SumModule", "backpack", "extend", "BatchGrad", "SqrtGGNExact", "SqrtGGNMC", "ViViTGGNExact", "ViViTGGNMC"]

@@ -360,3 +360,173 @@ class MultiheadSelfAttention(nn.Sequential):
                 new[0].bias.copy_(mha.in_proj_bias)
                 new[2].bias.copy_(mha.out_proj.bias)
         return new
+
+
+def _checked_lengths(lengths, name: str):
+    """A ``set_lengths`` argument as an integer tensor ``[N]`` (``None`` stays ``None``)."""
+    if lengths is None:
+        return None
+    lengths = torch.as_tensor(lengths)
+    if lengths.dim() != 1 or lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
+        raise ValueError(f"{name} must be integers [N], got {lengths.dtype} {tuple(lengths.shape)}")
+    return lengths
+
+
+def _lengths_for(lengths, name: str, N: int, T: int, device):
+    """``lengths`` of set_lengths() for a batch of ``N`` samples of ``T`` positions as int32 on ``device``, checked on the host only."""
+    if lengths is None:
+        return None
+    if lengths.shape[0] != N:
+        raise ValueError(f"set_lengths() was given {lengths.shape[0]} {name}, the batch has {N} samples")
+    if lengths.device.type == "cpu" and N > 0 and (int(lengths.min()) < 0 or int(lengths.max()) > T):
+        raise ValueError(f"{name} must lie in [0, T = {T}], got {lengths.tolist()}")
+    return lengths.to(device=device, dtype=torch.int32)
+
+
+class ScaledDotProductCrossAttention(nn.Module):
+    """Multi-head scaled dot-product attention of queries over a SECOND sequence (no counterpart in BackPACK): a parameter-free leaf
+    of two inputs, ``forward(q, kv)``.
+
+    ``q [N, Tq, H d]`` (head ``h`` owns the columns ``h d .. (h + 1) d``) and ``kv [N, Tk, 2 Hkv d]`` = k | v: ``Hkv`` key heads of
+    ``d`` columns, then ``Hkv`` value heads -- the packed layout of :class:`ScaledDotProductAttention` without its query part.
+    ``num_kv_heads`` (``None``: ``Hkv = H``): query head ``h`` attends to key / value head ``h // (H / Hkv)``.  Output ``[N, Tq, H d]``:
+    per head ``softmax(scale q k^T) v`` with ``scale = 1 / sqrt(d)`` by default.
+
+    NOT supported: no causal mask and no window (with ``Tq != Tk`` there is no agreed alignment of the diagonal), no dropout, no
+    arbitrary or additive mask.
+
+    Padded batches: ``set_lengths(query_lengths, key_lengths)`` gives sample ``n`` the queries ``0 .. query_lengths[n] - 1`` and the
+    keys ``0 .. key_lengths[n] - 1`` (RIGHT padding only; either may be ``None``: every position) for every forward pass until it is
+    reset.  Key ``j`` is live iff ``j < key_lengths[n]``; query ``i`` is live iff ``i < query_lengths[n]`` AND ``key_lengths[n] > 0``:
+    a query with no key to look at is dead, it is not a NaN.  Dead keys are invisible, the output rows of dead queries are exact
+    zeros, nothing flows back to a dead position, and whatever the inputs hold there (NaN included) reaches no live position.  The
+    softmax has no empty row: a dead query is given key 0 to look at (on zeroed data), and its output row is set to zero.  Lengths
+    are a sequence or an integer tensor ``[N]``: one on the host is checked to lie in ``[0, Tq]`` / ``[0, Tk]`` at the next forward
+    pass; one on a device is never read on the host and is clamped, as the kernel of the extensions' rule clamps it.  The forward
+    pass keeps the int32 tensors it used on the module (``forward_query_lengths``, ``forward_key_lengths``), and the rule reads
+    those: the very lengths of the forward pass."""
+
+    def __init__(self, num_heads: int, scale: float = None, num_kv_heads: int = None):
+        super().__init__()
+        if num_heads < 1:
+            raise ValueError(f"num_heads must be positive, got {num_heads}")
+        self.num_heads, self.scale = int(num_heads), scale
+        self.num_kv_heads = _kv_heads(num_heads, num_kv_heads)
+        self._query_lengths = self._key_lengths = None                  # what set_lengths() was given
+        self.forward_query_lengths = self.forward_key_lengths = None    # int32 [N] on the inputs' device: what the last forward() used
+
+    def set_lengths(self, query_lengths=None, key_lengths=None) -> None:
+        """Per-sample lengths of the two sequences of the batches to come (``None``: none); see the class docstring."""
+        query_lengths = _checked_lengths(query_lengths, "query_lengths")
+        self._query_lengths, self._key_lengths = query_lengths, _checked_lengths(key_lengths, "key_lengths")
+
+    @property
+    def kv_heads(self) -> int:
+        """``Hkv``: ``num_kv_heads``, or ``num_heads`` where none was given."""
+        return self.num_heads if self.num_kv_heads is None else self.num_kv_heads
+
+    def head_dim(self, q: Tensor, kv: Tensor) -> int:
+        """The head dimension ``d`` of ``q [N, Tq, H d]`` and ``kv [N, Tk, 2 Hkv d]``, checked."""
+        H, Hkv = self.num_heads, self.kv_heads
+        if q.dim() != 3 or q.shape[2] == 0 or q.shape[2] % H != 0:
+            raise ValueError(f"expected queries [N, Tq, H d] with H = {H}, got {tuple(q.shape)}")
+        d = q.shape[2] // H
+        if kv.dim() != 3 or kv.shape[0] != q.shape[0] or kv.shape[1] == 0 or kv.shape[2] != 2 * Hkv * d:
+            raise ValueError(f"expected keys and values [N = {q.shape[0]}, Tk, 2 Hkv d = 2 * {Hkv} * {d}], got {tuple(kv.shape)}")
+        return d
+
+    def scale_for(self, d: int) -> float:
+        return float(self.scale) if self.scale is not None else d ** -0.5
+
+    def forward(self, q: Tensor, kv: Tensor) -> Tensor:
+        self.head_dim(q, kv)
+        N, Tq, Tk = q.shape[0], q.shape[1], kv.shape[1]
+        self.forward_query_lengths = _lengths_for(self._query_lengths, "query_lengths", N, Tq, q.device)
+        self.forward_key_lengths = _lengths_for(self._key_lengths, "key_lengths", N, Tk, q.device)
+        return self.attend(q, kv, self.forward_query_lengths, self.forward_key_lengths)
+
+    @staticmethod
+    def masks(N: int, Tq: int, Tk: int, query_lengths, key_lengths, device):
+        """``(hidden, dead_q, dead_k)`` for lengths given as int32 ``[N]`` on ``device`` or ``None``; three ``None`` without any.
+        ``hidden [N, 1, 1, Tq, Tk]``: the pairs (query, key) that do not see each other -- a dead query keeps key 0, so that no row
+        is empty; ``dead_q [N, Tq, 1]``, ``dead_k [N, Tk, 1]``: the dead positions."""
+        if query_lengths is None and key_lengths is None:
+            return None, None, None
+        lk = torch.full((N,), Tk, dtype=torch.int32, device=device) if key_lengths is None else key_lengths
+        lq = torch.full((N,), Tq, dtype=torch.int32, device=device) if query_lengths is None else query_lengths
+        lq = torch.where(lk > 0, lq, torch.zeros_like(lq))              # no key to look at: the queries are dead
+        dead_q = torch.arange(Tq, device=device)[None, :] >= lq[:, None]    # [N, Tq]
+        dead_k = torch.arange(Tk, device=device)[None, :] >= lk[:, None]    # [N, Tk]
+        first = torch.arange(Tk, device=device) == 0
+        hidden = torch.where(dead_q[:, :, None], ~first[None, None, :], dead_k[:, None, :])
+        return hidden[:, None, None], dead_q[:, :, None], dead_k[:, :, None]
+
+    def split(self, q: Tensor, kv: Tensor, d: int) -> Tuple[Tensor, Tensor, Tensor]:
+        """Views ``q [*B, Hkv, R, Tq, d]`` and ``k``, ``v [*B, Hkv, 1, Tk, d]`` of ``q [*B, Tq, H d]`` and ``kv [*B, Tk, 2 Hkv d]``."""
+        Hkv, nb = self.kv_heads, q.dim() - 2
+        qh = q.unflatten(-1, (Hkv, self.num_heads // Hkv, d)).permute(*range(nb), nb + 1, nb + 2, nb, nb + 3)
+        k, v = kv.unflatten(-1, (2 * Hkv, d)).split((Hkv, Hkv), -2)
+        heads = lambda t: t.permute(*range(nb), nb + 1, nb, nb + 2).unsqueeze(-3)   # [*B, Tk, Hkv, d] -> [*B, Hkv, 1, Tk, d]  # noqa: E731
+        return qh, heads(k), heads(v)
+
+    def attend(self, q: Tensor, kv: Tensor, query_lengths, key_lengths) -> Tensor:
+        """The forward pass with explicit lengths (int32 ``[N]`` on the device of the inputs, or ``None``)."""
+        d = self.head_dim(q, kv)
+        N, Tq, H = q.shape[0], q.shape[1], self.num_heads
+        hidden, dead_q, dead_k = self.masks(N, Tq, kv.shape[1], query_lengths, key_lengths, q.device)
+        if hidden is not None:   # the dead rows of q, k and v are zeros, whatever the inputs hold there
+            q, kv = q.masked_fill(dead_q, 0.0), kv.masked_fill(dead_k, 0.0)
+        qh, k, v = self.split(q, kv, d)
+        s = (qh @ k.transpose(-1, -2)) * self.scale_for(d)                 # (the matmul broadcasts k and v over the group)
+        if hidden is not None:
+            s = s.masked_fill(hidden, float("-inf"))
+        out = (s.softmax(-1) @ v).reshape(N, H, Tq, d).transpose(1, 2).reshape(N, Tq, H * d)
+        return out if dead_q is None else out.masked_fill(dead_q, 0.0)     # (a dead query saw key 0, which may be live)
+
+
+class MultiheadCrossAttention(nn.Module):
+    """``nn.MultiheadAttention(batch_first=True)`` applied to ``(x, memory, memory)`` as a container of leaves the extensions have
+    rules for: ``q_proj = Linear(E, H d)`` on ``x [N, Tq, E]``, ``kv_proj = Linear(kdim or E, 2 Hkv d)`` on ``memory [N, Tk, kdim]``,
+    :class:`ScaledDotProductCrossAttention`, ``out_proj = Linear(E, E)``; ``d = E / H``, ``Hkv = num_kv_heads or H``.  ``set_lengths``
+    is that of the leaf (right-padded batches on either side).  No causal mask, no window, no dropout, no arbitrary mask."""
+
+    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True, num_kv_heads: int = None, kdim: int = None):
+        super().__init__()
+        if embed_dim % num_heads != 0:
+            raise ValueError(f"embed_dim ({embed_dim}) is not divisible by num_heads ({num_heads})")
+        self.attention = ScaledDotProductCrossAttention(num_heads, num_kv_heads=num_kv_heads)
+        self.embed_dim, self.num_heads, self.kdim = int(embed_dim), int(num_heads), int(embed_dim if kdim is None else kdim)
+        self.q_proj = nn.Linear(embed_dim, embed_dim, bias=bias)
+        self.kv_proj = nn.Linear(self.kdim, 2 * self.attention.kv_heads * (embed_dim // num_heads), bias=bias)
+        self.out_proj = nn.Linear(embed_dim, embed_dim, bias=bias)
+
+    def forward(self, x: Tensor, memory: Tensor) -> Tensor:
+        return self.out_proj(self.attention(self.q_proj(x), self.kv_proj(memory)))
+
+    def set_lengths(self, query_lengths=None, key_lengths=None) -> None:
+        """Per-sample lengths of ``x`` and of ``memory`` for the padded batches to come (``None``: none), handed to the leaf."""
+        self.attention.set_lengths(query_lengths, key_lengths)
+
+    @classmethod
+    def from_torch(cls, mha: nn.MultiheadAttention) -> "MultiheadCrossAttention":
+        """A copy of ``mha``'s projections: of a packed ``in_proj_weight`` the rows ``[:E]`` go to ``q_proj`` and the rows ``[E:]`` (k | v)
+        to ``kv_proj``; of separate ``q / k / v_proj_weight`` (``kdim != embed_dim``) k and v are stacked, which needs ``kdim == vdim``."""
+        if mha.kdim != mha.vdim:
+            raise ValueError("nn.MultiheadAttention with equal k / v dimensions is required")
+        if not mha.batch_first or mha.bias_k is not None or mha.add_zero_attn or mha.dropout != 0.0:
+            raise ValueError("batch_first=True, no dropout, no bias_k / bias_v and no add_zero_attn are required")
+        E = mha.embed_dim
+        if mha.in_proj_weight is not None:
+            wq, wkv = mha.in_proj_weight[:E], mha.in_proj_weight[E:]
+        else:
+            wq, wkv = mha.q_proj_weight, torch.cat((mha.k_proj_weight, mha.v_proj_weight), 0)
+        new = cls(E, mha.num_heads, bias=mha.in_proj_bias is not None, kdim=mha.kdim).to(device=wq.device, dtype=wq.dtype)
+        with torch.no_grad():
+            new.q_proj.weight.copy_(wq)
+            new.kv_proj.weight.copy_(wkv)
+            new.out_proj.weight.copy_(mha.out_proj.weight)
+            if mha.in_proj_bias is not None:
+                new.q_proj.bias.copy_(mha.in_proj_bias[:E])
+                new.kv_proj.bias.copy_(mha.in_proj_bias[E:])
+                new.out_proj.bias.copy_(mha.out_proj.bias)
+        return new

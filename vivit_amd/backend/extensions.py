@@ -11,14 +11,15 @@ Data contract (identical to BackPACK's):
       ``[N,*,in]`` with a large explicit factor, ``s=[C,N,*,out], z=[N,*,in]`` (``_linear_seq_weight_closures``).
 """
 import math
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 
 from vivit_amd import _lib, kernels
-from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, Permute, ProductModule, RotaryEmbedding, ScaledDotProductAttention, ScaleModule,
+from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, Permute, ProductModule, RotaryEmbedding, ScaledDotProductAttention,
+                                              ScaledDotProductCrossAttention, ScaleModule,
                                               Slicing, SumModule, _gqa_split)
 from vivit_amd.utils.ggn import Vmp
 from vivit_amd.utils.gram import mVp, pairwise_dot
@@ -650,6 +651,89 @@ def _attention_jac_t_torch(module, M: Tensor, x: Tensor, out: Tensor, lengths: O
     return G if dead is None else G.masked_fill(dead, 0.0)   # (a dead query saw itself: P = 1 on zeros; the sign of a zero)
 
 
+def _cross_attention_lengths(module, q: Tensor, subsampling) -> Tuple[Optional[Tensor], Optional[Tensor]]:
+    """The query and key lengths the forward pass of a :class:`ScaledDotProductCrossAttention` used (int32 ``[N]``, kept on the
+    module), sub-sampled as ``q`` was; ``None`` for a side that had none."""
+    both = []
+    for name in ("forward_query_lengths", "forward_key_lengths"):
+        lengths = getattr(module, name, None)
+        if lengths is not None:
+            lengths = subsample(lengths, 0, subsampling).to(q.device)
+            if lengths.shape[0] != q.shape[0]:
+                raise ValueError(f"ScaledDotProductCrossAttention: the forward pass used {lengths.shape[0]} {name[8:]} after "
+                                 f"sub-sampling, the input has {q.shape[0]} samples")
+        both.append(lengths)
+    return both[0], both[1]
+
+
+def _cross_attention_out(module, q: Tensor, kv: Tensor, lengths, subsampling) -> Tensor:
+    """The forward output of a :class:`ScaledDotProductCrossAttention` for the samples of ``q``, as :func:`_attention_out`: an output
+    that does not belong to the inputs (samples, queries, device or dtype) is an error, never a second forward."""
+    out = getattr(module, "output", None)
+    if out is None:
+        with torch.no_grad():
+            return module.attend(q, kv, *lengths)
+    out = subsample(out.detach(), 0, subsampling)
+    if tuple(out.shape) != tuple(q.shape) or out.device != q.device or out.dtype != q.dtype:
+        raise ValueError(f"ScaledDotProductCrossAttention: module.output {tuple(out.shape)} {out.dtype} on {out.device} after "
+                         f"sub-sampling does not belong to the queries {tuple(q.shape)} {q.dtype} on {q.device}")
+    return out
+
+
+def _cross_attention_jac_t_torch(module, M: Tensor, q: Tensor, kv: Tensor, out: Tensor, query_lengths: Optional[Tensor] = None,
+                                 key_lengths: Optional[Tensor] = None, want=(True, True)):
+    """The rule of ``vivit_attention_cross_jac_t_f32`` in plain torch (non-HIP or non-fp32 tensors, head dimensions above 128):
+    ``M [V, N, Tq, H d]``, ``q [N, Tq, H d]``, ``kv [N, Tk, 2 Hkv d]``, ``out [N, Tq, H d]`` -> ``(Gq [V, N, Tq, H d] | None,
+    Gkv [V, N, Tk, 2 Hkv d] | None)`` as ``want`` says.  K and V are broadcast views over the group axis, never expanded copies;
+    the rows of the dead positions (the module's docstring) are exact zeros.  No autograd."""
+    d, H, Hkv = module.head_dim(q, kv), module.num_heads, module.kv_heads
+    scale, R = module.scale_for(d), H // Hkv
+    V, (N, Tq), Tk = M.shape[0], q.shape[:2], kv.shape[1]
+    M = M.reshape(V, N, Tq, H * d)
+    hidden, dead_q, dead_k = module.masks(N, Tq, Tk, query_lengths, key_lengths, q.device)
+    if hidden is not None:   # whatever the dead positions hold is not used
+        M, q, out, kv = M.masked_fill(dead_q, 0.0), q.masked_fill(dead_q, 0.0), out.masked_fill(dead_q, 0.0), kv.masked_fill(dead_k, 0.0)
+    qh, k, v = module.split(q, kv, d)                                             # qh [N, Hkv, R, Tq, d]; k, v [N, Hkv, 1, Tk, d]
+    S = (qh @ k.transpose(-1, -2)) * scale
+    if hidden is not None:
+        S = S.masked_fill(hidden, float("-inf"))
+    P = S.softmax(-1)                                                             # [N, Hkv, R, Tq, Tk], shared by the V slices
+    dO = M.reshape(V, N, Tq, Hkv, R, d).permute(0, 1, 3, 4, 2, 5)                 # [V, N, Hkv, R, Tq, d]
+    D = (dO * out.reshape(N, Tq, Hkv, R, d).permute(0, 2, 3, 1, 4)).sum(-1, keepdim=True)
+    dS = P * (dO @ v.transpose(-1, -2) - D)                                       # (a dead query saw key 0: P = 1 times dO = 0)
+    Gq = Gkv = None
+    if want[0]:
+        Gq = ((dS @ k) * scale).permute(0, 1, 4, 2, 3, 5).reshape(V, N, Tq, H * d)
+        if dead_q is not None:
+            Gq = Gq.masked_fill(dead_q, 0.0)                                      # (the sign of a zero)
+    if want[1]:   # the sum over the group's heads and over the queries is one contraction of length R Tq
+        dV = P.reshape(N, Hkv, R * Tq, Tk).transpose(-1, -2) @ dO.reshape(V, N, Hkv, R * Tq, d)
+        dK = (dS.reshape(V, N, Hkv, R * Tq, Tk).transpose(-1, -2) @ qh.reshape(N, Hkv, R * Tq, d)) * scale
+        Gkv = torch.cat((dK.permute(0, 1, 3, 2, 4).reshape(V, N, Tk, Hkv * d), dV.permute(0, 1, 3, 2, 4).reshape(V, N, Tk, Hkv * d)), -1)
+        if dead_k is not None:
+            Gkv = Gkv.masked_fill(dead_k, 0.0)
+    return Gq, Gkv
+
+
+def _cross_attention_jac_t(module, M: Tensor, subsampling, want):
+    """``(Gq | None, Gkv | None)``: the factor ``M [V, N, Tq, H d]`` at the output of a :class:`ScaledDotProductCrossAttention` taken
+    to its two inputs -- the kernel for HIP fp32 tensors with head dimensions up to 128 (sizes beyond its index arithmetic come back
+    as VIVIT_E_UNSUPPORTED), the same formula in torch for everything else."""
+    q, kv = (subsample(t.detach(), 0, subsampling) for t in module.inputs)
+    d = module.head_dim(q, kv)
+    lengths = _cross_attention_lengths(module, q, subsampling)
+    out = _cross_attention_out(module, q, kv, lengths, subsampling)
+    M = M.reshape(M.shape[0], *q.shape[:2], -1)
+    if M.is_cuda and M.dtype == torch.float32 and d <= 128:
+        try:
+            return kernels.cross_attention_jac_t(M, q, kv, out, module.num_heads, module.scale_for(d), num_kv_heads=module.kv_heads,
+                                                 query_lengths=lengths[0], key_lengths=lengths[1], want=want)
+        except _lib.VivitHipError as exc:
+            if exc.status != _lib.VIVIT_E_UNSUPPORTED:
+                raise
+    return _cross_attention_jac_t_torch(module, M, q, kv, out, *lengths, want=want)
+
+
 def _rope_jac_t_torch(module, M: Tensor, x: Tensor) -> Tensor:
     """The rule of ``vivit_rope_gqa_jac_t_f32`` in plain torch (non-HIP or non-fp32 tensors): the transposed rotation on the
     ``H + Hkv`` heads of the q and k parts of ``M [V, N, T, (H + 2 Hkv) d]`` with the tables of the forward pass, the ``Hkv d`` columns
@@ -1120,6 +1204,13 @@ class _SqrtGGN(_Extension):
                 else:
                     parts = (M * b.unsqueeze(0) if need[0] else None, M * a.unsqueeze(0) if need[1] else None)
                 for inp, g in zip(module.inputs, parts):
+                    if g is not None:
+                        ctx.put(self, inp, g)
+            return
+        if isinstance(module, ScaledDotProductCrossAttention):  # dQ goes to the queries, dK | dV to the second sequence
+            need = tuple(t.requires_grad for t in module.inputs)
+            if any(need):   # (a frozen memory: the key owner is not launched)
+                for inp, g in zip(module.inputs, _cross_attention_jac_t(module, M, sub, need)):
                     if g is not None:
                         ctx.put(self, inp, g)
             return

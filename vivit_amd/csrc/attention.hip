@@ -42,6 +42,18 @@
 // pair, so the sums have the terms and the order they had: with no lengths and no window the bytes of the unmasked kernels, and
 // G[v, n, :Tn] has the bytes of the sample cut to Tn and run alone with T = Tn.  A workgroup whose own block starts at or beyond Tn
 // has an empty walk: it loads nothing and writes its zero rows of G (G is uninitialised memory: every row < T has one writer).
+//
+// CROSS-ATTENTION (vivit_attention_cross_jac_t_f32): the queries q [N, Tq, H d] and the keys and values kv [N, Tk, 2 Hkv d] (k | v,
+// the packed layout without its query part) are two sequences with a length each, Lq[n] and Lk[n] (right padding, clamped to
+// [0, Tq] and [0, Tk]); the results are Gq [V, N, Tq, H d] and Gkv [V, N, Tk, 2 Hkv d] = dK | dV.  There is NO causal flag and NO
+// window: with Tq != Tk there is no agreed alignment of the diagonal.  Key j is live iff j < Lk[n], query i iff i < Lq[n] and
+// Lk[n] > 0 (a query with no key to look at is dead, not a NaN); a live query sees every live key.  The same four kernels are
+// compiled a second time from the geometry AttGeomX: the second sequence -- its base, row pitch, T, block count and lengths -- is
+// a COMPILE-TIME variant (the kernels' template parameter Geo and the overloads on it below), so the self-attention instances are compiled from exactly the
+// expressions they had and keep their registers (the key owner's scalar file is full).  The query-block owners walk
+// the key blocks 0 .. ceil(Lk / 32) - 1, the key-block owner the query blocks 0 .. ceil(Lq / 32) - 1 of each head, in the order
+// above: with Tq = Tk, equal lengths and the packed projection split in two, the tiles, the order and the bytes of the non-causal
+// self-attention call.  Either result may be left out (a frozen memory needs no Gkv): its owner is not launched.
 #include <math.h>
 
 #include "common.h"
@@ -146,42 +158,109 @@ __device__ __forceinline__ int att_len(const AttGeom &g, int64_t n) {
 // blocks a window reaches to either side of the diagonal (the head of the file); KBn where there is no window
 __device__ __forceinline__ int att_reach(const AttGeom &g, int KBn) { return g.window > 0 ? (g.window + 30) >> 5 : KBn; }
 
-__device__ __forceinline__ bool att_valid(const AttGeom &g, int Tn, int gi, int gj) {
-  const int dist = gi - gj;
+struct AttLive { int q, k; };   // live queries and live keys of a sample (self-attention: the same number): rows beyond are never loaded
+
+__device__ __forceinline__ bool att_valid(const AttGeom &g, AttLive L, int gi, int gj) {
+  const int dist = gi - gj, Tn = L.q;
   return gi < Tn && gj < Tn && (!g.causal || dist >= 0) && (g.window <= 0 || (dist < g.window && -dist < g.window));
 }
 
+// cross-attention (the head of the file): the kernels' first pointer is q, their result Gq; the second sequence travels here
+struct AttGeomX {
+  int N, Tq, Tk, H, d, KBq, KBk;   // KBq, KBk = blocks of 32 along Tq and Tk
+  int Hkv, R;
+  int qpitch, kpitch, voff;        // of a row of q and Gq: H d columns; of kv and Gkv: 2 Hkv d columns, v from column Hkv d
+  int vec;
+  float scale;
+  const float *kv;                 // [N, Tk, 2 Hkv d]
+  float *Gkv;                      // [V, N, Tk, 2 Hkv d], or null (the key owner is then not launched)
+  const int32_t *qlengths, *klengths;   // [N] on the device, or null
+};
+
+// WHAT THE KERNELS ASK OF A GEOMETRY, once per kind: self-attention answers every question about the queries and the keys from
+// its one sequence (the same expressions the kernels held before there was a second kind), cross-attention from its two.
+__device__ __forceinline__ AttLive att_live(const AttGeom &g, int64_t n) {
+  const int Tn = att_len(g, n);
+  return {Tn, Tn};
+}
+__device__ __forceinline__ AttLive att_live(const AttGeomX &g, int64_t n) {
+  const int k = g.klengths ? min(max(g.klengths[n], 0), g.Tk) : g.Tk, q = g.qlengths ? min(max(g.qlengths[n], 0), g.Tq) : g.Tq;
+  return {k > 0 ? q : 0, k};   // (no key to look at: the queries are dead)
+}
+__device__ __forceinline__ int att_Tq(const AttGeom &g) { return g.T; }
+__device__ __forceinline__ int att_Tk(const AttGeom &g) { return g.T; }
+__device__ __forceinline__ int att_KBq(const AttGeom &g) { return g.KB; }
+__device__ __forceinline__ int att_KBk(const AttGeom &g) { return g.KB; }
+__device__ __forceinline__ int64_t att_qpitch(const AttGeom &g) { return g.pitch; }
+__device__ __forceinline__ int64_t att_kpitch(const AttGeom &g) { return g.pitch; }
+__device__ __forceinline__ int att_k_to_v(const AttGeom &g) { return g.voff - g.koff; }
+__device__ __forceinline__ int att_Tq(const AttGeomX &g) { return g.Tq; }
+__device__ __forceinline__ int att_Tk(const AttGeomX &g) { return g.Tk; }
+__device__ __forceinline__ int att_KBq(const AttGeomX &g) { return g.KBq; }
+__device__ __forceinline__ int att_KBk(const AttGeomX &g) { return g.KBk; }
+__device__ __forceinline__ int64_t att_qpitch(const AttGeomX &g) { return g.qpitch; }
+__device__ __forceinline__ int64_t att_kpitch(const AttGeomX &g) { return g.kpitch; }
+__device__ __forceinline__ int att_k_to_v(const AttGeomX &g) { return g.voff; }
+// query rows of sample (or factor slice) r: `p` is qkv or G -- q or Gq -- as the kernel was given it
+template <class P> __device__ __forceinline__ P att_q_rows(const AttGeom &g, P p, int64_t r) { return p + r * g.T * (int64_t)g.pitch; }
+template <class P> __device__ __forceinline__ P att_q_rows(const AttGeomX &g, P p, int64_t r) { return p + r * g.Tq * (int64_t)g.qpitch; }
+// key rows and value rows (head 0) of sample r, whose query rows start at `base`; the rows of dK of factor slice r, whose rows of dQ
+// start at `gbase` (the rows of dV are att_k_to_v columns on)
+__device__ __forceinline__ const float *att_k_rows(const AttGeom &g, const float *base, int64_t) { return base + g.koff; }
+__device__ __forceinline__ const float *att_v_rows(const AttGeom &g, const float *base, int64_t) { return base + g.voff; }
+__device__ __forceinline__ float *att_gk_rows(const AttGeom &g, float *gbase, int64_t) { return gbase + g.koff; }
+__device__ __forceinline__ const float *att_k_rows(const AttGeomX &g, const float *, int64_t r) { return g.kv + r * g.Tk * (int64_t)g.kpitch; }
+__device__ __forceinline__ const float *att_v_rows(const AttGeomX &g, const float *, int64_t r) {
+  return g.kv + r * g.Tk * (int64_t)g.kpitch + g.voff;
+}
+__device__ __forceinline__ float *att_gk_rows(const AttGeomX &g, float *, int64_t r) { return g.Gkv + r * g.Tk * (int64_t)g.kpitch; }
+// does query gi see key gj
+__device__ __forceinline__ bool att_valid(const AttGeomX &, AttLive L, int gi, int gj) { return gi < L.q && gj < L.k; }
+// the block ranges of the walks (BLOCK RANGES at the head of the file) are written once, in the kernels, from att_reach and
+// att_causal: cross-attention has no window and no diagonal, every block is within reach (ib + reach stays an int: ib < 2^26)
+__device__ __forceinline__ int att_reach(const AttGeomX &, int) { return 1 << 30; }
+__device__ __forceinline__ bool att_causal(const AttGeom &g) { return g.causal; }
+__device__ __forceinline__ bool att_causal(const AttGeomX &) { return false; }
+// the queries q_lo .. q_hi that see key gj (empty for a dead key)
+__device__ __forceinline__ void att_query_range(const AttGeom &g, AttLive L, int gj, int &q_lo, int &q_hi) {
+  const int Tn = L.q, reach = g.window > 0 ? g.window - 1 : Tn;
+  q_lo = gj < Tn ? (g.causal ? gj : gj - reach) : 0x7fffffff;
+  q_hi = (int)min((int64_t)gj + reach, (int64_t)Tn - 1);
+}
+__device__ __forceinline__ void att_query_range(const AttGeomX &, AttLive L, int gj, int &q_lo, int &q_hi) {
+  q_lo = gj < L.k ? 0 : 0x7fffffff, q_hi = L.q - 1;
+}
+
 // ---- row log-sum-exp --------------------------------------------------------------------------------------------------------------
-template <int NT>
-__global__ __launch_bounds__(256) void attn_lse_kernel(const float *__restrict__ qkv, float *__restrict__ lse, AttGeom g) {
+template <int NT, class Geo>
+__global__ __launch_bounds__(256) void attn_lse_kernel(const float *__restrict__ qkv, float *__restrict__ lse, Geo g) {
   extern __shared__ __attribute__((aligned(16))) float att_smem[];
   using C = AttCfg<NT>;
   float *sQ = att_smem, *sK = sQ + C::BLK, *sS = sK + C::BLK;   // sS [32][33]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t nh = blockIdx.x / g.KB;
-  const int ib = (int)(blockIdx.x - nh * g.KB), i0 = ib * ATT_B;
+  const int64_t nh = blockIdx.x / att_KBq(g);
+  const int ib = (int)(blockIdx.x - nh * att_KBq(g)), i0 = ib * ATT_B;
   const int64_t n = nh / g.H;
   const int h = (int)(nh - n * g.H), dk = (g.d + 3) & ~3;
-  const int64_t pitch = g.pitch;
-  const int Tn = att_len(g, n);
-  if (i0 >= Tn) return;   // a dead query block: its lse is never read
-  const int KBn = (Tn + ATT_B - 1) / ATT_B, wb = att_reach(g, KBn);
-  const float *base = qkv + n * g.T * pitch, *kbase = base + g.koff + (int64_t)(h / g.R) * g.d;
-  att_load_block<NT>(sQ, base + (int64_t)h * g.d, pitch, i0, Tn, g.d, g.vec);
+  const AttLive L = att_live(g, n);
+  if (i0 >= L.q) return;   // a dead query block: its lse is never read
+  const float *base = att_q_rows(g, qkv, n), *kbase = att_k_rows(g, base, n) + (int64_t)(h / g.R) * g.d;
+  att_load_block<NT>(sQ, base + (int64_t)h * g.d, att_qpitch(g), i0, L.q, g.d, g.vec);
   const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
   const int row = tid >> 3, sub = tid & 7;
   float m = -INFINITY, l = 0.f;
-  const int jb_lo = max(ib - wb, 0), jb_hi = g.causal ? ib : min(ib + wb, KBn - 1);
+  const int KBn = (L.k + ATT_B - 1) / ATT_B, wb = att_reach(g, KBn);
+  const int jb_lo = max(ib - wb, 0), jb_hi = att_causal(g) ? ib : min(ib + wb, KBn - 1);
   for (int jb = jb_lo; jb <= jb_hi; ++jb) {
     const int j0 = jb * ATT_B;
     __syncthreads();   // the previous block's reads of sK and sS are done
-    att_load_block<NT>(sK, kbase, pitch, j0, Tn, g.d, g.vec);
+    att_load_block<NT>(sK, kbase, att_kpitch(g), j0, L.k, g.d, g.vec);
     __syncthreads();
     const att_f32x4 s = att_tile_nt<NT>(sQ + 16 * ri * C::LD, sK + 16 * cj * C::LD, dk, lane);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int r = 16 * ri + 4 * kq + e, c = 16 * cj + j;
-      sS[r * 33 + c] = att_valid(g, Tn, i0 + r, j0 + c) ? s[e] * g.scale : -INFINITY;
+      sS[r * 33 + c] = att_valid(g, L, i0 + r, j0 + c) ? s[e] * g.scale : -INFINITY;
     }
     __syncthreads();
     // eight lanes per row, four columns each; every lane of a row keeps the same (m, l)
@@ -199,30 +278,32 @@ __global__ __launch_bounds__(256) void attn_lse_kernel(const float *__restrict__
     l = l * expf(m - mref) + ts;
     m = mn;
   }
-  if (sub == 0 && i0 + row < Tn) lse[nh * g.T + i0 + row] = m + logf(l);
+  if (sub == 0 && i0 + row < L.q) lse[nh * att_Tq(g) + i0 + row] = m + logf(l);
 }
 
-// ---- D[v, n, h, i] = sum_c M[v, n, i, h d + c] O[n, i, h d + c], i < Tn --------------------------------------------------------------
+// ---- D[v, n, h, i] = sum_c M[v, n, i, h d + c] O[n, i, h d + c], i a live query ---------------------------------------------------
+template <class Geo>
 __global__ __launch_bounds__(256) void attn_rowdot_kernel(const float *__restrict__ M, const float *__restrict__ O, float *__restrict__ D,
-                                                          int64_t total, AttGeom g) {
+                                                          int64_t total, Geo g) {
   const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (e >= total) return;
-  const int64_t vnh = e / g.T;
-  const int t = (int)(e - vnh * g.T);
+  const int64_t T = att_Tq(g), vnh = e / T;
+  const int t = (int)(e - vnh * T);
   const int64_t vn = vnh / g.H;
   const int h = (int)(vnh - vn * g.H);
   const int64_t n = vn % g.N, E = (int64_t)g.H * g.d;
-  if (t >= att_len(g, n)) return;   // a dead row: D is never read there
-  const float *m = M + (vn * g.T + t) * E + (int64_t)h * g.d, *o = O + (n * g.T + t) * E + (int64_t)h * g.d;
+  if (t >= att_live(g, n).q) return;   // a dead row: D is never read there
+  const float *m = M + (vn * T + t) * E + (int64_t)h * g.d, *o = O + (n * T + t) * E + (int64_t)h * g.d;
   float a = 0.f;
   for (int c = 0; c < g.d; ++c) a = fmaf(m[c], o[c], a);
   D[e] = a;
 }
 
-// what the two owners share: the dO blocks and D of the workgroup's factor rows for the query block at i0 (rows >= Tn: zero)
-template <int NT>
+// what the two owners share: the dO blocks and D of the workgroup's factor rows for the query block at i0 (rows >= Tn, the live
+// queries: zero)
+template <int NT, class Geo>
 __device__ __forceinline__ void att_load_factor(float *__restrict__ sdO, float *__restrict__ sD, const float *__restrict__ M,
-                                                const float *__restrict__ Dws, const AttGeom &g, int Tn, int64_t v0, int nv, int64_t n,
+                                                const float *__restrict__ Dws, const Geo &g, int Tn, int64_t v0, int nv, int64_t n,
                                                 int h, int i0) {
   using C = AttCfg<NT>;
   const int64_t E = (int64_t)g.H * g.d;
@@ -230,9 +311,9 @@ __device__ __forceinline__ void att_load_factor(float *__restrict__ sdO, float *
   for (int vi = 0; vi < C::VC; ++vi)
     if (vi < nv) {
       const int64_t vn = (v0 + vi) * g.N + n;
-      att_load_block<NT>(sdO + vi * C::BLK, M + vn * g.T * E + (int64_t)h * g.d, E, i0, Tn, g.d, g.vec);
+      att_load_block<NT>(sdO + vi * C::BLK, M + vn * att_Tq(g) * E + (int64_t)h * g.d, E, i0, Tn, g.d, g.vec);
       if (threadIdx.x < ATT_B)
-        sD[vi * ATT_B + threadIdx.x] = i0 + (int)threadIdx.x < Tn ? Dws[(vn * g.H + h) * g.T + i0 + threadIdx.x] : 0.f;
+        sD[vi * ATT_B + threadIdx.x] = i0 + (int)threadIdx.x < Tn ? Dws[(vn * g.H + h) * att_Tq(g) + i0 + threadIdx.x] : 0.f;
     }
 }
 
@@ -253,39 +334,40 @@ __device__ __forceinline__ att_f32x4 att_p_tile(const float *__restrict__ sQ, co
 }
 
 // ---- key-block owner: dK and dV ---------------------------------------------------------------------------------------------------
-template <int NT>
+template <int NT, class Geo>
 __global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__ M, const float *__restrict__ qkv,
                                                        const float *__restrict__ lse, const float *__restrict__ Dws, float *__restrict__ G,
-                                                       int64_t V, AttGeom g) {
+                                                       int64_t V, Geo g) {
   extern __shared__ __attribute__((aligned(16))) float att_smem[];
   using C = AttCfg<NT>;
   float *sK = att_smem, *sV = sK + C::BLK, *sQ = sV + C::BLK, *sdO = sQ + C::BLK;
   float *sP = sdO + C::VC * C::BLK, *sdS = sP + C::TILE, *sL = sdS + C::VC * C::TILE, *sD = sL + ATT_B;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t ng = blockIdx.x / g.KB;
-  const int jb = (int)(blockIdx.x - ng * g.KB), j0 = jb * ATT_B;
+  const int64_t ng = blockIdx.x / att_KBk(g);
+  const int jb = (int)(blockIdx.x - ng * att_KBk(g)), j0 = jb * ATT_B;
   const int64_t n = ng / g.Hkv;
   const int kv = (int)(ng - n * g.Hkv), dk = (g.d + 3) & ~3;
-  const int64_t pitch = g.pitch;
+  const int64_t qpitch = att_qpitch(g), kpitch = att_kpitch(g);
   const int64_t v0 = (int64_t)blockIdx.y * C::VC;
   const int nv = V - v0 < C::VC ? (int)(V - v0) : C::VC;
-  const float *base = qkv + n * g.T * pitch;
-  const int Tn = att_len(g, n), KBn = (Tn + ATT_B - 1) / ATT_B, wb = att_reach(g, KBn);
-  // the query blocks that see this key block (the head of the file); a dead key block (j0 >= Tn) has none, loads nothing and
+  const float *base = att_q_rows(g, qkv, n);
+  const AttLive L = att_live(g, n);
+  // the query blocks that see this key block (the head of the file); a dead key block (j0 >= L.k) has none, loads nothing and
   // stores its zeros
-  const int ib_lo = g.causal ? jb : max(jb - wb, 0), ib_hi = min(jb + wb, KBn - 1);
-  const int per_head = j0 < Tn ? ib_hi - ib_lo + 1 : 0;
+  const int KBn = (L.q + ATT_B - 1) / ATT_B, wb = att_reach(g, KBn);
+  const int ib_lo = att_causal(g) ? jb : max(jb - wb, 0), ib_hi = min(jb + wb, KBn - 1);
+  const int per_head = j0 < L.k ? ib_hi - ib_lo + 1 : 0;
   if (per_head > 0) {
-    att_load_block<NT>(sK, base + g.koff + (int64_t)kv * g.d, pitch, j0, Tn, g.d, g.vec);
-    att_load_block<NT>(sV, base + g.voff + (int64_t)kv * g.d, pitch, j0, Tn, g.d, g.vec);
+    att_load_block<NT>(sK, att_k_rows(g, base, n) + (int64_t)kv * g.d, kpitch, j0, L.k, g.d, g.vec);
+    att_load_block<NT>(sV, att_v_rows(g, base, n) + (int64_t)kv * g.d, kpitch, j0, L.k, g.d, g.vec);
   }
   const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
   // att_valid for the lane's key gj, which is the same in every tile of the walk, as the range q_lo .. q_hi of the queries that see
   // it (empty for a dead key): two registers of the lane instead of Tn, the window and the causal flag in the scalar file, which this
   // kernel fills
-  const int gj = j0 + 16 * cj + j, reach = g.window > 0 ? g.window - 1 : Tn;
-  const int q_lo = gj < Tn ? (g.causal ? gj : gj - reach) : 0x7fffffff;
-  const int q_hi = (int)min((int64_t)gj + reach, (int64_t)Tn - 1);
+  const int gj = j0 + 16 * cj + j;
+  int q_lo, q_hi;
+  att_query_range(g, L, gj, q_lo, q_hi);
   att_f32x4 accK[C::VC][C::TPW], accV[C::VC][C::TPW];
 #pragma unroll
   for (int vi = 0; vi < C::VC; ++vi)
@@ -297,9 +379,9 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__
     const int h = kv * g.R + hr, i0 = ib * ATT_B;
     const int64_t nh = n * g.H + h;
     __syncthreads();   // the previous query block's tiles and operands have been read
-    att_load_block<NT>(sQ, base + (int64_t)h * g.d, pitch, i0, Tn, g.d, g.vec);
-    if (tid < ATT_B) sL[tid] = i0 + tid < Tn ? lse[nh * g.T + i0 + tid] : 0.f;
-    att_load_factor<NT>(sdO, sD, M, Dws, g, Tn, v0, nv, n, h, i0);
+    att_load_block<NT>(sQ, base + (int64_t)h * g.d, qpitch, i0, L.q, g.d, g.vec);
+    if (tid < ATT_B) sL[tid] = i0 + tid < L.q ? lse[nh * att_Tq(g) + i0 + tid] : 0.f;
+    att_load_factor<NT>(sdO, sD, M, Dws, g, L.q, v0, nv, n, h, i0);
     __syncthreads();
     const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g.scale, dk, lane, ri, cj, [&](int r, int) { return i0 + r >= q_lo && i0 + r <= q_hi; });
 #pragma unroll
@@ -335,14 +417,14 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__
 #pragma unroll
       for (int vi = 0; vi < C::VC; ++vi)
         if (vi < nv) {
-          float *gk = G + ((v0 + vi) * g.N + n) * g.T * pitch + g.koff + (int64_t)kv * g.d + c;
-          const int kv_to_v = g.voff - g.koff;
+          float *gk = att_gk_rows(g, att_q_rows(g, G, (v0 + vi) * g.N + n), (v0 + vi) * g.N + n) + (int64_t)kv * g.d + c;
+          const int kv_to_v = att_k_to_v(g);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int r = j0 + 16 * rt + 4 * kq + e;
-            if (r < g.T) {   // (a dead key's row: +0 whatever the sign of the scale)
-              gk[(int64_t)r * pitch] = r < Tn ? g.scale * accK[vi][u][e] : 0.f;
-              gk[(int64_t)r * pitch + kv_to_v] = r < Tn ? accV[vi][u][e] : 0.f;
+            if (r < att_Tk(g)) {   // (a dead key's row: +0 whatever the sign of the scale)
+              gk[(int64_t)r * kpitch] = r < L.k ? g.scale * accK[vi][u][e] : 0.f;
+              gk[(int64_t)r * kpitch + kv_to_v] = r < L.k ? accV[vi][u][e] : 0.f;
             }
           }
         }
@@ -351,31 +433,32 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__
 }
 
 // ---- query-block owner: dQ --------------------------------------------------------------------------------------------------------
-template <int NT>
+template <int NT, class Geo>
 __global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ M, const float *__restrict__ qkv,
                                                       const float *__restrict__ lse, const float *__restrict__ Dws, float *__restrict__ G,
-                                                      int64_t V, AttGeom g) {
+                                                      int64_t V, Geo g) {
   extern __shared__ __attribute__((aligned(16))) float att_smem[];
   using C = AttCfg<NT>;
   float *sK = att_smem, *sV = sK + C::BLK, *sQ = sV + C::BLK, *sdO = sQ + C::BLK;
   float *sdS = sdO + C::VC * C::BLK + C::TILE, *sL = sdS + C::VC * C::TILE, *sD = sL + ATT_B;   // (the P tile's room is unused here)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t nh = blockIdx.x / g.KB;
-  const int ib = (int)(blockIdx.x - nh * g.KB), i0 = ib * ATT_B;
+  const int64_t nh = blockIdx.x / att_KBq(g);
+  const int ib = (int)(blockIdx.x - nh * att_KBq(g)), i0 = ib * ATT_B;
   const int64_t n = nh / g.H;
   const int h = (int)(nh - n * g.H), dk = (g.d + 3) & ~3;
-  const int64_t pitch = g.pitch;
+  const int64_t qpitch = att_qpitch(g), kpitch = att_kpitch(g);
   const int64_t v0 = (int64_t)blockIdx.y * C::VC;
   const int nv = V - v0 < C::VC ? (int)(V - v0) : C::VC;
-  const float *base = qkv + n * g.T * pitch, *kbase = base + g.koff + (int64_t)(h / g.R) * g.d;
-  const int Tn = att_len(g, n), KBn = (Tn + ATT_B - 1) / ATT_B, wb = att_reach(g, KBn);
-  // the key blocks this query block sees (the head of the file); a dead query block (i0 >= Tn) has none, loads nothing and stores
+  const float *base = att_q_rows(g, qkv, n), *kbase = att_k_rows(g, base, n) + (int64_t)(h / g.R) * g.d;
+  const AttLive L = att_live(g, n);
+  // the key blocks this query block sees (the head of the file); a dead query block (i0 >= L.q) has none, loads nothing and stores
   // its zeros
-  const int jb_lo = max(ib - wb, 0), jb_hi = i0 < Tn ? (g.causal ? ib : min(ib + wb, KBn - 1)) : -1;
+  const int KBn = (L.k + ATT_B - 1) / ATT_B, wb = att_reach(g, KBn);
+  const int jb_lo = max(ib - wb, 0), jb_hi = i0 < L.q ? (att_causal(g) ? ib : min(ib + wb, KBn - 1)) : -1;
   if (jb_lo <= jb_hi) {
-    att_load_block<NT>(sQ, base + (int64_t)h * g.d, pitch, i0, Tn, g.d, g.vec);
-    if (tid < ATT_B) sL[tid] = i0 + tid < Tn ? lse[nh * g.T + i0 + tid] : 0.f;
-    att_load_factor<NT>(sdO, sD, M, Dws, g, Tn, v0, nv, n, h, i0);
+    att_load_block<NT>(sQ, base + (int64_t)h * g.d, qpitch, i0, L.q, g.d, g.vec);
+    if (tid < ATT_B) sL[tid] = i0 + tid < L.q ? lse[nh * att_Tq(g) + i0 + tid] : 0.f;
+    att_load_factor<NT>(sdO, sD, M, Dws, g, L.q, v0, nv, n, h, i0);
   }
   const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
   att_f32x4 accQ[C::VC][C::TPW];
@@ -386,10 +469,10 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ 
   for (int jb = jb_lo; jb <= jb_hi; ++jb) {
     const int j0 = jb * ATT_B;
     __syncthreads();   // the previous key block's tiles and operands have been read
-    att_load_block<NT>(sK, kbase, pitch, j0, Tn, g.d, g.vec);
-    att_load_block<NT>(sV, kbase + (g.voff - g.koff), pitch, j0, Tn, g.d, g.vec);
+    att_load_block<NT>(sK, kbase, kpitch, j0, L.k, g.d, g.vec);
+    att_load_block<NT>(sV, kbase + att_k_to_v(g), kpitch, j0, L.k, g.d, g.vec);
     __syncthreads();
-    const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g.scale, dk, lane, ri, cj, [&](int r, int c) { return att_valid(g, Tn, i0 + r, j0 + c); });
+    const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g.scale, dk, lane, ri, cj, [&](int r, int c) { return att_valid(g, L, i0 + r, j0 + c); });
 #pragma unroll
     for (int vi = 0; vi < C::VC; ++vi)
       if (vi < nv) {
@@ -418,11 +501,11 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ 
 #pragma unroll
       for (int vi = 0; vi < C::VC; ++vi)
         if (vi < nv) {
-          float *gq = G + ((v0 + vi) * g.N + n) * g.T * pitch + (int64_t)h * g.d + c;
+          float *gq = att_q_rows(g, G, (v0 + vi) * g.N + n) + (int64_t)h * g.d + c;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int r = i0 + 16 * rt + 4 * kq + e;
-            if (r < g.T) gq[(int64_t)r * pitch] = r < Tn ? g.scale * accQ[vi][u][e] : 0.f;   // (a dead query's row: +0)
+            if (r < att_Tq(g)) gq[(int64_t)r * qpitch] = r < L.q ? g.scale * accQ[vi][u][e] : 0.f;   // (a dead query's row: +0)
           }
         }
     }
@@ -455,28 +538,54 @@ static AttPlan attention_plan(int64_t V, int64_t N, int64_t T, int64_t H, int64_
   return p;
 }
 
-template <int NT>
-static int attention_launch(const float *M, const float *qkv, const float *out, float *G, float *lse, float *Dws, int64_t V,
-                            const AttGeom &g, hipStream_t s) {
+// the cross-attention entry's plan: that of the query sequence (the workspace is counted in queries) and the limits of the keys'
+static AttPlan attention_cross_plan(int64_t V, int64_t N, int64_t Tq, int64_t Tk, int64_t H, int64_t Hkv, int64_t d, int64_t &KBk) {
+  if (Tk <= 0) return AttPlan{VIVIT_E_BADARG, 0, 0, 0};
+  AttPlan p = attention_plan(V, N, Tq, H, Hkv, d);
+  if (p.status != VIVIT_OK) return p;
+  // 32-bit: Tk + 32, the block index N Hkv KBk of the key owner (its R KBq steps, the pitches H d and 2 Hkv d < (H + 2 Hkv) d and
+  // the blocks N H KBq of the query owners are the plan's); 64-bit: every element offset of kv and Gkv
+  const int64_t lim = 0x7fffffffLL;
+  KBk = cdiv(Tk, ATT_B);
+  const int64_t per_k = N * Hkv * Tk;   // (N Hkv < 2^31 by the plan)
+  if (Tk > lim - ATT_B || N * Hkv > lim / KBk || per_k > (int64_t)1 << 40 || V > ((int64_t)1 << 58) / (per_k * 2 * d))
+    return AttPlan{VIVIT_E_UNSUPPORTED, 0, 0, 0};
+  return p;
+}
+
+// the four launches; `G`: the result of the query owner (null: not launched), `Gkv`: that of the key owner (null: not launched; for
+// self-attention the same packed tensor as G)
+template <int NT, class Geo>
+static int attention_launch(const float *M, const float *qkv, const float *out, float *G, float *Gkv, float *lse, float *Dws,
+                            int64_t V, const Geo &g, int T, int KBq, int KBk, hipStream_t s) {
   using C = AttCfg<NT>;
   static unsigned long long attr_done = 0;
   constexpr int lse_lds = C::LSE_FLOATS * 4, own_lds = C::OWN_FLOATS * 4;
   if (own_lds > 64 * 1024) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return VIVIT_E_LAUNCH;
-    if (!ensure_dynamic_lds(reinterpret_cast<const void *>(attn_dkv_kernel<NT>), own_lds, attr_done) ||
-        !ensure_dynamic_lds(reinterpret_cast<const void *>(attn_dq_kernel<NT>), own_lds, attr_done))
+    if (!ensure_dynamic_lds(reinterpret_cast<const void *>(attn_dkv_kernel<NT, Geo>), own_lds, attr_done) ||
+        !ensure_dynamic_lds(reinterpret_cast<const void *>(attn_dq_kernel<NT, Geo>), own_lds, attr_done))
       return VIVIT_E_LAUNCH;
     attr_done |= 1ull << (dev & 63);
   }
-  const int64_t NH = (int64_t)g.N * g.H, total = V * NH * g.T;
-  const unsigned blocks = (unsigned)(NH * g.KB), kv_blocks = (unsigned)((int64_t)g.N * g.Hkv * g.KB);
-  attn_lse_kernel<NT><<<blocks, 256, lse_lds, s>>>(qkv, lse, g);
-  attn_rowdot_kernel<<<(unsigned)cdiv(total, 256), 256, 0, s>>>(M, out, Dws, total, g);
+  const int64_t NH = (int64_t)g.N * g.H, total = V * NH * T;
+  const unsigned blocks = (unsigned)(NH * KBq), kv_blocks = (unsigned)((int64_t)g.N * g.Hkv * KBk);
+  attn_lse_kernel<NT, Geo><<<blocks, 256, lse_lds, s>>>(qkv, lse, g);
+  attn_rowdot_kernel<Geo><<<(unsigned)cdiv(total, 256), 256, 0, s>>>(M, out, Dws, total, g);
   const unsigned chunks = (unsigned)cdiv(V, C::VC);
-  attn_dkv_kernel<NT><<<dim3(kv_blocks, chunks), 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g);
-  attn_dq_kernel<NT><<<dim3(blocks, chunks), 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g);
+  if (Gkv) attn_dkv_kernel<NT, Geo><<<dim3(kv_blocks, chunks), 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g);
+  if (G) attn_dq_kernel<NT, Geo><<<dim3(blocks, chunks), 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g);
   return launch_status();
+}
+
+template <class Geo>
+static int attention_launch_d(const float *M, const float *qkv, const float *out, float *G, float *Gkv, float *lse, float *Dws,
+                              int64_t V, const Geo &g, int T, int KBq, int KBk, hipStream_t s) {
+  if (g.d <= 16) return attention_launch<1>(M, qkv, out, G, Gkv, lse, Dws, V, g, T, KBq, KBk, s);
+  if (g.d <= 32) return attention_launch<2>(M, qkv, out, G, Gkv, lse, Dws, V, g, T, KBq, KBk, s);
+  if (g.d <= 64) return attention_launch<4>(M, qkv, out, G, Gkv, lse, Dws, V, g, T, KBq, KBk, s);
+  return attention_launch<8>(M, qkv, out, G, Gkv, lse, Dws, V, g, T, KBq, KBk, s);
 }
 
 static inline bool att_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -512,10 +621,37 @@ int vivit_attention_masked_jac_t_f32(const float *M, const float *qkv, const flo
   float *lse = static_cast<float *>(workspace);
   float *Dws = reinterpret_cast<float *>(static_cast<char *>(workspace) + p.lse_bytes);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (d <= 16) return attention_launch<1>(M, qkv, out, G, lse, Dws, V, g, s);
-  if (d <= 32) return attention_launch<2>(M, qkv, out, G, lse, Dws, V, g, s);
-  if (d <= 64) return attention_launch<4>(M, qkv, out, G, lse, Dws, V, g, s);
-  return attention_launch<8>(M, qkv, out, G, lse, Dws, V, g, s);
+  return attention_launch_d(M, qkv, out, G, G, lse, Dws, V, g, g.T, g.KB, g.KB, s);
+}
+
+// cross-attention (the head of the file): q_lengths, k_lengths [N] int32 on the device or null; Gq or Gkv may be null, not both
+size_t vivit_attention_cross_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t Tq, int64_t Tk, int64_t H, int64_t Hkv,
+                                                       int64_t d) {
+  int64_t KBk = 0;
+  const AttPlan p = attention_cross_plan(V, N, Tq, Tk, H, Hkv, d, KBk);
+  return p.status == VIVIT_OK ? p.bytes : 0;
+}
+
+int vivit_attention_cross_jac_t_f32(const float *M, const float *q, const float *kv, const float *out, float *Gq, float *Gkv, int64_t V,
+                                    int64_t N, int64_t Tq, int64_t Tk, int64_t H, int64_t Hkv, int64_t d, float scale,
+                                    const int32_t *q_lengths, const int32_t *k_lengths, void *workspace, size_t workspace_bytes,
+                                    void *stream) {
+  if (!M || !q || !kv || !out || (!Gq && !Gkv)) return VIVIT_E_BADARG;
+  int64_t KBk = 0;
+  const AttPlan p = attention_cross_plan(V, N, Tq, Tk, H, Hkv, d, KBk);
+  if (p.status != VIVIT_OK) return p.status;
+  if (!workspace || workspace_bytes < p.bytes) return VIVIT_E_WORKSPACE;
+  AttGeomX g;
+  g.N = (int)N, g.Tq = (int)Tq, g.Tk = (int)Tk, g.H = (int)H, g.d = (int)d, g.KBq = (int)p.KB, g.KBk = (int)KBk;
+  g.Hkv = (int)Hkv, g.R = (int)(H / Hkv);
+  g.qpitch = (int)(H * d), g.kpitch = (int)(2 * Hkv * d), g.voff = (int)(Hkv * d);
+  g.vec = (d & 3) == 0 && att_aligned16(M) && att_aligned16(q) && att_aligned16(kv);
+  g.scale = scale;
+  g.kv = kv, g.Gkv = Gkv;
+  g.qlengths = q_lengths, g.klengths = k_lengths;
+  float *lse = static_cast<float *>(workspace);
+  float *Dws = reinterpret_cast<float *>(static_cast<char *>(workspace) + p.lse_bytes);
+  return attention_launch_d(M, q, out, Gq, Gkv, lse, Dws, V, g, g.Tq, g.KBq, g.KBk, static_cast<hipStream_t>(stream));
 }
 
 // grouped-query attention without lengths or a window

@@ -737,6 +737,71 @@ def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num
     return G
 
 
+def _device_lengths(lengths, name: str, N, device):
+    """``lengths`` (anything ``torch.as_tensor`` turns into ``N`` integers) as int32 on ``device``, never read on the host."""
+    lengths = torch.as_tensor(lengths)
+    if lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
+        raise ValueError(f"{name} must be integers, got {lengths.dtype}")
+    if lengths.dim() != 1 or N is None or lengths.shape[0] != N:
+        raise ValueError(f"{name} must be [N] = [{'?' if N is None else N}], got {tuple(lengths.shape)}")
+    return lengths.to(device=device, dtype=torch.int32).contiguous()
+
+
+@_launcher
+def cross_attention_jac_t(M, q, kv, out, num_heads: int, scale: float, num_kv_heads: int = None, query_lengths=None, key_lengths=None,
+                          want=(True, True)):
+    """Transposed input Jacobians of scaled dot-product cross-attention (``vivit_attention_cross_jac_t_f32``): ``M [V, N, Tq, E]`` (the
+    factor at the module output), ``q [N, Tq, E]`` (the queries, ``E = num_heads * d``), ``kv [N, Tk, 2 * Hkv * d]`` (the second
+    sequence, k | v: ``Hkv`` key heads, then ``Hkv`` value heads; ``Hkv = num_kv_heads``, ``None`` is ``num_heads``), ``out [N, Tq, E]``
+    (the module output of the forward pass) -> ``(Gq [V, N, Tq, E], Gkv [V, N, Tk, 2 * Hkv * d])``, ``Gkv`` packed ``dK | dV`` like
+    ``kv``.  Query head ``h`` attends to key / value head ``h // (num_heads // Hkv)``; no ``Tq x Tk`` tensor is allocated.
+
+    There is no causal mask and no window: with ``Tq != Tk`` there is no agreed alignment of the diagonal.  ``query_lengths`` /
+    ``key_lengths`` (each anything ``torch.as_tensor`` turns into ``N`` integers, or ``None``): right padding, clamped by the kernel
+    to ``[0, Tq]`` and ``[0, Tk]``.  Key ``j`` of sample ``n`` is live iff ``j < key_lengths[n]``; query ``i`` iff
+    ``i < query_lengths[n]`` and ``key_lengths[n] > 0`` (a query with no key to look at is dead, not a NaN).  Dead rows of both
+    results are exact zeros, and whatever ``M``, ``q``, ``kv`` and ``out`` hold at dead positions is never read.  The values go to
+    ``M``'s device as int32 and are not looked at on the host.
+
+    ``want``: which of the two results to compute; the other is ``None`` and its kernel is not launched (``want=(True, False)``: a
+    frozen memory that needs no gradient)."""
+    _require_device(M, q, kv, out)
+    want = tuple(bool(w) for w in want)
+    if len(want) != 2 or not any(want):
+        raise ValueError(f"want must name at least one of (Gq, Gkv), got {want!r}")
+    N0 = q.shape[0] if q.dim() == 3 else None
+    if query_lengths is not None:
+        query_lengths = _device_lengths(query_lengths, "query_lengths", N0, M.device)
+    if key_lengths is not None:
+        key_lengths = _device_lengths(key_lengths, "key_lengths", N0, M.device)
+    M, q, kv, out = M.contiguous(), q.contiguous(), kv.contiguous(), out.contiguous()
+    Hkv, _ = _packed_heads(num_heads, num_kv_heads)
+    if q.dim() != 3 or num_heads < 1 or q.shape[2] == 0 or q.shape[2] % num_heads != 0:
+        raise ValueError(f"q must be [N, Tq, {num_heads} * d], got {tuple(q.shape)}")
+    N, Tq, E = q.shape
+    d = E // num_heads
+    if kv.dim() != 3 or kv.shape[0] != N or kv.shape[2] != 2 * Hkv * d:
+        raise ValueError(f"kv must be [{N}, Tk, 2 * {Hkv} * {d}], got {tuple(kv.shape)}")
+    Tk = kv.shape[1]
+    if tuple(out.shape) != (N, Tq, E):
+        raise ValueError(f"out must be {(N, Tq, E)}, got {tuple(out.shape)}")
+    if M.dim() != 4 or tuple(M.shape[1:]) != (N, Tq, E):
+        raise ValueError(f"M must be [V, {N}, {Tq}, {E}], got {tuple(M.shape)}")
+    Vd = M.shape[0]
+    if Vd == 0 or N == 0 or Tq == 0 or Tk == 0:
+        raise ValueError(f"empty operands: M {tuple(M.shape)}, kv {tuple(kv.shape)}")
+    Gq = torch.empty((Vd, N, Tq, E), dtype=torch.float32, device=M.device) if want[0] else None
+    Gkv = torch.empty((Vd, N, Tk, 2 * Hkv * d), dtype=torch.float32, device=M.device) if want[1] else None
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    lib = _lib.load()
+    ws, ws_bytes = _workspace(lib.vivit_attention_cross_jac_t_f32_workspace_bytes(Vd, N, Tq, Tk, num_heads, Hkv, d), M)
+    st = lib.vivit_attention_cross_jac_t_f32(M.data_ptr(), q.data_ptr(), kv.data_ptr(), out.data_ptr(), ptr(Gq), ptr(Gkv), Vd, N, Tq, Tk,
+                                             num_heads, Hkv, d, float(scale), ptr(query_lengths), ptr(key_lengths), ws, ws_bytes,
+                                             _stream(M))
+    _lib.check(st, "vivit_attention_cross_jac_t_f32")
+    return Gq, Gkv
+
+
 _I32_MAX = 2 ** 31 - 1
 
 
