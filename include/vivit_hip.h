@@ -220,8 +220,9 @@ int vivit_conv2d_weight_mjp_f32(const float *M, const float *x, float *V, int64_
  * ------------------------------------------------------------------------------------------- */
 /* out[v, e] = M[v, e] * f'(x[e]), e < per_v (= N * features).  kind: 0 ReLU, 1 Sigmoid, 2 Tanh, 3 LeakyReLU (param =
  * negative slope), 4 LogSigmoid, 5 ELU (param = alpha), 6 SELU, 7 GELU (erf form: Phi(x) + x phi(x)), 8 GELU (tanh
- * approximation, nn.GELU(approximate='tanh')), 9 SiLU (s (1 + x (1 - s)), s = sigmoid(x)).  Replaces SqrtGGN{ReLU,Sigmoid,Tanh,
- * LeakyReLU,LogSigmoid,ELU,SELU} (__init__.py:87-93); 7 .. 9 have no counterpart in the reference.  A NaN in x: as torch's
+ * approximation, nn.GELU(approximate='tanh')), 9 SiLU (s (1 + x (1 - s)), s = sigmoid(x)), 10 soft cap (f = param tanh(x / param),
+ * f' = 1 - tanh^2(x / param); param = the cap, which must be finite and > 0: VIVIT_E_BADARG otherwise; Gemma-2's final logits).  Replaces SqrtGGN{ReLU,Sigmoid,Tanh,
+ * LeakyReLU,LogSigmoid,ELU,SELU} (__init__.py:87-93); 7 .. 10 have no counterpart in the reference.  A NaN in x: as torch's
  * autograd of the module -- ReLU passes the factor unchanged and LeakyReLU scales it by the slope (the branch a failed
  * comparison selects there), every other rule gives NaN.  GELU and SiLU at x = +-inf give NaN (the inf * 0 of torch's backward
  * formulas, which are evaluated term by term here), at large finite |x| exactly 1 or (+-)0: no deliberate difference from
@@ -376,6 +377,24 @@ size_t vivit_attention_masked_jac_t_f32_workspace_bytes(int64_t V, int64_t N, in
 int vivit_attention_masked_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
                                      int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths,
                                      int64_t window, void *workspace, size_t workspace_bytes, void *stream);
+/* The same rule for a modified score function (attention.hip; call site vivit_amd/kernels.py:attention_jac_t with softcap or bias, for
+ * vivit_amd.backend.ScaledDotProductAttention(softcap=, bias=)): a logit cap and an additive bias per head and distance.  With
+ * z_ij = scale q_i k_j:  u = c tanh(z / c) for softcap c > 0 (softcap == 0: u = z; Gemma-2, Grok-1),  s_ij = u + bias[h, j - i + T - 1]
+ * for bias [H, 2 T - 1] fp32 on the device (NULL: s = u; ALiBi, relative-position tables), then the mask of the masked entry point
+ * exactly as it is, P = softmax_rows(s): the cap comes before the bias and the mask.  The rule:  dS = P o (dP - D),
+ * dZ = dS o (1 - t^2) with t = u / c (no cap: dZ = dS),  dQ_h = scale dZ K_g,  dK_g = scale sum_{h in g} dZ_h^T Q_h,  dV as above.  The
+ * table is a constant and receives no factor.  Only entries of visible pairs are read, both positions < Tn <= T, so no index leaves
+ * [0, 2 T - 2]; the table needs no alignment beyond its four bytes.  Tiles, block ranges, summation orders, dead positions and +0
+ * rows are those of the masked entry point, no atomics, no T x T data in memory; the bytes of G[v, n] depend on the shape parameters,
+ * the cap, the table and the data of (v, n) only.  With softcap == 0 and bias == NULL the call IS
+ * vivit_attention_masked_jac_t_f32 (it is forwarded: the same kernels, the same bytes).  softcap negative, NaN or inf:
+ * VIVIT_E_BADARG; every other refusal (BADARG, UNSUPPORTED, WORKSPACE) is that of the masked entry point, and all come before any
+ * launch.  The workspace is that of the masked entry point.  There is no such entry for cross-attention. */
+size_t vivit_attention_scoremod_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d);
+int vivit_attention_scoremod_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
+                                       int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths,
+                                       int64_t window, float softcap, const float *bias, void *workspace, size_t workspace_bytes,
+                                       void *stream);
 /* Cross-attention: the same rule when the queries and the keys come from two sequences (attention.hip; call site
  * vivit_amd/kernels.py:cross_attention_jac_t, for vivit_amd.backend.ScaledDotProductCrossAttention).  All tensors dense:
  * q [N, Tq, H d], kv [N, Tk, 2 Hkv d] = k | v (Hkv key heads of d columns, then Hkv value heads: the packed layout above without

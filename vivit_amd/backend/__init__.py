@@ -8,7 +8,8 @@ provided here for feed-forward and residual nets (Linear, Conv1d/2d/3d, ConvTran
 eval mode, element-wise activations, pooling, Flatten, Dropout in eval mode, and the branching modules
 ``Parallel`` / ``SumModule`` / ``Pad`` / ``Slicing`` / ``ScaleModule`` of ``backpack.custom_module``, LayerNorm / GroupNorm,
 the self-attention modules ``ScaledDotProductAttention`` / ``MultiheadSelfAttention`` of ``custom_module`` (causal,
-grouped queries, sliding windows, right-padded batches through ``set_lengths``), the cross-attention modules
+grouped queries, sliding windows, right-padded batches through ``set_lengths``, logit soft-capping and relative-position
+bias tables such as ``alibi_bias``; ``SoftCap`` for capped final logits), the cross-attention modules
 ``ScaledDotProductCrossAttention`` / ``MultiheadCrossAttention`` (queries over a second sequence), ``nn.Embedding``,
 ``nn.RMSNorm`` and the modules ``ProductModule`` (gated MLPs) / ``RotaryEmbedding`` of ``custom_module``;
 CrossEntropyLoss / MSELoss with ``reduction='mean'`` or ``'sum'``, on outputs ``[N, C]`` and on outputs with positions
@@ -33,7 +34,9 @@ from vivit_amd.backend.custom_module import (
     ScaledDotProductCrossAttention,
     ScaleModule,
     Slicing,
+    SoftCap,
     SumModule,
+    alibi_bias,
 )
 from vivit_amd.backend.engine import backpack, extend
 from vivit_amd.backend.extensions import (
@@ -44,4 +47,4 @@ from vivit_amd.backend.extensions import (
     ViViTGGNMC,
 )
 
-__all__ = ["ActiveIdentity", "MultiheadCrossAttention", "MultiheadSelfAttention", "Pad", "Parallel", "Permute", "ProductModule", "RotaryEmbedding", "ScaledDotProductAttention", "ScaledDotProductCrossAttention", "ScaleModule", "Slicing", "SumModule", "backpack", "extend", "BatchGrad", "SqrtGGNExact", "SqrtGGNMC", "ViViTGGNExact", "ViViTGGNMC"]
+__all__ = ["ActiveIdentity", "MultiheadCrossAttention", "MultiheadSelfAttention", "Pad", "Parallel", "Permute", "ProductModule", "RotaryEmbedding", "ScaledDotProductAttention", "ScaledDotProductCrossAttention", "ScaleModule", "Slicing", "SoftCap", "SumModule", "alibi_bias", "backpack", "extend", "BatchGrad", "SqrtGGNExact", "SqrtGGNMC", "ViViTGGNExact", "ViViTGGNMC"]

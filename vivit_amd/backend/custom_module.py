@@ -7,6 +7,8 @@ support (vivit/extensions/secondorder/vivit/__init__.py:113-117) and its tests u
 """
 from typing import Sequence, Tuple, Union
 
+import math
+
 import torch
 from torch import Tensor, nn
 from torch.nn import functional as F
@@ -178,6 +180,55 @@ def attention_visible(T: int, lengths, causal: bool, window, device) -> Tensor:
     return vis
 
 
+def _softcap(cap):
+    """The ``softcap`` argument of the attention modules and of :class:`SoftCap`, validated (``None`` stays ``None``: no cap)."""
+    if cap is None:
+        return None
+    if isinstance(cap, bool) or not isinstance(cap, (int, float)) or not (cap > 0) or math.isinf(cap):
+        raise ValueError(f"softcap must be a finite float > 0 (or None), got {cap!r}")
+    return float(cap)
+
+
+class SoftCap(nn.Module):
+    """``cap * tanh(x / cap)`` (no counterpart in BackPACK): the soft cap of Gemma-2's and Grok-1's final logits, an elementwise
+    leaf (the rule is the activation kind ``"softcap"`` of ``kernels.act_jac_t``)."""
+
+    def __init__(self, cap: float):
+        super().__init__()
+        if cap is None:
+            raise ValueError("SoftCap needs a cap")
+        self.cap = _softcap(cap)
+
+    def forward(self, x: Tensor) -> Tensor:
+        return self.cap * torch.tanh(x / self.cap)
+
+    def extra_repr(self) -> str:
+        return f"cap={self.cap}"
+
+
+def alibi_slopes(num_heads: int) -> Tensor:
+    """The head slopes ``m_h`` of ALiBi (Press et al., 2022) in float64: for ``H`` a power of two the geometric sequence
+    ``2^(-8 (h + 1) / H)``; for another ``H`` the slopes of the next lower power of two ``P``, then every second slope of ``2 P``
+    (the first, third, ... of that sequence) until there are ``H``."""
+    if num_heads < 1:
+        raise ValueError(f"num_heads must be positive, got {num_heads}")
+    geometric = lambda n: [2.0 ** (-8.0 * (h + 1) / n) for h in range(n)]   # noqa: E731
+    P = 1 << (int(num_heads).bit_length() - 1)
+    slopes = geometric(P)
+    if P < num_heads:
+        slopes += geometric(2 * P)[0::2][:num_heads - P]
+    return torch.tensor(slopes, dtype=torch.float64)
+
+
+def alibi_bias(num_heads: int, max_len: int) -> Tensor:
+    """The ALiBi table for ``ScaledDotProductAttention(bias=...)``: ``[H, 2 max_len - 1]`` float32, entry ``[h, j - i + max_len - 1]``
+    is ``-m_h |j - i|`` with the slopes of :func:`alibi_slopes`.  Under ``causal`` only the half ``j <= i`` is ever read."""
+    if max_len < 1:
+        raise ValueError(f"max_len must be positive, got {max_len}")
+    dist = torch.arange(-(max_len - 1), max_len, dtype=torch.float64).abs()
+    return (-alibi_slopes(num_heads)[:, None] * dist[None, :]).to(torch.float32)
+
+
 class ScaledDotProductAttention(nn.Module):
     """Multi-head scaled dot-product self-attention on a packed projection (no counterpart in BackPACK): a parameter-free leaf.
 
@@ -186,7 +237,16 @@ class ScaledDotProductAttention(nn.Module):
     ``[N, T, E]``: per head ``softmax(scale q k^T) v`` with ``scale = 1 / sqrt(d)`` by default; ``causal`` masks the keys ``j > i``.
     No dropout.  ``window`` (an integer ``>= 1``; sliding-window attention): query ``i`` sees the keys with ``|i - j| < window`` --
     with ``causal`` the ``window`` keys ``i - window + 1 .. i``, its own position included (Mistral's convention); ``window >= T`` is
-    no window.  No arbitrary or additive mask.
+    no window.  No arbitrary ``[T, T]`` or per-sample mask.
+
+    Score modifiers.  With ``z_ij = scale q_i k_j`` the logits are ``s_ij = u_ij + bias[h, j - i + L - 1]``, ``u = softcap *
+    tanh(z / softcap)``, then the mask: the cap comes before the bias, and both before the mask (Gemma-2's order).  ``softcap`` (a
+    finite float ``> 0``; ``None``: ``u = z``) is the logit cap of Gemma-2 and Grok-1.  ``bias`` (``None``: none) is a tensor
+    ``[H, 2 L - 1]`` for a maximum length ``L``: one value per query head and distance ``j - i``, as ALiBi (:func:`alibi_bias`) and
+    the relative-position tables of T5 and Swin have it.  A batch of ``T <= L`` positions uses the middle slice
+    ``bias[:, L - T : L + T - 1]``; ``T > L`` is a ``ValueError``.  The table is a buffer of the module (it moves with ``.to()``), its
+    entries must be finite, and it is a CONSTANT of the function: it receives no gradient and no factor, so a learned table is
+    treated as frozen.
 
     Padded batches: ``set_lengths(lengths)`` gives sample ``n`` the positions ``0 .. lengths[n] - 1`` (RIGHT padding only; a
     left-padded batch is not supported) for every forward pass until it is reset with ``set_lengths(None)``.  The positions beyond are
@@ -203,13 +263,24 @@ class ScaledDotProductAttention(nn.Module):
     ``h // (H / Hkv)`` (groups of consecutive heads, as LLaMA's ``repeat_kv``).  Output ``[N, T, H d]``.  ``Hkv == 1`` is multi-query
     attention."""
 
-    def __init__(self, num_heads: int, causal: bool = False, scale: float = None, num_kv_heads: int = None, window: int = None):
+    def __init__(self, num_heads: int, causal: bool = False, scale: float = None, num_kv_heads: int = None, window: int = None,
+                 softcap: float = None, bias: Tensor = None):
         super().__init__()
         if num_heads < 1:
             raise ValueError(f"num_heads must be positive, got {num_heads}")
         self.num_heads, self.causal, self.scale = int(num_heads), bool(causal), scale
         self.num_kv_heads = _kv_heads(num_heads, num_kv_heads)
         self.window = _window(window)
+        self.softcap = _softcap(softcap)
+        if bias is not None:
+            if not isinstance(bias, Tensor) or not bias.is_floating_point() or bias.dim() != 2 or bias.shape[0] != num_heads or \
+                    bias.shape[1] % 2 != 1:
+                raise ValueError(f"bias must be a floating-point tensor [H = {num_heads}, 2 L - 1], got "
+                                 f"{tuple(bias.shape) if isinstance(bias, Tensor) else type(bias).__name__}")
+            if not bool(torch.isfinite(bias).all()):
+                raise ValueError("bias must be finite (masking is what causal, window and set_lengths are for)")
+            bias = bias.detach().clone()
+        self.register_buffer("bias", bias)
         self._lengths = None          # what set_lengths() was given
         self.forward_lengths = None   # int32 [N] on the input's device: what the last forward() used (None: no lengths)
 
@@ -243,8 +314,30 @@ class ScaledDotProductAttention(nn.Module):
     def scale_for(self, d: int) -> float:
         return float(self.scale) if self.scale is not None else d ** -0.5
 
+    def bias_for(self, T: int):
+        """The table of a batch of ``T`` positions, ``[H, 2 T - 1]`` indexed by ``j - i + T - 1`` (a view: the middle slice of the
+        buffer); ``None`` without a table."""
+        if self.bias is None:
+            return None
+        L = (self.bias.shape[1] + 1) // 2
+        if T > L:
+            raise ValueError(f"the batch has T = {T} positions, the bias table was built for at most {L}")
+        return self.bias[:, L - T:L + T - 1]
+
+    def modify(self, z: Tensor) -> Tensor:
+        """The logits ``s [N, Hkv, R, T, T]`` before the mask from ``z = scale q k^T``: the cap, then the bias."""
+        T = z.shape[-1]
+        if self.softcap is not None:
+            z = self.softcap * torch.tanh(z / self.softcap)
+        table = self.bias_for(T)
+        if table is not None:
+            t = torch.arange(T, device=z.device)
+            z = z + table.to(z.dtype)[:, t[None, :] - t[:, None] + (T - 1)].view(z.shape[-4], z.shape[-3], T, T)
+        return z
+
     def forward(self, qkv: Tensor) -> Tensor:
         self.head_dim(qkv)
+        self.bias_for(qkv.shape[1])
         self.forward_lengths = self.lengths_for(qkv)
         return self.attend(qkv, self.forward_lengths)
 
@@ -270,7 +363,7 @@ class ScaledDotProductAttention(nn.Module):
         if dead is not None:   # the dead rows of q, k and v are zeros, whatever the input holds there
             qkv = qkv.masked_fill(dead, 0.0)
         q, k, v = _gqa_split(qkv, H, self.kv_heads, d)                    # q [N, Hkv, R, T, d]; k, v [N, Hkv, 1, T, d]: views
-        s = (q @ k.transpose(-1, -2)) * self.scale_for(d)                 # (the matmul broadcasts k and v over the group)
+        s = self.modify((q @ k.transpose(-1, -2)) * self.scale_for(d))    # (the matmul broadcasts k and v over the group)
         if hidden is not None:
             s = s.masked_fill(hidden, float("-inf"))
         return (s.softmax(-1) @ v).reshape(N, H, T, d).transpose(1, 2).reshape(N, T, H * d)   # (a new tensor: the heads are gathered)
@@ -330,13 +423,21 @@ class MultiheadSelfAttention(nn.Sequential):
     """``Linear(E, 3 E)`` -> :class:`ScaledDotProductAttention` -> ``Linear(E, E)``: ``nn.MultiheadAttention(batch_first=True)``
     applied to ``(x, x, x)`` as a container of single-input leaves, which is what the extensions' rules are written for.  With
     ``num_kv_heads`` (grouped-query attention) the first projection is ``Linear(E, (H + 2 Hkv) d)``, ``d = E / H``.  ``window`` and
-    ``set_lengths`` are those of :class:`ScaledDotProductAttention` (sliding-window attention; right-padded batches)."""
+    ``set_lengths`` are those of :class:`ScaledDotProductAttention` (sliding-window attention; right-padded batches), and so are
+    ``softcap`` and ``attention_bias`` (its ``bias``: the table ``[H, 2 L - 1]``, e.g. :func:`alibi_bias`; the name ``bias`` is taken
+    by the flag of the two projections, as in ``nn.MultiheadAttention`` -- a TENSOR given as ``bias`` is taken for the table and the
+    projections keep their bias vectors)."""
 
-    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True, causal: bool = False, num_kv_heads: int = None,
-                 window: int = None):
+    def __init__(self, embed_dim: int, num_heads: int, bias: Union[bool, Tensor] = True, causal: bool = False, num_kv_heads: int = None,
+                 window: int = None, softcap: float = None, attention_bias: Tensor = None):
         if embed_dim % num_heads != 0:
             raise ValueError(f"embed_dim ({embed_dim}) is not divisible by num_heads ({num_heads})")
-        attention = ScaledDotProductAttention(num_heads, causal=causal, num_kv_heads=num_kv_heads, window=window)
+        if isinstance(bias, Tensor):
+            if attention_bias is not None:
+                raise ValueError("two bias tables: give the table as bias or as attention_bias, not both")
+            bias, attention_bias = True, bias
+        attention = ScaledDotProductAttention(num_heads, causal=causal, num_kv_heads=num_kv_heads, window=window, softcap=softcap,
+                                              bias=attention_bias)
         packed = (num_heads + 2 * attention.kv_heads) * (embed_dim // num_heads)
         super().__init__(nn.Linear(embed_dim, packed, bias=bias), attention, nn.Linear(embed_dim, embed_dim, bias=bias))
 

@@ -20,7 +20,7 @@ from torch import Tensor, nn
 from vivit_amd import _lib, kernels
 from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, Permute, ProductModule, RotaryEmbedding, ScaledDotProductAttention,
                                               ScaledDotProductCrossAttention, ScaleModule,
-                                              Slicing, SumModule, _gqa_split)
+                                              Slicing, SoftCap, SumModule, _gqa_split)
 from vivit_amd.utils.ggn import Vmp
 from vivit_amd.utils.gram import mVp, pairwise_dot
 
@@ -571,7 +571,8 @@ def _conv_weight_factor(module, M: Tensor, x: Tensor) -> Tensor:
 
 _ACTIVATIONS = {nn.ReLU: ("relu", None), nn.Sigmoid: ("sigmoid", None), nn.Tanh: ("tanh", None),
                 nn.LeakyReLU: ("leaky_relu", "negative_slope"), nn.LogSigmoid: ("logsigmoid", None), nn.ELU: ("elu", "alpha"),
-                nn.SELU: ("selu", None), nn.GELU: ("gelu", None), nn.SiLU: ("silu", None)}   # (GELU: see _activation_kind)
+                nn.SELU: ("selu", None), nn.GELU: ("gelu", None), nn.SiLU: ("silu", None),   # (GELU: see _activation_kind)
+                SoftCap: ("softcap", "cap")}
 
 
 def _activation_kind(module):
@@ -626,7 +627,8 @@ def _attention_jac_t_torch(module, M: Tensor, x: Tensor, out: Tensor, lengths: O
     ``out [N, T, H d]`` -> ``[V, N, T, (H + 2 Hkv) d]``.  Query head ``h`` uses key / value head ``h // R``; dK and dV of a group are
     the sums over its ``R = H / Hkv`` query heads (multi-head attention: ``R = 1``).  K and V are broadcast views over the group axis,
     never expanded copies.  ``lengths`` (int32 ``[N]`` or ``None``) and ``module.window``: the mask of the forward pass; the rows of
-    the dead positions are exact zeros.  No autograd."""
+    the dead positions are exact zeros.  ``module.softcap`` and ``module.bias``: the score function of the forward pass
+    (``module.modify``), and ``dZ = dS (1 - t^2)`` in the place of ``dS`` under a cap.  No autograd."""
     d, H, Hkv = module.head_dim(x), module.num_heads, module.kv_heads
     scale, R = module.scale_for(d), H // Hkv
     V, (N, T) = M.shape[0], x.shape[:2]
@@ -635,13 +637,16 @@ def _attention_jac_t_torch(module, M: Tensor, x: Tensor, out: Tensor, lengths: O
     if dead is not None:   # whatever the dead positions hold is not used
         M, x, out = M.masked_fill(dead, 0.0), x.masked_fill(dead, 0.0), out.masked_fill(dead, 0.0)
     q, k, v = _gqa_split(x, H, Hkv, d)                                             # q [N, Hkv, R, T, d]; k, v [N, Hkv, 1, T, d]
-    S = (q @ k.transpose(-1, -2)) * scale
+    Z = (q @ k.transpose(-1, -2)) * scale
+    S = module.modify(Z)
     if hidden is not None:
         S = S.masked_fill(hidden, float("-inf"))
     P = S.softmax(-1)                                                             # [N, Hkv, R, T, T], shared by the V slices
     dO = M.reshape(V, N, T, Hkv, R, d).permute(0, 1, 3, 4, 2, 5)                  # [V, N, Hkv, R, T, d]
     D = (dO * out.view(N, T, Hkv, R, d).permute(0, 2, 3, 1, 4)).sum(-1, keepdim=True)
     dS = P * (dO @ v.transpose(-1, -2) - D)
+    if module.softcap is not None:   # dZ: the cap's derivative 1 - t^2, t = tanh(z / c)
+        dS = dS * (1.0 - torch.tanh(Z / module.softcap) ** 2)
     dQ = (dS @ k) * scale                                                         # [V, N, Hkv, R, T, d]
     # the sum over the group's heads and over the queries is one contraction of length R T
     dV = P.reshape(N, Hkv, R * T, T).transpose(-1, -2) @ dO.reshape(V, N, Hkv, R * T, d)
@@ -750,7 +755,7 @@ def _rope_jac_t_torch(module, M: Tensor, x: Tensor) -> Tensor:
 
 def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optional[Tensor]:
     """The layer rules that have a HIP kernel (csrc/jacobians.hip, csrc/norm_rules.hip, csrc/llama_rules.hip, csrc/attention.hip): activations (ReLU, Sigmoid, Tanh, LeakyReLU,
-    LogSigmoid, ELU, SELU, GELU in both forms, SiLU), Flatten / Identity / ActiveIdentity / Dropout(eval), ScaleModule,
+    LogSigmoid, ELU, SELU, GELU in both forms, SiLU, SoftCap), Flatten / Identity / ActiveIdentity / Dropout(eval), ScaleModule,
     Max/AvgPool1d/2d, Conv1d / Conv2d and ConvTranspose1d / 2d (any groups, zero padding), Pad / ZeroPad2d / Slicing,
     BatchNorm (eval), LayerNorm and GroupNorm (with or without affine parameters; the same visit of the factor serves their
     parameter rules), RMSNorm (likewise), RotaryEmbedding, ScaledDotProductAttention (head dimensions up to 128; the forward output it needs is ``module.output``,
@@ -853,11 +858,16 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
         # the kernel's index arithmetic come back as VIVIT_E_UNSUPPORTED and the caller falls through likewise)
         d = module.head_dim(x)
         lengths = _attention_lengths(module, x, subsampling)
-        if d > 128:   # (with lengths the formula in torch: the generic rule's forward pass would not know the sub-sampled ones)
-            return None if lengths is None else _attention_jac_t_torch(module, M, x, _attention_out(module, x, subsampling), lengths)
+        table = module.bias_for(x.shape[1])
+        if d > 128:   # (with lengths the formula in torch: the generic rule's forward pass would not know the sub-sampled ones; with a
+            # score modifier likewise: the generic rule would hold [V, N, H, T, T] several times over)
+            if lengths is None and module.softcap is None and table is None:
+                return None
+            return _attention_jac_t_torch(module, M, x, _attention_out(module, x, subsampling), lengths)
         return kernels.attention_jac_t(M.reshape(M.shape[0], *x.shape[:2], -1), x, _attention_out(module, x, subsampling), module.num_heads,
                                        module.scale_for(d), module.causal, num_kv_heads=module.kv_heads, lengths=lengths,
-                                       window=module.window)
+                                       window=module.window, softcap=module.softcap,
+                                       bias=None if table is None else table.to(torch.float32).contiguous())
     if isinstance(module, _BATCHNORM) and x.dim() >= 2:
         if _own_params(module):   # the parameter rules want the two row sums of the same pass
             return _bn_eval_rules(module, M, x)[0]

@@ -54,6 +54,19 @@
 // the key blocks 0 .. ceil(Lk / 32) - 1, the key-block owner the query blocks 0 .. ceil(Lq / 32) - 1 of each head, in the order
 // above: with Tq = Tk, equal lengths and the packed projection split in two, the tiles, the order and the bytes of the non-causal
 // self-attention call.  Either result may be left out (a frozen memory needs no Gkv): its owner is not launched.
+//
+// SCORE MODIFIERS (vivit_attention_scoremod_jac_t_f32; self-attention only): a logit cap c > 0 and a table B [H, 2 T - 1] of biases
+// per head and distance.  With z_ij = scale q_i k_j,
+//   u = c tanh(z / c)  (no cap: u = z),   s_ij = u + B[h, j - i + T - 1]  (no table: s = u),   then the mask,  P = softmax_rows(s),
+//   dS = P o (dP - D),   dZ = dS o (1 - t^2) with t = u / c  (no cap: dZ = dS),   dQ_h = scale dZ K_g,   dK_g = scale sum_h dZ_h^T Q_h,
+// and dV as it was; the table is a constant and gets no factor.  The variant is COMPILE TIME again: the kernels' second template
+// parameter Mod is AttPlain (the expressions that were there; every instance above) or AttScoreMod, whose instances exist for
+// AttGeom alone.  att_logit forms s_ij from the product q_i k_j for lse and for both owners, the same operations in the same order and
+// none of them contracted with a neighbour, so exp(s - lse) sees the very s that lse summed.  Neither owner keeps a second tile: the
+// weight P o (1 - t^2) of (dP - D) is formed in the registers of P once P itself is in LDS (the key owner, for dV) or in its place
+// (the query owner, which never uses P alone).  A table entry is read through the caches, for visible pairs only: both positions
+// are then < Tn <= T, so j - i + T - 1 stays in [0, 2 T - 2].  Summation order, block ranges, dead positions and +0 rows are those
+// above; the bytes of G[v, n] depend on the cap and the table besides.
 #include <math.h>
 
 #include "common.h"
@@ -231,9 +244,38 @@ __device__ __forceinline__ void att_query_range(const AttGeomX &, AttLive L, int
   q_lo = gj < L.k ? 0 : 0x7fffffff, q_hi = L.q - 1;
 }
 
+// ---- the score function (SCORE MODIFIERS at the head of the file) -------------------------------------------------------------------
+struct AttPlain {};
+struct AttScoreMod {
+  float cap;           // c > 0, or 0: none
+  const float *bias;   // [H, 2 T - 1] on the device, or null: none
+};
+
+// the table row of head h, offset so that it is indexed by j - i in (-T, T)
+__device__ __forceinline__ const float *att_bias_row(const AttPlain &, int, int) { return nullptr; }
+__device__ __forceinline__ const float *att_bias_row(const AttScoreMod &m, int T, int h) {
+  return m.bias ? m.bias + (int64_t)h * (2 * (int64_t)T - 1) + (T - 1) : nullptr;
+}
+
+// the logit s_ij of a VISIBLE pair from qk = q_i k_j (dji = j - i, `row` from att_bias_row); keep = 1 - t^2, the factor of dS in dZ
+__device__ __forceinline__ float att_logit(const AttPlain &, float qk, float scale, const float *, int, float &) { return qk * scale; }
+__device__ __forceinline__ float att_logit(const AttScoreMod &m, float qk, float scale, const float *row, int dji, float &keep) {
+#pragma clang fp contract(off)   // (lse stores s, the owners subtract lse from it: no product here may fuse with what follows)
+  float u = qk * scale;
+  if (m.cap > 0.f) {
+    const float t = tanhf(u / m.cap);
+    u = m.cap * t;
+    keep = 1.f - t * t;
+  }
+  return row ? u + row[dji] : u;
+}
+// the weight of (dP - D) in dZ
+__device__ __forceinline__ float att_dz_weight(const AttPlain &, float p, float) { return p; }
+__device__ __forceinline__ float att_dz_weight(const AttScoreMod &, float p, float keep) { return p * keep; }
+
 // ---- row log-sum-exp --------------------------------------------------------------------------------------------------------------
-template <int NT, class Geo>
-__global__ __launch_bounds__(256) void attn_lse_kernel(const float *__restrict__ qkv, float *__restrict__ lse, Geo g) {
+template <int NT, class Geo, class Mod>
+__global__ __launch_bounds__(256) void attn_lse_kernel(const float *__restrict__ qkv, float *__restrict__ lse, Geo g, Mod mod) {
   extern __shared__ __attribute__((aligned(16))) float att_smem[];
   using C = AttCfg<NT>;
   float *sQ = att_smem, *sK = sQ + C::BLK, *sS = sK + C::BLK;   // sS [32][33]
@@ -249,6 +291,7 @@ __global__ __launch_bounds__(256) void attn_lse_kernel(const float *__restrict__
   const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
   const int row = tid >> 3, sub = tid & 7;
   float m = -INFINITY, l = 0.f;
+  const float *brow = att_bias_row(mod, att_Tq(g), h);
   const int KBn = (L.k + ATT_B - 1) / ATT_B, wb = att_reach(g, KBn);
   const int jb_lo = max(ib - wb, 0), jb_hi = att_causal(g) ? ib : min(ib + wb, KBn - 1);
   for (int jb = jb_lo; jb <= jb_hi; ++jb) {
@@ -260,7 +303,8 @@ __global__ __launch_bounds__(256) void attn_lse_kernel(const float *__restrict__
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int r = 16 * ri + 4 * kq + e, c = 16 * cj + j;
-      sS[r * 33 + c] = att_valid(g, L, i0 + r, j0 + c) ? s[e] * g.scale : -INFINITY;
+      float keep;
+      sS[r * 33 + c] = att_valid(g, L, i0 + r, j0 + c) ? att_logit(mod, s[e], g.scale, brow, j0 - i0 + c - r, keep) : -INFINITY;
     }
     __syncthreads();
     // eight lanes per row, four columns each; every lane of a row keeps the same (m, l)
@@ -318,26 +362,30 @@ __device__ __forceinline__ void att_load_factor(float *__restrict__ sdO, float *
 }
 
 // one wave's 16 x 16 part of P = exp(S - lse) for the tile (query block at i0, key block at j0); zero where masked or beyond Tn
-// (`visible(r, c)`: att_valid of the pair at row r and column c of the tile, in whatever form the owner keeps it)
-template <int NT, class Visible>
+// (`visible(r, c)`: att_valid of the pair at row r and column c of the tile, in whatever form the owner keeps it).  `w`: the weight
+// of (dP - D) in dZ, P itself without a cap; `brow`, `dj0 = j0 - i0`: the head's table row and the tile's distance for att_logit
+template <int NT, class Mod, class Visible>
 __device__ __forceinline__ att_f32x4 att_p_tile(const float *__restrict__ sQ, const float *__restrict__ sK, const float *__restrict__ sL,
-                                                float scale, int dk, int lane, int ri, int cj, Visible visible) {
+                                                float scale, int dk, int lane, int ri, int cj, const Mod &mod,
+                                                const float *__restrict__ brow, int dj0, att_f32x4 &w, Visible visible) {
   using C = AttCfg<NT>;
   const att_f32x4 s = att_tile_nt<NT>(sQ + 16 * ri * C::LD, sK + 16 * cj * C::LD, dk, lane);
   att_f32x4 p;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int r = 16 * ri + 4 * (lane >> 4) + e, c = 16 * cj + (lane & 15);
-    p[e] = visible(r, c) ? expf(s[e] * scale - sL[r]) : 0.f;
+    float keep = 1.f;
+    p[e] = visible(r, c) ? expf(att_logit(mod, s[e], scale, brow, dj0 + c - r, keep) - sL[r]) : 0.f;
+    w[e] = att_dz_weight(mod, p[e], keep);
   }
   return p;
 }
 
 // ---- key-block owner: dK and dV ---------------------------------------------------------------------------------------------------
-template <int NT, class Geo>
+template <int NT, class Geo, class Mod>
 __global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__ M, const float *__restrict__ qkv,
                                                        const float *__restrict__ lse, const float *__restrict__ Dws, float *__restrict__ G,
-                                                       int64_t V, Geo g) {
+                                                       int64_t V, Geo g, Mod mod) {
   extern __shared__ __attribute__((aligned(16))) float att_smem[];
   using C = AttCfg<NT>;
   float *sK = att_smem, *sV = sK + C::BLK, *sQ = sV + C::BLK, *sdO = sQ + C::BLK;
@@ -383,7 +431,9 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__
     if (tid < ATT_B) sL[tid] = i0 + tid < L.q ? lse[nh * att_Tq(g) + i0 + tid] : 0.f;
     att_load_factor<NT>(sdO, sD, M, Dws, g, L.q, v0, nv, n, h, i0);
     __syncthreads();
-    const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g.scale, dk, lane, ri, cj, [&](int r, int) { return i0 + r >= q_lo && i0 + r <= q_hi; });
+    att_f32x4 w;
+    const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g.scale, dk, lane, ri, cj, mod, att_bias_row(mod, att_Tq(g), h), j0 - i0, w,
+                                       [&](int r, int) { return i0 + r >= q_lo && i0 + r <= q_hi; });
 #pragma unroll
     for (int e = 0; e < 4; ++e) sP[(16 * ri + 4 * kq + e) * ATT_LDP + 16 * cj + j] = p[e];
 #pragma unroll
@@ -393,7 +443,7 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int r = 16 * ri + 4 * kq + e;
-          sdS[vi * C::TILE + r * ATT_LDP + 16 * cj + j] = p[e] * (dp[e] - sD[vi * ATT_B + r]);
+          sdS[vi * C::TILE + r * ATT_LDP + 16 * cj + j] = w[e] * (dp[e] - sD[vi * ATT_B + r]);
         }
       }
     __syncthreads();
@@ -433,10 +483,10 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__
 }
 
 // ---- query-block owner: dQ --------------------------------------------------------------------------------------------------------
-template <int NT, class Geo>
+template <int NT, class Geo, class Mod>
 __global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ M, const float *__restrict__ qkv,
                                                       const float *__restrict__ lse, const float *__restrict__ Dws, float *__restrict__ G,
-                                                      int64_t V, Geo g) {
+                                                      int64_t V, Geo g, Mod mod) {
   extern __shared__ __attribute__((aligned(16))) float att_smem[];
   using C = AttCfg<NT>;
   float *sK = att_smem, *sV = sK + C::BLK, *sQ = sV + C::BLK, *sdO = sQ + C::BLK;
@@ -461,6 +511,7 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ 
     att_load_factor<NT>(sdO, sD, M, Dws, g, L.q, v0, nv, n, h, i0);
   }
   const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
+  const float *brow = att_bias_row(mod, att_Tq(g), h);
   att_f32x4 accQ[C::VC][C::TPW];
 #pragma unroll
   for (int vi = 0; vi < C::VC; ++vi)
@@ -472,7 +523,8 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ 
     att_load_block<NT>(sK, kbase, kpitch, j0, L.k, g.d, g.vec);
     att_load_block<NT>(sV, kbase + att_k_to_v(g), kpitch, j0, L.k, g.d, g.vec);
     __syncthreads();
-    const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g.scale, dk, lane, ri, cj, [&](int r, int c) { return att_valid(g, L, i0 + r, j0 + c); });
+    att_f32x4 w;   // (P alone is not used here)
+    att_p_tile<NT>(sQ, sK, sL, g.scale, dk, lane, ri, cj, mod, brow, j0 - i0, w, [&](int r, int c) { return att_valid(g, L, i0 + r, j0 + c); });
 #pragma unroll
     for (int vi = 0; vi < C::VC; ++vi)
       if (vi < nv) {
@@ -480,7 +532,7 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const int r = 16 * ri + 4 * kq + e;
-          sdS[vi * C::TILE + r * ATT_LDP + 16 * cj + j] = p[e] * (dp[e] - sD[vi * ATT_B + r]);
+          sdS[vi * C::TILE + r * ATT_LDP + 16 * cj + j] = w[e] * (dp[e] - sD[vi * ATT_B + r]);
         }
       }
     __syncthreads();
@@ -555,56 +607,46 @@ static AttPlan attention_cross_plan(int64_t V, int64_t N, int64_t Tq, int64_t Tk
 
 // the four launches; `G`: the result of the query owner (null: not launched), `Gkv`: that of the key owner (null: not launched; for
 // self-attention the same packed tensor as G)
-template <int NT, class Geo>
+template <int NT, class Geo, class Mod>
 static int attention_launch(const float *M, const float *qkv, const float *out, float *G, float *Gkv, float *lse, float *Dws,
-                            int64_t V, const Geo &g, int T, int KBq, int KBk, hipStream_t s) {
+                            int64_t V, const Geo &g, const Mod &mod, int T, int KBq, int KBk, hipStream_t s) {
   using C = AttCfg<NT>;
   static unsigned long long attr_done = 0;
   constexpr int lse_lds = C::LSE_FLOATS * 4, own_lds = C::OWN_FLOATS * 4;
   if (own_lds > 64 * 1024) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return VIVIT_E_LAUNCH;
-    if (!ensure_dynamic_lds(reinterpret_cast<const void *>(attn_dkv_kernel<NT, Geo>), own_lds, attr_done) ||
-        !ensure_dynamic_lds(reinterpret_cast<const void *>(attn_dq_kernel<NT, Geo>), own_lds, attr_done))
+    if (!ensure_dynamic_lds(reinterpret_cast<const void *>(attn_dkv_kernel<NT, Geo, Mod>), own_lds, attr_done) ||
+        !ensure_dynamic_lds(reinterpret_cast<const void *>(attn_dq_kernel<NT, Geo, Mod>), own_lds, attr_done))
       return VIVIT_E_LAUNCH;
     attr_done |= 1ull << (dev & 63);
   }
   const int64_t NH = (int64_t)g.N * g.H, total = V * NH * T;
   const unsigned blocks = (unsigned)(NH * KBq), kv_blocks = (unsigned)((int64_t)g.N * g.Hkv * KBk);
-  attn_lse_kernel<NT, Geo><<<blocks, 256, lse_lds, s>>>(qkv, lse, g);
+  attn_lse_kernel<NT, Geo, Mod><<<blocks, 256, lse_lds, s>>>(qkv, lse, g, mod);
   attn_rowdot_kernel<Geo><<<(unsigned)cdiv(total, 256), 256, 0, s>>>(M, out, Dws, total, g);
   const unsigned chunks = (unsigned)cdiv(V, C::VC);
-  if (Gkv) attn_dkv_kernel<NT, Geo><<<dim3(kv_blocks, chunks), 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g);
-  if (G) attn_dq_kernel<NT, Geo><<<dim3(blocks, chunks), 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g);
+  if (Gkv) attn_dkv_kernel<NT, Geo, Mod><<<dim3(kv_blocks, chunks), 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g, mod);
+  if (G) attn_dq_kernel<NT, Geo, Mod><<<dim3(blocks, chunks), 256, own_lds, s>>>(M, qkv, lse, Dws, G, V, g, mod);
   return launch_status();
 }
 
-template <class Geo>
+template <class Geo, class Mod>
 static int attention_launch_d(const float *M, const float *qkv, const float *out, float *G, float *Gkv, float *lse, float *Dws,
-                              int64_t V, const Geo &g, int T, int KBq, int KBk, hipStream_t s) {
-  if (g.d <= 16) return attention_launch<1>(M, qkv, out, G, Gkv, lse, Dws, V, g, T, KBq, KBk, s);
-  if (g.d <= 32) return attention_launch<2>(M, qkv, out, G, Gkv, lse, Dws, V, g, T, KBq, KBk, s);
-  if (g.d <= 64) return attention_launch<4>(M, qkv, out, G, Gkv, lse, Dws, V, g, T, KBq, KBk, s);
-  return attention_launch<8>(M, qkv, out, G, Gkv, lse, Dws, V, g, T, KBq, KBk, s);
+                              int64_t V, const Geo &g, const Mod &mod, int T, int KBq, int KBk, hipStream_t s) {
+  if (g.d <= 16) return attention_launch<1>(M, qkv, out, G, Gkv, lse, Dws, V, g, mod, T, KBq, KBk, s);
+  if (g.d <= 32) return attention_launch<2>(M, qkv, out, G, Gkv, lse, Dws, V, g, mod, T, KBq, KBk, s);
+  if (g.d <= 64) return attention_launch<4>(M, qkv, out, G, Gkv, lse, Dws, V, g, mod, T, KBq, KBk, s);
+  return attention_launch<8>(M, qkv, out, G, Gkv, lse, Dws, V, g, mod, T, KBq, KBk, s);
 }
 
 static inline bool att_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-} // namespace vivit
-
-using namespace vivit;
-
-extern "C" {
-
-size_t vivit_attention_masked_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d) {
-  const AttPlan p = attention_plan(V, N, T, H, Hkv, d);
-  return p.status == VIVIT_OK ? p.bytes : 0;
-}
-
-// lengths [N] int32 on the device or null; window >= 1 or 0 (none): the one entry that launches, the others below call it
-int vivit_attention_masked_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
-                                     int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths,
-                                     int64_t window, void *workspace, size_t workspace_bytes, void *stream) {
+// the self-attention entries: every refusal, then the four launches with the score function `mod`
+template <class Mod>
+static int attention_self(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T, int64_t H,
+                          int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths, int64_t window, const Mod &mod,
+                          void *workspace, size_t workspace_bytes, void *stream) {
   if (!M || !qkv || !out || !G || window < 0) return VIVIT_E_BADARG;
   const AttPlan p = attention_plan(V, N, T, H, Hkv, d);
   if (p.status != VIVIT_OK) return p.status;
@@ -621,7 +663,43 @@ int vivit_attention_masked_jac_t_f32(const float *M, const float *qkv, const flo
   float *lse = static_cast<float *>(workspace);
   float *Dws = reinterpret_cast<float *>(static_cast<char *>(workspace) + p.lse_bytes);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  return attention_launch_d(M, qkv, out, G, G, lse, Dws, V, g, g.T, g.KB, g.KB, s);
+  return attention_launch_d(M, qkv, out, G, G, lse, Dws, V, g, mod, g.T, g.KB, g.KB, s);
+}
+
+} // namespace vivit
+
+using namespace vivit;
+
+extern "C" {
+
+size_t vivit_attention_masked_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d) {
+  const AttPlan p = attention_plan(V, N, T, H, Hkv, d);
+  return p.status == VIVIT_OK ? p.bytes : 0;
+}
+
+// lengths [N] int32 on the device or null; window >= 1 or 0 (none): the one entry that launches, the others below call it
+int vivit_attention_masked_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
+                                     int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths,
+                                     int64_t window, void *workspace, size_t workspace_bytes, void *stream) {
+  return attention_self(M, qkv, out, G, V, N, T, H, Hkv, d, scale, causal, lengths, window, AttPlain{}, workspace, workspace_bytes, stream);
+}
+
+// the score modifiers (the head of the file): softcap > 0 or 0 (none), bias [H, 2 T - 1] on the device or null (none); with neither
+// the masked entry, its plain instances and its bytes
+size_t vivit_attention_scoremod_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d) {
+  return vivit_attention_masked_jac_t_f32_workspace_bytes(V, N, T, H, Hkv, d);
+}
+
+int vivit_attention_scoremod_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
+                                       int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths,
+                                       int64_t window, float softcap, const float *bias, void *workspace, size_t workspace_bytes,
+                                       void *stream) {
+  if (!(softcap >= 0.f) || isinf(softcap)) return VIVIT_E_BADARG;   // (negative, NaN, inf)
+  if (softcap == 0.f && !bias)
+    return vivit_attention_masked_jac_t_f32(M, qkv, out, G, V, N, T, H, Hkv, d, scale, causal, lengths, window, workspace, workspace_bytes,
+                                            stream);
+  return attention_self(M, qkv, out, G, V, N, T, H, Hkv, d, scale, causal, lengths, window, AttScoreMod{softcap, bias}, workspace,
+                        workspace_bytes, stream);
 }
 
 // cross-attention (the head of the file): q_lengths, k_lengths [N] int32 on the device or null; Gq or Gkv may be null, not both
@@ -651,7 +729,7 @@ int vivit_attention_cross_jac_t_f32(const float *M, const float *q, const float 
   g.qlengths = q_lengths, g.klengths = k_lengths;
   float *lse = static_cast<float *>(workspace);
   float *Dws = reinterpret_cast<float *>(static_cast<char *>(workspace) + p.lse_bytes);
-  return attention_launch_d(M, q, out, Gq, Gkv, lse, Dws, V, g, g.Tq, g.KBq, g.KBk, static_cast<hipStream_t>(stream));
+  return attention_launch_d(M, q, out, Gq, Gkv, lse, Dws, V, g, AttPlain{}, g.Tq, g.KBq, g.KBk, static_cast<hipStream_t>(stream));
 }
 
 // grouped-query attention without lengths or a window

@@ -14,7 +14,7 @@ namespace vivit {
 
 // ---- elementwise activations: out[v, n, e] = M[v, n, e] * f'(x[n, e]) ----------------------------------------------
 enum { ACT_RELU = 0, ACT_SIGMOID = 1, ACT_TANH = 2, ACT_LEAKY_RELU = 3, ACT_LOGSIGMOID = 4, ACT_ELU = 5, ACT_SELU = 6, ACT_GELU = 7,
-       ACT_GELU_TANH = 8, ACT_SILU = 9 };
+       ACT_GELU_TANH = 8, ACT_SILU = 9, ACT_SOFTCAP = 10 };
 
 // A NaN input fails every comparison.  ReLU and LeakyReLU test what torch's backward kernels test (x <= 0 and x > 0), so the
 // factor passes unchanged through ReLU and with the negative slope through LeakyReLU, as in torch's autograd; every other
@@ -41,6 +41,7 @@ __device__ __forceinline__ float act_derivative(int kind, float x, float a) {
       return 0.5f * (1.f + t) + left * dtanh * du;
     }
     case ACT_SILU: { const float s = 1.f / (1.f + expf(-x)); return s * (1.f + x * (1.f - s)); }
+    case ACT_SOFTCAP: { const float t = tanhf(x / a); return 1.f - t * t; }   // f = a tanh(x / a), a > 0 the cap
     default: {  // SELU
       const float scale = 1.0507009873554804934193349852946f, alpha = 1.6732632423543772848170429916717f;
       return x > 0.f ? scale : scale * alpha * expf(x);
@@ -589,7 +590,8 @@ extern "C" {
 
 int vivit_act_jac_t_f32(const float *M, const float *x, float *out, int64_t Vd, int64_t per_v, int kind, float param,
                         void *stream) {
-  if (Vd < 0 || per_v < 0 || kind < 0 || kind > ACT_SILU) return VIVIT_E_BADARG;
+  if (Vd < 0 || per_v < 0 || kind < 0 || kind > ACT_SOFTCAP) return VIVIT_E_BADARG;
+  if (kind == ACT_SOFTCAP && !(param > 0.f && param <= 3.402823466e38f)) return VIVIT_E_BADARG;   // (a cap <= 0, NaN or inf)
   if (Vd == 0 || per_v == 0) return VIVIT_OK;
   if (!M || !x || !out) return VIVIT_E_BADARG;
   act_jac_t_kernel<<<grid_for(Vd * per_v), 256, 0, static_cast<hipStream_t>(stream)>>>(M, x, out, Vd * per_v, per_v, kind, param);

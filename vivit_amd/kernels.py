@@ -7,6 +7,7 @@ path and no backend switch (host-logic tests monkeypatch these functions from ``
 """
 import ctypes
 import functools
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -373,14 +374,17 @@ def conv2d_weight_mjp(M, x, kernel_size, stride, padding, dilation):
 
 
 ACTIVATION_KINDS = {"relu": 0, "sigmoid": 1, "tanh": 2, "leaky_relu": 3, "logsigmoid": 4, "elu": 5, "selu": 6, "gelu": 7,
-                    "gelu_tanh": 8, "silu": 9}
+                    "gelu_tanh": 8, "silu": 9, "softcap": 10}
 
 
 @_launcher
 def act_jac_t(M, x, kind: str, param: float = 0.0):
     """``out[v, n, ...] = M[v, n, ...] * f'(x[n, ...])`` for an elementwise activation ``f`` (``kind`` in
     :data:`ACTIVATION_KINDS`): the transposed input-Jacobian of SqrtGGN{ReLU,Sigmoid,Tanh,...} and of GELU (``"gelu"``: erf form,
-    ``"gelu_tanh"``: ``approximate='tanh'``) and SiLU."""
+    ``"gelu_tanh"``: ``approximate='tanh'``) and SiLU.  ``"softcap"``: ``f(x) = param * tanh(x / param)`` with the cap ``param``, a
+    finite float ``> 0`` (Gemma-2's final logits)."""
+    if kind == "softcap":
+        param = _softcap(param)
     _require_device(M, x)
     M, x = M.contiguous(), x.contiguous()
     if tuple(M.shape[1:]) != tuple(x.shape):
@@ -686,8 +690,16 @@ def rope_jac_t(M, cos, sin, num_heads: int, out=None, num_kv_heads: int = None):
     return G
 
 
+def _softcap(cap) -> float:
+    """A logit cap, checked: a finite float ``> 0``."""
+    if isinstance(cap, bool) or not isinstance(cap, (int, float)) or not (cap > 0) or math.isinf(cap):
+        raise ValueError(f"softcap must be a finite float > 0, got {cap!r}")
+    return float(cap)
+
+
 @_launcher
-def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None, window: int = None):
+def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None, window: int = None,
+                    softcap: float = None, bias=None):
     """Transposed input Jacobian of scaled dot-product self-attention (``vivit_attention_masked_jac_t_f32``, the one entry that
     launches): ``M [V, N, T, E]`` (the factor at the module output), ``qkv [N, T, 3 E]`` (the module input, q | k | v), ``out [N, T, E]``
     (the module output of the forward pass) -> ``[V, N, T, 3 E]``.  ``E = num_heads * d``; no ``T x T`` tensor is allocated.
@@ -701,8 +713,20 @@ def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num
     looked at on the host.  ``window`` (an integer ``>= 1``): query ``i`` sees the keys with ``|i - j| < window`` (with ``causal`` the
     ``window`` keys up to and including its own).  With both ``None`` (a null pointer and ``window = 0`` for the entry) the kernels
     walk every key block unmasked: what the entries without them, ``vivit_attention_jac_t_f32`` and
-    ``vivit_attention_gqa_jac_t_f32``, hand to the same entry."""
+    ``vivit_attention_gqa_jac_t_f32``, hand to the same entry.
+
+    ``softcap`` (a finite float ``c > 0``) and ``bias`` (a float32 tensor ``[num_heads, 2 T - 1]`` on ``M``'s device): the score
+    function ``s_ij = c tanh(scale q_i k_j / c) + bias[h, j - i + T - 1]`` (either part alone where only one is given), the cap before
+    the bias and both before the mask; the table is a constant, it gets no factor.  With either the call goes to
+    ``vivit_attention_scoremod_jac_t_f32``; with both ``None`` it is the call above, unchanged."""
+    if softcap is not None:
+        softcap = _softcap(softcap)
     _require_device(M, qkv, out)
+    if bias is not None:
+        _require_device(bias)
+        if bias.dtype != torch.float32 or bias.device != M.device:
+            raise ValueError(f"bias must be a float32 tensor on {M.device}, got {bias.dtype} on {bias.device}")
+        bias = bias.contiguous()
     if window is not None and (isinstance(window, bool) or int(window) != window or window < 1):
         raise ValueError(f"window must be an integer >= 1 (or None), got {window!r}")
     if lengths is not None:
@@ -727,8 +751,18 @@ def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num
     Vd = M.shape[0]
     if Vd == 0 or N == 0 or T == 0:
         raise ValueError(f"empty operands: M {tuple(M.shape)}")
+    if bias is not None and tuple(bias.shape) != (num_heads, 2 * T - 1):
+        raise ValueError(f"bias must be [H, 2 T - 1] = {(num_heads, 2 * T - 1)}, got {tuple(bias.shape)}")
     G = torch.empty((Vd, N, T, E3), dtype=torch.float32, device=M.device)
     lib = _lib.load()
+    if softcap is not None or bias is not None:
+        ws, ws_bytes = _workspace(lib.vivit_attention_scoremod_jac_t_f32_workspace_bytes(Vd, N, T, num_heads, Hkv, d), M)
+        st = lib.vivit_attention_scoremod_jac_t_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), G.data_ptr(), Vd, N, T, num_heads, Hkv, d,
+                                                    float(scale), int(bool(causal)), None if lengths is None else lengths.data_ptr(),
+                                                    0 if window is None else int(window), 0.0 if softcap is None else softcap,
+                                                    None if bias is None else bias.data_ptr(), ws, ws_bytes, _stream(M))
+        _lib.check(st, "vivit_attention_scoremod_jac_t_f32")
+        return G
     ws, ws_bytes = _workspace(lib.vivit_attention_masked_jac_t_f32_workspace_bytes(Vd, N, T, num_heads, Hkv, d), M)
     st = lib.vivit_attention_masked_jac_t_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), G.data_ptr(), Vd, N, T, num_heads, Hkv, d,
                                               float(scale), int(bool(causal)), None if lengths is None else lengths.data_ptr(),
