@@ -395,6 +395,36 @@ int vivit_attention_scoremod_jac_t_f32(const float *M, const float *qkv, const f
                                        int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths,
                                        int64_t window, float softcap, const float *bias, void *workspace, size_t workspace_bytes,
                                        void *stream);
+/* The factor of a LEARNED bias table (attention.hip; call site vivit_amd/kernels.py:attention_bias_factor, for
+ * vivit_amd.backend.ScaledDotProductAttention(bias=, learn_bias=True)): the transposed Jacobian of the function of the score-modifier
+ * entry point with respect to its table, applied to M.  Per factor row v, sample n and query head h,
+ *   Gb[v, n, h, b] = sum over the distances r = j - i with index[r + T - 1] == b of  sum_{(i, j) visible, j - i = r} dS[v, n, h, i, j],
+ * dS = P o (dP - D) of that entry point: the table is added behind the cap, so it is dS and not dZ that is summed.  bias [H, 2 T - 1]
+ * fp32 on the device is the EFFECTIVE table of the T positions (not NULL); index [2 T - 1] int32 on the device (not NULL) sends the
+ * distance r to column index[r + T - 1] of Gb [V, N, H, R] (fp32, dense, uninitialised memory: every element has exactly one writer).
+ * A plain table built for L >= T positions: index[k] = k + (L - T), R = 2 L - 1; a table indexed through buckets (T5): the middle
+ * slice of the bucket map, R the number of buckets.  The index is never read on the host and its values cannot be checked: a value
+ * outside [0, R) is SKIPPED by the fold (it equals no column), so that no value can carry a store out of bounds -- the distance then
+ * contributes to no column.  lengths, window, softcap, scale and causal are those of the score-modifier entry point.
+ * Launches: the row log-sum-exp and the row dots as that entry point has them, then the DIAGONAL OWNER -- one workgroup per block
+ * diagonal delta = jb - ib of one (n, h) and chunk of factor rows walks the query blocks ib in ascending order over exactly the tiles
+ * (ib, ib + delta) that the block ranges above call non-empty, recomputes dS per tile, and adds its 63 diagonals rho = -31 .. 31
+ * (i ascending inside a tile) into registers that live across the walk; it writes partial[v, n, h, delta, rho] -- and a fold: a
+ * distance r lies on the block diagonals floor(r / 32) (at rho = r mod 32) and, for rho >= 1, the next one (at rho - 32);
+ * Gb[v, n, h, b] is ONE chain of sums over r ascending, each r the sum of its two block diagonals (delta ascending).  No atomics; the bytes of Gb[v, n] depend
+ * on the shape parameters, the cap, the table, the index and the data of (v, n) only; a padded sample has the bytes of the sample
+ * cut to Tn and run alone with the index shifted by T - Tn; no operand row of a dead position is loaded; a column that no visible
+ * distance maps to, and every column of a dead sample, is written as +0.  No T x T data in memory.
+ * Workspace: that of the score-modifier entry point followed by the partial sums [V, N, H, 2 ceil(T / 32) - 1, 64] fp32, i.e.
+ * 4 * 64 * (2 ceil(T / 32) - 1) bytes more per (v, n, h); the query returns 0 for arguments the entry point refuses.
+ * VIVIT_E_BADARG: bias == NULL, index == NULL, R < 1, and what the score-modifier entry point refuses so; VIVIT_E_UNSUPPORTED: as
+ * there, and N H (2 ceil(T / 32) - 1) above 2^31 - 1 (the diagonal owner's grid); VIVIT_E_WORKSPACE: a missing or short workspace.
+ * Every refusal comes before any launch. */
+size_t vivit_attention_bias_factor_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d);
+int vivit_attention_bias_factor_f32(const float *M, const float *qkv, const float *out, float *Gb, int64_t V, int64_t N, int64_t T,
+                                    int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths,
+                                    int64_t window, float softcap, const float *bias, const int32_t *index, int64_t R,
+                                    void *workspace, size_t workspace_bytes, void *stream);
 /* Cross-attention: the same rule when the queries and the keys come from two sequences (attention.hip; call site
  * vivit_amd/kernels.py:cross_attention_jac_t, for vivit_amd.backend.ScaledDotProductCrossAttention).  All tensors dense:
  * q [N, Tq, H d], kv [N, Tk, 2 Hkv d] = k | v (Hkv key heads of d columns, then Hkv value heads: the packed layout above without

@@ -64,6 +64,9 @@ SIGNATURES = {
     "vivit_attention_masked_jac_t_f32": (_int, [_ptr, _ptr, _ptr, _ptr] + [_i64] * 6 + [_f32, _int, _ptr, _i64, _ptr, _sz, _ptr]),
     "vivit_attention_scoremod_jac_t_f32_workspace_bytes": (_sz, [_i64] * 6),
     "vivit_attention_scoremod_jac_t_f32": (_int, [_ptr, _ptr, _ptr, _ptr] + [_i64] * 6 + [_f32, _int, _ptr, _i64, _f32, _ptr, _ptr, _sz, _ptr]),
+    "vivit_attention_bias_factor_f32_workspace_bytes": (_sz, [_i64] * 6),
+    "vivit_attention_bias_factor_f32": (_int, [_ptr, _ptr, _ptr, _ptr] + [_i64] * 6 + [_f32, _int, _ptr, _i64, _f32, _ptr, _ptr, _i64, _ptr, _sz,
+                                               _ptr]),
     "vivit_attention_cross_jac_t_f32_workspace_bytes": (_sz, [_i64] * 7),
     "vivit_attention_cross_jac_t_f32": (_int, [_ptr] * 6 + [_i64] * 7 + [_f32, _ptr, _ptr, _ptr, _sz, _ptr]),
     "vivit_embedding_compact_f32":(_int, [_ptr] * 5 + [_i64] * 4 + [_ptr]),

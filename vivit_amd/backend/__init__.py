@@ -9,7 +9,7 @@ eval mode, element-wise activations, pooling, Flatten, Dropout in eval mode, and
 ``Parallel`` / ``SumModule`` / ``Pad`` / ``Slicing`` / ``ScaleModule`` of ``backpack.custom_module``, LayerNorm / GroupNorm,
 the self-attention modules ``ScaledDotProductAttention`` / ``MultiheadSelfAttention`` of ``custom_module`` (causal,
 grouped queries, sliding windows, right-padded batches through ``set_lengths``, logit soft-capping and relative-position
-bias tables such as ``alibi_bias``; ``SoftCap`` for capped final logits), the cross-attention modules
+bias tables, constant such as ``alibi_bias`` or learned, plain or indexed through ``relative_position_buckets``; ``SoftCap`` for capped final logits), the cross-attention modules
 ``ScaledDotProductCrossAttention`` / ``MultiheadCrossAttention`` (queries over a second sequence), ``nn.Embedding``,
 ``nn.RMSNorm`` and the modules ``ProductModule`` (gated MLPs) / ``RotaryEmbedding`` of ``custom_module``;
 CrossEntropyLoss / MSELoss with ``reduction='mean'`` or ``'sum'``, on outputs ``[N, C]`` and on outputs with positions
@@ -37,6 +37,7 @@ from vivit_amd.backend.custom_module import (
     SoftCap,
     SumModule,
     alibi_bias,
+    relative_position_buckets,
 )
 from vivit_amd.backend.engine import backpack, extend
 from vivit_amd.backend.extensions import (
@@ -47,4 +48,4 @@ from vivit_amd.backend.extensions import (
     ViViTGGNMC,
 )
 
-__all__ = ["ActiveIdentity", "MultiheadCrossAttention", "MultiheadSelfAttention", "Pad", "Parallel", "Permute", "ProductModule", "RotaryEmbedding", "ScaledDotProductAttention", "ScaledDotProductCrossAttention", "ScaleModule", "Slicing", "SoftCap", "SumModule", "alibi_bias", "backpack", "extend", "BatchGrad", "SqrtGGNExact", "SqrtGGNMC", "ViViTGGNExact", "ViViTGGNMC"]
+__all__ = ["ActiveIdentity", "MultiheadCrossAttention", "MultiheadSelfAttention", "Pad", "Parallel", "Permute", "ProductModule", "RotaryEmbedding", "ScaledDotProductAttention", "ScaledDotProductCrossAttention", "ScaleModule", "Slicing", "SoftCap", "SumModule", "alibi_bias", "relative_position_buckets", "backpack", "extend", "BatchGrad", "SqrtGGNExact", "SqrtGGNMC", "ViViTGGNExact", "ViViTGGNMC"]

@@ -206,6 +206,45 @@ class SoftCap(nn.Module):
         return f"cap={self.cap}"
 
 
+def _bias_index(index) -> Tensor:
+    """The ``bias_index`` argument of the attention modules, validated: an integer tensor ``[2 L - 1]`` of values ``>= 0``."""
+    if not isinstance(index, Tensor) or index.is_floating_point() or index.is_complex() or index.dtype == torch.bool:
+        raise ValueError(f"bias_index must be an integer tensor [2 L - 1], got "
+                         f"{index.dtype if isinstance(index, Tensor) else type(index).__name__}")
+    if index.dim() != 1 or index.shape[0] % 2 != 1:
+        raise ValueError(f"bias_index must be [2 L - 1] (an odd width), got {tuple(index.shape)}")
+    if int(index.min()) < 0:
+        raise ValueError(f"bias_index must lie in [0, R), got {int(index.min())}")
+    return index.detach().clone().to(torch.int64)
+
+
+def relative_position_buckets(max_len: int, num_buckets: int = 32, max_distance: int = 128, bidirectional: bool = True) -> Tensor:
+    """T5's bucket of every relative position (Raffel et al., 2020) for ``ScaledDotProductAttention(bias_index=...)``: int64
+    ``[2 max_len - 1]``, entry ``r + max_len - 1`` is the bucket of the distance ``r = j - i`` (key minus query).  Bidirectional:
+    half the buckets serve ``r > 0``, the other half ``r <= 0``; otherwise every ``r > 0`` shares bucket 0 with ``r = 0``.  Within a
+    half the first ``max_exact = half // 2`` distances have a bucket each, the rest share logarithmically spaced buckets up to
+    ``max_distance``, beyond which all fall into the last.  The logarithm is taken in float32, as T5's implementation does."""
+    if max_len < 1:
+        raise ValueError(f"max_len must be positive, got {max_len}")
+    if num_buckets < (4 if bidirectional else 2) or max_distance < 2:
+        raise ValueError(f"num_buckets ({num_buckets}) and max_distance ({max_distance}) are too small for a logarithmic range")
+    r = torch.arange(-(max_len - 1), max_len, dtype=torch.int64)
+    offset = torch.zeros_like(r)
+    if bidirectional:
+        num_buckets //= 2
+        offset = (r > 0).to(torch.int64) * num_buckets
+        r = r.abs()
+    else:
+        r = (-r).clamp(min=0)
+    max_exact = num_buckets // 2
+    if max_distance <= max_exact:
+        raise ValueError(f"max_distance ({max_distance}) must exceed the exact range ({max_exact})")
+    far = r.clamp(min=1).to(torch.float32)    # (the clamp only keeps log(0) out of the entries r < max_exact, which do not use it)
+    far = max_exact + (torch.log(far / max_exact) / math.log(max_distance / max_exact) * (num_buckets - max_exact)).to(torch.int64)
+    far = far.clamp(max=num_buckets - 1)
+    return offset + torch.where(r < max_exact, r, far)
+
+
 def alibi_slopes(num_heads: int) -> Tensor:
     """The head slopes ``m_h`` of ALiBi (Press et al., 2022) in float64: for ``H`` a power of two the geometric sequence
     ``2^(-8 (h + 1) / H)``; for another ``H`` the slopes of the next lower power of two ``P``, then every second slope of ``2 P``
@@ -230,7 +269,8 @@ def alibi_bias(num_heads: int, max_len: int) -> Tensor:
 
 
 class ScaledDotProductAttention(nn.Module):
-    """Multi-head scaled dot-product self-attention on a packed projection (no counterpart in BackPACK): a parameter-free leaf.
+    """Multi-head scaled dot-product self-attention on a packed projection (no counterpart in BackPACK): a leaf whose one possible parameter is a
+    learned bias table (``learn_bias``, below).
 
     Input ``qkv [N, T, 3 E]`` with ``q = qkv[..., :E]``, ``k = qkv[..., E:2 E]``, ``v = qkv[..., 2 E:]``; head ``h`` owns the columns
     ``h d .. (h + 1) d`` of each third (``d = E / num_heads``, the layout of ``nn.MultiheadAttention``'s packed projection).  Output
@@ -244,9 +284,14 @@ class ScaledDotProductAttention(nn.Module):
     finite float ``> 0``; ``None``: ``u = z``) is the logit cap of Gemma-2 and Grok-1.  ``bias`` (``None``: none) is a tensor
     ``[H, 2 L - 1]`` for a maximum length ``L``: one value per query head and distance ``j - i``, as ALiBi (:func:`alibi_bias`) and
     the relative-position tables of T5 and Swin have it.  A batch of ``T <= L`` positions uses the middle slice
-    ``bias[:, L - T : L + T - 1]``; ``T > L`` is a ``ValueError``.  The table is a buffer of the module (it moves with ``.to()``), its
-    entries must be finite, and it is a CONSTANT of the function: it receives no gradient and no factor, so a learned table is
-    treated as frozen.
+    ``bias[:, L - T : L + T - 1]``; ``T > L`` is a ``ValueError``.  The table is a buffer of the module (it moves with ``.to()``) and
+    a constant of the function, unless ``learn_bias=True``: the table is then an ``nn.Parameter`` of the same name (the
+    ``state_dict`` keys stay the same), autograd reaches it through the forward pass, and the extensions give it its own factor
+    ``[V, N, *bias.shape]`` (the diagonal sums of ``dS``: ``kernels.attention_bias_factor``).  Its entries must be finite; that is
+    checked at construction only, the forward pass never reads the table on the host.  ``bias_index`` (an integer tensor
+    ``[2 L - 1]`` with values in ``[0, R)``; a buffer) indexes the table through buckets, as T5 does: the table is then ``bias [H, R]``
+    and distance ``j - i`` reads ``bias[h, bias_index[j - i + L - 1]]`` -- many distances share one entry
+    (:func:`relative_position_buckets`).
 
     Padded batches: ``set_lengths(lengths)`` gives sample ``n`` the positions ``0 .. lengths[n] - 1`` (RIGHT padding only; a
     left-padded batch is not supported) for every forward pass until it is reset with ``set_lengths(None)``.  The positions beyond are
@@ -264,23 +309,36 @@ class ScaledDotProductAttention(nn.Module):
     attention."""
 
     def __init__(self, num_heads: int, causal: bool = False, scale: float = None, num_kv_heads: int = None, window: int = None,
-                 softcap: float = None, bias: Tensor = None):
+                 softcap: float = None, bias: Tensor = None, learn_bias: bool = False, bias_index: Tensor = None):
         super().__init__()
         if num_heads < 1:
             raise ValueError(f"num_heads must be positive, got {num_heads}")
+        if bias is None and learn_bias:
+            raise ValueError("learn_bias=True needs a bias table to learn")
+        if bias is None and bias_index is not None:
+            raise ValueError("bias_index indexes a bias table: give one")
+        if bias_index is not None:
+            bias_index = _bias_index(bias_index)
         self.num_heads, self.causal, self.scale = int(num_heads), bool(causal), scale
         self.num_kv_heads = _kv_heads(num_heads, num_kv_heads)
         self.window = _window(window)
         self.softcap = _softcap(softcap)
         if bias is not None:
             if not isinstance(bias, Tensor) or not bias.is_floating_point() or bias.dim() != 2 or bias.shape[0] != num_heads or \
-                    bias.shape[1] % 2 != 1:
-                raise ValueError(f"bias must be a floating-point tensor [H = {num_heads}, 2 L - 1], got "
+                    (bias_index is None and bias.shape[1] % 2 != 1) or bias.shape[1] < 1:
+                raise ValueError(f"bias must be a floating-point tensor [H = {num_heads}, {'2 L - 1' if bias_index is None else 'R'}], got "
                                  f"{tuple(bias.shape) if isinstance(bias, Tensor) else type(bias).__name__}")
+            if bias_index is not None and int(bias_index.max()) >= bias.shape[1]:
+                raise ValueError(f"bias_index reaches entry {int(bias_index.max())}, the bias table [H, R] has R = {bias.shape[1]}")
             if not bool(torch.isfinite(bias).all()):
                 raise ValueError("bias must be finite (masking is what causal, window and set_lengths are for)")
             bias = bias.detach().clone()
-        self.register_buffer("bias", bias)
+        self.learn_bias = bool(learn_bias)
+        if self.learn_bias:
+            self.bias = nn.Parameter(bias)
+        else:
+            self.register_buffer("bias", bias)
+        self.register_buffer("bias_index", bias_index)
         self._lengths = None          # what set_lengths() was given
         self.forward_lengths = None   # int32 [N] on the input's device: what the last forward() used (None: no lengths)
 
@@ -314,14 +372,30 @@ class ScaledDotProductAttention(nn.Module):
     def scale_for(self, d: int) -> float:
         return float(self.scale) if self.scale is not None else d ** -0.5
 
-    def bias_for(self, T: int):
-        """The table of a batch of ``T`` positions, ``[H, 2 T - 1]`` indexed by ``j - i + T - 1`` (a view: the middle slice of the
-        buffer); ``None`` without a table."""
-        if self.bias is None:
-            return None
-        L = (self.bias.shape[1] + 1) // 2
+    def bias_max_len(self) -> int:
+        """``L``: the most positions the table (through its index, where it has one) was built for."""
+        return ((self.bias.shape[1] if self.bias_index is None else self.bias_index.shape[0]) + 1) // 2
+
+    def bias_columns(self, T: int, device=None) -> Tensor:
+        """Where the distances of a batch of ``T`` positions sit in the table: integers ``[2 T - 1]``, entry ``j - i + T - 1`` is the
+        column of ``bias`` that distance reads -- the middle slice of ``bias_index``, or ``k + (L - T)`` for a plain table."""
+        L = self.bias_max_len()
         if T > L:
             raise ValueError(f"the batch has T = {T} positions, the bias table was built for at most {L}")
+        if self.bias_index is None:
+            return torch.arange(L - T, L + T - 1, device=self.bias.device if device is None else device)
+        return self.bias_index[L - T:L + T - 1]
+
+    def bias_for(self, T: int):
+        """The table of a batch of ``T`` positions, ``[H, 2 T - 1]`` indexed by ``j - i + T - 1`` (without an index a view: the middle
+        slice of the table; with one ``bias[:, bias_index]``'s middle slice); ``None`` without a table."""
+        if self.bias is None:
+            return None
+        L = self.bias_max_len()
+        if T > L:
+            raise ValueError(f"the batch has T = {T} positions, the bias table was built for at most {L}")
+        if self.bias_index is not None:
+            return self.bias[:, self.bias_index[L - T:L + T - 1]]
         return self.bias[:, L - T:L + T - 1]
 
     def modify(self, z: Tensor) -> Tensor:
@@ -426,10 +500,12 @@ class MultiheadSelfAttention(nn.Sequential):
     ``set_lengths`` are those of :class:`ScaledDotProductAttention` (sliding-window attention; right-padded batches), and so are
     ``softcap`` and ``attention_bias`` (its ``bias``: the table ``[H, 2 L - 1]``, e.g. :func:`alibi_bias`; the name ``bias`` is taken
     by the flag of the two projections, as in ``nn.MultiheadAttention`` -- a TENSOR given as ``bias`` is taken for the table and the
-    projections keep their bias vectors)."""
+    projections keep their bias vectors).  ``learn_attention_bias`` and ``attention_bias_index`` are the leaf's ``learn_bias`` and
+    ``bias_index``: a learned table, and a table indexed through buckets."""
 
     def __init__(self, embed_dim: int, num_heads: int, bias: Union[bool, Tensor] = True, causal: bool = False, num_kv_heads: int = None,
-                 window: int = None, softcap: float = None, attention_bias: Tensor = None):
+                 window: int = None, softcap: float = None, attention_bias: Tensor = None, learn_attention_bias: bool = False,
+                 attention_bias_index: Tensor = None):
         if embed_dim % num_heads != 0:
             raise ValueError(f"embed_dim ({embed_dim}) is not divisible by num_heads ({num_heads})")
         if isinstance(bias, Tensor):
@@ -437,7 +513,7 @@ class MultiheadSelfAttention(nn.Sequential):
                 raise ValueError("two bias tables: give the table as bias or as attention_bias, not both")
             bias, attention_bias = True, bias
         attention = ScaledDotProductAttention(num_heads, causal=causal, num_kv_heads=num_kv_heads, window=window, softcap=softcap,
-                                              bias=attention_bias)
+                                              bias=attention_bias, learn_bias=learn_attention_bias, bias_index=attention_bias_index)
         packed = (num_heads + 2 * attention.kv_heads) * (embed_dim // num_heads)
         super().__init__(nn.Linear(embed_dim, packed, bias=bias), attention, nn.Linear(embed_dim, embed_dim, bias=bias))
 

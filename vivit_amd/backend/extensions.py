@@ -269,8 +269,9 @@ def _rms_norm_jac_t_torch(module, M: Tensor, x: Tensor) -> Tensor:
     return rstd * (h - xhat * (h * xhat).mean(dims, keepdim=True))
 
 
-def _param_factor(module, name: str, M: Tensor, x: Tensor) -> Tensor:
-    """``param_mjp(..., sum_batch=False)``: ``M`` [V, N, *out] -> [V, N, *param.shape]."""
+def _param_factor(module, name: str, M: Tensor, x: Tensor, subsampling=None) -> Tensor:
+    """``param_mjp(..., sum_batch=False)``: ``M`` [V, N, *out] -> [V, N, *param.shape].  ``subsampling``: the indices ``x`` was
+    sub-sampled with (a rule that reads what the forward pass left on the module sub-samples it likewise)."""
     if isinstance(module, nn.Linear):
         if name == "bias":
             return M if M.dim() == 3 else M.flatten(2, -2).sum(2)
@@ -323,7 +324,17 @@ def _param_factor(module, name: str, M: Tensor, x: Tensor) -> Tensor:
     if isinstance(module, nn.Embedding):
         B, ids = _embedding_compact(module, M, x)
         return _embedding_factor(B, ids, module.num_embeddings)
+    if isinstance(module, ScaledDotProductAttention) and name == "bias":   # a learned relative-position table
+        return _attention_bias_factor(module, M, x, subsampling)
     raise NotImplementedError(f"no parameter rule for {type(module).__name__}")
+
+
+def _param_factor_of(module, name: str, M: Tensor, x: Tensor, subsampling) -> Tensor:
+    """:func:`_param_factor` as the extensions call it: the sub-sampling goes to the one rule that reads what the forward pass left on
+    the module (the attention leaf's table); every other rule is called with the four arguments it always had."""
+    if isinstance(module, ScaledDotProductAttention):
+        return _param_factor(module, name, M, x, subsampling=subsampling)
+    return _param_factor(module, name, M, x)
 
 
 def _linear_seq_weight_factor(M: Tensor, x: Tensor) -> Tensor:
@@ -622,13 +633,9 @@ def _attention_lengths(module, x: Tensor, subsampling) -> Optional[Tensor]:
     return lengths
 
 
-def _attention_jac_t_torch(module, M: Tensor, x: Tensor, out: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
-    """The rule of csrc/attention.hip in plain torch (non-HIP or non-fp32 tensors): ``M [V, N, T, H d]``, ``x [N, T, (H + 2 Hkv) d]``,
-    ``out [N, T, H d]`` -> ``[V, N, T, (H + 2 Hkv) d]``.  Query head ``h`` uses key / value head ``h // R``; dK and dV of a group are
-    the sums over its ``R = H / Hkv`` query heads (multi-head attention: ``R = 1``).  K and V are broadcast views over the group axis,
-    never expanded copies.  ``lengths`` (int32 ``[N]`` or ``None``) and ``module.window``: the mask of the forward pass; the rows of
-    the dead positions are exact zeros.  ``module.softcap`` and ``module.bias``: the score function of the forward pass
-    (``module.modify``), and ``dZ = dS (1 - t^2)`` in the place of ``dS`` under a cap.  No autograd."""
+def _attention_ds_torch(module, M: Tensor, x: Tensor, out: Tensor, lengths: Optional[Tensor]):
+    """What the input rule and the table's rule share, in plain torch: the sizes, the operands split into heads, the logits ``Z`` before
+    the score modifiers, ``P``, ``dO`` and ``dS = P (dP - D)`` ``[V, N, Hkv, R, T, T]``.  No autograd (the table is read detached)."""
     d, H, Hkv = module.head_dim(x), module.num_heads, module.kv_heads
     scale, R = module.scale_for(d), H // Hkv
     V, (N, T) = M.shape[0], x.shape[:2]
@@ -638,13 +645,59 @@ def _attention_jac_t_torch(module, M: Tensor, x: Tensor, out: Tensor, lengths: O
         M, x, out = M.masked_fill(dead, 0.0), x.masked_fill(dead, 0.0), out.masked_fill(dead, 0.0)
     q, k, v = _gqa_split(x, H, Hkv, d)                                             # q [N, Hkv, R, T, d]; k, v [N, Hkv, 1, T, d]
     Z = (q @ k.transpose(-1, -2)) * scale
-    S = module.modify(Z)
+    with torch.no_grad():
+        S = module.modify(Z)
     if hidden is not None:
         S = S.masked_fill(hidden, float("-inf"))
     P = S.softmax(-1)                                                             # [N, Hkv, R, T, T], shared by the V slices
     dO = M.reshape(V, N, T, Hkv, R, d).permute(0, 1, 3, 4, 2, 5)                  # [V, N, Hkv, R, T, d]
     D = (dO * out.view(N, T, Hkv, R, d).permute(0, 2, 3, 1, 4)).sum(-1, keepdim=True)
     dS = P * (dO @ v.transpose(-1, -2) - D)
+    return d, H, Hkv, scale, R, V, N, T, dead, q, k, Z, P, dO, dS
+
+
+def _attention_bias_factor_torch(module, M: Tensor, x: Tensor, out: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
+    """The factor of a learned bias table in plain torch (non-HIP or non-fp32 tensors, head dimensions above 128): ``M [V, N, T, H d]``
+    -> ``[V, N, *module.bias.shape]``, column ``b`` the sum of ``dS`` over the visible pairs whose distance reads column ``b`` of the
+    table (``module.bias_columns``).  The table sits behind the cap: it is ``dS`` that is summed, not ``dZ``.  The sums over the
+    diagonals are one reduction of a skewed view, the distances go to their columns through a product with a one-hot matrix: no
+    scatter with atomics, the bytes are a function of the operands.  No autograd."""
+    _, H, _, _, _, V, N, T, _, _, _, _, _, _, dS = _attention_ds_torch(module, M, x, out, lengths)
+    # row i' = T - 1 - i of the flipped tile, padded to 2 T columns and re-read with 2 T - 1 columns, has entry (i, j) in column
+    # i' + j = j - i + T - 1
+    skew = F.pad(dS.reshape(V, N, H, T, T).flip(-2), (0, T)).flatten(-2)[..., :T * (2 * T - 1)].view(V, N, H, T, 2 * T - 1)
+    diag = skew.sum(-2)                                                            # [V, N, H, 2 T - 1], by distance
+    onehot = F.one_hot(module.bias_columns(T, x.device).long(), module.bias.shape[1]).to(diag.dtype)   # [2 T - 1, width]
+    return diag @ onehot
+
+
+def _attention_bias_factor(module, M: Tensor, x: Tensor, subsampling) -> Tensor:
+    """The factor ``[V, N, *bias.shape]`` of the learned table of a :class:`ScaledDotProductAttention`: the kernel for HIP fp32 tensors
+    with ``d <= 128`` (sizes beyond its index arithmetic come back as VIVIT_E_UNSUPPORTED), the same formula in torch otherwise.  The
+    forward output and the lengths are those of the forward pass, sub-sampled as ``x`` was."""
+    d, T = module.head_dim(x), x.shape[1]
+    lengths, out = _attention_lengths(module, x, subsampling), _attention_out(module, x, subsampling)
+    if M.is_cuda and M.dtype == torch.float32 and x.dtype == torch.float32 and d <= 128:
+        try:
+            return kernels.attention_bias_factor(M.reshape(M.shape[0], *x.shape[:2], -1), x, out, module.num_heads, module.scale_for(d),
+                                                 module.causal, module.bias_for(T).detach().to(torch.float32).contiguous(),
+                                                 index=module.bias_columns(T, x.device), width=module.bias.shape[1],
+                                                 num_kv_heads=module.kv_heads, lengths=lengths, window=module.window,
+                                                 softcap=module.softcap)
+        except _lib.VivitHipError as exc:   # a shape beyond the kernel's launch limits: the formula below
+            if exc.status != _lib.VIVIT_E_UNSUPPORTED:
+                raise
+    return _attention_bias_factor_torch(module, M, x, out, lengths)
+
+
+def _attention_jac_t_torch(module, M: Tensor, x: Tensor, out: Tensor, lengths: Optional[Tensor] = None) -> Tensor:
+    """The rule of csrc/attention.hip in plain torch (non-HIP or non-fp32 tensors): ``M [V, N, T, H d]``, ``x [N, T, (H + 2 Hkv) d]``,
+    ``out [N, T, H d]`` -> ``[V, N, T, (H + 2 Hkv) d]``.  Query head ``h`` uses key / value head ``h // R``; dK and dV of a group are
+    the sums over its ``R = H / Hkv`` query heads (multi-head attention: ``R = 1``).  K and V are broadcast views over the group axis,
+    never expanded copies.  ``lengths`` (int32 ``[N]`` or ``None``) and ``module.window``: the mask of the forward pass; the rows of
+    the dead positions are exact zeros.  ``module.softcap`` and ``module.bias``: the score function of the forward pass
+    (``module.modify``), and ``dZ = dS (1 - t^2)`` in the place of ``dS`` under a cap.  No autograd."""
+    d, H, Hkv, scale, R, V, N, T, dead, q, k, Z, P, dO, dS = _attention_ds_torch(module, M, x, out, lengths)
     if module.softcap is not None:   # dZ: the cap's derivative 1 - t^2, t = tanh(z / c)
         dS = dS * (1.0 - torch.tanh(Z / module.softcap) ** 2)
     dQ = (dS @ k) * scale                                                         # [V, N, Hkv, R, T, d]
@@ -867,7 +920,7 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
         return kernels.attention_jac_t(M.reshape(M.shape[0], *x.shape[:2], -1), x, _attention_out(module, x, subsampling), module.num_heads,
                                        module.scale_for(d), module.causal, num_kv_heads=module.kv_heads, lengths=lengths,
                                        window=module.window, softcap=module.softcap,
-                                       bias=None if table is None else table.to(torch.float32).contiguous())
+                                       bias=None if table is None else table.detach().to(torch.float32).contiguous())
     if isinstance(module, _BATCHNORM) and x.dim() >= 2:
         if _own_params(module):   # the parameter rules want the two row sums of the same pass
             return _bn_eval_rules(module, M, x)[0]
@@ -985,7 +1038,7 @@ class BatchGrad(_Extension):
             if self._factorised and isinstance(module, nn.Linear) and name == "weight" and g.dim() == 3:
                 setattr(p, self.savefield, LinearFactor(g[0], x))
             else:
-                setattr(p, self.savefield, _param_factor(module, name, g, x)[0])
+                setattr(p, self.savefield, _param_factor_of(module, name, g, x, sub)[0])
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1185,11 +1238,11 @@ class _SqrtGGN(_Extension):
     def get_num_mc_samples(self) -> int:
         return self._mc_samples
 
-    def _store(self, module, name, param, M, x):
+    def _store(self, module, name, param, M, x, subsampling=None):
         if self._factorised and isinstance(module, nn.Linear) and name == "weight" and M.dim() == 3:
             setattr(param, self.savefield, LinearFactor(M, x))
         else:
-            setattr(param, self.savefield, _param_factor(module, name, M, x))
+            setattr(param, self.savefield, _param_factor_of(module, name, M, x, subsampling))
 
     def apply(self, ctx, module, g_out):
         sub = self.get_subsampling()
@@ -1226,7 +1279,7 @@ class _SqrtGGN(_Extension):
             return
         x = subsample(module.input0.detach(), 0, sub)
         for name, p in _own_params(module):
-            self._store(module, name, p, M, x)
+            self._store(module, name, p, M, x, subsampling=sub)
         if module.input0.requires_grad:
             ctx.put(self, module.input0, _jac_t_mat_prod(module, M, x, sub))
 
@@ -1518,7 +1571,7 @@ class _ViViTGGN(_SqrtGGN):
     """Functional access to ``V``, ``V^T`` and the Gram matrix
     (vivit/extensions/secondorder/vivit/__init__.py:63-133)."""
 
-    def _store(self, module, name, param, M, x):
+    def _store(self, module, name, param, M, x, subsampling=None):
         if isinstance(module, nn.Linear) and name == "weight" and M.dim() == 3:
             closures = _linear_weight_closures(M, x)
         elif (isinstance(module, nn.Linear) and name == "weight" and M.dim() > 3 and M.is_cuda and M.dtype == torch.float32
@@ -1527,7 +1580,7 @@ class _ViViTGGN(_SqrtGGN):
         elif isinstance(module, nn.Embedding):
             closures = _embedding_closures(M, x, module)
         else:
-            closures = _materialised_closures(_param_factor(module, name, M, x))
+            closures = _materialised_closures(_param_factor_of(module, name, M, x, subsampling))
         setattr(param, self.savefield, closures)
 
 

@@ -59,7 +59,7 @@
 // per head and distance.  With z_ij = scale q_i k_j,
 //   u = c tanh(z / c)  (no cap: u = z),   s_ij = u + B[h, j - i + T - 1]  (no table: s = u),   then the mask,  P = softmax_rows(s),
 //   dS = P o (dP - D),   dZ = dS o (1 - t^2) with t = u / c  (no cap: dZ = dS),   dQ_h = scale dZ K_g,   dK_g = scale sum_h dZ_h^T Q_h,
-// and dV as it was; the table is a constant and gets no factor.  The variant is COMPILE TIME again: the kernels' second template
+// and dV as it was; the table is a constant for the input rule; its own factor: the diagonal owner (below).  The variant is COMPILE TIME again: the kernels' second template
 // parameter Mod is AttPlain (the expressions that were there; every instance above) or AttScoreMod, whose instances exist for
 // AttGeom alone.  att_logit forms s_ij from the product q_i k_j for lse and for both owners, the same operations in the same order and
 // none of them contracted with a neighbour, so exp(s - lse) sees the very s that lse summed.  Neither owner keeps a second tile: the
@@ -67,6 +67,28 @@
 // (the query owner, which never uses P alone).  A table entry is read through the caches, for visible pairs only: both positions
 // are then < Tn <= T, so j - i + T - 1 stays in [0, 2 T - 2].  Summation order, block ranges, dead positions and +0 rows are those
 // above; the bytes of G[v, n] depend on the cap and the table besides.
+//
+// THE TABLE'S OWN FACTOR (vivit_attention_bias_factor_f32): a learned table is a parameter, and its per-sample factor is
+//   Gb[v, n, h, r] = sum_{(i, j) visible, j - i = r} dS[v, n, h, i, j],   dS = P o (dP - D)
+// -- the bias is added BEHIND the cap, so it is dS and not dZ that is summed: the diagonal sums of the dS tiles the two owners
+// recompute and throw away.  Neither owner's instance is touched (the key owner's scalar file is full); a third owner is launched
+// behind the same lse and row-dot launches:
+//   attn_dbias_kernel       the DIAGONAL owner of one (n, h): block diagonal delta = jb - ib, -(KB - 1) .. KB - 1; it walks the query
+//                           blocks ib in ascending order with jb = ib + delta over exactly the tiles the block ranges above call
+//                           non-empty (both blocks < KBn, delta <= 0 when causal, |delta| <= WB), reloads Q, K, V, lse, dO and D per
+//                           tile, forms s with att_logit and the mask with att_valid as attn_lse_kernel does, then dS for its VC factor
+//                           rows, and adds the 63 diagonals rho = -31 .. 31 of each tile into one register per (vc, rho), i ascending;
+//                           at the end partial[v, n, h, delta, rho] (pitch 64), zeros for a diagonal with no tile
+//   attn_dbias_fold_kernel  distance r lies on the block diagonals floor(r / 32) at rho = r mod 32 and, for rho >= 1, the next one at
+//                           rho - 32; column b of Gb[v, n, h] is ONE chain over the distances with index[r + T - 1] == b, r ascending,
+//                           each distance the sum of its two block diagonals, delta ascending.  The index sends distances to columns (a table of maximum length L >= T:
+//                           r + L - 1; T5's buckets: many distances to one column); a value outside [0, R) equals no column and is
+//                           skipped.
+// SUMMATION ORDER: blocks ascending, i ascending inside a block, then the fold's order; no atomics.  The bytes of Gb[v, n] depend on
+// the shape parameters, the cap, the table, the index and the data of (v, n) only; a padded sample has the bytes of the sample cut
+// to Tn and run alone with the index shifted by T - Tn (masked pairs and diagonals without a tile add zeros, which change no sum
+// that starts at +0); dead positions are never loaded; columns no visible distance maps to are +0.  Workspace: 64 floats per
+// (v, n, h, block diagonal) behind that of the input rule, O(T) per (v, n, h).
 #include <math.h>
 
 #include "common.h"
@@ -564,6 +586,117 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const float *__restrict__ 
   }
 }
 
+// ---- diagonal owner: the factor of the bias table (THE TABLE'S OWN FACTOR at the head of the file) ---------------------------------
+// One workgroup owns the block diagonal delta = jb - ib of one (n, h) for VC factor rows: it walks the query blocks ib in ascending
+// order with jb = ib + delta and, per tile, recomputes dS = P o (dP - D) of its VC rows as the query owner does (without the cap's
+// derivative: the table is added behind the cap).  Thread (vc, rho), rho = -31 .. 31, then adds the diagonal j - i = rho of tile vc,
+// i ascending, to ONE register that lives across the walk.  LDS banks of that read (ds_read_b32: bank = word mod 32 within a half
+// wave): at step i the thread reads word vc TILE + 36 i + c of row i, c = i + rho its column (clamped to the row where the diagonal
+// does not cross it) -- a diagonal steps by 37 words, but that is a stride in time, not across lanes: at one step the lanes of a
+// half wave read ONE row each of at most two tiles, lanes with the same column read the same word (a broadcast), and where a half
+// straddles two factor rows (63 threads each) the columns of the first tile's lanes all lie above those of the second's, so with
+// TILE = 1152 = 0 mod 32 different words never share a bank: no conflict.
+template <int NT, class Geo, class Mod>
+__global__ __launch_bounds__(256) void attn_dbias_kernel(const float *__restrict__ M, const float *__restrict__ qkv,
+                                                         const float *__restrict__ lse, const float *__restrict__ Dws,
+                                                         float *__restrict__ partial, int64_t V, Geo g, Mod mod) {
+  extern __shared__ __attribute__((aligned(16))) float att_smem[];
+  using C = AttCfg<NT>;
+  float *sK = att_smem, *sV = sK + C::BLK, *sQ = sV + C::BLK, *sdO = sQ + C::BLK;
+  float *sdS = sdO + C::VC * C::BLK + C::TILE, *sL = sdS + C::VC * C::TILE, *sD = sL + ATT_B;   // (the P tile's room is unused here)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ND = 2 * g.KB - 1;   // block diagonals -(KB - 1) .. KB - 1
+  const int64_t nh = blockIdx.x / ND;
+  const int delta = (int)(blockIdx.x - nh * ND) - (g.KB - 1);
+  const int64_t n = nh / g.H;
+  const int h = (int)(nh - n * g.H), dk = (g.d + 3) & ~3;
+  const int64_t v0 = (int64_t)blockIdx.y * C::VC;
+  const int nv = V - v0 < C::VC ? (int)(V - v0) : C::VC;
+  const float *base = att_q_rows(g, qkv, n), *kbase = att_k_rows(g, base, n) + (int64_t)(h / g.R) * g.d;
+  const AttLive L = att_live(g, n);
+  // the tiles of this diagonal that the owners' block ranges call non-empty (the head of the file): both blocks live, delta <= 0
+  // when causal, |delta| within the window's reach; a diagonal with none loads nothing and stores its zeros
+  const int KBn = (L.q + ATT_B - 1) / ATT_B, wb = att_reach(g, KBn);
+  const bool reached = delta >= -wb && delta <= (att_causal(g) ? 0 : wb);
+  const int ib_lo = max(-delta, 0), ib_hi = reached ? KBn - 1 - max(delta, 0) : -1;
+  const int ri = wave >> 1, cj = wave & 1, j = lane & 15, kq = lane >> 4;
+  const float *brow = att_bias_row(mod, att_Tq(g), h);
+  const int vc = tid / 63, rho = tid - 63 * vc - 31;   // the thread's diagonal (vc < nv: it has one)
+  float acc = 0.f;
+  for (int ib = ib_lo; ib <= ib_hi; ++ib) {
+    const int i0 = ib * ATT_B, j0 = (ib + delta) * ATT_B;
+    __syncthreads();   // the previous tile's dS and operands have been read
+    att_load_block<NT>(sQ, base + (int64_t)h * g.d, att_qpitch(g), i0, L.q, g.d, g.vec);
+    if (tid < ATT_B) sL[tid] = i0 + tid < L.q ? lse[nh * att_Tq(g) + i0 + tid] : 0.f;
+    att_load_factor<NT>(sdO, sD, M, Dws, g, L.q, v0, nv, n, h, i0);
+    att_load_block<NT>(sK, kbase, att_kpitch(g), j0, L.k, g.d, g.vec);
+    att_load_block<NT>(sV, kbase + att_k_to_v(g), att_kpitch(g), j0, L.k, g.d, g.vec);
+    __syncthreads();
+    att_f32x4 w;   // (the weight with the cap's derivative is not used here)
+    const att_f32x4 p = att_p_tile<NT>(sQ, sK, sL, g.scale, dk, lane, ri, cj, mod, brow, j0 - i0, w,
+                                       [&](int r, int c) { return att_valid(g, L, i0 + r, j0 + c); });
+#pragma unroll
+    for (int vi = 0; vi < C::VC; ++vi)
+      if (vi < nv) {
+        const att_f32x4 dp = att_tile_nt<NT>(sdO + vi * C::BLK + 16 * ri * C::LD, sV + 16 * cj * C::LD, dk, lane);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int r = 16 * ri + 4 * kq + e;
+          sdS[vi * C::TILE + r * ATT_LDP + 16 * cj + j] = p[e] * (dp[e] - sD[vi * ATT_B + r]);
+        }
+      }
+    __syncthreads();
+    if (vc < nv) {
+      // (all 32 reads are issued before the chain of additions; a row the diagonal does not cross reads a clamped column and
+      // adds +0, which changes no sum that started at +0)
+      const float *t = sdS + vc * C::TILE;
+      float x[ATT_B];
+#pragma unroll
+      for (int i = 0; i < ATT_B; ++i) x[i] = t[i * ATT_LDP + min(max(i + rho, 0), ATT_B - 1)];
+#pragma unroll
+      for (int i = 0; i < ATT_B; ++i) acc += (unsigned)(i + rho) < (unsigned)ATT_B ? x[i] : 0.f;
+    }
+  }
+  if (vc < nv) partial[((((v0 + vc) * g.N + n) * g.H + h) * ND + (delta + g.KB - 1)) * 64 + rho + 31] = acc;
+}
+
+// the fold: Gb[vnh, b] = the sum over the distances r = -(T - 1) .. T - 1 with index[r + T - 1] == b, r ascending, of the (at most)
+// two block diagonals that hold r -- delta = floor(r / 32) at rho = r - 32 delta plus delta + 1 at rho - 32, added to each other
+// first -- one chain per element (a term meets at most T - 1 additions on its diagonal, one here and one per distance of the column).  A workgroup owns 256 columns b of one (v, n, h) and passes over the index in pieces of 256 that it keeps in
+// LDS with the piece's partial sums (a diagonal that does not exist: +0, which changes no sum).  An index value outside [0, R) is
+// equal to no column and is skipped, so no value can carry a store out of bounds; a column nothing maps to is written as +0.
+__global__ __launch_bounds__(256) void attn_dbias_fold_kernel(const float *__restrict__ partial, const int32_t *__restrict__ index,
+                                                              float *__restrict__ Gb, int64_t VNH, int T, int KB, int64_t R) {
+  __shared__ int32_t sI[256];
+  __shared__ float sA[256], sB[256];
+  const int tid = threadIdx.x, ND = 2 * KB - 1;
+  const int64_t RB = (R + 255) / 256, total = VNH * RB, width = 2 * (int64_t)T - 1;
+  for (int64_t item = blockIdx.x; item < total; item += gridDim.x) {
+    const int64_t vnh = item / RB, b = (item - vnh * RB) * 256 + tid;
+    const float *p = partial + vnh * ND * 64;
+    float acc = 0.f;
+    for (int64_t k0 = 0; k0 < width; k0 += 256) {
+      __syncthreads();   // the previous piece has been read
+      const int64_t k = k0 + tid;
+      int32_t col = -1;
+      float a0 = 0.f, a1 = 0.f;
+      if (k < width) {
+        const int r = (int)(k - (T - 1)), delta = r >> 5, rho = r & 31;   // (floor and remainder, r < 0 included)
+        col = index[k];
+        if (delta >= -(KB - 1)) a0 = p[(int64_t)(delta + KB - 1) * 64 + rho + 31];
+        if (rho >= 1 && delta + 1 <= KB - 1) a1 = p[(int64_t)(delta + KB) * 64 + rho - 1];
+      }
+      sI[tid] = col, sA[tid] = a0, sB[tid] = a1;
+      __syncthreads();
+      const int cnt = (int)min((int64_t)256, width - k0);
+      if (b < R)
+        for (int u = 0; u < cnt; ++u)
+          if ((int64_t)sI[u] == b) acc += sA[u] + sB[u];
+    }
+    if (b < R) Gb[vnh * R + b] = acc;
+  }
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 struct AttPlan {
   int status;            // VIVIT_OK, or why nothing is launched
@@ -642,6 +775,21 @@ static int attention_launch_d(const float *M, const float *qkv, const float *out
 
 static inline bool att_aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// the geometry of a self-attention call that the plan has accepted
+static AttGeom attention_self_geom(const float *M, const float *qkv, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d, int64_t KB,
+                                   float scale, int causal, const int32_t *lengths, int64_t window) {
+  AttGeom g;
+  g.N = (int)N, g.T = (int)T, g.H = (int)H, g.d = (int)d, g.KB = (int)KB;
+  g.Hkv = (int)Hkv, g.R = (int)(H / Hkv);
+  g.pitch = (int)((H + 2 * Hkv) * d), g.koff = (int)(H * d), g.voff = (int)((H + Hkv) * d);
+  g.causal = causal != 0;
+  g.vec = (d & 3) == 0 && att_aligned16(M) && att_aligned16(qkv);
+  g.scale = scale;
+  g.lengths = lengths;
+  g.window = window >= T ? 0 : (int)window;   // (a window of T or more cuts nothing; this also covers every value beyond an int)
+  return g;
+}
+
 // the self-attention entries: every refusal, then the four launches with the score function `mod`
 template <class Mod>
 static int attention_self(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T, int64_t H,
@@ -651,19 +799,47 @@ static int attention_self(const float *M, const float *qkv, const float *out, fl
   const AttPlan p = attention_plan(V, N, T, H, Hkv, d);
   if (p.status != VIVIT_OK) return p.status;
   if (!workspace || workspace_bytes < p.bytes) return VIVIT_E_WORKSPACE;
-  AttGeom g;
-  g.N = (int)N, g.T = (int)T, g.H = (int)H, g.d = (int)d, g.KB = (int)p.KB;
-  g.Hkv = (int)Hkv, g.R = (int)(H / Hkv);
-  g.pitch = (int)((H + 2 * Hkv) * d), g.koff = (int)(H * d), g.voff = (int)((H + Hkv) * d);
-  g.causal = causal != 0;
-  g.vec = (d & 3) == 0 && att_aligned16(M) && att_aligned16(qkv);
-  g.scale = scale;
-  g.lengths = lengths;
-  g.window = window >= T ? 0 : (int)window;   // (a window of T or more cuts nothing; this also covers every value beyond an int)
+  const AttGeom g = attention_self_geom(M, qkv, N, T, H, Hkv, d, p.KB, scale, causal, lengths, window);
   float *lse = static_cast<float *>(workspace);
   float *Dws = reinterpret_cast<float *>(static_cast<char *>(workspace) + p.lse_bytes);
   hipStream_t s = static_cast<hipStream_t>(stream);
   return attention_launch_d(M, qkv, out, G, G, lse, Dws, V, g, mod, g.T, g.KB, g.KB, s);
+}
+
+// ---- the table's own factor ---------------------------------------------------------------------------------------------------------
+// the plan of the scoremod entry and, behind its workspace, the partial sums [V, N, H, 2 KB - 1, 64] of the diagonal owner
+static AttPlan attention_bias_plan(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d, size_t &partial_off) {
+  AttPlan p = attention_plan(V, N, T, H, Hkv, d);
+  if (p.status != VIVIT_OK) return p;
+  // 32-bit: the diagonal owner's block index N H (2 KB - 1) (N H KB is the plan's); 64-bit: every element offset (V <= 4 * 65535 by
+  // the plan's chunk limit, so V N H (2 KB - 1) 256 < 2^58)
+  if (N * H > 0x7fffffffLL / (2 * p.KB - 1)) return p.status = VIVIT_E_UNSUPPORTED, p;
+  partial_off = p.bytes;
+  p.bytes += (size_t)(V * N * H) * (size_t)(2 * p.KB - 1) * 64 * 4;
+  return p;
+}
+
+template <int NT>
+static int attention_bias_launch(const float *M, const float *qkv, const float *out, float *Gb, float *lse, float *Dws, float *partial,
+                                 int64_t V, const AttGeom &g, const AttScoreMod &mod, const int32_t *index, int64_t R, hipStream_t s) {
+  using C = AttCfg<NT>;
+  static unsigned long long attr_done = 0;
+  constexpr int lse_lds = C::LSE_FLOATS * 4, own_lds = C::OWN_FLOATS * 4;
+  if (own_lds > 64 * 1024) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return VIVIT_E_LAUNCH;
+    if (!ensure_dynamic_lds(reinterpret_cast<const void *>(attn_dbias_kernel<NT, AttGeom, AttScoreMod>), own_lds, attr_done))
+      return VIVIT_E_LAUNCH;
+    attr_done |= 1ull << (dev & 63);
+  }
+  const int64_t NH = (int64_t)g.N * g.H, total = V * NH * g.T, ND = 2 * (int64_t)g.KB - 1;
+  attn_lse_kernel<NT, AttGeom, AttScoreMod><<<(unsigned)(NH * g.KB), 256, lse_lds, s>>>(qkv, lse, g, mod);
+  attn_rowdot_kernel<AttGeom><<<(unsigned)cdiv(total, 256), 256, 0, s>>>(M, out, Dws, total, g);
+  attn_dbias_kernel<NT, AttGeom, AttScoreMod><<<dim3((unsigned)(NH * ND), (unsigned)cdiv(V, C::VC)), 256, own_lds, s>>>(M, qkv, lse, Dws, partial,
+                                                                                                                    V, g, mod);
+  const int64_t items = V * NH * cdiv(R, 256);
+  attn_dbias_fold_kernel<<<(unsigned)(items < 0x7fffffffLL ? items : 0x7fffffffLL), 256, 0, s>>>(partial, index, Gb, V * NH, g.T, g.KB, R);
+  return launch_status();
 }
 
 } // namespace vivit
@@ -700,6 +876,34 @@ int vivit_attention_scoremod_jac_t_f32(const float *M, const float *qkv, const f
                                             stream);
   return attention_self(M, qkv, out, G, V, N, T, H, Hkv, d, scale, causal, lengths, window, AttScoreMod{softcap, bias}, workspace,
                         workspace_bytes, stream);
+}
+
+// the factor of the bias table (the head of the file): bias [H, 2 T - 1] and index [2 T - 1] on the device, neither null; Gb [V, N, H, R]
+size_t vivit_attention_bias_factor_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d) {
+  size_t off = 0;
+  const AttPlan p = attention_bias_plan(V, N, T, H, Hkv, d, off);
+  return p.status == VIVIT_OK ? p.bytes : 0;
+}
+
+int vivit_attention_bias_factor_f32(const float *M, const float *qkv, const float *out, float *Gb, int64_t V, int64_t N, int64_t T,
+                                    int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths, int64_t window,
+                                    float softcap, const float *bias, const int32_t *index, int64_t R, void *workspace,
+                                    size_t workspace_bytes, void *stream) {
+  if (!(softcap >= 0.f) || isinf(softcap)) return VIVIT_E_BADARG;   // (negative, NaN, inf)
+  if (!M || !qkv || !out || !Gb || !bias || !index || R < 1 || window < 0) return VIVIT_E_BADARG;
+  size_t off = 0;
+  const AttPlan p = attention_bias_plan(V, N, T, H, Hkv, d, off);
+  if (p.status != VIVIT_OK) return p.status;
+  if (!workspace || workspace_bytes < p.bytes) return VIVIT_E_WORKSPACE;
+  const AttGeom g = attention_self_geom(M, qkv, N, T, H, Hkv, d, p.KB, scale, causal, lengths, window);
+  const AttScoreMod mod{softcap, bias};
+  char *ws = static_cast<char *>(workspace);
+  float *lse = reinterpret_cast<float *>(ws), *Dws = reinterpret_cast<float *>(ws + p.lse_bytes), *partial = reinterpret_cast<float *>(ws + off);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (d <= 16) return attention_bias_launch<1>(M, qkv, out, Gb, lse, Dws, partial, V, g, mod, index, R, s);
+  if (d <= 32) return attention_bias_launch<2>(M, qkv, out, Gb, lse, Dws, partial, V, g, mod, index, R, s);
+  if (d <= 64) return attention_bias_launch<4>(M, qkv, out, Gb, lse, Dws, partial, V, g, mod, index, R, s);
+  return attention_bias_launch<8>(M, qkv, out, Gb, lse, Dws, partial, V, g, mod, index, R, s);
 }
 
 // cross-attention (the head of the file): q_lengths, k_lengths [N] int32 on the device or null; Gq or Gkv may be null, not both

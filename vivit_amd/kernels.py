@@ -717,7 +717,8 @@ def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num
 
     ``softcap`` (a finite float ``c > 0``) and ``bias`` (a float32 tensor ``[num_heads, 2 T - 1]`` on ``M``'s device): the score
     function ``s_ij = c tanh(scale q_i k_j / c) + bias[h, j - i + T - 1]`` (either part alone where only one is given), the cap before
-    the bias and both before the mask; the table is a constant, it gets no factor.  With either the call goes to
+    the bias and both before the mask; the table is a constant of this rule (a learned table's own factor:
+    :func:`attention_bias_factor`).  With either the call goes to
     ``vivit_attention_scoremod_jac_t_f32``; with both ``None`` it is the call above, unchanged."""
     if softcap is not None:
         softcap = _softcap(softcap)
@@ -769,6 +770,69 @@ def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num
                                               0 if window is None else int(window), ws, ws_bytes, _stream(M))
     _lib.check(st, "vivit_attention_masked_jac_t_f32")
     return G
+
+
+@_launcher
+def attention_bias_factor(M, qkv, out, num_heads: int, scale: float, causal: bool, bias, index=None, width: int = None,
+                          num_kv_heads: int = None, lengths=None, window: int = None, softcap: float = None):
+    """The factor of a learned relative-position table of scaled dot-product self-attention (``vivit_attention_bias_factor_f32``):
+    ``M [V, N, T, E]``, ``qkv``, ``out``, ``num_kv_heads``, ``lengths``, ``window`` and ``softcap`` as :func:`attention_jac_t` has
+    them, ``bias`` the EFFECTIVE table ``[num_heads, 2 T - 1]`` of the ``T`` positions (float32 on ``M``'s device) ->
+    ``[V, N, num_heads, width]``: column ``b`` is the sum of ``dS[v, n, h, i, j]`` over the visible pairs whose distance ``r = j - i``
+    has ``index[r + T - 1] == b``.  ``index`` (``2 T - 1`` integers, anything ``torch.as_tensor`` takes; it goes to ``M``'s device as
+    int32 and is not looked at on the host) sends distances to columns, ``width`` is the number of columns: a table built for
+    ``L >= T`` positions passes ``index[k] = k + (L - T)`` and ``width = 2 L - 1``, a table indexed through buckets the middle slice
+    of its bucket map and the number of buckets.  A value outside ``[0, width)`` is skipped by the kernel.  ``index=None`` is the
+    identity map of a ``[H, 2 T - 1]`` table (``width`` must then be ``None`` or ``2 T - 1``).  No ``T x T`` tensor is allocated, no
+    atomics: the bytes of the result are a function of the operands."""
+    if softcap is not None:
+        softcap = _softcap(softcap)
+    _require_device(M, qkv, out, bias)
+    if bias.dtype != torch.float32 or bias.device != M.device:
+        raise ValueError(f"bias must be a float32 tensor on {M.device}, got {bias.dtype} on {bias.device}")
+    if window is not None and (isinstance(window, bool) or int(window) != window or window < 1):
+        raise ValueError(f"window must be an integer >= 1 (or None), got {window!r}")
+    if lengths is not None:
+        lengths = _device_lengths(lengths, "lengths", qkv.shape[0] if qkv.dim() == 3 else None, M.device)
+    M, qkv, out, bias = M.contiguous(), qkv.contiguous(), out.contiguous(), bias.contiguous()
+    Hkv, heads_text = _packed_heads(num_heads, num_kv_heads)
+    heads = num_heads + 2 * Hkv
+    if qkv.dim() != 3 or num_heads < 1 or qkv.shape[2] == 0 or qkv.shape[2] % heads != 0:
+        raise ValueError(f"qkv must be [N, T, {heads_text} * d], got {tuple(qkv.shape)}")
+    N, T, E3 = qkv.shape
+    d = E3 // heads
+    E = num_heads * d
+    if tuple(out.shape) != (N, T, E):
+        raise ValueError(f"out must be {(N, T, E)}, got {tuple(out.shape)}")
+    if M.dim() != 4 or tuple(M.shape[1:]) != (N, T, E):
+        raise ValueError(f"M must be [V, {N}, {T}, {E}], got {tuple(M.shape)}")
+    Vd = M.shape[0]
+    if Vd == 0 or N == 0 or T == 0:
+        raise ValueError(f"empty operands: M {tuple(M.shape)}")
+    if tuple(bias.shape) != (num_heads, 2 * T - 1):
+        raise ValueError(f"bias must be [H, 2 T - 1] = {(num_heads, 2 * T - 1)}, got {tuple(bias.shape)}")
+    if index is None:
+        if width is not None and width != 2 * T - 1:
+            raise ValueError(f"width must be 2 T - 1 = {2 * T - 1} (or None) without an index, got {width!r}")
+        index, width = torch.arange(2 * T - 1, dtype=torch.int32, device=M.device), 2 * T - 1
+    else:
+        index = torch.as_tensor(index)
+        if index.is_floating_point() or index.is_complex() or index.dtype == torch.bool:
+            raise ValueError(f"index must be integers, got {index.dtype}")
+        if tuple(index.shape) != (2 * T - 1,):
+            raise ValueError(f"index must be [2 T - 1] = [{2 * T - 1}], got {tuple(index.shape)}")
+        if width is None or isinstance(width, bool) or int(width) != width or width < 1:
+            raise ValueError(f"width must be an integer >= 1 with an index, got {width!r}")
+        index, width = index.to(device=M.device, dtype=torch.int32).contiguous(), int(width)
+    Gb = torch.empty((Vd, N, num_heads, width), dtype=torch.float32, device=M.device)
+    lib = _lib.load()
+    ws, ws_bytes = _workspace(lib.vivit_attention_bias_factor_f32_workspace_bytes(Vd, N, T, num_heads, Hkv, d), M)
+    st = lib.vivit_attention_bias_factor_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), Gb.data_ptr(), Vd, N, T, num_heads, Hkv, d,
+                                             float(scale), int(bool(causal)), None if lengths is None else lengths.data_ptr(),
+                                             0 if window is None else int(window), 0.0 if softcap is None else softcap,
+                                             bias.data_ptr(), index.data_ptr(), width, ws, ws_bytes, _stream(M))
+    _lib.check(st, "vivit_attention_bias_factor_f32")
+    return Gb
 
 
 def _device_lengths(lengths, name: str, N, device):
