@@ -395,6 +395,16 @@ int vivit_attention_scoremod_jac_t_f32(const float *M, const float *qkv, const f
                                        int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths,
                                        int64_t window, float softcap, const float *bias, void *workspace, size_t workspace_bytes,
                                        void *stream);
+
+/* The same rule for head dimensions 128 < d <= 256 (csrc/attention_wide.hip: owners that keep their own operands in LDS at full
+ * width and stream the others in column halves of 128): the arguments, their meaning, the contract and the order of the refusals of
+ * vivit_attention_scoremod_jac_t_f32 (softcap 0 and bias null: the plain score function).  d <= 128 (the entries above) and
+ * d > 256: VIVIT_E_UNSUPPORTED, and the workspace query returns 0.  The workspace is lse [N, H, T] (rounded up to 256 bytes) and
+ * D [V, N, H, T], as above. */
+size_t vivit_attention_wide_jac_t_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d);
+int vivit_attention_wide_jac_t_f32(const float *M, const float *qkv, const float *out, float *G, int64_t V, int64_t N, int64_t T,
+                                   int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths, int64_t window,
+                                   float softcap, const float *bias, void *workspace, size_t workspace_bytes, void *stream);
 /* The factor of a LEARNED bias table (attention.hip; call site vivit_amd/kernels.py:attention_bias_factor, for
  * vivit_amd.backend.ScaledDotProductAttention(bias=, learn_bias=True)): the transposed Jacobian of the function of the score-modifier
  * entry point with respect to its table, applied to M.  Per factor row v, sample n and query head h,

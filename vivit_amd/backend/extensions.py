@@ -811,7 +811,7 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
     LogSigmoid, ELU, SELU, GELU in both forms, SiLU, SoftCap), Flatten / Identity / ActiveIdentity / Dropout(eval), ScaleModule,
     Max/AvgPool1d/2d, Conv1d / Conv2d and ConvTranspose1d / 2d (any groups, zero padding), Pad / ZeroPad2d / Slicing,
     BatchNorm (eval), LayerNorm and GroupNorm (with or without affine parameters; the same visit of the factor serves their
-    parameter rules), RMSNorm (likewise), RotaryEmbedding, ScaledDotProductAttention (head dimensions up to 128; the forward output it needs is ``module.output``,
+    parameter rules), RMSNorm (likewise), RotaryEmbedding, ScaledDotProductAttention (head dimensions up to 256; the forward output it needs is ``module.output``,
     sub-sampled by ``subsampling`` as ``x`` was), and -- on the same two-dimensional kernels -- Conv3d, ConvTranspose3d, MaxPool3d,
     AvgPool3d.  ``None``: no kernel for this module (custom modules, unsupported options such as ceil_mode) -- the generic autograd
     rule takes over."""
@@ -907,20 +907,21 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
         return kernels.rope_jac_t(M.reshape(M.shape[0], *x.shape), *module.tables(x.shape[1], d, x.device, x.dtype), module.num_heads,
                                   num_kv_heads=module.kv_heads)
     if isinstance(module, ScaledDotProductAttention):
-        # (a head dimension above the kernel's 128 has no kernel: the generic rule, before any operand is prepared; sizes beyond
-        # the kernel's index arithmetic come back as VIVIT_E_UNSUPPORTED and the caller falls through likewise)
+        # (head dimensions up to 128: csrc/attention.hip; 129 to 256: csrc/attention_wide.hip.  Above 256 there is no kernel: the
+        # generic rule, before any operand is prepared; sizes beyond the kernels' index arithmetic come back as VIVIT_E_UNSUPPORTED
+        # and the caller falls through likewise)
         d = module.head_dim(x)
         lengths = _attention_lengths(module, x, subsampling)
         table = module.bias_for(x.shape[1])
-        if d > 128:   # (with lengths the formula in torch: the generic rule's forward pass would not know the sub-sampled ones; with a
+        if d > 256:   # (with lengths the formula in torch: the generic rule's forward pass would not know the sub-sampled ones; with a
             # score modifier likewise: the generic rule would hold [V, N, H, T, T] several times over)
             if lengths is None and module.softcap is None and table is None:
                 return None
             return _attention_jac_t_torch(module, M, x, _attention_out(module, x, subsampling), lengths)
-        return kernels.attention_jac_t(M.reshape(M.shape[0], *x.shape[:2], -1), x, _attention_out(module, x, subsampling), module.num_heads,
-                                       module.scale_for(d), module.causal, num_kv_heads=module.kv_heads, lengths=lengths,
-                                       window=module.window, softcap=module.softcap,
-                                       bias=None if table is None else table.detach().to(torch.float32).contiguous())
+        rule = kernels.attention_wide_jac_t if d > 128 else kernels.attention_jac_t
+        return rule(M.reshape(M.shape[0], *x.shape[:2], -1), x, _attention_out(module, x, subsampling), module.num_heads, module.scale_for(d),
+                    module.causal, num_kv_heads=module.kv_heads, lengths=lengths, window=module.window, softcap=module.softcap,
+                    bias=None if table is None else table.detach().to(torch.float32).contiguous())
     if isinstance(module, _BATCHNORM) and x.dim() >= 2:
         if _own_params(module):   # the parameter rules want the two row sums of the same pass
             return _bn_eval_rules(module, M, x)[0]

@@ -697,29 +697,9 @@ def _softcap(cap) -> float:
     return float(cap)
 
 
-@_launcher
-def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None, window: int = None,
-                    softcap: float = None, bias=None):
-    """Transposed input Jacobian of scaled dot-product self-attention (``vivit_attention_masked_jac_t_f32``, the one entry that
-    launches): ``M [V, N, T, E]`` (the factor at the module output), ``qkv [N, T, 3 E]`` (the module input, q | k | v), ``out [N, T, E]``
-    (the module output of the forward pass) -> ``[V, N, T, 3 E]``.  ``E = num_heads * d``; no ``T x T`` tensor is allocated.
-    ``num_kv_heads`` (grouped-query attention; ``None`` is ``num_heads``, the three thirds): ``qkv [N, T, (num_heads + 2 *
-    num_kv_heads) * d]``, query head ``h`` attends to key / value head ``h // (num_heads // num_kv_heads)``; the result is packed
-    ``dQ | dK | dV`` like ``qkv``.
-
-    ``lengths`` (anything ``torch.as_tensor`` turns into ``N`` integers): sample ``n`` has the positions ``0 .. lengths[n] - 1``
-    (right padding; the kernel clamps to ``[0, T]``).  The positions beyond are dead: invisible as keys, rows of exact zeros in the
-    result, and whatever ``M``, ``qkv`` and ``out`` hold there is never read.  The values go to ``M``'s device as int32 and are not
-    looked at on the host.  ``window`` (an integer ``>= 1``): query ``i`` sees the keys with ``|i - j| < window`` (with ``causal`` the
-    ``window`` keys up to and including its own).  With both ``None`` (a null pointer and ``window = 0`` for the entry) the kernels
-    walk every key block unmasked: what the entries without them, ``vivit_attention_jac_t_f32`` and
-    ``vivit_attention_gqa_jac_t_f32``, hand to the same entry.
-
-    ``softcap`` (a finite float ``c > 0``) and ``bias`` (a float32 tensor ``[num_heads, 2 T - 1]`` on ``M``'s device): the score
-    function ``s_ij = c tanh(scale q_i k_j / c) + bias[h, j - i + T - 1]`` (either part alone where only one is given), the cap before
-    the bias and both before the mask; the table is a constant of this rule (a learned table's own factor:
-    :func:`attention_bias_factor`).  With either the call goes to
-    ``vivit_attention_scoremod_jac_t_f32``; with both ``None`` it is the call above, unchanged."""
+def _attention_self_operands(M, qkv, out, num_heads, num_kv_heads, lengths, window, softcap, bias):
+    """The checks of :func:`attention_jac_t` and :func:`attention_wide_jac_t`, before any launch: the operands made contiguous,
+    ``lengths`` as int32 on ``M``'s device, the cap as a float, and the sizes ``(Hkv, N, T, d, E3, Vd)``."""
     if softcap is not None:
         softcap = _softcap(softcap)
     _require_device(M, qkv, out)
@@ -754,6 +734,34 @@ def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num
         raise ValueError(f"empty operands: M {tuple(M.shape)}")
     if bias is not None and tuple(bias.shape) != (num_heads, 2 * T - 1):
         raise ValueError(f"bias must be [H, 2 T - 1] = {(num_heads, 2 * T - 1)}, got {tuple(bias.shape)}")
+    return M, qkv, out, lengths, softcap, bias, (Hkv, N, T, d, E3, Vd)
+
+
+@_launcher
+def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None, window: int = None,
+                    softcap: float = None, bias=None):
+    """Transposed input Jacobian of scaled dot-product self-attention (``vivit_attention_masked_jac_t_f32``, the one entry that
+    launches): ``M [V, N, T, E]`` (the factor at the module output), ``qkv [N, T, 3 E]`` (the module input, q | k | v), ``out [N, T, E]``
+    (the module output of the forward pass) -> ``[V, N, T, 3 E]``.  ``E = num_heads * d``; no ``T x T`` tensor is allocated.
+    ``num_kv_heads`` (grouped-query attention; ``None`` is ``num_heads``, the three thirds): ``qkv [N, T, (num_heads + 2 *
+    num_kv_heads) * d]``, query head ``h`` attends to key / value head ``h // (num_heads // num_kv_heads)``; the result is packed
+    ``dQ | dK | dV`` like ``qkv``.
+
+    ``lengths`` (anything ``torch.as_tensor`` turns into ``N`` integers): sample ``n`` has the positions ``0 .. lengths[n] - 1``
+    (right padding; the kernel clamps to ``[0, T]``).  The positions beyond are dead: invisible as keys, rows of exact zeros in the
+    result, and whatever ``M``, ``qkv`` and ``out`` hold there is never read.  The values go to ``M``'s device as int32 and are not
+    looked at on the host.  ``window`` (an integer ``>= 1``): query ``i`` sees the keys with ``|i - j| < window`` (with ``causal`` the
+    ``window`` keys up to and including its own).  With both ``None`` (a null pointer and ``window = 0`` for the entry) the kernels
+    walk every key block unmasked: what the entries without them, ``vivit_attention_jac_t_f32`` and
+    ``vivit_attention_gqa_jac_t_f32``, hand to the same entry.
+
+    ``softcap`` (a finite float ``c > 0``) and ``bias`` (a float32 tensor ``[num_heads, 2 T - 1]`` on ``M``'s device): the score
+    function ``s_ij = c tanh(scale q_i k_j / c) + bias[h, j - i + T - 1]`` (either part alone where only one is given), the cap before
+    the bias and both before the mask; the table is a constant of this rule (a learned table's own factor:
+    :func:`attention_bias_factor`).  With either the call goes to
+    ``vivit_attention_scoremod_jac_t_f32``; with both ``None`` it is the call above, unchanged."""
+    M, qkv, out, lengths, softcap, bias, (Hkv, N, T, d, E3, Vd) = _attention_self_operands(M, qkv, out, num_heads, num_kv_heads, lengths, window,
+                                                                                           softcap, bias)
     G = torch.empty((Vd, N, T, E3), dtype=torch.float32, device=M.device)
     lib = _lib.load()
     if softcap is not None or bias is not None:
@@ -769,6 +777,26 @@ def attention_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num
                                               float(scale), int(bool(causal)), None if lengths is None else lengths.data_ptr(),
                                               0 if window is None else int(window), ws, ws_bytes, _stream(M))
     _lib.check(st, "vivit_attention_masked_jac_t_f32")
+    return G
+
+
+@_launcher
+def attention_wide_jac_t(M, qkv, out, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None, window: int = None,
+                         softcap: float = None, bias=None):
+    """:func:`attention_jac_t` for head dimensions ``128 < d <= 256`` (``vivit_attention_wide_jac_t_f32``, csrc/attention_wide.hip):
+    the same operands, arguments, result and promises -- no ``T x T`` tensor, dead positions never read and rows of ``+0`` for them,
+    bytes of ``G[v, n]`` that depend on the shape parameters and the data of ``(v, n)`` only.  Any other head dimension raises
+    ``VIVIT_E_UNSUPPORTED``."""
+    M, qkv, out, lengths, softcap, bias, (Hkv, N, T, d, E3, Vd) = _attention_self_operands(M, qkv, out, num_heads, num_kv_heads, lengths, window,
+                                                                                           softcap, bias)
+    G = torch.empty((Vd, N, T, E3), dtype=torch.float32, device=M.device)
+    lib = _lib.load()
+    ws, ws_bytes = _workspace(lib.vivit_attention_wide_jac_t_f32_workspace_bytes(Vd, N, T, num_heads, Hkv, d), M)
+    st = lib.vivit_attention_wide_jac_t_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), G.data_ptr(), Vd, N, T, num_heads, Hkv, d,
+                                            float(scale), int(bool(causal)), None if lengths is None else lengths.data_ptr(),
+                                            0 if window is None else int(window), 0.0 if softcap is None else softcap,
+                                            None if bias is None else bias.data_ptr(), ws, ws_bytes, _stream(M))
+    _lib.check(st, "vivit_attention_wide_jac_t_f32")
     return G
 
 
