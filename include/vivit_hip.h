@@ -463,6 +463,28 @@ int vivit_attention_cross_jac_t_f32(const float *M, const float *q, const float 
                                     int64_t V, int64_t N, int64_t Tq, int64_t Tk, int64_t H, int64_t Hkv, int64_t d, float scale,
                                     const int32_t *q_lengths, const int32_t *k_lengths, void *workspace, size_t workspace_bytes,
                                     void *stream);
+/* The FORWARD pass of the attention modules (attention_forward.hip; call sites vivit_amd/kernels.py:attention_forward and
+ * cross_attention_forward, for the modules built with fused_forward=True): the function whose transposed Jacobian the entries above
+ * apply.  qkv, lengths, window, softcap, bias, scale and causal are those of vivit_attention_scoremod_jac_t_f32 (softcap 0 and bias
+ * NULL: the plain score function; its AttPlain instances); q, kv, q_lengths and k_lengths those of vivit_attention_cross_jac_t_f32.
+ * Per sample n and query head h of group g:  P = softmax_rows(s) of the visible pairs,  out[n, i, h d ..] = P V_g  (out [N, T, H d] or
+ * [N, Tq, H d], fp32, dense, uninitialised memory: every row has exactly one writer),  lse[n, h, i] = log sum_j exp(s_ij)
+ * (lse [N, H, T] or [N, H, Tq], or NULL: not wanted; the bytes of out do not depend on it).  One launch, flash-style: a workgroup per
+ * (n, h, block of 32 queries) walks the key blocks of the block ranges above in ascending order with the running row maximum and
+ * row sum in registers and the output block in MFMA accumulators, rescaled per key block.  NO workspace, no atomics, no T x T
+ * (Tq x Tk) data in memory; one summation order (key blocks ascending, k ascending within a block): the bytes of out[n] and lse[n]
+ * depend on the shape parameters, the cap, the table, the length(s) of n and the data of sample n only, and out[n, :Tn] has the
+ * bytes of the sample cut to Tn and run alone.  No operand row of a dead position is loaded; the rows of dead queries are +0 in out
+ * and in lse.  A live query has a visible key (itself; any live key), so no row of the softmax is empty.
+ * The refusals are those of the two rule entries with V = 1, in their order, all before the launch: VIVIT_E_BADARG (softcap
+ * negative, NaN or inf; qkv / q / kv / out NULL; window < 0; non-positive sizes; H % Hkv != 0), VIVIT_E_UNSUPPORTED (d > 128: the
+ * modules keep the torch formula there; sizes beyond the kernels' index arithmetic, as above). */
+int vivit_attention_forward_f32(const float *qkv, float *out, float *lse, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d,
+                                float scale, int causal, const int32_t *lengths, int64_t window, float softcap, const float *bias,
+                                void *stream);
+int vivit_attention_cross_forward_f32(const float *q, const float *kv, float *out, float *lse, int64_t N, int64_t Tq, int64_t Tk,
+                                      int64_t H, int64_t Hkv, int64_t d, float scale, const int32_t *q_lengths,
+                                      const int32_t *k_lengths, void *stream);
 /* nn.Embedding (embedding.hip; the reference has no rule for it): the weight factor Vt[v, n, w, :] = sum_{t: idx[n, t] = w} M[v, n, t, :]
  * of the factor M [V, N, T, D] at the module output has at most T non-zero rows per (v, n) out of W = num_embeddings and is kept
  * compact: ids [N, T] int32 holds sample n's distinct tokens in strictly increasing order in its first U_n slots and -1 in the rest,

@@ -11,7 +11,10 @@ import math
 
 import torch
 from torch import Tensor, nn
+from torch.autograd.function import once_differentiable
 from torch.nn import functional as F
+
+from vivit_amd import _lib, kernels
 
 
 class SumModule(nn.Module):
@@ -268,6 +271,68 @@ def alibi_bias(num_heads: int, max_len: int) -> Tensor:
     return (-alibi_slopes(num_heads)[:, None] * dist[None, :]).to(torch.float32)
 
 
+def _fused_forward_applies(flag: bool, d: int, *tensors: Tensor) -> bool:
+    """Whether a module built with ``fused_forward=flag`` takes the flash-style kernel for these inputs: HIP fp32 tensors and a
+    head dimension the kernel has (sizes beyond its index arithmetic come back as VIVIT_E_UNSUPPORTED from the call itself)."""
+    return flag and d <= 128 and all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
+
+
+class _FusedAttention(torch.autograd.Function):
+    """``ScaledDotProductAttention.attend`` as ONE flash-style launch (``kernels.attention_forward``) whose backward pass is the
+    extensions' rule applied to the gradient as a factor of one row (``kernels.attention_jac_t``; for a learned table
+    ``kernels.attention_bias_factor``, summed over the samples): no ``T x T`` tensor is allocated in either pass.  ``bias``: the
+    learned table (the parameter, so that autograd reaches it) or ``None``; a constant table and the lengths get no gradient."""
+
+    @staticmethod
+    def forward(ctx, qkv: Tensor, bias, module, lengths):
+        T, d = qkv.shape[1], module.head_dim(qkv)
+        table = module.bias_for(T)
+        if table is not None:
+            table = table.detach().to(torch.float32).contiguous()
+        ctx.call = dict(num_heads=module.num_heads, scale=module.scale_for(d), causal=module.causal, num_kv_heads=module.kv_heads,
+                        lengths=lengths, window=module.window, softcap=module.softcap)
+        out = kernels.attention_forward(qkv, bias=table, **ctx.call)
+        if bias is not None:   # where the distances of this batch sit in the parameter: the mapping of the extensions' rule
+            ctx.columns, ctx.width, ctx.bias_dtype = module.bias_columns(T, qkv.device), bias.shape[1], bias.dtype
+        ctx.save_for_backward(qkv, out, table)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad: Tensor):
+        qkv, out, table = ctx.saved_tensors
+        M = grad.contiguous()[None]
+        dqkv = dbias = None
+        if ctx.needs_input_grad[0]:
+            dqkv = kernels.attention_jac_t(M, qkv, out, bias=table, **ctx.call)[0]
+        if ctx.needs_input_grad[1]:
+            call = dict(ctx.call)
+            dbias = kernels.attention_bias_factor(M, qkv, out, call.pop("num_heads"), call.pop("scale"), call.pop("causal"), table,
+                                                  index=ctx.columns, width=ctx.width, **call)[0].sum(0).to(ctx.bias_dtype)
+        return dqkv, dbias, None, None
+
+
+class _FusedCrossAttention(torch.autograd.Function):
+    """``ScaledDotProductCrossAttention.attend`` as one flash-style launch (``kernels.cross_attention_forward``); the backward
+    pass is ``kernels.cross_attention_jac_t`` on the gradient as a factor of one row, for the inputs that need one (a frozen
+    memory skips its owner)."""
+
+    @staticmethod
+    def forward(ctx, q: Tensor, kv: Tensor, module, query_lengths, key_lengths):
+        ctx.call = dict(num_heads=module.num_heads, scale=module.scale_for(module.head_dim(q, kv)), num_kv_heads=module.kv_heads,
+                        query_lengths=query_lengths, key_lengths=key_lengths)
+        out = kernels.cross_attention_forward(q, kv, **ctx.call)
+        ctx.save_for_backward(q, kv, out)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad: Tensor):
+        q, kv, out = ctx.saved_tensors
+        Gq, Gkv = kernels.cross_attention_jac_t(grad.contiguous()[None], q, kv, out, want=ctx.needs_input_grad[:2], **ctx.call)
+        return (None if Gq is None else Gq[0]), (None if Gkv is None else Gkv[0]), None, None, None
+
+
 class ScaledDotProductAttention(nn.Module):
     """Multi-head scaled dot-product self-attention on a packed projection (no counterpart in BackPACK): a leaf whose one possible parameter is a
     learned bias table (``learn_bias``, below).
@@ -306,11 +371,24 @@ class ScaledDotProductAttention(nn.Module):
     query heads share ``Hkv = num_kv_heads`` key / value heads, ``H % Hkv == 0``.  Input ``qkv [N, T, (H + 2 Hkv) d]``: ``q`` is the
     first ``H d`` columns, ``k`` the next ``Hkv d``, ``v`` the last ``Hkv d``; query head ``h`` attends to key / value head
     ``h // (H / Hkv)`` (groups of consecutive heads, as LLaMA's ``repeat_kv``).  Output ``[N, T, H d]``.  ``Hkv == 1`` is multi-query
-    attention."""
+    attention.
+
+    ``fused_forward`` (default ``False``: the torch formula of :meth:`attend`, which allocates up to four ``[N, H, T, T]`` tensors
+    and keeps one or two for autograd).  With ``True`` a HIP fp32 input with ``d <= 128`` runs the forward pass as one flash-style
+    kernel (``kernels.attention_forward``) and autograd's backward pass as the extensions' rule on the gradient
+    (``kernels.attention_jac_t``, ``kernels.attention_bias_factor`` for a learned table): the same function and the same gradients
+    to rounding, no ``T x T`` tensor in either pass, and tiles that no live pair reaches are skipped.  CPU tensors, other dtypes,
+    ``d > 128`` and sizes the kernel refuses run the torch formula unchanged.  Measured on one MI355X with 12 heads of 64
+    (profiles/attention_forward_time.log): the forward pass alone is faster with the flag at every shape measured
+    (1.3 times at T = 512, 1.4 at T = 2048, 6.8 on a causal batch with half of every sequence padded); forward + backward is SLOWER
+    with the flag on unmasked batches (0.77 of the torch path's speed at T = 512, 0.66 at T = 2048: the rule's fp32 kernels against
+    rocBLAS) and 3.2 times faster on the half-padded causal batch; its peak memory at T = 2048 is 120 MiB instead of 3.1 GiB."""
 
     def __init__(self, num_heads: int, causal: bool = False, scale: float = None, num_kv_heads: int = None, window: int = None,
-                 softcap: float = None, bias: Tensor = None, learn_bias: bool = False, bias_index: Tensor = None):
+                 softcap: float = None, bias: Tensor = None, learn_bias: bool = False, bias_index: Tensor = None,
+                 fused_forward: bool = False):
         super().__init__()
+        self.fused_forward = bool(fused_forward)
         if num_heads < 1:
             raise ValueError(f"num_heads must be positive, got {num_heads}")
         if bias is None and learn_bias:
@@ -433,6 +511,12 @@ class ScaledDotProductAttention(nn.Module):
         """The forward pass with explicit ``lengths`` (int32 ``[N]`` on the device of ``qkv``, or ``None``)."""
         d = self.head_dim(qkv)
         N, T, H = qkv.shape[0], qkv.shape[1], self.num_heads
+        if _fused_forward_applies(self.fused_forward, d, qkv):
+            try:
+                return _FusedAttention.apply(qkv, self.bias if self.learn_bias else None, self, lengths)
+            except _lib.VivitHipError as exc:   # a shape beyond the kernel's launch limits: the formula below
+                if exc.status != _lib.VIVIT_E_UNSUPPORTED:
+                    raise
         hidden, dead = self.masks(T, lengths, qkv.device)
         if dead is not None:   # the dead rows of q, k and v are zeros, whatever the input holds there
             qkv = qkv.masked_fill(dead, 0.0)
@@ -501,11 +585,11 @@ class MultiheadSelfAttention(nn.Sequential):
     ``softcap`` and ``attention_bias`` (its ``bias``: the table ``[H, 2 L - 1]``, e.g. :func:`alibi_bias`; the name ``bias`` is taken
     by the flag of the two projections, as in ``nn.MultiheadAttention`` -- a TENSOR given as ``bias`` is taken for the table and the
     projections keep their bias vectors).  ``learn_attention_bias`` and ``attention_bias_index`` are the leaf's ``learn_bias`` and
-    ``bias_index``: a learned table, and a table indexed through buckets."""
+    ``bias_index``: a learned table, and a table indexed through buckets.  ``fused_forward`` is the leaf's."""
 
     def __init__(self, embed_dim: int, num_heads: int, bias: Union[bool, Tensor] = True, causal: bool = False, num_kv_heads: int = None,
                  window: int = None, softcap: float = None, attention_bias: Tensor = None, learn_attention_bias: bool = False,
-                 attention_bias_index: Tensor = None):
+                 attention_bias_index: Tensor = None, fused_forward: bool = False):
         if embed_dim % num_heads != 0:
             raise ValueError(f"embed_dim ({embed_dim}) is not divisible by num_heads ({num_heads})")
         if isinstance(bias, Tensor):
@@ -513,7 +597,8 @@ class MultiheadSelfAttention(nn.Sequential):
                 raise ValueError("two bias tables: give the table as bias or as attention_bias, not both")
             bias, attention_bias = True, bias
         attention = ScaledDotProductAttention(num_heads, causal=causal, num_kv_heads=num_kv_heads, window=window, softcap=softcap,
-                                              bias=attention_bias, learn_bias=learn_attention_bias, bias_index=attention_bias_index)
+                                              bias=attention_bias, learn_bias=learn_attention_bias, bias_index=attention_bias_index,
+                                              fused_forward=fused_forward)
         packed = (num_heads + 2 * attention.kv_heads) * (embed_dim // num_heads)
         super().__init__(nn.Linear(embed_dim, packed, bias=bias), attention, nn.Linear(embed_dim, embed_dim, bias=bias))
 
@@ -581,10 +666,15 @@ class ScaledDotProductCrossAttention(nn.Module):
     are a sequence or an integer tensor ``[N]``: one on the host is checked to lie in ``[0, Tq]`` / ``[0, Tk]`` at the next forward
     pass; one on a device is never read on the host and is clamped, as the kernel of the extensions' rule clamps it.  The forward
     pass keeps the int32 tensors it used on the module (``forward_query_lengths``, ``forward_key_lengths``), and the rule reads
-    those: the very lengths of the forward pass."""
+    those: the very lengths of the forward pass.
 
-    def __init__(self, num_heads: int, scale: float = None, num_kv_heads: int = None):
+    ``fused_forward`` (default ``False``) is that of :class:`ScaledDotProductAttention`: a HIP fp32 forward pass with ``d <= 128``
+    as one flash-style kernel (``kernels.cross_attention_forward``), autograd's backward pass as ``kernels.cross_attention_jac_t``
+    for the inputs that need a gradient, no ``Tq x Tk`` tensor in either pass; everything else runs the torch formula."""
+
+    def __init__(self, num_heads: int, scale: float = None, num_kv_heads: int = None, fused_forward: bool = False):
         super().__init__()
+        self.fused_forward = bool(fused_forward)
         if num_heads < 1:
             raise ValueError(f"num_heads must be positive, got {num_heads}")
         self.num_heads, self.scale = int(num_heads), scale
@@ -650,6 +740,12 @@ class ScaledDotProductCrossAttention(nn.Module):
         """The forward pass with explicit lengths (int32 ``[N]`` on the device of the inputs, or ``None``)."""
         d = self.head_dim(q, kv)
         N, Tq, H = q.shape[0], q.shape[1], self.num_heads
+        if _fused_forward_applies(self.fused_forward, d, q, kv):
+            try:
+                return _FusedCrossAttention.apply(q, kv, self, query_lengths, key_lengths)
+            except _lib.VivitHipError as exc:   # a shape beyond the kernel's launch limits: the formula below
+                if exc.status != _lib.VIVIT_E_UNSUPPORTED:
+                    raise
         hidden, dead_q, dead_k = self.masks(N, Tq, kv.shape[1], query_lengths, key_lengths, q.device)
         if hidden is not None:   # the dead rows of q, k and v are zeros, whatever the inputs hold there
             q, kv = q.masked_fill(dead_q, 0.0), kv.masked_fill(dead_k, 0.0)
@@ -667,11 +763,12 @@ class MultiheadCrossAttention(nn.Module):
     :class:`ScaledDotProductCrossAttention`, ``out_proj = Linear(E, E)``; ``d = E / H``, ``Hkv = num_kv_heads or H``.  ``set_lengths``
     is that of the leaf (right-padded batches on either side).  No causal mask, no window, no dropout, no arbitrary mask."""
 
-    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True, num_kv_heads: int = None, kdim: int = None):
+    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True, num_kv_heads: int = None, kdim: int = None,
+                 fused_forward: bool = False):
         super().__init__()
         if embed_dim % num_heads != 0:
             raise ValueError(f"embed_dim ({embed_dim}) is not divisible by num_heads ({num_heads})")
-        self.attention = ScaledDotProductCrossAttention(num_heads, num_kv_heads=num_kv_heads)
+        self.attention = ScaledDotProductCrossAttention(num_heads, num_kv_heads=num_kv_heads, fused_forward=fused_forward)
         self.embed_dim, self.num_heads, self.kdim = int(embed_dim), int(num_heads), int(embed_dim if kdim is None else kdim)
         self.q_proj = nn.Linear(embed_dim, embed_dim, bias=bias)
         self.kv_proj = nn.Linear(self.kdim, 2 * self.attention.kv_heads * (embed_dim // num_heads), bias=bias)

@@ -93,8 +93,6 @@
 
 namespace vivit {
 
-constexpr int ATT_D_MAX = 128;   // the head dimensions of this unit (129 to 256: attention_wide.hip)
-
 // what the two owners share: the dO blocks and D of the workgroup's factor rows for the query block at i0 (rows >= Tn, the live
 // queries: zero)
 template <int NT, class Geo>
@@ -428,21 +426,7 @@ __global__ __launch_bounds__(256) void attn_dbias_fold_kernel(const float *__res
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-// the cross-attention entry's plan: that of the query sequence (the workspace is counted in queries) and the limits of the keys'
-static AttPlan attention_cross_plan(int64_t V, int64_t N, int64_t Tq, int64_t Tk, int64_t H, int64_t Hkv, int64_t d, int64_t &KBk) {
-  if (Tk <= 0) return AttPlan{VIVIT_E_BADARG, 0, 0, 0};
-  AttPlan p = attention_plan(V, N, Tq, H, Hkv, d, ATT_D_MAX);
-  if (p.status != VIVIT_OK) return p;
-  // 32-bit: Tk + 32, the block index N Hkv KBk of the key owner (its R KBq steps, the pitches H d and 2 Hkv d < (H + 2 Hkv) d and
-  // the blocks N H KBq of the query owners are the plan's); 64-bit: every element offset of kv and Gkv
-  const int64_t lim = 0x7fffffffLL;
-  KBk = cdiv(Tk, ATT_B);
-  const int64_t per_k = N * Hkv * Tk;   // (N Hkv < 2^31 by the plan)
-  if (Tk > lim - ATT_B || N * Hkv > lim / KBk || per_k > (int64_t)1 << 40 || V > ((int64_t)1 << 58) / (per_k * 2 * d))
-    return AttPlan{VIVIT_E_UNSUPPORTED, 0, 0, 0};
-  return p;
-}
-
+// (the plans and the geometries of the entries: attention_common.h)
 // the four launches; `G`: the result of the query owner (null: not launched), `Gkv`: that of the key owner (null: not launched; for
 // self-attention the same packed tensor as G)
 template <int NT, class Geo, class Mod>
@@ -611,14 +595,7 @@ int vivit_attention_cross_jac_t_f32(const float *M, const float *q, const float 
   const AttPlan p = attention_cross_plan(V, N, Tq, Tk, H, Hkv, d, KBk);
   if (p.status != VIVIT_OK) return p.status;
   if (!workspace || workspace_bytes < p.bytes) return VIVIT_E_WORKSPACE;
-  AttGeomX g;
-  g.N = (int)N, g.Tq = (int)Tq, g.Tk = (int)Tk, g.H = (int)H, g.d = (int)d, g.KBq = (int)p.KB, g.KBk = (int)KBk;
-  g.Hkv = (int)Hkv, g.R = (int)(H / Hkv);
-  g.qpitch = (int)(H * d), g.kpitch = (int)(2 * Hkv * d), g.voff = (int)(Hkv * d);
-  g.vec = (d & 3) == 0 && att_aligned16(M) && att_aligned16(q) && att_aligned16(kv);
-  g.scale = scale;
-  g.kv = kv, g.Gkv = Gkv;
-  g.qlengths = q_lengths, g.klengths = k_lengths;
+  const AttGeomX g = attention_cross_geom(M, q, kv, Gkv, N, Tq, Tk, H, Hkv, d, p.KB, KBk, scale, q_lengths, k_lengths);
   float *lse = static_cast<float *>(workspace);
   float *Dws = reinterpret_cast<float *>(static_cast<char *>(workspace) + p.lse_bytes);
   return attention_launch_d(M, q, out, Gq, Gkv, lse, Dws, V, g, AttPlain{}, g.Tq, g.KBq, g.KBk, static_cast<hipStream_t>(stream));

@@ -1,4 +1,5 @@
-// What the attention translation units share (attention.hip: head dimensions up to 128; attention_wide.hip: 129 to 256): the tile
+// What the attention translation units share (attention.hip: head dimensions up to 128; attention_wide.hip: 129 to 256;
+// attention_forward.hip: the forward pass, up to 128): the tile
 // configuration, the LDS block loader and the MFMA tile products, the two geometries with their mask and block-range helpers, the
 // score function, the row log-sum-exp and row-dot kernels, and the host plan.  The contract they serve stands at the head of
 // attention.hip.
@@ -320,6 +321,38 @@ static AttGeom attention_self_geom(const float *M, const float *qkv, int64_t N, 
   g.scale = scale;
   g.lengths = lengths;
   g.window = window >= T ? 0 : (int)window;   // (a window of T or more cuts nothing; this also covers every value beyond an int)
+  return g;
+}
+
+constexpr int ATT_D_MAX = 128;   // the head dimensions of attention.hip and attention_forward.hip (129 to 256: attention_wide.hip)
+
+// the cross-attention entries' plan: that of the query sequence (the workspace is counted in queries) and the limits of the keys'
+static AttPlan attention_cross_plan(int64_t V, int64_t N, int64_t Tq, int64_t Tk, int64_t H, int64_t Hkv, int64_t d, int64_t &KBk) {
+  if (Tk <= 0) return AttPlan{VIVIT_E_BADARG, 0, 0, 0};
+  AttPlan p = attention_plan(V, N, Tq, H, Hkv, d, ATT_D_MAX);
+  if (p.status != VIVIT_OK) return p;
+  // 32-bit: Tk + 32, the block index N Hkv KBk of the key owner (its R KBq steps, the pitches H d and 2 Hkv d < (H + 2 Hkv) d and
+  // the blocks N H KBq of the query owners are the plan's); 64-bit: every element offset of kv and Gkv
+  const int64_t lim = 0x7fffffffLL;
+  KBk = cdiv(Tk, ATT_B);
+  const int64_t per_k = N * Hkv * Tk;   // (N Hkv < 2^31 by the plan)
+  if (Tk > lim - ATT_B || N * Hkv > lim / KBk || per_k > (int64_t)1 << 40 || V > ((int64_t)1 << 58) / (per_k * 2 * d))
+    return AttPlan{VIVIT_E_UNSUPPORTED, 0, 0, 0};
+  return p;
+}
+
+// the geometry of a cross-attention call that the plan has accepted (M: the factor, or q again where there is none)
+static AttGeomX attention_cross_geom(const float *M, const float *q, const float *kv, float *Gkv, int64_t N, int64_t Tq, int64_t Tk,
+                                     int64_t H, int64_t Hkv, int64_t d, int64_t KBq, int64_t KBk, float scale,
+                                     const int32_t *q_lengths, const int32_t *k_lengths) {
+  AttGeomX g;
+  g.N = (int)N, g.Tq = (int)Tq, g.Tk = (int)Tk, g.H = (int)H, g.d = (int)d, g.KBq = (int)KBq, g.KBk = (int)KBk;
+  g.Hkv = (int)Hkv, g.R = (int)(H / Hkv);
+  g.qpitch = (int)(H * d), g.kpitch = (int)(2 * Hkv * d), g.voff = (int)(Hkv * d);
+  g.vec = (d & 3) == 0 && att_aligned16(M) && att_aligned16(q) && att_aligned16(kv);
+  g.scale = scale;
+  g.kv = kv, g.Gkv = Gkv;
+  g.qlengths = q_lengths, g.klengths = k_lengths;
   return g;
 }
 

@@ -928,6 +928,68 @@ def cross_attention_jac_t(M, q, kv, out, num_heads: int, scale: float, num_kv_he
     return Gq, Gkv
 
 
+@_launcher
+def attention_forward(qkv, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None, window: int = None,
+                      softcap: float = None, bias=None, return_lse: bool = False):
+    """The forward pass of scaled dot-product self-attention in one flash-style launch (``vivit_attention_forward_f32``,
+    csrc/attention_forward.hip): ``qkv [N, T, (num_heads + 2 * Hkv) * d]`` -> ``out [N, T, num_heads * d]``, and with ``return_lse``
+    ``(out, lse [N, num_heads, T])``, the row log-sum-exp of the logits (the bytes of ``out`` are the same either way).  Every
+    argument is that of :func:`attention_jac_t`, whose function this is; no ``T x T`` tensor and no workspace is allocated, the rows
+    of dead positions are exact zeros (in ``lse`` too) and what ``qkv`` holds there is never read.  ``d > 128`` raises
+    ``VIVIT_E_UNSUPPORTED``."""
+    _require_device(qkv)
+    Hkv, _ = _packed_heads(num_heads, num_kv_heads)
+    heads = num_heads + 2 * Hkv
+    if qkv.dim() != 3 or num_heads < 1 or qkv.shape[2] == 0 or qkv.shape[2] % heads != 0:
+        raise ValueError(f"qkv must be [N, T, (H + 2 Hkv) * d], got {tuple(qkv.shape)}")
+    N, T, E = qkv.shape[0], qkv.shape[1], qkv.shape[2] // heads * num_heads
+    # (the operand checks of the rule, with the output buffer standing in for the factor and for the forward output it asks for)
+    out = torch.empty((N, T, E), dtype=torch.float32, device=qkv.device)
+    _, qkv, _, lengths, softcap, bias, (Hkv, N, T, d, _, _) = _attention_self_operands(out[None], qkv, out, num_heads, num_kv_heads, lengths,
+                                                                                      window, softcap, bias)
+    lse = torch.empty((N, num_heads, T), dtype=torch.float32, device=qkv.device) if return_lse else None
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    st = _lib.load().vivit_attention_forward_f32(qkv.data_ptr(), out.data_ptr(), ptr(lse), N, T, num_heads, Hkv, d, float(scale),
+                                                 int(bool(causal)), ptr(lengths), 0 if window is None else int(window),
+                                                 0.0 if softcap is None else softcap, ptr(bias), _stream(qkv))
+    _lib.check(st, "vivit_attention_forward_f32")
+    return (out, lse) if return_lse else out
+
+
+@_launcher
+def cross_attention_forward(q, kv, num_heads: int, scale: float, num_kv_heads: int = None, query_lengths=None, key_lengths=None,
+                            return_lse: bool = False):
+    """The forward pass of scaled dot-product cross-attention in one flash-style launch (``vivit_attention_cross_forward_f32``):
+    ``q [N, Tq, num_heads * d]``, ``kv [N, Tk, 2 * Hkv * d]`` -> ``out [N, Tq, num_heads * d]``, and with ``return_lse``
+    ``(out, lse [N, num_heads, Tq])``.  Every argument is that of :func:`cross_attention_jac_t`, whose function this is; no
+    ``Tq x Tk`` tensor and no workspace is allocated, the rows of dead queries are exact zeros and dead positions are never read.
+    ``d > 128`` raises ``VIVIT_E_UNSUPPORTED``."""
+    _require_device(q, kv)
+    N0 = q.shape[0] if q.dim() == 3 else None
+    if query_lengths is not None:
+        query_lengths = _device_lengths(query_lengths, "query_lengths", N0, q.device)
+    if key_lengths is not None:
+        key_lengths = _device_lengths(key_lengths, "key_lengths", N0, q.device)
+    q, kv = q.contiguous(), kv.contiguous()
+    Hkv, _ = _packed_heads(num_heads, num_kv_heads)
+    if q.dim() != 3 or num_heads < 1 or q.shape[2] == 0 or q.shape[2] % num_heads != 0:
+        raise ValueError(f"q must be [N, Tq, {num_heads} * d], got {tuple(q.shape)}")
+    N, Tq, E = q.shape
+    d = E // num_heads
+    if kv.dim() != 3 or kv.shape[0] != N or kv.shape[2] != 2 * Hkv * d:
+        raise ValueError(f"kv must be [{N}, Tk, 2 * {Hkv} * {d}], got {tuple(kv.shape)}")
+    Tk = kv.shape[1]
+    if N == 0 or Tq == 0 or Tk == 0:
+        raise ValueError(f"empty operands: q {tuple(q.shape)}, kv {tuple(kv.shape)}")
+    out = torch.empty((N, Tq, E), dtype=torch.float32, device=q.device)
+    lse = torch.empty((N, num_heads, Tq), dtype=torch.float32, device=q.device) if return_lse else None
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    st = _lib.load().vivit_attention_cross_forward_f32(q.data_ptr(), kv.data_ptr(), out.data_ptr(), ptr(lse), N, Tq, Tk, num_heads, Hkv, d,
+                                                       float(scale), ptr(query_lengths), ptr(key_lengths), _stream(q))
+    _lib.check(st, "vivit_attention_cross_forward_f32")
+    return (out, lse) if return_lse else out
+
+
 _I32_MAX = 2 ** 31 - 1
 
 
