@@ -485,6 +485,35 @@ int vivit_attention_forward_f32(const float *qkv, float *out, float *lse, int64_
 int vivit_attention_cross_forward_f32(const float *q, const float *kv, float *out, float *lse, int64_t N, int64_t Tq, int64_t Tk,
                                       int64_t H, int64_t Hkv, int64_t d, float scale, const int32_t *q_lengths,
                                       const int32_t *k_lengths, void *stream);
+/* The BACKWARD pass of the attention modules from the forward's saved statistics (attention_backward.hip; call sites
+ * vivit_amd/kernels.py:attention_backward and cross_attention_backward, for the modules built with fused_forward=True): the gradient
+ * of the function above for ONE row dout [N, T, H d] ([N, Tq, H d]), given the forward's inputs, its out and its lse [N, H, T]
+ * ([N, H, Tq]) as the forward entry wrote them.  Every other argument is the forward entry's.  Results: dqkv [N, T, (H + 2 Hkv) d] =
+ * dQ | dK | dV; for cross-attention dq [N, Tq, H d] and dkv [N, Tk, 2 Hkv d] = dK | dV, either of which may be NULL (its owner is
+ * then not launched), not both.  fp32, dense, uninitialised memory: every row has exactly one writer.  The jac_t entries above serve
+ * V >= 2 factor rows, recompute lse and cannot take a saved one; here there are two launches -- the query-block owner, which also
+ * forms D_i = sum_c dout_ic out_ic of its rows, and behind it the key-block owner -- with one row of everything, no lse launch, no
+ * atomics and no T x T (Tq x Tk) data in memory.  The workspace is D [N, H, T] floats and nothing else:
+ * vivit_attention_backward_f32_workspace_bytes(N, T, H, Hkv, d) (cross: (N, Tq, Tk, H, Hkv, d)) bytes; the query returns 0 for
+ * arguments the entry point refuses.  One summation order (dQ: key blocks ascending, k ascending within a block; dK, dV: the heads of
+ * the group ascending, the query blocks ascending, k ascending; D: eight chains per row folded by a butterfly): the bytes of sample
+ * n's rows depend on the shape parameters, the cap, the table, the length(s) of n and the data of sample n only, and with lengths
+ * they are those of the sample cut to its length (every operand, lse included) and run alone.  No row of any operand at a dead
+ * position is loaded -- lse and D there are never read --, and the rows of dead positions are +0 in the results.
+ * The refusals are those of the forward entries, in their order, all before any launch: VIVIT_E_BADARG (softcap negative, NaN or
+ * inf; dout / qkv / q / kv / out / lse / dqkv NULL, dq and dkv both NULL; window < 0; non-positive sizes; H % Hkv != 0),
+ * VIVIT_E_UNSUPPORTED (d > 128; sizes beyond the kernels' index arithmetic, as above; before the workspace is looked at), then
+ * VIVIT_E_WORKSPACE: a missing or short workspace. */
+size_t vivit_attention_backward_f32_workspace_bytes(int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d);
+int vivit_attention_backward_f32(const float *dout, const float *qkv, const float *out, const float *lse, float *dqkv, int64_t N,
+                                 int64_t T, int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths,
+                                 int64_t window, float softcap, const float *bias, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+size_t vivit_attention_cross_backward_f32_workspace_bytes(int64_t N, int64_t Tq, int64_t Tk, int64_t H, int64_t Hkv, int64_t d);
+int vivit_attention_cross_backward_f32(const float *dout, const float *q, const float *kv, const float *out, const float *lse,
+                                       float *dq, float *dkv, int64_t N, int64_t Tq, int64_t Tk, int64_t H, int64_t Hkv, int64_t d,
+                                       float scale, const int32_t *q_lengths, const int32_t *k_lengths, void *workspace,
+                                       size_t workspace_bytes, void *stream);
 /* nn.Embedding (embedding.hip; the reference has no rule for it): the weight factor Vt[v, n, w, :] = sum_{t: idx[n, t] = w} M[v, n, t, :]
  * of the factor M [V, N, T, D] at the module output has at most T non-zero rows per (v, n) out of W = num_embeddings and is kept
  * compact: ids [N, T] int32 holds sample n's distinct tokens in strictly increasing order in its first U_n slots and -1 in the rest,

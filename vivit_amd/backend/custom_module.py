@@ -278,10 +278,11 @@ def _fused_forward_applies(flag: bool, d: int, *tensors: Tensor) -> bool:
 
 
 class _FusedAttention(torch.autograd.Function):
-    """``ScaledDotProductAttention.attend`` as ONE flash-style launch (``kernels.attention_forward``) whose backward pass is the
-    extensions' rule applied to the gradient as a factor of one row (``kernels.attention_jac_t``; for a learned table
-    ``kernels.attention_bias_factor``, summed over the samples): no ``T x T`` tensor is allocated in either pass.  ``bias``: the
-    learned table (the parameter, so that autograd reaches it) or ``None``; a constant table and the lengths get no gradient."""
+    """``ScaledDotProductAttention.attend`` as ONE flash-style launch (``kernels.attention_forward``), which also returns the row
+    log-sum-exp ``lse [N, H, T]``; the backward pass is the one-row kernels that reuse it (``kernels.attention_backward``; for a
+    learned table the extensions' rule on the gradient as a factor of one row, ``kernels.attention_bias_factor``, summed over the
+    samples): no ``T x T`` tensor is allocated in either pass.  ``bias``: the learned table (the parameter, so that autograd
+    reaches it) or ``None``; a constant table and the lengths get no gradient."""
 
     @staticmethod
     def forward(ctx, qkv: Tensor, bias, module, lengths):
@@ -291,46 +292,46 @@ class _FusedAttention(torch.autograd.Function):
             table = table.detach().to(torch.float32).contiguous()
         ctx.call = dict(num_heads=module.num_heads, scale=module.scale_for(d), causal=module.causal, num_kv_heads=module.kv_heads,
                         lengths=lengths, window=module.window, softcap=module.softcap)
-        out = kernels.attention_forward(qkv, bias=table, **ctx.call)
+        out, lse = kernels.attention_forward(qkv, bias=table, return_lse=True, **ctx.call)
         if bias is not None:   # where the distances of this batch sit in the parameter: the mapping of the extensions' rule
             ctx.columns, ctx.width, ctx.bias_dtype = module.bias_columns(T, qkv.device), bias.shape[1], bias.dtype
-        ctx.save_for_backward(qkv, out, table)
+        ctx.save_for_backward(qkv, out, lse, table)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad: Tensor):
-        qkv, out, table = ctx.saved_tensors
-        M = grad.contiguous()[None]
+        qkv, out, lse, table = ctx.saved_tensors
+        grad = grad.contiguous()
         dqkv = dbias = None
         if ctx.needs_input_grad[0]:
-            dqkv = kernels.attention_jac_t(M, qkv, out, bias=table, **ctx.call)[0]
+            dqkv = kernels.attention_backward(grad, qkv, out, lse, bias=table, **ctx.call)
         if ctx.needs_input_grad[1]:
             call = dict(ctx.call)
-            dbias = kernels.attention_bias_factor(M, qkv, out, call.pop("num_heads"), call.pop("scale"), call.pop("causal"), table,
+            dbias = kernels.attention_bias_factor(grad[None], qkv, out, call.pop("num_heads"), call.pop("scale"), call.pop("causal"), table,
                                                   index=ctx.columns, width=ctx.width, **call)[0].sum(0).to(ctx.bias_dtype)
         return dqkv, dbias, None, None
 
 
 class _FusedCrossAttention(torch.autograd.Function):
-    """``ScaledDotProductCrossAttention.attend`` as one flash-style launch (``kernels.cross_attention_forward``); the backward
-    pass is ``kernels.cross_attention_jac_t`` on the gradient as a factor of one row, for the inputs that need one (a frozen
-    memory skips its owner)."""
+    """``ScaledDotProductCrossAttention.attend`` as one flash-style launch (``kernels.cross_attention_forward``), which also returns
+    ``lse [N, H, Tq]``; the backward pass is ``kernels.cross_attention_backward`` from the saved ``out`` and ``lse``, for the inputs
+    that need a gradient (a frozen side skips its owner)."""
 
     @staticmethod
     def forward(ctx, q: Tensor, kv: Tensor, module, query_lengths, key_lengths):
         ctx.call = dict(num_heads=module.num_heads, scale=module.scale_for(module.head_dim(q, kv)), num_kv_heads=module.kv_heads,
                         query_lengths=query_lengths, key_lengths=key_lengths)
-        out = kernels.cross_attention_forward(q, kv, **ctx.call)
-        ctx.save_for_backward(q, kv, out)
+        out, lse = kernels.cross_attention_forward(q, kv, return_lse=True, **ctx.call)
+        ctx.save_for_backward(q, kv, out, lse)
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad: Tensor):
-        q, kv, out = ctx.saved_tensors
-        Gq, Gkv = kernels.cross_attention_jac_t(grad.contiguous()[None], q, kv, out, want=ctx.needs_input_grad[:2], **ctx.call)
-        return (None if Gq is None else Gq[0]), (None if Gkv is None else Gkv[0]), None, None, None
+        q, kv, out, lse = ctx.saved_tensors
+        dq, dkv = kernels.cross_attention_backward(grad, q, kv, out, lse, want=ctx.needs_input_grad[:2], **ctx.call)
+        return dq, dkv, None, None, None
 
 
 class ScaledDotProductAttention(nn.Module):
@@ -375,14 +376,16 @@ class ScaledDotProductAttention(nn.Module):
 
     ``fused_forward`` (default ``False``: the torch formula of :meth:`attend`, which allocates up to four ``[N, H, T, T]`` tensors
     and keeps one or two for autograd).  With ``True`` a HIP fp32 input with ``d <= 128`` runs the forward pass as one flash-style
-    kernel (``kernels.attention_forward``) and autograd's backward pass as the extensions' rule on the gradient
-    (``kernels.attention_jac_t``, ``kernels.attention_bias_factor`` for a learned table): the same function and the same gradients
-    to rounding, no ``T x T`` tensor in either pass, and tiles that no live pair reaches are skipped.  CPU tensors, other dtypes,
-    ``d > 128`` and sizes the kernel refuses run the torch formula unchanged.  Measured on one MI355X with 12 heads of 64
-    (profiles/attention_forward_time.log): the forward pass alone is faster with the flag at every shape measured
-    (1.3 times at T = 512, 1.4 at T = 2048, 6.8 on a causal batch with half of every sequence padded); forward + backward is SLOWER
-    with the flag on unmasked batches (0.77 of the torch path's speed at T = 512, 0.66 at T = 2048: the rule's fp32 kernels against
-    rocBLAS) and 3.2 times faster on the half-padded causal batch; its peak memory at T = 2048 is 120 MiB instead of 3.1 GiB."""
+    kernel (``kernels.attention_forward``), which keeps its row log-sum-exp (``N H T`` floats), and autograd's backward pass as the
+    one-row kernels that reuse it (``kernels.attention_backward``; ``kernels.attention_bias_factor`` for a learned table): the same
+    function and the same gradients to rounding, no ``T x T`` tensor in either pass, and tiles that no live pair reaches are
+    skipped.  CPU tensors, other dtypes, ``d > 128`` and sizes the kernel refuses run the torch formula unchanged.  Measured on one
+    MI355X with 12 heads of 64 (profiles/attention_forward_time.log, profiles/attention_backward_time.log): the
+    forward pass alone is faster with the flag at every shape measured (1.3 times at T = 512, 1.4 at T = 2048, 6.8 on a causal batch
+    with half of every sequence padded); forward + backward is level with the torch formula on unmasked batches (1.08 times its
+    speed at T = 512, 0.97 at T = 2048) and 4.6 times faster on the half-padded causal batch, but at 32 heads of 128 and T = 2048 it
+    runs at 0.47 of the torch path's speed (fp32 MFMAs against rocBLAS); its peak memory at T = 2048 is about 120 MiB instead of
+    3.1 GiB."""
 
     def __init__(self, num_heads: int, causal: bool = False, scale: float = None, num_kv_heads: int = None, window: int = None,
                  softcap: float = None, bias: Tensor = None, learn_bias: bool = False, bias_index: Tensor = None,

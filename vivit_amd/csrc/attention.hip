@@ -111,26 +111,6 @@ __device__ __forceinline__ void att_load_factor(float *__restrict__ sdO, float *
     }
 }
 
-// one wave's 16 x 16 part of P = exp(S - lse) for the tile (query block at i0, key block at j0); zero where masked or beyond Tn
-// (`visible(r, c)`: att_valid of the pair at row r and column c of the tile, in whatever form the owner keeps it).  `w`: the weight
-// of (dP - D) in dZ, P itself without a cap; `brow`, `dj0 = j0 - i0`: the head's table row and the tile's distance for att_logit
-template <int NT, class Mod, class Visible>
-__device__ __forceinline__ att_f32x4 att_p_tile(const float *__restrict__ sQ, const float *__restrict__ sK, const float *__restrict__ sL,
-                                                float scale, int dk, int lane, int ri, int cj, const Mod &mod,
-                                                const float *__restrict__ brow, int dj0, att_f32x4 &w, Visible visible) {
-  using C = AttCfg<NT>;
-  const att_f32x4 s = att_tile_nt<NT>(sQ + 16 * ri * C::LD, sK + 16 * cj * C::LD, dk, lane);
-  att_f32x4 p;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int r = 16 * ri + 4 * (lane >> 4) + e, c = 16 * cj + (lane & 15);
-    float keep = 1.f;
-    p[e] = visible(r, c) ? expf(att_logit(mod, s[e], scale, brow, dj0 + c - r, keep) - sL[r]) : 0.f;
-    w[e] = att_dz_weight(mod, p[e], keep);
-  }
-  return p;
-}
-
 // ---- key-block owner: dK and dV ---------------------------------------------------------------------------------------------------
 template <int NT, class Geo, class Mod>
 __global__ __launch_bounds__(256) void attn_dkv_kernel(const float *__restrict__ M, const float *__restrict__ qkv,

@@ -1,5 +1,5 @@
 // What the attention translation units share (attention.hip: head dimensions up to 128; attention_wide.hip: 129 to 256;
-// attention_forward.hip: the forward pass, up to 128): the tile
+// attention_forward.hip: the forward pass, up to 128; attention_backward.hip: its gradient from the saved lse, up to 128): the tile
 // configuration, the LDS block loader and the MFMA tile products, the two geometries with their mask and block-range helpers, the
 // score function, the row log-sum-exp and row-dot kernels, and the host plan.  The contract they serve stands at the head of
 // attention.hip.
@@ -208,6 +208,33 @@ __device__ __forceinline__ float att_logit(const AttScoreMod &m, float qk, float
 // the weight of (dP - D) in dZ
 __device__ __forceinline__ float att_dz_weight(const AttPlain &, float p, float) { return p; }
 __device__ __forceinline__ float att_dz_weight(const AttScoreMod &, float p, float keep) { return p * keep; }
+
+// one wave's 16 x 16 part of P = exp(S - lse) for the tile (query block at i0, key block at j0), from its part `s` of the products
+// q_i k_j; zero where masked or beyond Tn (`visible(r, c)`: att_valid of the pair at row r and column c of the tile, in whatever
+// form the owner keeps it).  `w`: the weight of (dP - D) in dZ, P itself without a cap; `brow`, `dj0 = j0 - i0`: the head's table
+// row and the tile's distance for att_logit; sL: lse of the block's 32 queries
+template <class Mod, class Visible>
+__device__ __forceinline__ att_f32x4 att_p_of(const att_f32x4 &s, const float *__restrict__ sL, float scale, int lane, int ri, int cj,
+                                              const Mod &mod, const float *__restrict__ brow, int dj0, att_f32x4 &w, Visible visible) {
+  att_f32x4 p;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int r = 16 * ri + 4 * (lane >> 4) + e, c = 16 * cj + (lane & 15);
+    float keep = 1.f;
+    p[e] = visible(r, c) ? expf(att_logit(mod, s[e], scale, brow, dj0 + c - r, keep) - sL[r]) : 0.f;
+    w[e] = att_dz_weight(mod, p[e], keep);
+  }
+  return p;
+}
+// the same with the product: sQ, sK the [32][LD] blocks of the queries and the keys (the owners of attention.hip)
+template <int NT, class Mod, class Visible>
+__device__ __forceinline__ att_f32x4 att_p_tile(const float *__restrict__ sQ, const float *__restrict__ sK, const float *__restrict__ sL,
+                                                float scale, int dk, int lane, int ri, int cj, const Mod &mod,
+                                                const float *__restrict__ brow, int dj0, att_f32x4 &w, Visible visible) {
+  using C = AttCfg<NT>;
+  const att_f32x4 s = att_tile_nt<NT>(sQ + 16 * ri * C::LD, sK + 16 * cj * C::LD, dk, lane);
+  return att_p_of(s, sL, scale, lane, ri, cj, mod, brow, dj0, w, visible);
+}
 
 // ---- row log-sum-exp --------------------------------------------------------------------------------------------------------------
 template <int NT, class Geo, class Mod>

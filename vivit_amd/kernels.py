@@ -990,6 +990,80 @@ def cross_attention_forward(q, kv, num_heads: int, scale: float, num_kv_heads: i
     return (out, lse) if return_lse else out
 
 
+def _saved_lse(lse, N, H, T, device):
+    """The forward's ``lse``, checked: float32 ``[N, H, T]`` on ``device``, contiguous."""
+    _require_device(lse)
+    if lse.dtype != torch.float32 or lse.device != device or tuple(lse.shape) != (N, H, T):
+        raise ValueError(f"lse must be a float32 tensor {(N, H, T)} on {device}, got {lse.dtype} {tuple(lse.shape)} on {lse.device}")
+    return lse.contiguous()
+
+
+@_launcher
+def attention_backward(dout, qkv, out, lse, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None,
+                       window: int = None, softcap: float = None, bias=None):
+    """The gradient of :func:`attention_forward` from what it saved (``vivit_attention_backward_f32``, csrc/attention_backward.hip):
+    ``dout [N, T, num_heads * d]`` (the gradient at the output), ``qkv``, and ``out``, ``lse [N, num_heads, T]`` as
+    ``attention_forward(..., return_lse=True)`` returned them -> ``dqkv`` like ``qkv``, packed ``dQ | dK | dV``.  Every other argument
+    is the forward's.  Two launches built for one row (:func:`attention_jac_t` serves ``V >= 2`` factor rows and recomputes ``lse``); the
+    workspace is ``N * num_heads * T`` floats, no ``T x T`` tensor is allocated, the rows of dead positions are exact zeros and what
+    any operand holds there is never read.  ``d > 128`` raises ``VIVIT_E_UNSUPPORTED``."""
+    M, qkv, out, lengths, softcap, bias, (Hkv, N, T, d, _, _) = _attention_self_operands(dout[None], qkv, out, num_heads, num_kv_heads, lengths,
+                                                                                        window, softcap, bias)
+    lse = _saved_lse(lse, N, num_heads, T, M.device)
+    dqkv = torch.empty_like(qkv)
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    lib = _lib.load()
+    ws, ws_bytes = _workspace(lib.vivit_attention_backward_f32_workspace_bytes(N, T, num_heads, Hkv, d), M)
+    st = lib.vivit_attention_backward_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), N, T, num_heads,
+                                          Hkv, d, float(scale), int(bool(causal)), ptr(lengths), 0 if window is None else int(window),
+                                          0.0 if softcap is None else softcap, ptr(bias), ws, ws_bytes, _stream(M))
+    _lib.check(st, "vivit_attention_backward_f32")
+    return dqkv
+
+
+@_launcher
+def cross_attention_backward(dout, q, kv, out, lse, num_heads: int, scale: float, num_kv_heads: int = None, query_lengths=None,
+                             key_lengths=None, want=(True, True)):
+    """The gradients of :func:`cross_attention_forward` from what it saved (``vivit_attention_cross_backward_f32``):
+    ``dout [N, Tq, num_heads * d]``, ``q``, ``kv``, and ``out``, ``lse [N, num_heads, Tq]`` as the forward returned them ->
+    ``(dq like q, dkv like kv)``, ``dkv`` packed ``dK | dV``.  ``want``: which of the two to compute; the other is ``None`` and its
+    kernel is not launched, and the bytes of the one computed do not depend on it.  Every other argument and every promise is that
+    of :func:`cross_attention_jac_t` and :func:`attention_backward`."""
+    _require_device(dout, q, kv, out)
+    want = tuple(bool(w) for w in want)
+    if len(want) != 2 or not any(want):
+        raise ValueError(f"want must name at least one of (dq, dkv), got {want!r}")
+    N0 = q.shape[0] if q.dim() == 3 else None
+    if query_lengths is not None:
+        query_lengths = _device_lengths(query_lengths, "query_lengths", N0, dout.device)
+    if key_lengths is not None:
+        key_lengths = _device_lengths(key_lengths, "key_lengths", N0, dout.device)
+    dout, q, kv, out = dout.contiguous(), q.contiguous(), kv.contiguous(), out.contiguous()
+    Hkv, _ = _packed_heads(num_heads, num_kv_heads)
+    if q.dim() != 3 or num_heads < 1 or q.shape[2] == 0 or q.shape[2] % num_heads != 0:
+        raise ValueError(f"q must be [N, Tq, {num_heads} * d], got {tuple(q.shape)}")
+    N, Tq, E = q.shape
+    d = E // num_heads
+    if kv.dim() != 3 or kv.shape[0] != N or kv.shape[2] != 2 * Hkv * d:
+        raise ValueError(f"kv must be [{N}, Tk, 2 * {Hkv} * {d}], got {tuple(kv.shape)}")
+    Tk = kv.shape[1]
+    if tuple(out.shape) != (N, Tq, E) or tuple(dout.shape) != (N, Tq, E):
+        raise ValueError(f"out and dout must be {(N, Tq, E)}, got {tuple(out.shape)} and {tuple(dout.shape)}")
+    if N == 0 or Tq == 0 or Tk == 0:
+        raise ValueError(f"empty operands: q {tuple(q.shape)}, kv {tuple(kv.shape)}")
+    lse = _saved_lse(lse, N, num_heads, Tq, dout.device)
+    dq = torch.empty_like(q) if want[0] else None
+    dkv = torch.empty_like(kv) if want[1] else None
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    lib = _lib.load()
+    ws, ws_bytes = _workspace(lib.vivit_attention_cross_backward_f32_workspace_bytes(N, Tq, Tk, num_heads, Hkv, d), dout)
+    st = lib.vivit_attention_cross_backward_f32(dout.data_ptr(), q.data_ptr(), kv.data_ptr(), out.data_ptr(), lse.data_ptr(), ptr(dq),
+                                                ptr(dkv), N, Tq, Tk, num_heads, Hkv, d, float(scale), ptr(query_lengths),
+                                                ptr(key_lengths), ws, ws_bytes, _stream(dout))
+    _lib.check(st, "vivit_attention_cross_backward_f32")
+    return dq, dkv
+
+
 _I32_MAX = 2 ** 31 - 1
 
 
