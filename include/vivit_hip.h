@@ -514,6 +514,25 @@ int vivit_attention_cross_backward_f32(const float *dout, const float *q, const 
                                        float *dq, float *dkv, int64_t N, int64_t Tq, int64_t Tk, int64_t H, int64_t Hkv, int64_t d,
                                        float scale, const int32_t *q_lengths, const int32_t *k_lengths, void *workspace,
                                        size_t workspace_bytes, void *stream);
+/* The forward and the backward pass of SELF-attention for head dimensions 128 < d <= 256 (attention_wide_forward.hip,
+ * attention_wide_backward.hip; call sites vivit_amd/kernels.py:attention_wide_forward and attention_wide_backward, for
+ * ScaledDotProductAttention and MultiheadSelfAttention built with fused_forward=True): the arguments, their meaning, the results,
+ * the workspace (backward: D [N, H, T] floats and nothing else; forward: none), the contract and the order of the refusals of
+ * vivit_attention_forward_f32 and vivit_attention_backward_f32, with owners that keep their resident operand in LDS at full width
+ * and stream the others in column halves of 128 (attention_wide.hip).  Every logit has the bits the wide rule's lse launch gives it.
+ * One summation order, no atomics, no T x T data in memory; no operand row of a dead position is loaded (lse and D there are never
+ * read) and the rows of dead positions are +0 in out, lse and dqkv; a padded sample has the bytes of the sample cut to its length
+ * and run alone.  d <= 128 (the entries above) and d > 256: VIVIT_E_UNSUPPORTED, before the workspace is looked at, and the
+ * workspace query returns 0.  There is no cross-attention entry and no learned-table factor at this width: those modules keep the
+ * torch formula for d > 128. */
+int vivit_attention_wide_forward_f32(const float *qkv, float *out, float *lse, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d,
+                                     float scale, int causal, const int32_t *lengths, int64_t window, float softcap, const float *bias,
+                                     void *stream);
+size_t vivit_attention_wide_backward_f32_workspace_bytes(int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d);
+int vivit_attention_wide_backward_f32(const float *dout, const float *qkv, const float *out, const float *lse, float *dqkv, int64_t N,
+                                      int64_t T, int64_t H, int64_t Hkv, int64_t d, float scale, int causal, const int32_t *lengths,
+                                      int64_t window, float softcap, const float *bias, void *workspace, size_t workspace_bytes,
+                                      void *stream);
 /* nn.Embedding (embedding.hip; the reference has no rule for it): the weight factor Vt[v, n, w, :] = sum_{t: idx[n, t] = w} M[v, n, t, :]
  * of the factor M [V, N, T, D] at the module output has at most T non-zero rows per (v, n) out of W = num_embeddings and is kept
  * compact: ids [N, T] int32 holds sample n's distinct tokens in strictly increasing order in its first U_n slots and -1 in the rest,

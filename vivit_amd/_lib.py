@@ -77,6 +77,9 @@ SIGNATURES = {
     "vivit_attention_backward_f32": (_int, [_ptr] * 5 + [_i64] * 5 + [_f32, _int, _ptr, _i64, _f32, _ptr, _ptr, _sz, _ptr]),
     "vivit_attention_cross_backward_f32_workspace_bytes": (_sz, [_i64] * 6),
     "vivit_attention_cross_backward_f32": (_int, [_ptr] * 7 + [_i64] * 6 + [_f32, _ptr, _ptr, _ptr, _sz, _ptr]),
+    "vivit_attention_wide_forward_f32": (_int, [_ptr, _ptr, _ptr] + [_i64] * 5 + [_f32, _int, _ptr, _i64, _f32, _ptr, _ptr]),
+    "vivit_attention_wide_backward_f32_workspace_bytes": (_sz, [_i64] * 5),
+    "vivit_attention_wide_backward_f32": (_int, [_ptr] * 5 + [_i64] * 5 + [_f32, _int, _ptr, _i64, _f32, _ptr, _ptr, _sz, _ptr]),
     "vivit_embedding_compact_f32":(_int, [_ptr] * 5 + [_i64] * 4 + [_ptr]),
     "vivit_embedding_gram_f32_workspace_bytes": (_sz, [_i64] * 4),
     "vivit_embedding_gram_f32": (_int, [_ptr, _ptr, _ptr] + [_i64] * 4 + [_f32, _f32, _ptr, _sz, _ptr]),

@@ -271,18 +271,20 @@ def alibi_bias(num_heads: int, max_len: int) -> Tensor:
     return (-alibi_slopes(num_heads)[:, None] * dist[None, :]).to(torch.float32)
 
 
-def _fused_forward_applies(flag: bool, d: int, *tensors: Tensor) -> bool:
+def _fused_forward_applies(flag: bool, d: int, *tensors: Tensor, d_max: int = 128) -> bool:
     """Whether a module built with ``fused_forward=flag`` takes the flash-style kernel for these inputs: HIP fp32 tensors and a
-    head dimension the kernel has (sizes beyond its index arithmetic come back as VIVIT_E_UNSUPPORTED from the call itself)."""
-    return flag and d <= 128 and all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
+    head dimension the kernel has (``d_max``: 256 for self-attention without a learned table, whose wide kernels serve 129 to 256);
+    sizes beyond its index arithmetic come back as VIVIT_E_UNSUPPORTED from the call itself."""
+    return flag and d <= d_max and all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
 
 
 class _FusedAttention(torch.autograd.Function):
     """``ScaledDotProductAttention.attend`` as ONE flash-style launch (``kernels.attention_forward``), which also returns the row
     log-sum-exp ``lse [N, H, T]``; the backward pass is the one-row kernels that reuse it (``kernels.attention_backward``; for a
     learned table the extensions' rule on the gradient as a factor of one row, ``kernels.attention_bias_factor``, summed over the
-    samples): no ``T x T`` tensor is allocated in either pass.  ``bias``: the learned table (the parameter, so that autograd
-    reaches it) or ``None``; a constant table and the lengths get no gradient."""
+    samples): no ``T x T`` tensor is allocated in either pass.  Head dimensions 129 to 256 take the wide pair
+    (``kernels.attention_wide_forward``, ``kernels.attention_wide_backward``; there is no learned table at that width).  ``bias``:
+    the learned table (the parameter, so that autograd reaches it) or ``None``; a constant table and the lengths get no gradient."""
 
     @staticmethod
     def forward(ctx, qkv: Tensor, bias, module, lengths):
@@ -292,7 +294,8 @@ class _FusedAttention(torch.autograd.Function):
             table = table.detach().to(torch.float32).contiguous()
         ctx.call = dict(num_heads=module.num_heads, scale=module.scale_for(d), causal=module.causal, num_kv_heads=module.kv_heads,
                         lengths=lengths, window=module.window, softcap=module.softcap)
-        out, lse = kernels.attention_forward(qkv, bias=table, return_lse=True, **ctx.call)
+        ctx.wide = d > 128
+        out, lse = (kernels.attention_wide_forward if ctx.wide else kernels.attention_forward)(qkv, bias=table, return_lse=True, **ctx.call)
         if bias is not None:   # where the distances of this batch sit in the parameter: the mapping of the extensions' rule
             ctx.columns, ctx.width, ctx.bias_dtype = module.bias_columns(T, qkv.device), bias.shape[1], bias.dtype
         ctx.save_for_backward(qkv, out, lse, table)
@@ -305,7 +308,7 @@ class _FusedAttention(torch.autograd.Function):
         grad = grad.contiguous()
         dqkv = dbias = None
         if ctx.needs_input_grad[0]:
-            dqkv = kernels.attention_backward(grad, qkv, out, lse, bias=table, **ctx.call)
+            dqkv = (kernels.attention_wide_backward if ctx.wide else kernels.attention_backward)(grad, qkv, out, lse, bias=table, **ctx.call)
         if ctx.needs_input_grad[1]:
             call = dict(ctx.call)
             dbias = kernels.attention_bias_factor(grad[None], qkv, out, call.pop("num_heads"), call.pop("scale"), call.pop("causal"), table,
@@ -379,13 +382,19 @@ class ScaledDotProductAttention(nn.Module):
     kernel (``kernels.attention_forward``), which keeps its row log-sum-exp (``N H T`` floats), and autograd's backward pass as the
     one-row kernels that reuse it (``kernels.attention_backward``; ``kernels.attention_bias_factor`` for a learned table): the same
     function and the same gradients to rounding, no ``T x T`` tensor in either pass, and tiles that no live pair reaches are
-    skipped.  CPU tensors, other dtypes, ``d > 128`` and sizes the kernel refuses run the torch formula unchanged.  Measured on one
+    skipped.  Head dimensions 129 to 256 take kernels of their own (``kernels.attention_wide_forward``,
+    ``kernels.attention_wide_backward``: the resident operand in LDS at full width, the others streamed in column halves) unless the
+    table is learned (``learn_bias=True``: its factor kernel stops at 128).  CPU tensors, other dtypes, ``d > 256``, ``d > 128`` with a
+    learned table and sizes the kernel refuses run the torch formula unchanged.  Measured on one
     MI355X with 12 heads of 64 (profiles/attention_forward_time.log, profiles/attention_backward_time.log): the
     forward pass alone is faster with the flag at every shape measured (1.3 times at T = 512, 1.4 at T = 2048, 6.8 on a causal batch
     with half of every sequence padded); forward + backward is level with the torch formula on unmasked batches (1.08 times its
     speed at T = 512, 0.97 at T = 2048) and 4.6 times faster on the half-padded causal batch, but at 32 heads of 128 and T = 2048 it
     runs at 0.47 of the torch path's speed (fp32 MFMAs against rocBLAS); its peak memory at T = 2048 is about 120 MiB instead of
-    3.1 GiB."""
+    3.1 GiB.  At 8 heads of 256 or 192 (profiles/attention_wide_fused_time.log) the fused forward pass alone is the slower one on
+    unmasked batches (0.54 to 0.83 of the torch formula's speed) and 3.0 times faster on the half-padded causal batch; forward +
+    backward runs at 0.26 to 0.46 of the torch path's speed unmasked and 1.3 times faster on the padded batch, with a peak of
+    128 MiB instead of 1.1 GiB at T = 2048: at this width the flag buys memory, not time."""
 
     def __init__(self, num_heads: int, causal: bool = False, scale: float = None, num_kv_heads: int = None, window: int = None,
                  softcap: float = None, bias: Tensor = None, learn_bias: bool = False, bias_index: Tensor = None,
@@ -514,7 +523,7 @@ class ScaledDotProductAttention(nn.Module):
         """The forward pass with explicit ``lengths`` (int32 ``[N]`` on the device of ``qkv``, or ``None``)."""
         d = self.head_dim(qkv)
         N, T, H = qkv.shape[0], qkv.shape[1], self.num_heads
-        if _fused_forward_applies(self.fused_forward, d, qkv):
+        if _fused_forward_applies(self.fused_forward, d, qkv, d_max=128 if self.learn_bias else 256):
             try:
                 return _FusedAttention.apply(qkv, self.bias if self.learn_bias else None, self, lengths)
             except _lib.VivitHipError as exc:   # a shape beyond the kernel's launch limits: the formula below
@@ -673,7 +682,8 @@ class ScaledDotProductCrossAttention(nn.Module):
 
     ``fused_forward`` (default ``False``) is that of :class:`ScaledDotProductAttention`: a HIP fp32 forward pass with ``d <= 128``
     as one flash-style kernel (``kernels.cross_attention_forward``), autograd's backward pass as ``kernels.cross_attention_jac_t``
-    for the inputs that need a gradient, no ``Tq x Tk`` tensor in either pass; everything else runs the torch formula."""
+    for the inputs that need a gradient, no ``Tq x Tk`` tensor in either pass; everything else runs the torch formula (cross-attention
+    has no kernels for ``d > 128``: the wide pair of :class:`ScaledDotProductAttention` is self-attention only)."""
 
     def __init__(self, num_heads: int, scale: float = None, num_kv_heads: int = None, fused_forward: bool = False):
         super().__init__()

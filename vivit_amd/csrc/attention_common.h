@@ -1,5 +1,6 @@
 // What the attention translation units share (attention.hip: head dimensions up to 128; attention_wide.hip: 129 to 256;
-// attention_forward.hip: the forward pass, up to 128; attention_backward.hip: its gradient from the saved lse, up to 128): the tile
+// attention_forward.hip: the forward pass, up to 128; attention_backward.hip: its gradient from the saved lse, up to 128;
+// attention_wide_forward.hip and attention_wide_backward.hip: the same two for 129 to 256, through attention_wide_common.h): the tile
 // configuration, the LDS block loader and the MFMA tile products, the two geometries with their mask and block-range helpers, the
 // score function, the row log-sum-exp and row-dot kernels, and the host plan.  The contract they serve stands at the head of
 // attention.hip.

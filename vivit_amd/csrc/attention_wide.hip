@@ -23,58 +23,15 @@
 // LDS (VC = 2): key owner 2 x 33 280 (K, V) + 16 896 (Q half) + 2 x 16 896 (dO halves) + 3 x 4 608 (P, dS) + 384 = 131 456 bytes;
 // query owner 3 x 33 280 (Q, dO) + 2 x 16 896 (K, V halves) + 2 x 4 608 (dS) + 384 = 143 232 bytes: one workgroup of four waves
 // per CU either way.
-#include "attention_common.h"
+#include "attention_wide_common.h"
 
 namespace vivit {
 
-constexpr int ATT_WIDE_D_MIN = 129, ATT_WIDE_D_MAX = 256;
-constexpr int ATT_WIDE_HALF = 128;   // columns of a half
-using AttWF = AttCfg<16>;            // a block at full width
-using AttWH = AttCfg<8>;             // a column half of a block
 constexpr int ATT_WIDE_VC = AttWF::VC;
 static_assert(ATT_WIDE_VC == 2 && AttWH::VC == ATT_WIDE_VC && AttWH::DP == ATT_WIDE_HALF && AttWH::TPW == 4, "the halves of the wide owners");
 constexpr int ATT_WIDE_DKV_FLOATS = 2 * AttWF::BLK + (1 + ATT_WIDE_VC) * AttWH::BLK + (1 + ATT_WIDE_VC) * AttWF::TILE + ATT_B + ATT_WIDE_VC * ATT_B;
 constexpr int ATT_WIDE_DQ_FLOATS = (1 + ATT_WIDE_VC) * AttWF::BLK + 2 * AttWH::BLK + ATT_WIDE_VC * AttWF::TILE + ATT_B + ATT_WIDE_VC * ATT_B;
 static_assert(ATT_WIDE_DKV_FLOATS * 4 <= 160 * 1024 && ATT_WIDE_DQ_FLOATS * 4 <= 160 * 1024, "a CU has 160 KB of LDS");
-
-// att_tile_nt over nc columns (a multiple of 4) of one half, its two chains carried by the caller: A in a block of pitch LDA, B in a
-// block of pitch LDB, both at the half's first column.  After half 0 (nc = 128) and half 1 (nc = dk - 128), acc0 + acc1 has the
-// bits of att_tile_nt<16> over dk columns.
-template <int LDA, int LDB>
-__device__ __forceinline__ void att_wide_tile_nt(const float *__restrict__ A, const float *__restrict__ B, int nc, int lane,
-                                                 att_f32x4 &acc0, att_f32x4 &acc1) {
-  const float *a = A + (lane & 15) * LDA + (lane >> 4), *b = B + (lane & 15) * LDB + (lane >> 4);
-  int c = 0;
-  for (; c + 8 <= nc; c += 8) {
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], b[c], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c + 4], b[c + 4], acc1, 0, 0, 0);
-  }
-  if (c < nc) acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c], b[c], acc0, 0, 0, 0);
-}
-
-// The same product for the dP tiles, in FOUR interleaved chains (step c / 4 into chain (c / 4) mod 4, at the end (0 + 1) + (2 + 3)): dS =
-// P o (dP - D) subtracts two sums over up to 256 columns that nearly cancel, so what is left of them carries their rounding errors
-// at full size; four chains of at most 16 steps over partial sums a quarter as large halve the error of two chains of 32.  dP is
-// compared with nothing (S is: its two chains are those of the lse launch), and 128 = 32 steps, so half 1 starts at chain 0 again.
-template <int LDA, int LDB>
-__device__ __forceinline__ void att_wide_tile_nt4(const float *__restrict__ A, const float *__restrict__ B, int nc, int lane,
-                                                  att_f32x4 (&acc)[4]) {
-  const float *a = A + (lane & 15) * LDA + (lane >> 4), *b = B + (lane & 15) * LDB + (lane >> 4);
-  int c = 0;
-  for (; c + 16 <= nc; c += 16) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c + 4 * u], b[c + 4 * u], acc[u], 0, 0, 0);
-  }
-#pragma unroll
-  for (int u = 0; u < 3; ++u)
-    if (c + 4 * u < nc) acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[c + 4 * u], b[c + 4 * u], acc[u], 0, 0, 0);
-}
-
-// columns 128 half .. of rows r0 .. r0 + 31 of a [T][stride] matrix -> dst[32][132]; rows beyond T and columns beyond d are zero
-__device__ __forceinline__ void att_wide_load_half(float *__restrict__ dst, const float *__restrict__ src, int64_t stride, int r0, int T,
-                                                   int d, bool vec, int half) {
-  att_load_block<8>(dst, src + ATT_WIDE_HALF * half, stride, r0, T, d - ATT_WIDE_HALF * half, vec);
-}
 
 // half `half` of the dO blocks of the workgroup's factor rows for the query block at i0
 __device__ __forceinline__ void att_wide_load_factor_half(float *__restrict__ sdO, const float *__restrict__ M, const AttGeom &g, int Tn,
@@ -333,12 +290,6 @@ __global__ __launch_bounds__(256) void attn_wide_dq_kernel(const float *__restri
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static AttPlan attention_wide_plan(int64_t V, int64_t N, int64_t T, int64_t H, int64_t Hkv, int64_t d) {
-  AttPlan p = attention_plan(V, N, T, H, Hkv, d, ATT_WIDE_D_MAX);
-  if (p.status == VIVIT_OK && d < ATT_WIDE_D_MIN) p.status = VIVIT_E_UNSUPPORTED;   // (the narrow entries' head dimensions)
-  return p;
-}
-
 template <class Mod>
 static int attention_wide_launch(const float *M, const float *qkv, const float *out, float *G, float *lse, float *Dws, int64_t V,
                                  const AttGeom &g, const Mod &mod, hipStream_t s) {

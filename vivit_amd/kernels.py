@@ -928,15 +928,8 @@ def cross_attention_jac_t(M, q, kv, out, num_heads: int, scale: float, num_kv_he
     return Gq, Gkv
 
 
-@_launcher
-def attention_forward(qkv, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None, window: int = None,
-                      softcap: float = None, bias=None, return_lse: bool = False):
-    """The forward pass of scaled dot-product self-attention in one flash-style launch (``vivit_attention_forward_f32``,
-    csrc/attention_forward.hip): ``qkv [N, T, (num_heads + 2 * Hkv) * d]`` -> ``out [N, T, num_heads * d]``, and with ``return_lse``
-    ``(out, lse [N, num_heads, T])``, the row log-sum-exp of the logits (the bytes of ``out`` are the same either way).  Every
-    argument is that of :func:`attention_jac_t`, whose function this is; no ``T x T`` tensor and no workspace is allocated, the rows
-    of dead positions are exact zeros (in ``lse`` too) and what ``qkv`` holds there is never read.  ``d > 128`` raises
-    ``VIVIT_E_UNSUPPORTED``."""
+def _self_forward(entry, qkv, num_heads, scale, causal, num_kv_heads, lengths, window, softcap, bias, return_lse):
+    """The checks and the call of :func:`attention_forward` and :func:`attention_wide_forward`, whose entries take the same arguments."""
     _require_device(qkv)
     Hkv, _ = _packed_heads(num_heads, num_kv_heads)
     heads = num_heads + 2 * Hkv
@@ -949,11 +942,34 @@ def attention_forward(qkv, num_heads: int, scale: float, causal: bool, num_kv_he
                                                                                       window, softcap, bias)
     lse = torch.empty((N, num_heads, T), dtype=torch.float32, device=qkv.device) if return_lse else None
     ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-    st = _lib.load().vivit_attention_forward_f32(qkv.data_ptr(), out.data_ptr(), ptr(lse), N, T, num_heads, Hkv, d, float(scale),
-                                                 int(bool(causal)), ptr(lengths), 0 if window is None else int(window),
-                                                 0.0 if softcap is None else softcap, ptr(bias), _stream(qkv))
-    _lib.check(st, "vivit_attention_forward_f32")
+    st = getattr(_lib.load(), entry)(qkv.data_ptr(), out.data_ptr(), ptr(lse), N, T, num_heads, Hkv, d, float(scale), int(bool(causal)),
+                                     ptr(lengths), 0 if window is None else int(window), 0.0 if softcap is None else softcap, ptr(bias),
+                                     _stream(qkv))
+    _lib.check(st, entry)
     return (out, lse) if return_lse else out
+
+
+@_launcher
+def attention_forward(qkv, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None, window: int = None,
+                      softcap: float = None, bias=None, return_lse: bool = False):
+    """The forward pass of scaled dot-product self-attention in one flash-style launch (``vivit_attention_forward_f32``,
+    csrc/attention_forward.hip): ``qkv [N, T, (num_heads + 2 * Hkv) * d]`` -> ``out [N, T, num_heads * d]``, and with ``return_lse``
+    ``(out, lse [N, num_heads, T])``, the row log-sum-exp of the logits (the bytes of ``out`` are the same either way).  Every
+    argument is that of :func:`attention_jac_t`, whose function this is; no ``T x T`` tensor and no workspace is allocated, the rows
+    of dead positions are exact zeros (in ``lse`` too) and what ``qkv`` holds there is never read.  ``d > 128`` raises
+    ``VIVIT_E_UNSUPPORTED`` (129 to 256: :func:`attention_wide_forward`)."""
+    return _self_forward("vivit_attention_forward_f32", qkv, num_heads, scale, causal, num_kv_heads, lengths, window, softcap, bias, return_lse)
+
+
+@_launcher
+def attention_wide_forward(qkv, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None, window: int = None,
+                           softcap: float = None, bias=None, return_lse: bool = False):
+    """:func:`attention_forward` for head dimensions ``128 < d <= 256`` (``vivit_attention_wide_forward_f32``,
+    csrc/attention_wide_forward.hip): the same arguments, results and promises, from a kernel that keeps ``q`` in LDS at full width
+    and streams ``k`` and ``v`` in column halves of 128.  Every logit has the bits :func:`attention_wide_jac_t` recomputes.  Any other
+    head dimension raises ``VIVIT_E_UNSUPPORTED``."""
+    return _self_forward("vivit_attention_wide_forward_f32", qkv, num_heads, scale, causal, num_kv_heads, lengths, window, softcap, bias,
+                         return_lse)
 
 
 @_launcher
@@ -998,6 +1014,22 @@ def _saved_lse(lse, N, H, T, device):
     return lse.contiguous()
 
 
+def _self_backward(entry, dout, qkv, out, lse, num_heads, scale, causal, num_kv_heads, lengths, window, softcap, bias):
+    """The checks and the call of :func:`attention_backward` and :func:`attention_wide_backward`, whose entries take the same arguments."""
+    M, qkv, out, lengths, softcap, bias, (Hkv, N, T, d, _, _) = _attention_self_operands(dout[None], qkv, out, num_heads, num_kv_heads, lengths,
+                                                                                        window, softcap, bias)
+    lse = _saved_lse(lse, N, num_heads, T, M.device)
+    dqkv = torch.empty_like(qkv)
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    lib = _lib.load()
+    ws, ws_bytes = _workspace(getattr(lib, entry + "_workspace_bytes")(N, T, num_heads, Hkv, d), M)
+    st = getattr(lib, entry)(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), N, T, num_heads, Hkv, d,
+                             float(scale), int(bool(causal)), ptr(lengths), 0 if window is None else int(window),
+                             0.0 if softcap is None else softcap, ptr(bias), ws, ws_bytes, _stream(M))
+    _lib.check(st, entry)
+    return dqkv
+
+
 @_launcher
 def attention_backward(dout, qkv, out, lse, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None,
                        window: int = None, softcap: float = None, bias=None):
@@ -1006,19 +1038,20 @@ def attention_backward(dout, qkv, out, lse, num_heads: int, scale: float, causal
     ``attention_forward(..., return_lse=True)`` returned them -> ``dqkv`` like ``qkv``, packed ``dQ | dK | dV``.  Every other argument
     is the forward's.  Two launches built for one row (:func:`attention_jac_t` serves ``V >= 2`` factor rows and recomputes ``lse``); the
     workspace is ``N * num_heads * T`` floats, no ``T x T`` tensor is allocated, the rows of dead positions are exact zeros and what
-    any operand holds there is never read.  ``d > 128`` raises ``VIVIT_E_UNSUPPORTED``."""
-    M, qkv, out, lengths, softcap, bias, (Hkv, N, T, d, _, _) = _attention_self_operands(dout[None], qkv, out, num_heads, num_kv_heads, lengths,
-                                                                                        window, softcap, bias)
-    lse = _saved_lse(lse, N, num_heads, T, M.device)
-    dqkv = torch.empty_like(qkv)
-    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-    lib = _lib.load()
-    ws, ws_bytes = _workspace(lib.vivit_attention_backward_f32_workspace_bytes(N, T, num_heads, Hkv, d), M)
-    st = lib.vivit_attention_backward_f32(M.data_ptr(), qkv.data_ptr(), out.data_ptr(), lse.data_ptr(), dqkv.data_ptr(), N, T, num_heads,
-                                          Hkv, d, float(scale), int(bool(causal)), ptr(lengths), 0 if window is None else int(window),
-                                          0.0 if softcap is None else softcap, ptr(bias), ws, ws_bytes, _stream(M))
-    _lib.check(st, "vivit_attention_backward_f32")
-    return dqkv
+    any operand holds there is never read.  ``d > 128`` raises ``VIVIT_E_UNSUPPORTED`` (129 to 256: :func:`attention_wide_backward`)."""
+    return _self_backward("vivit_attention_backward_f32", dout, qkv, out, lse, num_heads, scale, causal, num_kv_heads, lengths, window, softcap,
+                          bias)
+
+
+@_launcher
+def attention_wide_backward(dout, qkv, out, lse, num_heads: int, scale: float, causal: bool, num_kv_heads: int = None, lengths=None,
+                            window: int = None, softcap: float = None, bias=None):
+    """:func:`attention_backward` for head dimensions ``128 < d <= 256`` (``vivit_attention_wide_backward_f32``,
+    csrc/attention_wide_backward.hip): the gradient of :func:`attention_wide_forward` from its ``out`` and ``lse``, with the same
+    arguments, result, workspace and promises.  :func:`attention_wide_jac_t` on one row computes the same thing with two more
+    launches and three times the workspace.  Any other head dimension raises ``VIVIT_E_UNSUPPORTED``."""
+    return _self_backward("vivit_attention_wide_backward_f32", dout, qkv, out, lse, num_heads, scale, causal, num_kv_heads, lengths, window,
+                          softcap, bias)
 
 
 @_launcher
