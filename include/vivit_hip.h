@@ -249,6 +249,28 @@ int vivit_avgpool2d_jac_t_f32(const float *M, float *out, int64_t rows_planes, i
 int vivit_conv2d_jac_t_f32(const float *M, const float *weight, float *out, int64_t rows, int64_t Cin, int64_t H, int64_t W,
                            int64_t Cout, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int64_t sh, int64_t sw, int64_t ph,
                            int64_t pw, int64_t dh, int64_t dw, void *stream);
+/* Depthwise Conv2d (groups = C, Cout = C mult with mult >= 1 the channel multiplier, zero padding; depthwise.hip): both rules of
+ * the layer in one launch each, without workspace and without atomics.  All tensors contiguous fp32; a Conv1d is the one-row image
+ * H = OH = KH = 1.
+ *   vivit_dwconv2d_jac_t_f32 (input rule, rows = V N):
+ *     out[r, c, h, w] = sum_{j < mult} sum_{a, b} M[r, c mult + j, oh, ow] weight[c mult + j, 0, a, b]
+ *     with oh sh - ph + a dh = h and ow sw - pw + b dw = w;  M [rows, C mult, OH, OW], weight [C mult, 1, KH, KW], out [rows, C, H, W].
+ *     Every element of out has exactly one writer (out may be uninitialised memory); a position no window reads is written as +0.
+ *   vivit_dwconv2d_weight_mjp_f32 (weight rule, rows class-major with sample n = r % N as in vivit_conv2d_weight_mjp_f32):
+ *     V[r, c mult + j, 0, a, b] = sum_{oh, ow} M[r, c mult + j, oh, ow] x[r % N, c, oh sh - ph + a dh, ow sw - pw + b dw]
+ *     x [N, C, H, W], V [rows, C mult KH KW].
+ * The summation order of an element is fixed by the arguments (head of depthwise.hip): the bytes of a result depend on the
+ * arguments and the data only.  Status, all before any launch: VIVIT_E_BADARG for a negative rows, a non-positive size, stride or
+ * dilation, a negative padding, a null operand (rows > 0), or an OH / OW beyond what the geometry admits ((OH - 1) sh + (KH - 1) dh
+ * - ph >= H + ph); rows == 0: VIVIT_OK, nothing is launched.  VIVIT_E_UNSUPPORTED for KH KW > 128 (ConvNeXt's 49, 9 x 9 and 11 x 11
+ * are served), a size above 2^30, a plane (H W or OH OW) of 2^31 elements or more, and a halo ((KH - 1) dh, (KW - 1) dw) that no
+ * tile fits the 64 KB of LDS with. */
+int vivit_dwconv2d_jac_t_f32(const float *M, const float *weight, float *out, int64_t rows, int64_t C, int64_t mult, int64_t H,
+                             int64_t W, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int64_t sh, int64_t sw, int64_t ph,
+                             int64_t pw, int64_t dh, int64_t dw, void *stream);
+int vivit_dwconv2d_weight_mjp_f32(const float *M, const float *x, float *V, int64_t rows, int64_t N, int64_t C, int64_t mult,
+                                  int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int64_t sh, int64_t sw,
+                                  int64_t ph, int64_t pw, int64_t dh, int64_t dw, void *stream);
 /* out[r] = sum_l M[r, l] * (X ? X[r % rows_x, l] : 1): bias rules (sum over the spatial positions) and the BatchNorm
  * weight rule (X = normalised input of the rows_x = N * C planes, shared by the V slices). */
 int vivit_row_dot_f32(const float *M, const float *X, float *out, int64_t rows, int64_t rows_x, int64_t L, void *stream);

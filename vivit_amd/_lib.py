@@ -45,6 +45,8 @@ SIGNATURES = {
     "vivit_maxpool2d_jac_t_f32": (_int, [_ptr, _ptr, _ptr, _ptr] + [_i64] * 12 + [_ptr]),
     "vivit_avgpool2d_jac_t_f32": (_int, [_ptr, _ptr] + [_i64] * 11 + [_ptr]),
     "vivit_conv2d_jac_t_f32": (_int, [_ptr, _ptr, _ptr] + [_i64] * 15 + [_ptr]),
+    "vivit_dwconv2d_jac_t_f32": (_int, [_ptr, _ptr, _ptr] + [_i64] * 15 + [_ptr]),
+    "vivit_dwconv2d_weight_mjp_f32": (_int, [_ptr, _ptr, _ptr] + [_i64] * 16 + [_ptr]),
     "vivit_row_dot_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr]),
     "vivit_bn_eval_rules_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr]),
     "vivit_norm_stats_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _f32, _ptr]),

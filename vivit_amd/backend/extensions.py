@@ -384,12 +384,20 @@ _CONV_FN = {nn.Conv1d: F.conv1d, nn.Conv2d: F.conv2d, nn.Conv3d: F.conv3d, nn.Co
             nn.ConvTranspose2d: F.conv_transpose2d, nn.ConvTranspose3d: F.conv_transpose3d}
 
 
+def _is_depthwise(module) -> bool:
+    """A Conv1d / Conv2d that takes the depthwise kernels (csrc/depthwise.hip: both rules in one launch each)."""
+    # groups >= 4: the per-group lowering of 2 or 3 groups costs little and is pinned by tests/test_conv_family_refs_host.py
+    return (isinstance(module, (nn.Conv1d, nn.Conv2d)) and module.groups == module.in_channels and module.groups >= 4
+            and math.prod(module.kernel_size) <= kernels.DWCONV_MAX_TAPS)
+
+
 def _hip_conv_weight_factor(module, M: Tensor, x: Tensor) -> Tensor:
     """Weight rule of Conv1d/2d and ConvTranspose1d/2d (any ``groups``, zero padding) on ONE HIP kernel
-    (csrc/jacobians.hip: unfold + "vnol,nkl->vnok", patch values gathered on the fly, no im2col buffer).
+    (csrc/factors.hip: unfold + "vnol,nkl->vnok", patch values gathered on the fly, no im2col buffer).
 
     * a 1-D convolution is the 2-D one with a single row;
-    * ``groups > 1``: one launch per group on the group's channel slices (the weight's leading axis is the groups'
+    * a depthwise layer (``groups == in_channels >= 4``, at most 128 taps): one launch of the depthwise kernel;
+    * other ``groups > 1``: one launch per group on the group's channel slices (the weight's leading axis is the groups'
       output channels one after the other -- convnd.py:9-30 through BackPACK's grouped unfold);
     * a transposed convolution y = conv_transpose(x, W) is the adjoint of a convolution with the same stride / padding /
       dilation, so dL/dW[ci, co, k] = sum_q x[ci, q] M[co, q s - p + k d] is the SAME contraction with the roles swapped:
@@ -404,6 +412,9 @@ def _hip_conv_weight_factor(module, M: Tensor, x: Tensor) -> Tensor:
     else:
         ks, st, pd, dl = module.kernel_size, module.stride, module.padding, module.dilation
     V, N, G = M.shape[0], M.shape[1], module.groups
+    if _is_depthwise(module):
+        out = kernels.dwconv2d_weight_mjp(M, x, ks, st, pd, dl)
+        return out.squeeze(4) if one_d else out
     if transposed:
         coef = x.unsqueeze(0).expand(V, *x.shape).reshape(1, V * N, *x.shape[1:])     # [1, V N, Cin, Hq, Wq]
         image = M.reshape(V * N, *M.shape[2:])                                         # [V N, Cout, H', W']
@@ -865,7 +876,8 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
                                            _pair(module.padding))
     if isinstance(module, (nn.Conv2d, nn.Conv1d)) and isinstance(module.padding, tuple) and module.padding_mode == "zeros":
         # (a shape neither kernel takes comes back as VIVIT_E_UNSUPPORTED: the caller falls through to the generic rule)
-        # a Conv1d is the Conv2d with one row: same kernel; groups > 1: one launch per group on its channel slices
+        # a Conv1d is the Conv2d with one row: same kernel; depthwise layers: one launch of the depthwise kernel; other groups > 1:
+        # one launch per group on its channel slices
         one_d = isinstance(module, nn.Conv1d)
         W = module.weight.detach()
         if one_d:
@@ -875,7 +887,9 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
             hw, st, pd, dl = x.shape[2:], module.stride, module.padding, module.dilation
         G = module.groups
         Co = module.out_channels // G
-        if G == 1:
+        if _is_depthwise(module):
+            g = kernels.dwconv2d_jac_t(M, W, hw, st, pd, dl, Co)
+        elif G == 1:
             g = kernels.conv2d_jac_t(M, W, hw, st, pd, dl)
         else:
             g = torch.cat([kernels.conv2d_jac_t(M[:, :, i * Co:(i + 1) * Co].contiguous(), W[i * Co:(i + 1) * Co].contiguous(), hw, st, pd, dl)

@@ -460,6 +460,55 @@ def conv2d_jac_t(M, weight, in_hw, stride, padding, dilation):
     return out
 
 
+# csrc/depthwise.hip: lanes of a workgroup, floats of LDS of a launch and those the weight rule keeps for its folded sums, columns of
+# an input-rule tile of a one-row image (the tests place a plane one row past a tile with them; change them together with the unit)
+DWCONV_LANES, DWCONV_LDS_FLOATS, DWCONV_RED_FLOATS, DWCONV_ROW_TILE = 256, 16384, 512, 1024
+DWCONV_MAX_TAPS, DWCONV_GRID_CAP = 128, 2048   # taps served; workgroups of a launch (looped over beyond)
+
+
+@_launcher
+def dwconv2d_jac_t(M, weight, in_hw, stride, padding, dilation, multiplier=1):
+    """Transposed input-Jacobian of a depthwise ``Conv2d`` (groups = C, zero padding; one launch): ``M [V, N, C mult, OH, OW]``,
+    ``weight [C mult, 1, KH, KW]`` -> ``[V, N, C, H, W]``.  ``multiplier``: the channel multiplier ``mult = out_channels / C``
+    (the two operands carry only the product)."""
+    _require_device(M, weight)
+    M, weight = M.contiguous(), weight.contiguous()
+    Vd, N, Cout, OH, OW = M.shape
+    Co, one, KH, KW = weight.shape
+    if Co != Cout or one != 1:
+        raise ValueError(f"weight must be [{Cout}, 1, KH, KW], got {tuple(weight.shape)}")
+    if multiplier < 1 or Cout % multiplier != 0:
+        raise ValueError(f"multiplier must divide the {Cout} channels of M, got {multiplier}")
+    H, W = in_hw
+    out = torch.empty((Vd, N, Cout // multiplier, H, W), dtype=torch.float32, device=M.device)
+    st = _lib.load().vivit_dwconv2d_jac_t_f32(M.data_ptr(), weight.data_ptr(), out.data_ptr(), Vd * N, Cout // multiplier, multiplier,
+                                             H, W, KH, KW, OH, OW,
+                                             stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], _stream(M))
+    _lib.check(st, "vivit_dwconv2d_jac_t_f32")
+    return out
+
+
+@_launcher
+def dwconv2d_weight_mjp(M, x, kernel_size, stride, padding, dilation):
+    """``param_mjp`` of a depthwise Conv2d weight (groups = C, zero padding; one launch): ``M [V, N, C mult, OH, OW]``,
+    ``x [N, C, H, W]`` -> ``[V, N, C mult, 1, KH, KW]``."""
+    _require_device(M, x)
+    M, x = M.contiguous(), x.contiguous()
+    Vd, N, Cout, OH, OW = M.shape
+    Nx, C, H, W = x.shape
+    if Nx != N:
+        raise ValueError(f"x must have batch size {N}, got {Nx}")
+    if Cout % C != 0:
+        raise ValueError(f"M must have a multiple of {C} channels, got {Cout}")
+    KH, KW = kernel_size
+    out = torch.empty((Vd, N, Cout, 1, KH, KW), dtype=torch.float32, device=M.device)
+    st = _lib.load().vivit_dwconv2d_weight_mjp_f32(
+        M.data_ptr(), x.data_ptr(), out.data_ptr(), Vd * N, N, C, Cout // C, H, W, KH, KW, OH, OW, stride[0], stride[1],
+        padding[0], padding[1], dilation[0], dilation[1], _stream(M))
+    _lib.check(st, "vivit_dwconv2d_weight_mjp_f32")
+    return out
+
+
 @_launcher
 def bn_eval_rules(M, x, scale, mean=None, rstd=None):
     """All rules of a BatchNorm in eval mode in one pass over the factor (``vivit_bn_eval_rules_f32``): ``M [V, N, C, *spatial]``,
