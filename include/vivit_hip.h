@@ -271,6 +271,35 @@ int vivit_dwconv2d_jac_t_f32(const float *M, const float *weight, float *out, in
 int vivit_dwconv2d_weight_mjp_f32(const float *M, const float *x, float *V, int64_t rows, int64_t N, int64_t C, int64_t mult,
                                   int64_t H, int64_t W, int64_t KH, int64_t KW, int64_t OH, int64_t OW, int64_t sh, int64_t sw,
                                   int64_t ph, int64_t pw, int64_t dh, int64_t dw, void *stream);
+/* Selective state-space scan (Mamba S6; selective_scan.hip): the forward pass, and the input rule and both parameter rules from
+ * one visit of the factor.  All tensors contiguous fp32.  x [N, T, 2 D + 2 S] = u | dt | B | C along the last axis (u, dt [N, T, D];
+ * B, C [N, T, S], shared by all channels), A_log [D, S], Dk [D] (the parameter "D"), y [N, T, D]:
+ *   Delta_t[d] = softplus(dt_t[d]) if delta_softplus else dt_t[d],   A[d, s] = -exp(A_log[d, s])
+ *   h_t[d, s] = exp(Delta_t[d] A[d, s]) h_{t-1}[d, s] + Delta_t[d] B_t[s] u_t[d],  h_{-1} = 0
+ *   y_t[d] = sum_s C_t[s] h_t[d, s] + Dk[d] u_t[d]
+ * Rules for a factor M [V, N, T, D], per (v, n), the adjoint running backwards in time:
+ *   a_t[d, s] = C_t[s] M_t[d] + exp(Delta_{t+1}[d] A[d, s]) a_{t+1}[d, s],  a_T = 0;   e_t[d, s] = a_t exp(Delta_t A) h_{t-1}
+ *   g_u[t, d] = sum_s a_t Delta_t B_t[s] + Dk[d] M_t[d]
+ *   g_dt[t, d] = (sum_s e_t A[d, s] + u_t[d] sum_s a_t B_t[s]) (sigmoid(dt_t[d]) if delta_softplus else 1)
+ *   g_B[t, s] = sum_d a_t Delta_t[d] u_t[d],   g_C[t, s] = sum_d M_t[d] h_t[d, s]
+ *   F_A[d, s] = sum_t e_t Delta_t[d] A[d, s],   F_Dk[d] = sum_t M_t[d] u_t[d]
+ * g [V, N, T, 2 D + 2 S] = g_u | g_dt | g_B | g_C (packed as x), F_A [V, N, D, S] (factor of A_log), F_Dk [V, N, D].  want: bit 0 the
+ * input rule (g), bit 1 F_A, bit 2 F_Dk; a result whose bit is clear is neither computed nor written and its pointer may be NULL.
+ * Every element has one writer, there are no atomics, and the summation orders (head of selective_scan.hip) depend on the sizes
+ * alone: the bytes of a result are a function of the arguments, the same for every `want`.
+ * The workspace holds h at the start of every chunk of 128 / SP time steps but the first, per workgroup (n, block of 64 channels,
+ * group of 4 columns): [N ceil(D / 64) ceil(V / 4)][nchunk - 1][SP][64] floats, SP = S rounded up to 16, 32 or 64, rounded up to 256
+ * bytes; then, for the input rule with D > 64, the channel blocks' partial sums of g_B | g_C [ceil(D / 64)][V][N][T][2 S].  The query
+ * returns 0 for arguments the entry refuses.
+ * Status, in this order and all before any device call: VIVIT_E_BADARG for a null operand or wanted result, want outside 1 .. 7 or
+ * a non-positive size; VIVIT_E_UNSUPPORTED for S > 64, a size above 2^30, more than 2^31 - 1 workgroups, or offsets beyond 2^56
+ * elements; VIVIT_E_WORKSPACE for a missing or short workspace. */
+int vivit_selective_scan_forward_f32(const float *x, const float *A_log, const float *Dk, float *y, int64_t N, int64_t T, int64_t D,
+                                     int64_t S, int delta_softplus, void *stream);
+size_t vivit_selective_scan_rules_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t D, int64_t S, int want);
+int vivit_selective_scan_rules_f32(const float *M, const float *x, const float *A_log, const float *Dk, float *g, float *F_A, float *F_Dk,
+                                   int64_t V, int64_t N, int64_t T, int64_t D, int64_t S, int delta_softplus, int want, void *workspace,
+                                   size_t workspace_bytes, void *stream);
 /* out[r] = sum_l M[r, l] * (X ? X[r % rows_x, l] : 1): bias rules (sum over the spatial positions) and the BatchNorm
  * weight rule (X = normalised input of the rows_x = N * C planes, shared by the V slices). */
 int vivit_row_dot_f32(const float *M, const float *X, float *out, int64_t rows, int64_t rows_x, int64_t L, void *stream);

@@ -817,3 +817,67 @@ class MultiheadCrossAttention(nn.Module):
                 new.kv_proj.bias.copy_(mha.in_proj_bias[E:])
                 new.out_proj.bias.copy_(mha.out_proj.bias)
         return new
+
+
+def _selective_scan_split(x: Tensor, D: int, S: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``u, dt [N, T, D]`` and ``B, C [N, T, S]`` of the packed ``x [N, T, 2 D + 2 S]``."""
+    if x.dim() != 3 or x.shape[2] != 2 * D + 2 * S:
+        raise ValueError(f"expected [N, T, {2 * D + 2 * S}] = u | dt | B | C, got {tuple(x.shape)}")
+    return x[..., :D], x[..., D:2 * D], x[..., 2 * D:2 * D + S], x[..., 2 * D + S:]
+
+
+class _FusedSelectiveScan(torch.autograd.Function):
+    """``SelectiveScan.forward`` as one launch (``kernels.selective_scan_forward``); the backward pass is the extensions' rule on the
+    gradient as a factor of one row (``kernels.selective_scan_rules``), summed over the samples for the two parameters."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, A_log: Tensor, D: Tensor, delta_softplus: bool):
+        ctx.delta_softplus = delta_softplus
+        ctx.save_for_backward(x, A_log, D)
+        return kernels.selective_scan_forward(x, A_log, D, delta_softplus)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad: Tensor):
+        x, A_log, D = ctx.saved_tensors
+        g, FA, FD = kernels.selective_scan_rules(grad.contiguous()[None], x, A_log, D, ctx.delta_softplus, want=ctx.needs_input_grad[:3])
+        return (None if g is None else g[0], None if FA is None else FA[0].sum(0), None if FD is None else FD[0].sum(0), None)
+
+
+class SelectiveScan(nn.Module):
+    """The selective state-space scan (S6) at the core of a Mamba block (no counterpart in BackPACK): a leaf on the packed input
+    ``x [N, T, 2 D + 2 S] = u | dt | B | C`` (``u, dt [N, T, D]``; ``B, C [N, T, S]``, shared by all channels as in Mamba-1), with the
+    parameters ``A_log [D, S]`` and ``D [D]`` named and initialised as in Mamba (``A_log = log(1 .. S)`` per channel, ``D = 1``):
+
+        ``Delta = softplus(dt)`` (``dt`` itself without ``delta_softplus``), ``A = -exp(A_log)``,
+        ``h_t = exp(Delta_t A) h_{t-1} + Delta_t B_t u_t`` from ``h_{-1} = 0``, ``y_t = sum_s C_t h_t + D u_t``   ->  ``y [N, T, D]``.
+
+    On HIP fp32 tensors the forward pass is one HIP kernel and autograd's backward pass the rules kernel of the extensions; on any
+    other tensor it is the plain loop over ``T`` in torch."""
+
+    def __init__(self, d_inner: int, d_state: int = 16, delta_softplus: bool = True):
+        super().__init__()
+        if d_inner < 1 or d_state < 1:
+            raise ValueError(f"d_inner and d_state must be positive, got {d_inner} and {d_state}")
+        self.d_inner, self.d_state, self.delta_softplus = int(d_inner), int(d_state), bool(delta_softplus)
+        self.A_log = nn.Parameter(torch.log(torch.arange(1, d_state + 1, dtype=torch.float32)).repeat(d_inner, 1))
+        self.D = nn.Parameter(torch.ones(d_inner))
+
+    def scan_loop(self, x: Tensor) -> Tensor:
+        """The plain loop in torch (any device and dtype; differentiable)."""
+        u, dt, B, C = _selective_scan_split(x, self.d_inner, self.d_state)
+        delta = F.softplus(dt, threshold=float("inf")) if self.delta_softplus else dt
+        A = -torch.exp(self.A_log.to(x.dtype))
+        h = x.new_zeros(x.shape[0], self.d_inner, self.d_state)
+        ys = []
+        for t in range(x.shape[1]):
+            h = torch.exp(delta[:, t, :, None] * A) * h + (delta[:, t] * u[:, t])[:, :, None] * B[:, t, None, :]
+            ys.append((h * C[:, t, None, :]).sum(-1))
+        return torch.stack(ys, 1) + self.D.to(x.dtype) * u
+
+    def forward(self, x: Tensor) -> Tensor:
+        _selective_scan_split(x, self.d_inner, self.d_state)
+        if (x.is_cuda and x.dtype == torch.float32 and self.A_log.dtype == torch.float32 and self.d_state <= kernels.SSCAN_MAX_STATE
+                and x.numel() > 0):
+            return _FusedSelectiveScan.apply(x, self.A_log, self.D, self.delta_softplus)
+        return self.scan_loop(x)

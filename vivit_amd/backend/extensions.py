@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from vivit_amd import _lib, kernels
-from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, Permute, ProductModule, RotaryEmbedding, ScaledDotProductAttention,
+from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, Permute, ProductModule, RotaryEmbedding, ScaledDotProductAttention, SelectiveScan,
                                               ScaledDotProductCrossAttention, ScaleModule,
                                               Slicing, SoftCap, SumModule, _gqa_split)
 from vivit_amd.utils.ggn import Vmp
@@ -269,6 +269,51 @@ def _rms_norm_jac_t_torch(module, M: Tensor, x: Tensor) -> Tensor:
     return rstd * (h - xhat * (h * xhat).mean(dims, keepdim=True))
 
 
+def _selective_scan_rules(module, M: Tensor, x: Tensor, input_rule: bool):
+    """``(input rule, factor of A_log, factor of D)`` of a SelectiveScan from ONE launch (``vivit_selective_scan_rules_f32``),
+    remembered on the factor tensor as :func:`_rms_norm_rules` does.  A frozen parameter is not computed (``None``), the input rule
+    only when ``input_rule`` says that it will be asked for.  Nothing is remembered on the module."""
+    memo = getattr(M, "_vivit_selective_scan_rules", None)
+    if memo is not None and memo[0] is module and (memo[1] is not None or not input_rule):
+        return memo[1:]
+    own = {name for name, _ in _own_params(module)}
+    want = (input_rule, "A_log" in own, "D" in own)
+    out = (None, None, None)
+    if any(want):
+        out = kernels.selective_scan_rules(M.reshape(M.shape[0], *x.shape[:2], -1), x, module.A_log.detach(), module.D.detach(),
+                                           module.delta_softplus, want)
+    memo = (module,) + tuple(out)
+    try:
+        M._vivit_selective_scan_rules = memo
+    except AttributeError:   # (tensor subclasses without a __dict__)
+        pass
+    return memo[1:]
+
+
+def _selective_scan_param_torch(module, name: str, M: Tensor, x: Tensor) -> Tensor:
+    """The two parameter rules of csrc/selective_scan.hip in plain torch (non-HIP or non-fp32 tensors, sizes beyond the kernel):
+    ``F_D = sum_t M u`` and ``F_A = sum_t e_t Delta_t A`` with ``e_t = a_t exp(Delta_t A) h_{t-1}`` and the adjoint
+    ``a_t = C_t M_t + exp(Delta_{t+1} A) a_{t+1}``.  No autograd."""
+    D, S = module.d_inner, module.d_state
+    M = M.reshape(M.shape[0], *x.shape[:2], D)
+    u, dt, B, C = x[..., :D], x[..., D:2 * D], x[..., 2 * D:2 * D + S], x[..., 2 * D + S:]
+    if name == "D":
+        return (M * u).sum(2)
+    delta = F.softplus(dt, threshold=float("inf")) if module.delta_softplus else dt
+    A = -torch.exp(module.A_log.detach().to(x.dtype))
+    T = x.shape[1]
+    decay = torch.exp(delta[..., None] * A)                                        # [N, T, D, S]
+    h, prev = x.new_zeros(x.shape[0], D, S), []
+    for t in range(T):
+        prev.append(h)
+        h = decay[:, t] * h + (delta[:, t] * u[:, t])[..., None] * B[:, t, None, :]
+    a, FA = None, 0.0
+    for t in range(T - 1, -1, -1):
+        a = M[:, :, t, :, None] * C[:, t, None, :] + (decay[:, t + 1] * a if a is not None else 0.0)
+        FA = FA + a * (decay[:, t] * prev[t]) * delta[:, t, :, None]
+    return FA * A
+
+
 def _param_factor(module, name: str, M: Tensor, x: Tensor, subsampling=None) -> Tensor:
     """``param_mjp(..., sum_batch=False)``: ``M`` [V, N, *out] -> [V, N, *param.shape].  ``subsampling``: the indices ``x`` was
     sub-sampled with (a rule that reads what the forward pass left on the module sub-samples it likewise)."""
@@ -326,6 +371,14 @@ def _param_factor(module, name: str, M: Tensor, x: Tensor, subsampling=None) -> 
         return _embedding_factor(B, ids, module.num_embeddings)
     if isinstance(module, ScaledDotProductAttention) and name == "bias":   # a learned relative-position table
         return _attention_bias_factor(module, M, x, subsampling)
+    if isinstance(module, SelectiveScan):   # A_log [D, S] and D [D]
+        if M.is_cuda and M.dtype == torch.float32:
+            try:   # (the input rule and the other parameter ride the same launch)
+                return _selective_scan_rules(module, M, x, module.input0.requires_grad)[1 if name == "A_log" else 2]
+            except _lib.VivitHipError as exc:  # sizes beyond the kernel: the torch statement below
+                if exc.status != _lib.VIVIT_E_UNSUPPORTED:
+                    raise
+        return _selective_scan_param_torch(module, name, M, x)
     raise NotImplementedError(f"no parameter rule for {type(module).__name__}")
 
 
@@ -916,6 +969,8 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
         return _norm_rules(module, M, x, True)[0]
     if isinstance(module, nn.RMSNorm):
         return _rms_norm_rules(module, M, x, True)[0]
+    if isinstance(module, SelectiveScan):
+        return _selective_scan_rules(module, M, x, True)[0]
     if isinstance(module, RotaryEmbedding):   # the very tables the forward pass used (cached on the module)
         d = module.head_dim(x)
         return kernels.rope_jac_t(M.reshape(M.shape[0], *x.shape), *module.tables(x.shape[1], d, x.device, x.dtype), module.num_heads,
@@ -993,7 +1048,8 @@ def _generic_jac_t_mat_prod(module, M: Tensor, x: Tensor) -> Tensor:
     forward (bypasses hooks)."""
     with torch.enable_grad():
         xi = x.detach().requires_grad_(True)
-        y = module.forward(xi)
+        # (a SelectiveScan: its loop in torch, which a batched vector-Jacobian product can be taken through)
+        y = module.scan_loop(xi) if isinstance(module, SelectiveScan) else module.forward(xi)
         (g,) = torch.autograd.grad(y, xi, grad_outputs=M.reshape(M.shape[0], *y.shape), is_grads_batched=True)
     return g
 

@@ -509,6 +509,60 @@ def dwconv2d_weight_mjp(M, x, kernel_size, stride, padding, dilation):
     return out
 
 
+# csrc/selective_scan.hip: time steps of a chunk of the rules kernel at up to 16 states (128 / S_padded in general: 4 at 32, 2 at 64
+# states), channels of a block, waves of a workgroup = factor columns it serves, largest state size (the tests name the edges with
+# them; change them together with the unit)
+SSCAN_CHUNK, SSCAN_CHAN, SSCAN_WAVES, SSCAN_MAX_STATE = 8, 64, 4, 64
+
+
+def _sscan_operands(x, A_log, D):
+    _require_device(x, A_log, D)
+    if A_log.dim() != 2 or D.dim() != 1 or D.shape[0] != A_log.shape[0]:
+        raise ValueError(f"A_log must be [D, S] and D [D], got {tuple(A_log.shape)} and {tuple(D.shape)}")
+    Dn, S = A_log.shape
+    if x.dim() != 3 or x.shape[2] != 2 * Dn + 2 * S or x.numel() == 0:
+        raise ValueError(f"x must be [N, T, {2 * Dn + 2 * S}] = u | dt | B | C, got {tuple(x.shape)}")
+    return x.contiguous(), A_log.contiguous(), D.contiguous(), Dn, S
+
+
+@_launcher
+def selective_scan_forward(x, A_log, D, delta_softplus=True):
+    """Selective state-space scan (Mamba S6, ``vivit_selective_scan_forward_f32``; one launch): packed ``x [N, T, 2 D + 2 S]`` =
+    ``u | dt | B | C``, ``A_log [D, S]``, ``D [D]`` -> ``y [N, T, D]``."""
+    x, A_log, D, Dn, S = _sscan_operands(x, A_log, D)
+    N, T = x.shape[:2]
+    y = torch.empty((N, T, Dn), dtype=torch.float32, device=x.device)
+    st = _lib.load().vivit_selective_scan_forward_f32(x.data_ptr(), A_log.data_ptr(), D.data_ptr(), y.data_ptr(), N, T, Dn, S,
+                                                     int(bool(delta_softplus)), _stream(x))
+    _lib.check(st, "vivit_selective_scan_forward_f32")
+    return y
+
+
+@_launcher
+def selective_scan_rules(M, x, A_log, D, delta_softplus=True, want=(True, True, True)):
+    """The rules of the selective scan from one visit of the factor (``vivit_selective_scan_rules_f32``): ``M [V, N, T, D]`` ->
+    ``(g [V, N, T, 2 D + 2 S], F_A [V, N, D, S], F_D [V, N, D])``, the transposed input Jacobian packed as ``x`` and the factors of
+    ``A_log`` and ``D``.  ``want``: which of the three to compute (``None`` for the others)."""
+    _require_device(M)
+    x, A_log, D, Dn, S = _sscan_operands(x, A_log, D)
+    M = M.contiguous()
+    N, T = x.shape[:2]
+    if M.dim() != 4 or tuple(M.shape[1:]) != (N, T, Dn) or M.numel() == 0:
+        raise ValueError(f"M must be [V, {N}, {T}, {Dn}], got {tuple(M.shape)}")
+    if len(want) != 3 or not any(want):
+        raise ValueError("nothing to compute")
+    Vd, bits = M.shape[0], sum(1 << i for i, w in enumerate(want) if w)
+    new = lambda *shape: torch.empty((Vd, N) + shape, dtype=torch.float32, device=M.device)   # noqa: E731
+    g, FA, FD = (new(*shape) if w else None for w, shape in zip(want, ((T, 2 * Dn + 2 * S), (Dn, S), (Dn,))))
+    lib = _lib.load()
+    ws, ws_bytes = _workspace(lib.vivit_selective_scan_rules_f32_workspace_bytes(Vd, N, T, Dn, S, bits), M)
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    st = lib.vivit_selective_scan_rules_f32(M.data_ptr(), x.data_ptr(), A_log.data_ptr(), D.data_ptr(), ptr(g), ptr(FA), ptr(FD), Vd, N, T,
+                                            Dn, S, int(bool(delta_softplus)), bits, ws, ws_bytes, _stream(M))
+    _lib.check(st, "vivit_selective_scan_rules_f32")
+    return g, FA, FD
+
+
 @_launcher
 def bn_eval_rules(M, x, scale, mean=None, rstd=None):
     """All rules of a BatchNorm in eval mode in one pass over the factor (``vivit_bn_eval_rules_f32``): ``M [V, N, C, *spatial]``,
