@@ -300,6 +300,33 @@ size_t vivit_selective_scan_rules_f32_workspace_bytes(int64_t V, int64_t N, int6
 int vivit_selective_scan_rules_f32(const float *M, const float *x, const float *A_log, const float *Dk, float *g, float *F_A, float *F_Dk,
                                    int64_t V, int64_t N, int64_t T, int64_t D, int64_t S, int delta_softplus, int want, void *workspace,
                                    size_t workspace_bytes, void *stream);
+/* Mamba-2 state-space-dual layer (SSD; ssd.hip): one scalar A per head turns a chunk of time steps into dense products, which run
+ * on the fp32 matrix pipe.  All tensors contiguous fp32.  x [N, T, H P + H + 2 G S] = X | dt | B | C along the last axis (X [N, T, H,
+ * P]; dt [N, T, H]; B, C [N, T, G, S], head h reads group h / (H / G)), A_log, Dk (the parameter "D"), dt_bias [H], y [N, T, H P].
+ * Per (n, h) the state Hs_t is P x S, Hs_{-1} = 0:
+ *   Delta_t = softplus(dt_t + dt_bias_h) if delta_softplus else dt_t + dt_bias_h,   A = -exp(A_log_h),   a_t = exp(Delta_t A)
+ *   Hs_t = a_t Hs_{t-1} + Delta_t x_t B_t^T,   y_t = Hs_t C_t + Dk_h x_t
+ * Rules for a factor M [V, N, T, H P], per (v, n, h), the adjoint running backwards in time, Lam_T = 0:
+ *   Lam_t = M_t C_t^T + a_{t+1} Lam_{t+1}   (P x S),   e_t = <Lam_t, a_t Hs_{t-1}>
+ *   g_x_t = Delta_t Lam_t B_t + Dk_h M_t,   g_dt_t = (A e_t + x_t^T Lam_t B_t) (sigmoid(dt_t + dt_bias_h) if delta_softplus else 1)
+ *   g_B_t[group] = sum over the group's heads of Delta_t Lam_t^T x_t,   g_C_t[group] = sum over the group's heads of Hs_t^T M_t
+ *   F_A = A sum_t e_t Delta_t,   F_Dk = sum_t M_t . x_t,   F_dtb = sum_t g_dt_t
+ * g [V, N, T, H P + H + 2 G S] = g_x | g_dt | g_B | g_C (packed as x); F_A (factor of A_log), F_Dk, F_dtb [V, N, H].  want: bit 0 the
+ * input rule (g), bit 1 F_A, bit 2 F_Dk, bit 3 F_dtb; a result whose bit is clear is neither computed nor written and its pointer
+ * may be NULL.  Every element has one writer, there are no atomics, and the summation orders (head of ssd.hip) depend on the sizes
+ * alone: the bytes of a result are a function of the arguments, the same on every run and for every `want`.
+ * The workspace (none for want == 4) holds Hs at the start of every chunk of 32 time steps but the first, [N H][nchunk - 1][PP][SP]
+ * floats (PP = 32 or 64 >= P, SP = 64 or 128 >= S), rounded up to 256 bytes; then, for the input rule with H > G, the heads' partial
+ * sums of g_B | g_C [H / G][V][N][T][G][2][S].  The query returns 0 for arguments the entry refuses.
+ * Status, in this order and all before any device call: VIVIT_E_BADARG for a null operand or wanted result, want outside 1 .. 15, a
+ * non-positive size or G not dividing H; VIVIT_E_UNSUPPORTED for S > 128, P > 64, a size above 2^30, more than 2^31 - 1 workgroups or
+ * offsets beyond 2^56 elements; VIVIT_E_WORKSPACE for a missing or short workspace. */
+int vivit_ssd_forward_f32(const float *x, const float *A_log, const float *Dk, const float *dt_bias, float *y, int64_t N, int64_t T,
+                          int64_t H, int64_t P, int64_t S, int64_t G, int delta_softplus, void *stream);
+size_t vivit_ssd_rules_f32_workspace_bytes(int64_t V, int64_t N, int64_t T, int64_t H, int64_t P, int64_t S, int64_t G, int want);
+int vivit_ssd_rules_f32(const float *M, const float *x, const float *A_log, const float *Dk, const float *dt_bias, float *g, float *F_A,
+                        float *F_Dk, float *F_dtb, int64_t V, int64_t N, int64_t T, int64_t H, int64_t P, int64_t S, int64_t G,
+                        int delta_softplus, int want, void *workspace, size_t workspace_bytes, void *stream);
 /* out[r] = sum_l M[r, l] * (X ? X[r % rows_x, l] : 1): bias rules (sum over the spatial positions) and the BatchNorm
  * weight rule (X = normalised input of the rows_x = N * C planes, shared by the V slices). */
 int vivit_row_dot_f32(const float *M, const float *X, float *out, int64_t rows, int64_t rows_x, int64_t L, void *stream);

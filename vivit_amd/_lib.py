@@ -50,6 +50,9 @@ SIGNATURES = {
     "vivit_selective_scan_forward_f32": (_int, [_ptr] * 4 + [_i64] * 4 + [_int, _ptr]),
     "vivit_selective_scan_rules_f32_workspace_bytes": (_sz, [_i64] * 5 + [_int]),
     "vivit_selective_scan_rules_f32": (_int, [_ptr] * 7 + [_i64] * 5 + [_int, _int, _ptr, _sz, _ptr]),
+    "vivit_ssd_forward_f32": (_int, [_ptr] * 5 + [_i64] * 6 + [_int, _ptr]),
+    "vivit_ssd_rules_f32_workspace_bytes": (_sz, [_i64] * 7 + [_int]),
+    "vivit_ssd_rules_f32": (_int, [_ptr] * 9 + [_i64] * 7 + [_int, _int, _ptr, _sz, _ptr]),
     "vivit_row_dot_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _ptr]),
     "vivit_bn_eval_rules_f32": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr]),
     "vivit_norm_stats_f32": (_int, [_ptr, _ptr, _ptr, _i64, _i64, _f32, _ptr]),

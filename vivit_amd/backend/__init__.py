@@ -11,7 +11,8 @@ the self-attention modules ``ScaledDotProductAttention`` / ``MultiheadSelfAttent
 grouped queries, sliding windows, right-padded batches through ``set_lengths``, logit soft-capping and relative-position
 bias tables, constant such as ``alibi_bias`` or learned, plain or indexed through ``relative_position_buckets``; ``SoftCap`` for capped final logits), the cross-attention modules
 ``ScaledDotProductCrossAttention`` / ``MultiheadCrossAttention`` (queries over a second sequence), ``nn.Embedding``,
-``nn.RMSNorm`` and the modules ``ProductModule`` (gated MLPs) / ``RotaryEmbedding`` / ``SelectiveScan`` (Mamba's S6 layer) of ``custom_module``;
+``nn.RMSNorm`` and the modules ``ProductModule`` (gated MLPs) / ``RotaryEmbedding`` / ``SelectiveScan`` (Mamba's S6 layer) /
+``SelectiveScanSSD`` (Mamba-2's state-space-dual layer) of ``custom_module``;
 CrossEntropyLoss / MSELoss with ``reduction='mean'`` or ``'sum'``, on outputs ``[N, C]`` and on outputs with positions
 ``[N, C, *D]`` -- next-token cross entropy over a whole sequence, segmentation, dense regression -- with ``Permute`` of
 ``custom_module`` to bring a head's ``[N, T, C]`` to ``[N, C, T]``).  When the real BackPACK is importable the Computation classes can be used
@@ -34,6 +35,7 @@ from vivit_amd.backend.custom_module import (
     ScaledDotProductCrossAttention,
     ScaleModule,
     SelectiveScan,
+    SelectiveScanSSD,
     Slicing,
     SoftCap,
     SumModule,
@@ -49,4 +51,4 @@ from vivit_amd.backend.extensions import (
     ViViTGGNMC,
 )
 
-__all__ = ["ActiveIdentity", "MultiheadCrossAttention", "MultiheadSelfAttention", "Pad", "Parallel", "Permute", "ProductModule", "RotaryEmbedding", "ScaledDotProductAttention", "ScaledDotProductCrossAttention", "ScaleModule", "SelectiveScan", "Slicing", "SoftCap", "SumModule", "alibi_bias", "relative_position_buckets", "backpack", "extend", "BatchGrad", "SqrtGGNExact", "SqrtGGNMC", "ViViTGGNExact", "ViViTGGNMC"]
+__all__ = ["ActiveIdentity", "MultiheadCrossAttention", "MultiheadSelfAttention", "Pad", "Parallel", "Permute", "ProductModule", "RotaryEmbedding", "ScaledDotProductAttention", "ScaledDotProductCrossAttention", "ScaleModule", "SelectiveScan", "SelectiveScanSSD", "Slicing", "SoftCap", "SumModule", "alibi_bias", "relative_position_buckets", "backpack", "extend", "BatchGrad", "SqrtGGNExact", "SqrtGGNMC", "ViViTGGNExact", "ViViTGGNMC"]

@@ -881,3 +881,87 @@ class SelectiveScan(nn.Module):
                 and x.numel() > 0):
             return _FusedSelectiveScan.apply(x, self.A_log, self.D, self.delta_softplus)
         return self.scan_loop(x)
+
+
+class _FusedSSD(torch.autograd.Function):
+    """``SelectiveScanSSD.forward`` as one launch (``kernels.ssd_forward``); the backward pass is the extensions' rule on the gradient
+    as a factor of one row (``kernels.ssd_rules``), summed over the samples for the three parameters."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, A_log: Tensor, D: Tensor, dt_bias: Tensor, geometry: tuple):
+        ctx.geometry = geometry
+        ctx.save_for_backward(x, A_log, D, dt_bias)
+        return kernels.ssd_forward(x, A_log, D, dt_bias, *geometry)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad: Tensor):
+        out = kernels.ssd_rules(grad.contiguous()[None], *ctx.saved_tensors, *ctx.geometry, want=ctx.needs_input_grad[:4])
+        return (None if out[0] is None else out[0][0],) + tuple(None if f is None else f[0].sum(0) for f in out[1:]) + (None,)
+
+
+class SelectiveScanSSD(nn.Module):
+    """The state-space-dual layer of Mamba-2 (no counterpart in BackPACK): a leaf on the packed input
+    ``x [N, T, H P + H + 2 G S] = X | dt | B | C`` (``X [N, T, H, P]``, ``dt [N, T, H]``, ``B, C [N, T, G, S]``; head ``h`` reads group
+    ``h // (H / G)``), with one scalar ``A`` per head and the parameters ``A_log``, ``D``, ``dt_bias [H]`` named and initialised as in
+    Mamba-2 (``A_log = log(1 .. H)``, ``D = 1``, ``dt_bias = 0``).  Per head the state ``Hs_t`` is ``P x S``:
+
+        ``Delta = softplus(dt + dt_bias)`` (``dt + dt_bias`` itself without ``delta_softplus``), ``A = -exp(A_log)``,
+        ``Hs_t = exp(Delta_t A) Hs_{t-1} + Delta_t x_t B_t^T`` from ``Hs_{-1} = 0``, ``y_t = Hs_t C_t + D x_t``   ->  ``y [N, T, H P]``.
+
+    On HIP fp32 tensors with ``P <= 64`` and ``S <= 128`` the forward pass is one chunked HIP kernel on the matrix pipe and autograd's
+    backward pass the rules kernel of the extensions; on any other tensor it is the plain loop over ``T`` in torch."""
+
+    def __init__(self, num_heads: int, head_dim: int, d_state: int, num_groups: int = 1, delta_softplus: bool = True):
+        super().__init__()
+        if min(num_heads, head_dim, d_state, num_groups) < 1:
+            raise ValueError(f"num_heads, head_dim, d_state and num_groups must be positive, got {num_heads}, {head_dim}, {d_state}, "
+                             f"{num_groups}")
+        if num_heads % num_groups != 0:
+            raise ValueError(f"num_groups must divide the {num_heads} heads, got {num_groups}")
+        self.num_heads, self.head_dim, self.d_state, self.num_groups = int(num_heads), int(head_dim), int(d_state), int(num_groups)
+        self.delta_softplus = bool(delta_softplus)
+        self.A_log = nn.Parameter(torch.log(torch.arange(1, num_heads + 1, dtype=torch.float32)))
+        self.D = nn.Parameter(torch.ones(num_heads))
+        self.dt_bias = nn.Parameter(torch.zeros(num_heads))
+
+    @property
+    def geometry(self) -> tuple:
+        return (self.num_heads, self.head_dim, self.d_state, self.num_groups, self.delta_softplus)
+
+    def split(self, x: Tensor) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+        """``X [N, T, H, P]``, ``dt [N, T, H]`` and ``B, C [N, T, H, S]`` (the groups repeated over their heads) of the packed ``x``."""
+        H, P, S, G = self.geometry[:4]
+        if x.dim() != 3 or x.shape[2] != H * P + H + 2 * G * S:
+            raise ValueError(f"expected [N, T, {H * P + H + 2 * G * S}] = X | dt | B | C, got {tuple(x.shape)}")
+        N, T = x.shape[:2]
+        B, C = (x[..., H * P + H + i * G * S:H * P + H + (i + 1) * G * S].reshape(N, T, G, S).repeat_interleave(H // G, 2) for i in (0, 1))
+        return x[..., :H * P].reshape(N, T, H, P), x[..., H * P:H * P + H], B, C
+
+    def scan_loop(self, x: Tensor) -> Tensor:
+        """The plain loop in torch (any device and dtype; differentiable)."""
+        X, dt, B, C = self.split(x)
+        dt = dt + self.dt_bias.to(x.dtype)
+        delta = F.softplus(dt, threshold=float("inf")) if self.delta_softplus else dt
+        decay = torch.exp(delta * -torch.exp(self.A_log.to(x.dtype)))
+        hs = x.new_zeros(x.shape[0], self.num_heads, self.head_dim, self.d_state)
+        ys = []
+        for t in range(x.shape[1]):
+            hs = decay[:, t, :, None, None] * hs + (delta[:, t, :, None] * X[:, t])[..., None] * B[:, t, :, None, :]
+            ys.append((hs * C[:, t, :, None, :]).sum(-1))
+        return (torch.stack(ys, 1) + self.D.to(x.dtype)[:, None] * X).flatten(2)
+
+    def fused(self, x: Tensor) -> bool:
+        """Whether ``x`` is within what csrc/ssd.hip serves."""
+        return (x.is_cuda and x.dtype == torch.float32 and self.A_log.dtype == torch.float32 and x.numel() > 0
+                and self.d_state <= kernels.SSD_MAX_STATE and self.head_dim <= kernels.SSD_MAX_HEAD_DIM)
+
+    def forward(self, x: Tensor) -> Tensor:
+        self.split(x)
+        if self.fused(x):
+            try:
+                return _FusedSSD.apply(x, self.A_log, self.D, self.dt_bias, self.geometry)
+            except _lib.VivitHipError as exc:   # sizes beyond the kernel's index arithmetic: the loop
+                if exc.status != _lib.VIVIT_E_UNSUPPORTED:
+                    raise
+        return self.scan_loop(x)

@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from torch import Tensor, nn
 
 from vivit_amd import _lib, kernels
-from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, Permute, ProductModule, RotaryEmbedding, ScaledDotProductAttention, SelectiveScan,
+from vivit_amd.backend.custom_module import (ActiveIdentity, Pad, Permute, ProductModule, RotaryEmbedding, ScaledDotProductAttention, SelectiveScan, SelectiveScanSSD,
                                               ScaledDotProductCrossAttention, ScaleModule,
                                               Slicing, SoftCap, SumModule, _gqa_split)
 from vivit_amd.utils.ggn import Vmp
@@ -314,6 +314,58 @@ def _selective_scan_param_torch(module, name: str, M: Tensor, x: Tensor) -> Tens
     return FA * A
 
 
+_SSD_PARAMS = ("A_log", "D", "dt_bias")
+
+
+def _ssd_rules(module, M: Tensor, x: Tensor, input_rule: bool):
+    """``(input rule, factors of A_log, D, dt_bias)`` of a SelectiveScanSSD from ONE launch (``vivit_ssd_rules_f32``), remembered on the
+    factor tensor as :func:`_selective_scan_rules` does.  A frozen parameter is not computed (``None``), the input rule only when
+    ``input_rule`` says that it will be asked for.  Nothing is remembered on the module."""
+    memo = getattr(M, "_vivit_ssd_rules", None)
+    if memo is not None and memo[0] is module and (memo[1] is not None or not input_rule):
+        return memo[1:]
+    own = {name for name, _ in _own_params(module)}
+    want = (input_rule,) + tuple(name in own for name in _SSD_PARAMS)
+    out = (None,) * 4
+    if any(want):
+        out = kernels.ssd_rules(M.reshape(M.shape[0], *x.shape[:2], -1), x, module.A_log.detach(), module.D.detach(),
+                                module.dt_bias.detach(), *module.geometry, want=want)
+    memo = (module,) + tuple(out)
+    try:
+        M._vivit_ssd_rules = memo
+    except AttributeError:   # (tensor subclasses without a __dict__)
+        pass
+    return memo[1:]
+
+
+def _ssd_param_torch(module, name: str, M: Tensor, x: Tensor) -> Tensor:
+    """The three parameter rules of csrc/ssd.hip in plain torch (non-HIP or non-fp32 tensors, sizes beyond the kernel):
+    ``F_D = sum_t M_t . x_t``, ``F_A = A sum_t e_t Delta_t`` and ``F_dt_bias = sum_t (A e_t + x_t^T Lam_t B_t) sigmoid`` with
+    ``e_t = <Lam_t, a_t Hs_{t-1}>`` and the adjoint ``Lam_t = M_t C_t^T + a_{t+1} Lam_{t+1}``.  No autograd."""
+    X, dt, B, C = module.split(x)
+    M = M.reshape(M.shape[0], *X.shape)
+    if name == "D":
+        return (M * X).sum((2, 4))
+    dt = dt + module.dt_bias.detach().to(x.dtype)
+    delta = F.softplus(dt, threshold=float("inf")) if module.delta_softplus else dt
+    sig = torch.sigmoid(dt) if module.delta_softplus else torch.ones_like(dt)
+    A = -torch.exp(module.A_log.detach().to(x.dtype))
+    decay = torch.exp(delta * A)                                                   # [N, T, H]
+    hs, prev = x.new_zeros(x.shape[0], *X.shape[2:], B.shape[3]), []
+    for t in range(x.shape[1]):
+        prev.append(hs)
+        hs = decay[:, t, :, None, None] * hs + (delta[:, t, :, None] * X[:, t])[..., None] * B[:, t, :, None, :]
+    lam, out = None, 0.0
+    for t in range(x.shape[1] - 1, -1, -1):
+        lam = M[:, :, t, :, :, None] * C[:, t, :, None, :] + (decay[:, t + 1, :, None, None] * lam if lam is not None else 0.0)
+        e = (lam * (decay[:, t, :, None, None] * prev[t])).sum((-1, -2))
+        if name == "A_log":
+            out = out + e * delta[:, t]
+        else:
+            out = out + (A * e + (X[:, t, :, :, None] * lam * B[:, t, :, None, :]).sum((-1, -2))) * sig[:, t]
+    return out * A if name == "A_log" else out
+
+
 def _param_factor(module, name: str, M: Tensor, x: Tensor, subsampling=None) -> Tensor:
     """``param_mjp(..., sum_batch=False)``: ``M`` [V, N, *out] -> [V, N, *param.shape].  ``subsampling``: the indices ``x`` was
     sub-sampled with (a rule that reads what the forward pass left on the module sub-samples it likewise)."""
@@ -379,6 +431,14 @@ def _param_factor(module, name: str, M: Tensor, x: Tensor, subsampling=None) -> 
                 if exc.status != _lib.VIVIT_E_UNSUPPORTED:
                     raise
         return _selective_scan_param_torch(module, name, M, x)
+    if isinstance(module, SelectiveScanSSD):   # A_log, D and dt_bias [H]
+        if module.fused(M) and module.fused(x):
+            try:   # (the input rule and the other parameters ride the same launch)
+                return _ssd_rules(module, M, x, module.input0.requires_grad)[1 + _SSD_PARAMS.index(name)]
+            except _lib.VivitHipError as exc:  # sizes beyond the kernel: the torch statement below
+                if exc.status != _lib.VIVIT_E_UNSUPPORTED:
+                    raise
+        return _ssd_param_torch(module, name, M, x)
     raise NotImplementedError(f"no parameter rule for {type(module).__name__}")
 
 
@@ -971,6 +1031,13 @@ def _hip_jac_t_mat_prod(module, M: Tensor, x: Tensor, subsampling=None) -> Optio
         return _rms_norm_rules(module, M, x, True)[0]
     if isinstance(module, SelectiveScan):
         return _selective_scan_rules(module, M, x, True)[0]
+    if isinstance(module, SelectiveScanSSD) and module.fused(M) and module.fused(x):
+        try:
+            return _ssd_rules(module, M, x, True)[0]
+        except _lib.VivitHipError as exc:  # sizes beyond the kernel: the generic rule through the loop
+            if exc.status != _lib.VIVIT_E_UNSUPPORTED:
+                raise
+        return _generic_jac_t_mat_prod(module, M, x)
     if isinstance(module, RotaryEmbedding):   # the very tables the forward pass used (cached on the module)
         d = module.head_dim(x)
         return kernels.rope_jac_t(M.reshape(M.shape[0], *x.shape), *module.tables(x.shape[1], d, x.device, x.dtype), module.num_heads,
@@ -1048,8 +1115,8 @@ def _generic_jac_t_mat_prod(module, M: Tensor, x: Tensor) -> Tensor:
     forward (bypasses hooks)."""
     with torch.enable_grad():
         xi = x.detach().requires_grad_(True)
-        # (a SelectiveScan: its loop in torch, which a batched vector-Jacobian product can be taken through)
-        y = module.scan_loop(xi) if isinstance(module, SelectiveScan) else module.forward(xi)
+        # (a SelectiveScan or SelectiveScanSSD: its loop in torch, which a batched vector-Jacobian product can be taken through)
+        y = module.scan_loop(xi) if isinstance(module, (SelectiveScan, SelectiveScanSSD)) else module.forward(xi)
         (g,) = torch.autograd.grad(y, xi, grad_outputs=M.reshape(M.shape[0], *y.shape), is_grads_batched=True)
     return g
 

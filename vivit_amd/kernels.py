@@ -563,6 +563,63 @@ def selective_scan_rules(M, x, A_log, D, delta_softplus=True, want=(True, True, 
     return g, FA, FD
 
 
+# csrc/ssd.hip: time steps of a chunk of the forward kernel (the rules kernel takes half of it), largest state size and head
+# dimension (the tests name the edges with them; change them together with the unit)
+SSD_CHUNK, SSD_MAX_STATE, SSD_MAX_HEAD_DIM = 64, 128, 64
+
+
+def _ssd_operands(x, A_log, D, dt_bias, H, P, S, G):
+    _require_device(x, A_log, D, dt_bias)
+    if min(H, P, S, G) < 1 or H % G != 0:
+        raise ValueError(f"num_heads, head_dim, d_state must be positive and num_groups divide num_heads, got {H}, {P}, {S}, {G}")
+    if any(t.dim() != 1 or t.shape[0] != H for t in (A_log, D, dt_bias)):
+        raise ValueError(f"A_log, D and dt_bias must be [{H}], got {tuple(A_log.shape)}, {tuple(D.shape)}, {tuple(dt_bias.shape)}")
+    width = H * P + H + 2 * G * S
+    if x.dim() != 3 or x.shape[2] != width or x.numel() == 0:
+        raise ValueError(f"x must be [N, T, {width}] = X | dt | B | C, got {tuple(x.shape)}")
+    return x.contiguous(), A_log.contiguous(), D.contiguous(), dt_bias.contiguous()
+
+
+@_launcher
+def ssd_forward(x, A_log, D, dt_bias, num_heads, head_dim, d_state, num_groups=1, delta_softplus=True):
+    """Mamba-2 SSD layer (``vivit_ssd_forward_f32``; one launch, chunked on the fp32 matrix pipe): packed
+    ``x [N, T, H P + H + 2 G S]`` = ``X | dt | B | C``, ``A_log``, ``D``, ``dt_bias [H]`` -> ``y [N, T, H P]``."""
+    H, P, S, G = int(num_heads), int(head_dim), int(d_state), int(num_groups)
+    x, A_log, D, dt_bias = _ssd_operands(x, A_log, D, dt_bias, H, P, S, G)
+    N, T = x.shape[:2]
+    y = torch.empty((N, T, H * P), dtype=torch.float32, device=x.device)
+    st = _lib.load().vivit_ssd_forward_f32(x.data_ptr(), A_log.data_ptr(), D.data_ptr(), dt_bias.data_ptr(), y.data_ptr(), N, T, H, P, S, G,
+                                          int(bool(delta_softplus)), _stream(x))
+    _lib.check(st, "vivit_ssd_forward_f32")
+    return y
+
+
+@_launcher
+def ssd_rules(M, x, A_log, D, dt_bias, num_heads, head_dim, d_state, num_groups=1, delta_softplus=True, want=(True, True, True, True)):
+    """The rules of the SSD layer from one visit of the factor (``vivit_ssd_rules_f32``): ``M [V, N, T, H P]`` ->
+    ``(g [V, N, T, H P + H + 2 G S], F_A, F_D, F_dt_bias [V, N, H])``, the transposed input Jacobian packed as ``x`` and the factors of
+    ``A_log``, ``D`` and ``dt_bias``.  ``want``: which of the four to compute (``None`` for the others)."""
+    _require_device(M)
+    H, P, S, G = int(num_heads), int(head_dim), int(d_state), int(num_groups)
+    x, A_log, D, dt_bias = _ssd_operands(x, A_log, D, dt_bias, H, P, S, G)
+    M = M.contiguous()
+    N, T = x.shape[:2]
+    if M.dim() != 4 or tuple(M.shape[1:]) != (N, T, H * P) or M.numel() == 0:
+        raise ValueError(f"M must be [V, {N}, {T}, {H * P}], got {tuple(M.shape)}")
+    if len(want) != 4 or not any(want):
+        raise ValueError("nothing to compute")
+    Vd, bits = M.shape[0], sum(1 << i for i, w in enumerate(want) if w)
+    new = lambda *shape: torch.empty((Vd, N) + shape, dtype=torch.float32, device=M.device)   # noqa: E731
+    g, FA, FD, Fb = (new(*shape) if w else None for w, shape in zip(want, ((T, x.shape[2]), (H,), (H,), (H,))))
+    lib = _lib.load()
+    ws, ws_bytes = _workspace(lib.vivit_ssd_rules_f32_workspace_bytes(Vd, N, T, H, P, S, G, bits), M)
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    st = lib.vivit_ssd_rules_f32(M.data_ptr(), x.data_ptr(), A_log.data_ptr(), D.data_ptr(), dt_bias.data_ptr(), ptr(g), ptr(FA), ptr(FD),
+                                 ptr(Fb), Vd, N, T, H, P, S, G, int(bool(delta_softplus)), bits, ws, ws_bytes, _stream(M))
+    _lib.check(st, "vivit_ssd_rules_f32")
+    return g, FA, FD, Fb
+
+
 @_launcher
 def bn_eval_rules(M, x, scale, mean=None, rstd=None):
     """All rules of a BatchNorm in eval mode in one pass over the factor (``vivit_bn_eval_rules_f32``): ``M [V, N, C, *spatial]``,
